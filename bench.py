@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the Chebyshev graph-CNN training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = forward + loss + backward + (RCCL gradient all-reduce) + TF-form Adam on one batch
@@ -9,6 +9,11 @@ of synthetic fMRI windows, inputs resident in HBM.  Workload = BASELINE.json con
 ChebNet K=5, 6 conv layers (F=32, no pooling, per-vertex biases), FC 512-256-22, the seeded
 synthetic N=10000 kNN graph (M=10466 after one coarsening level), block_dura=15, batch 64
 per GPU (weak scaling; configs[2] is the same at 8 GPUs).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps once and reports them.  --full adds
+everything else the line can carry: repeated timed regions, the instrumented pass (roofline,
+kernels), the kernel / layer / atlas / pooling / fit / data-parallel legs and the CPU baseline.
+--dump-outputs DIR writes what the last timed step handed its caller (dump_outputs).
 """
 import argparse
 import json
@@ -24,6 +29,10 @@ sys.path.insert(0, ROOT)
 METRIC = 'fMRI-windows/sec (fwd+bwd) 6-layer ChebNet K=5 N≈10k; HBM GB/s vs roofline'
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec (MI355X_MICROARCH.md)
 FP32_MFMA_PEAK_TFLOPS = 157.3
+# options that switch on the measurements beside the headline figure: (default with --full, default of a plain run);
+# a value given on the command line holds either way
+EXTRA_DEFAULTS = {'cpu_windows': (16, 0), 'kernel_legs': (1, 0), 'repeats': (3, 1), 'instrumented_steps': (10, 0)}
+DUMP_MAX_ELEMENTS = 1 << 19     # per dumped array (2 MB of float32): the 18 variables of the network stay under 40 MB
 
 
 def load_graph(n_nodes, levels, rank, world, barrier):
@@ -472,6 +481,21 @@ def ranks_seen(dist, dev):
     return int(t.item())
 
 
+def dump_outputs(net, loss_average, out_dir):
+    """What the last timed step handed its caller, as ``out_dir/<name>.npy`` in float32: ``loss_average`` (what
+    ``train_step`` returns) and every variable after that step's Adam update (``get_var``: the reference's shape and
+    vertex order), named by its TF name with '/' -> '_'.  A variable of more than DUMP_MAX_ELEMENTS elements is stored
+    as a fixed sample of its flattened values: the same seeded, sorted indices in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss_average.npy'), np.atleast_1d(loss_average.detach().float().cpu().numpy()))
+    for name in net.variables():
+        a = np.asarray(net.get_var(name), np.float32)
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name.replace('/', '_') + '.npy'), a)
+
+
 def stub_main(args, world, rank):
     """``--stub``: the launcher / rendezvous / timing / reporting path with a stand-in step on CPU tensors (backend
     gloo) -- what tests/test_bench_launcher.py runs where there is no GPU.  Not a measurement."""
@@ -520,8 +544,13 @@ def main():
     ap.add_argument('--nodes', type=int, default=10000)
     ap.add_argument('--korder', type=int, default=5)
     ap.add_argument('--block-dura', type=int, default=15)
-    ap.add_argument('--cpu-windows', type=int, default=16, help='0 disables the CPU baseline leg')
-    ap.add_argument('--kernel-legs', type=int, default=1,
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline figure; sets the defaults of --cpu-windows, '
+                         '--kernel-legs, --repeats and --instrumented-steps to 16, 1, 3 and 10 (plain run: 0, 0, 1, 0)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the last step\'s loss_average and variables as DIR/<name>.npy')
+    ap.add_argument('--cpu-windows', type=int, default=None, help='windows of the CPU baseline leg; 0 disables it')
+    ap.add_argument('--kernel-legs', type=int, default=None,
                     help='1: also time the recurrence kernels alone at the north-star shape (K=5, Fin=32, batch 256) and at '
                          'configs[3] (K=25, Fin=64, batch 64), the wide layer of configs[4] (Fin=60, Fout=256) forward + '
                          'backward in fp32 / bf16 / split bf16, the reference\'s own training shape (atlas graph, K=10, batch 128) '
@@ -529,10 +558,10 @@ def main():
     ap.add_argument('--overlap-bwd-w', type=int, default=-1,
                     help="contract_bwd_w on a second stream (ops.overlap_bwd_w): 1 / 0 force it, -1 = the library's default ('auto': wide "
                          'layers only)')
-    ap.add_argument('--repeats', type=int, default=3,
+    ap.add_argument('--repeats', type=int, default=None,
                     help='the timed region (exactly --steps steps) is run this many times; `value` comes from the FIRST, the '
                          'others are reported beside it (ms_per_step_repeats)')
-    ap.add_argument('--instrumented-steps', type=int, default=10,
+    ap.add_argument('--instrumented-steps', type=int, default=None,
                     help='steps of the separate instrumented pass AFTER the timed regions (HIP events around every hot-kernel '
                          'launch, no second stream): the source of `roofline` and `kernels`; 0 disables it')
     ap.add_argument('--step-graph', type=int, default=0,
@@ -540,6 +569,9 @@ def main():
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (nccl = RCCL)')
     ap.add_argument('--stub', action='store_true', help='launcher / reporting path with a stand-in CPU step (tests)')
     args = ap.parse_args()
+    for name, (full, plain) in EXTRA_DEFAULTS.items():
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else plain)
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -628,6 +660,8 @@ def main():
             dt_r = float(t.item())
         region_ms.append(1e3 * dt_r / args.steps)
     dt = region_ms[0] * args.steps / 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(net, loss, args.dump_outputs)
     loss = float(loss)
     # ---- separate instrumented pass: HIP events around every hot-kernel launch on the launch stream (no second stream
     # on these steps: a kernel's time must not include a neighbour)

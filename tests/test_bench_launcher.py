@@ -52,3 +52,32 @@ def test_bench_launcher_reports_child_failure():
 def test_bench_under_torchrun_world_mismatch_is_an_error():
     r = _run(['--gpus', '4', '--stub'], env_extra={'WORLD_SIZE': '2', 'RANK': '0', 'LOCAL_RANK': '0'})
     assert r.returncode != 0 and 'rank processes' in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_names_and_samples(tmp_path):
+    """``bench.dump_outputs``: one float32 .npy per variable ('/' -> '_') plus ``loss_average``; a variable larger than
+    DUMP_MAX_ELEMENTS becomes the same seeded sample of its flattened values in every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Net:
+        vars = {'conv1/weights': np.arange(12, dtype=np.float64).reshape(3, 4),
+                'fc1/weights': np.arange(bench.DUMP_MAX_ELEMENTS + 5, dtype=np.float32)}
+
+        def variables(self):
+            return list(self.vars)
+
+        def get_var(self, name):
+            return self.vars[name]
+
+    for d in ('a', 'b'):
+        bench.dump_outputs(Net(), torch.tensor(1.5), str(tmp_path / d))
+    assert sorted(os.listdir(tmp_path / 'a')) == ['conv1_weights.npy', 'fc1_weights.npy', 'loss_average.npy']
+    w = np.load(tmp_path / 'a' / 'conv1_weights.npy')
+    assert w.dtype == np.float32 and np.array_equal(w, Net.vars['conv1/weights'])
+    s = np.load(tmp_path / 'a' / 'fc1_weights.npy')
+    assert s.shape == (bench.DUMP_MAX_ELEMENTS,) and np.all(np.diff(s) > 0)        # distinct elements, in index order
+    assert np.array_equal(s, np.load(tmp_path / 'b' / 'fc1_weights.npy'))
+    assert np.load(tmp_path / 'a' / 'loss_average.npy').tolist() == [1.5]

@@ -251,14 +251,14 @@ def test_reference_training_shape_vs_oracle(ops, dev, n_nodes):
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_on_stdout():
-    """``python bench.py`` (kernel legs on: the dp_overhead leg brings up an RCCL communicator, which prints a version
-    banner to file descriptor 1): stdout must carry the result line and nothing else."""
+    """``python bench.py --full`` (kernel legs on: the dp_overhead leg brings up an RCCL communicator, which prints a
+    version banner to file descriptor 1): stdout must carry the result line and nothing else."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '3', '--repeats', '1',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '3', '--warmup', '3', '--repeats', '1',
                         '--instrumented-steps', '2', '--cpu-windows', '0'], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -269,6 +269,39 @@ def test_bench_prints_one_json_line_on_stdout():
     for key in ('roofline', 'step_roofline', 'kernels', 'northstar', 'config4', 'config5', 'dp_overhead', 'refshape', 'fit'):        # (cpu_baseline: --cpu-windows 0 here)
         assert key in line, key
     assert line['roofline']['bound'] == 'hbm' and 0.2 < line['roofline']['frac'] < 1.0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_only_its_steps_and_dumps_outputs(tmp_path):
+    """``python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`` without ``--full``: one timed region of exactly K
+    steps and none of the extra legs in the line; DIR holds the last step's loss and variables as float32 .npy files,
+    64 MB at most."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    out = tmp_path / 'outputs'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2',
+                        '--dump-outputs', str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[:2000]
+    line = json.loads(lines[0])
+    assert line['steps'] == 4 and line['warmup'] == 2 and line['ms_per_step'] > 0 and line['value'] > 0
+    assert line['ms_per_step_repeats']['all'] == [line['ms_per_step']]
+    for key in ('roofline', 'kernels', 'northstar', 'config4', 'config5', 'dp_overhead', 'refshape', 'pool6', 'fit', 'cpu_baseline'):
+        assert key not in line, key
+    files = sorted(p.name for p in out.iterdir())
+    assert 'loss_average.npy' in files and 'fc1_weights.npy' in files and 'conv6_bias.npy' in files, files
+    total = 0
+    for name in files:
+        a = np.load(out / name)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(out / 'loss_average.npy')[0] == pytest.approx(line['final_loss'])
 
 
 @pytest.mark.gpu

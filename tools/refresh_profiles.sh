@@ -7,7 +7,7 @@
 out=$GRAFT_REPO_ROOT/gpurun_out/refresh
 rm -rf $out; mkdir -p $out
 cd $GRAFT_REPO_ROOT
-python3 bench.py > $out/bench_line.json 2> $out/bench.err
+python3 bench.py --full > $out/bench_line.json 2> $out/bench.err
 python3 tools/kbench.py --json $out/kbench.json > $out/kbench.txt 2>&1
 python3 tools/kbench.py --planes 2 --B 64 256 --kernels recurrence_fwd recurrence_fwd_inplace recurrence_bwd > $out/kbench_two_planes.txt 2>&1
 # the kernels of rounds 1-3 (the caller's vertex numbering: four planes at batch 256, two at batch 64) beside the ordered ones
@@ -43,12 +43,13 @@ if lib_ok $GRAFT_REPO_ROOT/build_x/libchebgcn_f64.so; then
   CHEBGCN_LIB=$GRAFT_REPO_ROOT/build_x/libchebgcn_f64.so python3 tools/fused_check.py 2>&1 | grep -A30 "N=360 M=376 B=128 Fin=32" | grep -B1 -A13 "stamps" > $out/stampsf.txt
 fi
 cp gpurun_out/pmcmfma_refresh/available.txt $out/mfma_counters_available.txt 2>/dev/null
+repo=$PWD
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o bench -- python3 $GRAFT_REPO_ROOT/bench.py --cpu-windows 0 --kernel-legs 0 > $out/prof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o bench -- python3 $repo/bench.py --full --cpu-windows 0 --kernel-legs 0 > $out/prof.log 2>&1
 find $out/prof -name "*kernel_stats.csv" -exec cp {} $out/bench_kernel_stats.csv \;
 # the same command with every kernel ALONE on the device (no second stream for contract_bwd_w): the AverageNs of a kernel symbol
 # here is what `roofline` / `kernels_by_symbol` of the bench line (HIP events, instrumented pass) must agree with
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/profs -o benchs -- python3 $GRAFT_REPO_ROOT/bench.py --cpu-windows 0 --kernel-legs 0 --overlap-bwd-w 0 > $out/profs.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/profs -o benchs -- python3 $repo/bench.py --full --cpu-windows 0 --kernel-legs 0 --overlap-bwd-w 0 > $out/profs.log 2>&1
 find $out/profs -name "*kernel_stats.csv" -exec cp {} $out/bench_kernel_stats_serial.csv \;
 grep '^{"metric"' $out/profs.log | tail -1 > $out/bench_line_serial.json
 # configs[3] (K = 25, Fin = Fout = 64, batch 64): one program per recurrence entry, 30 launches each (the three warm-up launches of
