@@ -95,6 +95,12 @@ SIGNATURES = {
     'chebgcn_metis_one_level_f64': (_i, [_i64, _p, _p, _p, _p, _p, _i64, _p]),
     'chebgcn_compute_perm_level': (_i, [_p, _i64, _p, _i64, _p]),
     'chebgcn_bank_order': (_i, [_i, _p, _p, _i, _p, _p]),
+    'chebgcn_spectral_transform': (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    'chebgcn_spectral_mix_fwd': (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    'chebgcn_spectral_mix_bwd_x': (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    'chebgcn_spectral_mix_bwd_w': (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    'chebgcn_spectral_spline_expand': (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    'chebgcn_spectral_spline_expand_bwd': (_i, [_p, _p, _p, _i, _i, _i, _p]),
 }
 
 _lib = None

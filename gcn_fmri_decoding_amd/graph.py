@@ -2,9 +2,10 @@
 feed the Chebyshev hot path (reference citations are to that file).
 
 These run once per model build on NumPy/SciPy, like the reference; the results (CSR
-Laplacians) are uploaded to the GPU by ``ops.Graph``.  Out of scope here and absent on
-purpose: ``fourier`` / ``plot_spectrum`` (spectral models) and the dense NumPy
-recurrence ``chebyshev`` (the GPU kernel replaces it).
+Laplacians) are uploaded to the GPU by ``ops.Graph``; ``fourier`` gives the dense basis
+of the spectral filters (``cgcnn`` with ``filter='fourier'`` / ``'spline'``).  Out of scope
+here and absent on purpose: ``plot_spectrum`` and the dense NumPy recurrence ``chebyshev``
+(the GPU kernel replaces it).
 """
 import numpy as np
 import scipy.sparse as sp
@@ -102,6 +103,29 @@ def rescale_L(L, lmax=2):
     L = sp.csr_matrix(L, copy=True)
     L.data *= 1.0 / (lmax / 2)
     return sp.csr_matrix(L - sp.identity(L.shape[0], format='csr', dtype=L.dtype))
+
+
+def fourier(L, algo='eigh', k=1):
+    """The graph Fourier basis: eigenvalues ascending and the eigenvectors as columns (graph.py:110-128).
+
+    ``'eigh'`` (what the spectral filters use) and ``'eig'`` take the dense matrix, in its own dtype (a float32
+    Laplacian gives a float32 decomposition); ``'eigs'`` / ``'eigsh'`` the ``k`` smallest-magnitude pairs of the sparse one.
+    """
+    def ascending(lamb, U):
+        idx = lamb.argsort()
+        return lamb[idx], U[:, idx]
+
+    dense = L.toarray() if sp.issparse(L) else np.asarray(L)
+    if algo == 'eigh':
+        return np.linalg.eigh(dense)
+    if algo == 'eig':
+        return ascending(*np.linalg.eig(dense))
+    import scipy.sparse.linalg
+    if algo == 'eigs':
+        return ascending(*scipy.sparse.linalg.eigs(L, k=k, which='SM'))
+    if algo == 'eigsh':
+        return scipy.sparse.linalg.eigsh(L, k=k, which='SM')
+    raise ValueError('fourier: unknown algo %r' % (algo,))
 
 
 def rescaled_laplacian_csr(L):

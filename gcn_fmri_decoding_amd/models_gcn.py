@@ -366,7 +366,9 @@ class base_model(object):
         self._inference(x, 1.0)
         specs, self._specs = self._specs, None
         order = {'head': 0, 'convw': 1, 'convb': 2}
-        specs.sort(key=lambda s: order[s.group])        # stable: keeps creation order inside a group
+        # stable: keeps creation order inside a group; unregularised conv weights (spline filters, models_gcn.py:552) go
+        # behind the regularised ones so that those stay a prefix of the flat buffer
+        specs.sort(key=lambda s: (order[s.group], not s.regularized))
         self._spec_list = specs
         sizes = [int(np.prod(s.shape)) for s in specs]
         offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
@@ -383,8 +385,8 @@ class base_model(object):
             self._slices[s.name] = (int(a), int(b))
         n_head = sum(z for s, z in zip(specs, sizes) if s.group == 'head')
         n_reg = sum(z for s, z in zip(specs, sizes) if s.regularized)
-        if any(s.regularized for s in specs if s.group == 'convb') or not all(
-                s.regularized for s in specs if s.group != 'convb'):
+        nr = sum(s.regularized for s in specs)
+        if any(s.regularized for s in specs if s.group == 'convb') or not all(s.regularized for s in specs[:nr]):
             raise AssertionError('flat layout assumes regularised variables come first')
         self._n_head, self._n_reg, self._n_total = n_head, n_reg, n
         self.regularizers = [s.name for s in specs if s.regularized]
@@ -850,8 +852,9 @@ class base_model(object):
         # the first FC layer behind the conv stack reads one input per graph vertex: its rows follow the vertex order
         vaxis = 0 if (group == 'head' and getattr(self, '_fc_on_vertices', False)) else None
         self._fc_on_vertices = False
+        # TF's fan-in (variance_scaling_initializer): the product of all dimensions but the last
         return self._get_variable('weights', shape, self._weight_initial(), regularization, group,
-                                  fan_in=shape[-2] if len(shape) >= 2 else shape[0], vaxis=vaxis)
+                                  fan_in=int(np.prod(shape[:-1])) if len(shape) >= 2 else shape[0], vaxis=vaxis)
 
     def _bias_variable(self, shape, regularization=True):
         """``tf.get_variable('bias', ...)`` initialised to 0.2 (:349-355).  Conv biases are
@@ -869,9 +872,35 @@ class base_model(object):
         return self._get_variable('bias', shape, 'const', regularization, 'head')
 
 
+def bspline_basis(K, x, degree=3):
+    """Cubic (by default) B-spline basis ``[len(x), K]`` at the points ``x`` (or at ``x`` evenly spaced points of
+    [0, 1] when ``x`` is a number), on ``K - degree + 1`` evenly spaced knots over [min x, max x] with the end knots
+    repeated ``degree`` times; the last point is put in the last spline (models_gcn.py:363-402)."""
+    if np.isscalar(x):
+        x = np.linspace(0, 1, x)
+    lo, hi = x.min(), x.max()
+    knots = np.concatenate((lo * np.ones(degree), np.linspace(lo, hi, K - degree + 1), hi * np.ones(degree)))
+    # Cox - de Boor, bottom up: splines of degree 0 (indicators of the half-open knot spans), then each degree from the one
+    # below -- a span of zero width contributes nothing
+    nk = len(knots)
+    N = [((x - knots[k] >= 0) & (x - knots[k + 1] < 0)).astype(int) for k in range(nk - 1)]
+    for d in range(1, degree + 1):
+        up = []
+        for k in range(nk - 1 - d):
+            width1, width2 = knots[k + d] - knots[k], knots[k + d + 1] - knots[k + 1]
+            rise = ((x - knots[k]) / width1) * N[k] if width1 > 0 else 0
+            fall = ((-(x - knots[k + d + 1])) / width2) * N[k + 1] if width2 > 0 else 0
+            up.append(rise + fall)
+        N = up
+    basis = np.column_stack(N[:K])
+    basis[-1, -1] = 1
+    return basis
+
+
 class cgcnn(base_model):
     """Graph CNN with Chebyshev filters; see the reference's docstring (:405-444) for the
-    meaning of F, K, p, M and the training keywords."""
+    meaning of F, K, p, M and the training keywords.  ``filter='fourier'`` / ``'spline'`` select the spectral filters
+    (:512-556): fp32, layer by layer, eagerly trained (no captured step, no data parallelism)."""
 
     def __init__(self, config, L, F, K, p, M, filter='chebyshev5', brelu='b1relu', pool='mpool1', initial='normal',
                  channel=1, num_epochs=20, learning_rate=0.1, decay_rate=0.95, decay_steps=None, momentum=0.9,
@@ -989,6 +1018,12 @@ class cgcnn(base_model):
                 self._inv_order_dev = torch.as_tensor(inv).to(self.device)
                 self._order_pad = torch.as_tensor(np.concatenate([order, pad])).to(self.device)
                 self._inv_order_pad = torch.as_tensor(np.concatenate([inv, pad])).to(self.device)
+        # spectral filters: the Fourier basis of every distinct Laplacian (and the spline basis of every (Laplacian, K)) once,
+        # here on the host through graph.fourier, and on the device as the kernels' operands
+        self._spectral = {}
+        if filter in ('fourier', 'spline'):
+            for Li, Ki in zip(self.L, self.K):
+                self._spectral_of(Li, Ki if filter == 'spline' else None)
         self._ctor = dict(L=list(L), F=list(F), K=list(K), p=list(p), M=list(M), filter=filter, brelu=brelu, pool=pool,
                           initial=initial, channel=channel, num_epochs=num_epochs, learning_rate=learning_rate,
                           decay_rate=decay_rate, decay_steps=decay_steps, momentum=momentum,
@@ -1084,6 +1119,47 @@ class cgcnn(base_model):
             return torch.empty((N, M, int(Fout)), device='meta')
         y = ops.cheb_conv(ops.plane_storage(x), W, None, self._graph_of(L), K, precision=self.contraction)
         return ops.plane_view(y, M)
+
+    def _spectral_of(self, L, K=None):
+        """Fourier basis of ``L`` (``graph.fourier``: eigenvalues, eigenvectors, the device operand) and, with ``K``, the
+        spline basis at its eigenvalues; computed once per Laplacian and K."""
+        e = self._spectral.get(id(L))
+        if e is None:
+            lamb, U = graph_mod.fourier(L)
+            e = {'L': L, 'lamb': lamb, 'U': U, 'splines': {},
+                 'basis': ops.spectral_basis(U, self.device) if self.device.type == 'cuda' else None}
+            self._spectral[id(L)] = e
+        if K is not None and K not in e['splines']:
+            Bs = np.asarray(bspline_basis(K, e['lamb'], degree=3), np.float32)
+            e['splines'][K] = (Bs, torch.as_tensor(Bs).to(self.device) if self.device.type == 'cuda' else None)
+        return e
+
+    def filter_in_fourier(self, x, L, Fout, K, U, W, spline=None):
+        """Analysis by the Fourier basis, a ``[Fout x Fin]`` mix per frequency, synthesis (:512-528).  ``U``: the device
+        basis of ``L`` (``ops.spectral_basis``); ``W``: ``[M, Fout, Fin]``, or the ``[K, Fout*Fin]`` spline weights with
+        their basis ``spline`` ``[M, K]`` (expanded inside the layer, so that the gradient reaches them)."""
+        N, M, Fin = x.shape
+        y = ops.SpectralConv.apply(ops.plane_storage(x), W, U, spline, int(M), int(Fout))
+        return ops.plane_view(y, M)
+
+    def fourier(self, x, L, Fout, K):
+        """Spectral filter with one free weight matrix per frequency, ``[M, Fout, Fin]``, L2-regularised (:530-538).
+        ``K`` is not used."""
+        N, M, Fin = x.shape
+        W = self._weight_variable([int(M), int(Fout), int(Fin)], regularization=True)
+        if x.is_meta:
+            return torch.empty((N, M, int(Fout)), device='meta')
+        return self.filter_in_fourier(x, L, Fout, K, self._spectral_of(L)['basis'], W)
+
+    def spline(self, x, L, Fout, K):
+        """Spectral filter whose per-frequency weights are cubic B-splines of the eigenvalue with K control points:
+        ``W = B @ Wk``, ``Wk`` ``[K, Fout*Fin]`` (column ``fout*Fin + fin``), not regularised (:540-556)."""
+        N, M, Fin = x.shape
+        W = self._weight_variable([int(K), int(Fout) * int(Fin)], regularization=False)
+        if x.is_meta:
+            return torch.empty((N, M, int(Fout)), device='meta')
+        e = self._spectral_of(L, int(K))
+        return self.filter_in_fourier(x, L, Fout, K, e['basis'], W, spline=e['splines'][int(K)][1])
 
     def _brelu(self, x, per_vertex):
         N, M, F = x.shape

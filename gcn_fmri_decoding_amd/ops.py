@@ -960,6 +960,117 @@ class BiasReluPool(torch.autograd.Function):
         return dy, dbias, None, None, None, None, None
 
 
+# ------------------------------------------------------------------------------------
+# spectral filters (filter = 'fourier' / 'spline', models_gcn.py:512-556)
+# ------------------------------------------------------------------------------------
+
+def spectral_basis(U, device):
+    """The Fourier basis ``U[vertex, frequency]`` (``graph.fourier``) as the device operand of the spectral kernels:
+    ``[Mp, Mp]`` fp32, zero-padded."""
+    U = np.asarray(U, np.float32)
+    M = U.shape[0]
+    Mp = plane_stride(M)
+    host = np.zeros((Mp, Mp), np.float32)
+    host[:M, :M] = U
+    return torch.as_tensor(host).to(device)
+
+
+def _spectral_flops(R, Mp):
+    return 2.0 * R * Mp * Mp
+
+
+def spectral_transform(x, basis, M, transpose):
+    """Planes ``x[B, F, Mp]`` -> ``out[r][j] = sum_m x[r][m] U[m][j]`` (analysis) or ``sum_m x[r][m] U[j][m]``
+    (synthesis, ``transpose``) on the matrix cores (chebgcn_spectral_transform)."""
+    _require_cuda(x, basis)
+    x = x if x.is_contiguous() else x.contiguous()
+    B, F, Mp = x.shape
+    out = torch.empty_like(x)
+    R = B * F
+    _launch('spectral_synthesis' if transpose else 'spectral_analysis', 4.0 * (2 * R * Mp + Mp * Mp), _spectral_flops(R, Mp),
+            lambda: _lib.check(_lib.lib().chebgcn_spectral_transform(_p(x), _p(basis), _p(out), R, M, int(bool(transpose)),
+                                                                     _stream()), 'spectral_transform'))
+    return out
+
+
+def spectral_mix(xh, W, M, transpose=False):
+    """The per-frequency filter: ``y[b][o][m] = sum_i W[m][o][i] xh[b][i][m]`` (``transpose``: ``sum_o W[m][o][i] dy[b][o][m]``,
+    its input gradient); ``W`` is ``[M, Fout, Fin]``."""
+    B, Ni, Mp = xh.shape
+    _, Fout, Fin = W.shape
+    No = Fin if transpose else Fout
+    out = torch.empty((B, No, Mp), dtype=torch.float32, device=xh.device)
+    fn = _lib.lib().chebgcn_spectral_mix_bwd_x if transpose else _lib.lib().chebgcn_spectral_mix_fwd
+    _launch('spectral_mix_bwd_x' if transpose else 'spectral_mix_fwd', 4.0 * (B * (Ni + No) * Mp + W.numel()),
+            2.0 * B * M * Fin * Fout,
+            lambda: _lib.check(fn(_p(xh), _p(W), _p(out), B, M, Fin, Fout, _stream()),
+                               'spectral_mix_bwd_x' if transpose else 'spectral_mix_fwd'))
+    return out
+
+
+def spectral_mix_bwd_w(dyh, xh, M):
+    """``dW[m][o][fin] = sum_b dyh[b][o][m] xh[b][fin][m]``, summed over the windows in a fixed order."""
+    B, Fout, Mp = dyh.shape
+    Fin = xh.shape[1]
+    dW = torch.empty((M, Fout, Fin), dtype=torch.float32, device=dyh.device)
+    _launch('spectral_mix_bwd_w', 4.0 * (B * (Fin + Fout) * Mp + dW.numel()), 2.0 * B * M * Fin * Fout,
+            lambda: _lib.check(_lib.lib().chebgcn_spectral_mix_bwd_w(_p(dyh), _p(xh), _p(dW), B, M, Fin, Fout, _stream()),
+                               'spectral_mix_bwd_w'))
+    return dW
+
+
+def spline_expand(Bs, Wk, transpose=False):
+    """``W = Bs @ Wk`` ([M, K] x [K, C]); ``transpose``: ``dWk = Bs^T @ dW`` (``Wk`` is then dW [M, C])."""
+    M, K = Bs.shape
+    C = Wk.shape[1]
+    if transpose:
+        out = torch.empty((K, C), dtype=torch.float32, device=Wk.device)
+        fn, what = _lib.lib().chebgcn_spectral_spline_expand_bwd, 'spectral_spline_expand_bwd'
+    else:
+        out = torch.empty((M, C), dtype=torch.float32, device=Wk.device)
+        fn, what = _lib.lib().chebgcn_spectral_spline_expand, 'spectral_spline_expand'
+    _launch(what, 4.0 * (M * K + (M + K) * C), 2.0 * M * K * C,
+            lambda: _lib.check(fn(_p(Bs), _p(Wk), _p(out), M, K, C, _stream()), what))
+    return out
+
+
+class SpectralConv(torch.autograd.Function):
+    """``filter_in_fourier`` (models_gcn.py:512-528) on plane storage: analysis, the per-frequency ``[Fout x Fin]`` mix,
+    synthesis.  ``W``: ``[M, Fout, Fin]`` (``fourier``, :530-538), or, with the spline basis ``Bs [M, K]`` given, the
+    ``[K, Fout*Fin]`` control weights the filter is expanded from (``spline``, :540-556).  Saves the analysed input for
+    the weight gradient; returns no input gradient where the input needs none."""
+
+    @staticmethod
+    def forward(ctx, x, W, basis, Bs, M, Fout):
+        _require_cuda(x, W, basis, Bs)
+        x = x if x.is_contiguous() else x.contiguous()
+        B, Fin, Mp = x.shape
+        if basis.shape != (Mp, Mp):
+            raise ValueError('spectral conv: basis %s for planes of %d vertices' % (tuple(basis.shape), M))
+        Wd = W.detach().contiguous()
+        Wf = (spline_expand(Bs, Wd) if Bs is not None else Wd).view(M, Fout, Fin)
+        xh = spectral_transform(x, basis, M, False)
+        y = spectral_transform(spectral_mix(xh, Wf, M), basis, M, True)
+        ctx.save_for_backward(xh, Wf, basis, Bs)
+        ctx.M = M
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xh, Wf, basis, Bs = ctx.saved_tensors
+        M = ctx.M
+        gy = gy if gy.is_contiguous() else gy.contiguous()
+        dyh = spectral_transform(gy, basis, M, False)          # the adjoint of synthesis is analysis
+        dx = dW = None
+        if ctx.needs_input_grad[1]:
+            dW = spectral_mix_bwd_w(dyh, xh, M)
+            if Bs is not None:
+                dW = spline_expand(Bs, dW.view(M, -1), transpose=True)
+        if ctx.needs_input_grad[0]:
+            dx = spectral_transform(spectral_mix(dyh, Wf, M, transpose=True), basis, M, True)
+        return dx, dW, None, None, None, None
+
+
 class FeatureMean(torch.autograd.Function):
     """tf.reduce_mean(x, -1) (models_gcn.py:673): storage [B, F, Mp] -> dense [B, M]."""
 

@@ -434,6 +434,37 @@ int chebgcn_compute_perm_level(const int32_t* parent, int64_t n_fine, const int6
                                int64_t n_order, int64_t* out);
 
 
+/* ---- spectral filters: filter = 'fourier' / 'spline' (lib_new/models_gcn.py:512-556) ---------------------------------
+ * The graph Fourier basis U = the eigenvectors of the layer's Laplacian (lib_new/graph.py:110-128), U[vertex][frequency],
+ * lives on the device as [Mp][Mp] fp32 with zero padding (Mp = chebgcn_plane_stride(M)).  Planes are [R][Mp] (R = B*F) in
+ * the plane layout; the pad [M, Mp) of an input plane is never read, that of an output plane is written as 0.  Every sum
+ * runs in a fixed order (no atomics): repeated calls are bit-identical.
+ *
+ * transform (fp32-input matrix instructions, exact fp32 products):
+ *   transpose == 0 (analysis):  out[r][j] = sum_m in[r][m] * U[m][j]
+ *   transpose != 0 (synthesis): out[r][j] = sum_m in[r][m] * U[j][m]
+ * Not in place.  The gradient of either direction is the other one. */
+int chebgcn_spectral_transform(const float* in, const float* basis, float* out, int R, int M, int transpose,
+                               chebgcn_stream stream);
+/* The per-frequency filter, W [M][Fout][Fin] row-major (the reference's weight shape), xh / dxh [B][Fin][Mp],
+ * yh / dyh [B][Fout][Mp]:
+ *   mix_fwd:   yh[b][o][m]    = sum_fin W[m][o][fin] * xh[b][fin][m]
+ *   mix_bwd_x: dxh[b][fin][m] = sum_o   W[m][o][fin] * dyh[b][o][m]
+ *   mix_bwd_w: dW[m][o][fin]  = sum_b dyh[b][o][m] * xh[b][fin][m]   (written, not accumulated) */
+int chebgcn_spectral_mix_fwd(const float* xh, const float* W, float* yh, int B, int M, int Fin, int Fout,
+                             chebgcn_stream stream);
+int chebgcn_spectral_mix_bwd_x(const float* dyh, const float* W, float* dxh, int B, int M, int Fin, int Fout,
+                               chebgcn_stream stream);
+int chebgcn_spectral_mix_bwd_w(const float* dyh, const float* xh, float* dW, int B, int M, int Fin, int Fout,
+                               chebgcn_stream stream);
+/* Spline parametrisation of the filter (models_gcn.py:540-556): Bs [M][K] (the cubic B-spline basis at the eigenvalues),
+ * Wk [K][C], W [M][C], C = Fout*Fin (column fout*Fin + fin):
+ *   expand:     W[m][c]   = sum_k Bs[m][k] * Wk[k][c]
+ *   expand_bwd: dWk[k][c] = sum_m Bs[m][k] * dW[m][c]   (written, not accumulated) */
+int chebgcn_spectral_spline_expand(const float* Bs, const float* Wk, float* W, int M, int K, int C, chebgcn_stream stream);
+int chebgcn_spectral_spline_expand_bwd(const float* Bs, const float* dW, float* dWk, int M, int K, int C,
+                                       chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose
