@@ -207,7 +207,7 @@ pool_scatter_bwd_kernel(const float* __restrict__ dout, const float* __restrict_
     // EPT: pooled vertices a thread stages per window (prefetched one window ahead while Mpo <= EPT * NT): 2, 4 or 8
     const int f = blockIdx.y, pb = blockIdx.x, NPB = gridDim.x;
     const int b0 = (int)((long long)B * pb / NPB), b1 = (int)((long long)B * (pb + 1) / NPB);
-    const int Mq = Mp >> 2, pmask = (1 << lgp) - 1;
+    const int Mq = Mp >> 2;
     // blockIdx.z: the source quads are split between gridDim.z workgroups (each stages the whole pooled plane: an L2 hit for
     // all but the first) where batch parts x filters alone leave the chip short of workgroups
     const int qpz = (Mq + (int)gridDim.z - 1) / (int)gridDim.z;
@@ -215,6 +215,10 @@ pool_scatter_bwd_kernel(const float* __restrict__ dout, const float* __restrict_
     const float inv = 1.0f / (float)(1 << lgp);
     const bool pre = Mpo <= EPT * NT;
     const bool is_max = pool_kind == CHEBGCN_POOL_MAX;
+    // member index of a source vertex in its cluster.  The average reads it as a bit of the selection byte, which holds 8
+    // members: with ReLU the pool is at most 8 (the entry points refuse more), without it finish() sets all eight bits and the
+    // index is taken mod 8, so that every member takes its share at any pool size (a uniform mask: no work per element)
+    const int pmask = is_max ? (1 << lgp) - 1 : ((1 << lgp) - 1) & 7;
     // One pooled vertex of a window: {gradient (scaled for the average), selection byte with the dead flag}.  Requests and
     // their use are separate and free of data-dependent branches: every load of a window is in flight before the first is used
     // (a conditional load behind a loaded value made hipcc wait for each of them in turn)
@@ -625,13 +629,15 @@ extern "C" int chebgcn_brelu_pool_bwd(const float* dout, const float* out, const
     CG_REQUIRE(!relu || out || (pool == 1 && argmax), "brelu_pool_bwd: relu needs the forward output (or its mask at pool 1)");
     CG_REQUIRE(pool == 1 || argmax || (pool_kind == CHEBGCN_POOL_AVG && !relu), "brelu_pool_bwd: pooling needs argmax/mask");
     CG_REQUIRE(bias_kind == CHEBGCN_BIAS_NONE || dbias, "brelu_pool_bwd: dbias is NULL");
+    CG_REQUIRE(!(pool_kind == CHEBGCN_POOL_AVG && relu && argmax && pool > 8),
+               "brelu_pool_bwd: average pooling keeps a ReLU mask only for pool <= 8");
     const int Mp = plane_stride(M), Mpo = plane_stride(M / pool);
     // pooled layers: whole 16-byte pieces of dy per store, the pooled plane staged in LDS (pool_scatter_bwd_kernel; the scalar
     // kernel below ran at 0.18-0.22 of the HBM roofline in the six-level pooling network).  It needs the workspace
     // chebgcn_brelu_pool_bwd_workspace() reports; a caller without one gets the scalar kernel.
     // (planes of fewer than 2048 vertices: a workgroup's 512 threads have less than a quad each and a window is a latency chain --
     // the scalar kernel with its batch split over thread groups is faster there: 0.033 against 0.055 ms at M = 792, F = 128)
-    if (pool > 1 && dy && Mp >= 2048 && pool_scatter_fits(M, pool) && (pool_kind == CHEBGCN_POOL_MAX || pool <= 8 || !relu) &&
+    if (pool > 1 && dy && Mp >= 2048 && pool_scatter_fits(M, pool) &&
         (bias_kind == CHEBGCN_BIAS_NONE ||
          (workspace && workspace_bytes >= chebgcn_pool_scatter_bwd_workspace(B, M, F, pool, bias_kind))))
         return pool_scatter_launch(dout, out, argmax, nullptr, dy, dbias, bias_kind, B, M, F, pool, pool_kind, relu, workspace,
@@ -820,6 +826,8 @@ extern "C" int chebgcn_pool_scatter_bwd(const float* dout, const uint8_t* sel, c
     CG_REQUIRE(pool >= 2 && (pool & (pool - 1)) == 0 && pool <= 128 && M % pool == 0, "pool_scatter_bwd: bad pool %d", pool);
     CG_REQUIRE(sel || (pool_kind == CHEBGCN_POOL_AVG && !relu), "pool_scatter_bwd: pooling needs the forward's selection bytes");
     CG_REQUIRE(bias_kind == CHEBGCN_BIAS_NONE || dbias, "pool_scatter_bwd: dbias is NULL");
+    CG_REQUIRE(!(pool_kind == CHEBGCN_POOL_AVG && relu && sel && pool > 8),
+               "pool_scatter_bwd: average pooling keeps a ReLU mask only for pool <= 8");
     CG_REQUIRE(pool_scatter_fits(M, pool), "pool_scatter_bwd: a pooled plane of %d vertices does not fit the LDS", M / pool);
     return pool_scatter_launch(dout, nullptr, sel, smap, dy, dbias, bias_kind, B, M, F, pool, pool_kind, relu, workspace,
                                workspace_bytes, (hipStream_t)stream_);

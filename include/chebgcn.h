@@ -242,8 +242,9 @@ int chebgcn_brelu_pool_bwd(const float* dout, const float* out, const uint8_t* a
  *       average -- bit i set where member i was positive (pool <= 8).
  *   chebgcn_pool_scatter_bwd: dy[b][f][v] = gradient of source vertex v (MaxPoolGrad / AvgPoolGrad + ReluGrad) from
  *       dout [B][F][Mp(M/pool)] and sel; smap: int32 [M], smap[v] = j*pool + i (v is member i of pooled vertex j), NULL =
- *       the identity; dbias as chebgcn_brelu_pool_bwd (fixed-order sums: per-batch-part partials in `workspace`, at least
- *       chebgcn_pool_scatter_bwd_workspace() bytes, added in part order).  16-byte stores of dy; the pooled plane is staged
+ *       the identity; sel may be NULL for the average without ReLU (every member takes its share, at any pool), and the
+ *       average with ReLU is refused beyond pool 8 (its mask holds 8 members); dbias as chebgcn_brelu_pool_bwd (fixed-order
+ *       sums: per-batch-part partials in `workspace`, at least chebgcn_pool_scatter_bwd_workspace() bytes, added in part order).  16-byte stores of dy; the pooled plane is staged
  *       in LDS, so planes of more than 10240 pooled vertices are refused (CHEBGCN_EINVAL). */
 int chebgcn_pool_gather_fwd(const float* y, const int32_t* pmap, float* out, uint8_t* sel, int B, int M, int F,
                             int pool, int pool_kind, int relu, chebgcn_stream stream);

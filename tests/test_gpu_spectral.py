@@ -1,7 +1,8 @@
 """Spectral filters on the MI355X (cgcnn filter='fourier' / 'spline', lib_new/models_gcn.py:512-556): every kernel arm by
 its name against a float64 restatement, the networks against the reference's logits (tests/golden/inference_{fourier,
 spline}_n*.npz) with the fixture's basis injected, one training step's gradients against float64 autograd, three Adam
-steps, the spline model's L2 term, a checkpoint round trip and an eager fit()."""
+steps, the spline model's L2 term, the gradients of a Fourier network with average pooling at p = 16 (apool1), a checkpoint
+round trip and an eager fit()."""
 import numpy as np
 import pytest
 import torch
@@ -149,9 +150,9 @@ def _levels(p):
     return out
 
 
-def _restated_loss(z, params, x, labels, reg, names_reg):
-    """The network in float64 torch: filter_in_fourier (:512-528), bias, ReLU, max pooling, feature mean, FC head,
-    mean softmax cross-entropy (+ reg * sum of l2_loss over ``names_reg``)."""
+def _restated_loss(z, params, x, labels, reg, names_reg, pool='mpool1'):
+    """The network in float64 torch: filter_in_fourier (:512-528), bias, ReLU, max pooling (``pool='apool1'``: average
+    pooling), feature mean, FC head, mean softmax cross-entropy (+ reg * sum of l2_loss over ``names_reg``)."""
     F, K, p, Mfc = z['F'].tolist(), z['K'].tolist(), z['p'].tolist(), z['M'].tolist()
     spline, levels = str(z['filter']) == 'spline', _levels(p)
     h = x
@@ -165,7 +166,8 @@ def _restated_loss(z, params, x, labels, reg, names_reg):
         yh = torch.einsum('mof,nmf->nmo', W, xh)
         h = torch.relu(torch.einsum('jm,nmo->njo', U, yh) + params['conv%d/bias' % (i + 1)])
         if p[i] > 1:
-            h = h.reshape(N, M // p[i], p[i], F[i]).max(dim=2).values
+            h = h.reshape(N, M // p[i], p[i], F[i])
+            h = h.max(dim=2).values if pool == 'mpool1' else h.mean(dim=2)
     h = h.mean(dim=2)
     for i in range(len(Mfc)):
         scope = 'logits' if i == len(Mfc) - 1 else 'fc%d' % (i + 1)
@@ -219,6 +221,46 @@ def test_train_step_gradients_and_adam(monkeypatch, name):
                 p_ -= lr_t * m[n] / (torch.sqrt(v2[n]) + 1e-8)
         for n in params:
             assert_adam_params_close(net.get_var(n), params[n].detach().numpy(), v2[n].numpy(), step, ill, n)
+
+
+def _ring_laplacian(M):
+    """Normalised Laplacian of a ring of M vertices (host CSR, fp32): a level whose basis the test injects."""
+    import scipy.sparse as sp
+    i = np.arange(M)
+    A = sp.coo_matrix((np.ones(2 * M), (np.r_[i, i], np.r_[(i + 1) % M, (i - 1) % M])), shape=(M, M))
+    return (sp.identity(M) - 0.5 * A).tocsr().astype(np.float32)
+
+
+@pytest.mark.parametrize('p', [16])
+def test_fourier_apool1_train_step_gradients(monkeypatch, p):
+    """cgcnn(filter='fourier', pool='apool1') at a pool the 8-bit ReLU mask does not reach, on a level of 2048 vertices (the
+    16-byte-store gradient kernel of the average pooling): one training step's gradients against float64 autograd."""
+    M0, Fo, C, B = 2048, 4, 3, 4
+    rs = np.random.RandomState(p)
+    lamb = np.sort(2 * rs.rand(M0)).astype(np.float32)
+    U = np.linalg.qr(rs.randn(M0, M0))[0].astype(np.float32)          # a random orthonormal basis
+    Ls = [_ring_laplacian(M0 >> k) for k in range(int(np.log2(p)) + 1)]
+    monkeypatch.setattr(graph_mod, 'fourier', lambda L, algo='eigh', k=1: {M0: (lamb, U)}[L.shape[0]])
+    reg = 5e-4
+    net = models_gcn.cgcnn({'device': DEV}, Ls, [Fo], [3], [p], [C], filter='fourier', pool='apool1', channel=1, batch_size=B,
+                           regularization=reg, dropout=1, verbose=False)
+    assert not net._fusable() and net.vertex_order == 'reference'
+    z = {'F': np.array([Fo]), 'K': np.array([3]), 'p': np.array([p]), 'M': np.array([C]), 'filter': 'fourier', 'U0': U}
+    x = rs.randn(B, M0, 1).astype(np.float32)
+    labels = np.arange(B) % C
+    params = {n: torch.tensor(net.get_var(n), dtype=torch.float64, requires_grad=True) for n in net.variables()}
+    ce, loss = _restated_loss(z, params, torch.as_tensor(x, dtype=torch.float64), torch.as_tensor(labels), reg, net.regularizers,
+                              pool='apool1')
+    gce = torch.autograd.grad(ce, list(params.values()))
+    _, loss_avg = net.train_step(ops.plane_storage(torch.as_tensor(x).to(DEV)), torch.as_tensor(labels).to(DEV))
+    loss = float(loss.detach())
+    assert abs(float(loss_avg) - 0.1 * loss) <= 2e-5 * abs(0.1 * loss)
+    for n, g in zip(params, gce):
+        got = net.gradient(n).detach().cpu().numpy().astype(np.float64)
+        ref = g.numpy()
+        err = np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-30)
+        record_measured('spectral_apool1_train_grad', p=p, var=n, rel_err=err)
+        assert err <= 5e-5, 'apool1 p=%d %s: gradient rel err %.3e' % (p, n, err)
 
 
 @pytest.mark.parametrize('name', ['inference_fourier_n100_p21', 'inference_spline_n100'])
