@@ -47,6 +47,7 @@ SIGNATURES = {
     'chebgcn_adam_partials': (_i, [_i64]),
     'chebgcn_adam_step_sq': (_i, [_p, _p, _p, _p, _i64, _f, _p, _f, _f, _f, _f, _f, _p, _p]),
     'chebgcn_adam_step_sq_all': (_i, [_p, _p, _p, _p, _i64, _i64, _f, _p, _f, _f, _f, _f, _f, _p, _p]),
+    'chebgcn_nadam_step_sq_all': (_i, [_p, _p, _p, _p, _i64, _i64, _f, _p, _f, _f, _f, _f, _f, _p, _p]),
     'chebgcn_loss_bookkeeping': (_i, [_p, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p]),
     'chebgcn_set_scalars': (_i, [_p, C.c_float, C.c_float, _p]),
     'chebgcn_softmax_xent': (_i, [_p, _p, _i, _p, _p, _i, _i, _p]),
@@ -88,6 +89,8 @@ SIGNATURES = {
     'chebgcn_fc_fwd_workspace': (C.c_size_t, [_i, _i, _i]),
     'chebgcn_fc_fwd': (_i, [_p, _i64, _p, _p, _p, _p, C.c_size_t, _i, _i, _i, _i, _p]),
     'chebgcn_fc_bwd': (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _p]),
+    'chebgcn_planes_to_rows': (_i, [_p, _p, _p, _i, _i, _i, _i64, _p]),
+    'chebgcn_rows_to_planes': (_i, [_p, _p, _p, _i, _i, _i, _i64, _p]),
     'chebgcn_adam_step': (_i, [_p, _p, _p, _p, _i64, _f, _f, _f, _f, _f, _f, _p]),
     'chebgcn_adam_step_dev': (_i, [_p, _p, _p, _p, _i64, _p, _f, _f, _f, _f, _f, _p]),
     'chebgcn_metis_one_level_f32': (_i, [_i64, _p, _p, _p, _p, _p, _i64, _p]),

@@ -221,6 +221,49 @@ fc_bwd_x_kernel(const float* __restrict__ g, const float* __restrict__ y, const 
     }
 }
 
+// The flatten of finetuning_cgcnn's head (tf.reshape(conv, [N, M*F]), models_gcn.py:805-806) between plane storage and
+// reference rows:  rows[b][m*F + f] = planes[b][f][v']  where the reference vertex m sits at internal position v' (order[v'] = m;
+// order NULL: v' = m).  TO_ROWS: the gather; else its adjoint, which also zeroes the pad positions [M, Mp) of the planes.
+// One workgroup per (window, FLAT_V internal positions): a [32 filters][FLAT_V] tile goes through LDS, read along the vertex
+// axis and written as runs of consecutive filters per vertex.  Pure copies: no arithmetic, nothing to order.
+constexpr int FLAT_V = 64;
+template <bool TO_ROWS>
+__global__ void __launch_bounds__(256)
+planes_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ order, int M, int Mp, int F,
+                   long long ldr) {
+    __shared__ float tile[32][FLAT_V + 1];
+    const int b = blockIdx.y, v0 = blockIdx.x * FLAT_V;
+    const int nv = max(0, min(FLAT_V, M - v0));           // real vertices of this tile
+    const int nall = min(FLAT_V, Mp - v0);                // positions of this tile, pad included
+    for (int f0 = 0; f0 < F; f0 += 32) {
+        const int nf = min(32, F - f0);
+        if (TO_ROWS) {
+            for (int e = threadIdx.x; e < 32 * FLAT_V; e += 256) {
+                const int f = e / FLAT_V, vl = e % FLAT_V;
+                if (f < nf && vl < nv) tile[f][vl] = src[((size_t)b * F + f0 + f) * Mp + v0 + vl];
+            }
+            __syncthreads();
+            for (int e = threadIdx.x; e < nf * nv; e += 256) {
+                const int vl = e / nf, f = e % nf;
+                const int m = order ? order[v0 + vl] : v0 + vl;
+                dst[(size_t)b * ldr + (size_t)m * F + f0 + f] = tile[f][vl];
+            }
+        } else {
+            for (int e = threadIdx.x; e < nf * nv; e += 256) {
+                const int vl = e / nf, f = e % nf;
+                const int m = order ? order[v0 + vl] : v0 + vl;
+                tile[f][vl] = src[(size_t)b * ldr + (size_t)m * F + f0 + f];
+            }
+            __syncthreads();
+            for (int e = threadIdx.x; e < 32 * FLAT_V; e += 256) {
+                const int f = e / FLAT_V, vl = e % FLAT_V;
+                if (f < nf && vl < nall) dst[((size_t)b * F + f0 + f) * Mp + v0 + vl] = vl < nv ? tile[f][vl] : 0.f;
+            }
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace chebgcn
 
 namespace chebgcn {
@@ -364,6 +407,31 @@ extern "C" int chebgcn_fc_bwd(const float* x, int64_t ldx, const float* W, const
     }
     CG_HIP(hipGetLastError());
     return CHEBGCN_OK;
+}
+
+static int planes_rows(bool to_rows, const float* src, float* dst, const int32_t* order, int B, int M, int F, int64_t ldr,
+                       hipStream_t stream) {
+    CG_REQUIRE(src && dst && B > 0 && B <= 65535 && M > 0 && F > 0 && ldr >= (int64_t)M * F,
+               to_rows ? "planes_to_rows: bad argument" : "rows_to_planes: bad argument");
+    const int Mp = plane_stride(M);
+    dim3 grid(((to_rows ? M : Mp) + FLAT_V - 1) / FLAT_V, B);
+    note_dispatch(to_rows ? "planes_rows_kernel<to_rows>" : "planes_rows_kernel<to_planes>");
+    if (to_rows)
+        hipLaunchKernelGGL(planes_rows_kernel<true>, grid, dim3(256), 0, stream, src, dst, order, M, Mp, F, (long long)ldr);
+    else
+        hipLaunchKernelGGL(planes_rows_kernel<false>, grid, dim3(256), 0, stream, src, dst, order, M, Mp, F, (long long)ldr);
+    CG_HIP(hipGetLastError());
+    return CHEBGCN_OK;
+}
+
+extern "C" int chebgcn_planes_to_rows(const float* planes, float* rows, const int32_t* order, int B, int M, int F, int64_t ldr,
+                                      chebgcn_stream stream) {
+    return planes_rows(true, planes, rows, order, B, M, F, ldr, (hipStream_t)stream);
+}
+
+extern "C" int chebgcn_rows_to_planes(const float* rows, float* planes, const int32_t* order, int B, int M, int F, int64_t ldr,
+                                      chebgcn_stream stream) {
+    return planes_rows(false, rows, planes, order, B, M, F, ldr, (hipStream_t)stream);
 }
 
 extern "C" int chebgcn_softmax_xent(const float* logits, const void* labels, int labels_int64, float* loss, float* dlogits,

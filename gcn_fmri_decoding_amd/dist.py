@@ -25,6 +25,10 @@ import torch.distributed as dist
 
 class DataParallel:
     def __init__(self, model, process_group=None, conv_groups=2):
+        from .models_gcn import finetuning_cgcnn
+        if isinstance(model, finetuning_cgcnn):
+            raise NotImplementedError('DataParallel: finetuning_cgcnn trains on one GPU only (its trainable variables, its '
+                                      'optimizer and its frozen trunk have no data-parallel path)')
         if not dist.is_initialized():
             raise RuntimeError('torch.distributed is not initialised')
         self.model = model

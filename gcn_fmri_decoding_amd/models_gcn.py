@@ -365,10 +365,7 @@ class base_model(object):
         x = torch.empty((self.batch_size,) + tuple(M_0), device='meta')
         self._inference(x, 1.0)
         specs, self._specs = self._specs, None
-        order = {'head': 0, 'convw': 1, 'convb': 2}
-        # stable: keeps creation order inside a group; unregularised conv weights (spline filters, models_gcn.py:552) go
-        # behind the regularised ones so that those stay a prefix of the flat buffer
-        specs.sort(key=lambda s: (order[s.group], not s.regularized))
+        specs.sort(key=self._layout_key)
         self._spec_list = specs
         sizes = [int(np.prod(s.shape)) for s in specs]
         offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
@@ -395,6 +392,11 @@ class base_model(object):
         self.training_mode = False
         self._init_variables()
 
+    def _layout_key(self, spec):
+        # stable: keeps creation order inside a group; unregularised conv weights (spline filters, models_gcn.py:552) go
+        # behind the regularised ones so that those stay a prefix of the flat buffer
+        return ({'head': 0, 'convw': 1, 'convb': 2}[spec.group], not spec.regularized)
+
     def _reset_counters(self):
         self.global_step = 0
         if getattr(self, '_loss_ema', None) is not None and getattr(self, '_sg', None) is not None:
@@ -409,22 +411,25 @@ class base_model(object):
             return
         with torch.no_grad():
             for s in self._spec_list:
-                p = self._params[s.name]
-                if s.kind == 'const':
-                    if len(s.shape) == 2 and s.group == 'convb':       # [F, Mp]: keep the pad at zero
-                        p.zero_()
-                        p[:, :s.ref_shape[1]] = 0.2
-                    else:
-                        p.fill_(0.2)
-                elif s.kind == 'normal':
-                    torch.nn.init.trunc_normal_(p, 0.0, 0.2, -0.4, 0.4)
-                else:   # 'he': variance_scaling_initializer(factor=2, FAN_IN, truncated normal)
-                    std = math.sqrt(1.3 * 2.0 / s.fan_in)
-                    torch.nn.init.trunc_normal_(p, 0.0, std, -2 * std, 2 * std)
+                self._draw_variable(s)
             self._adam_m.zero_()
             self._adam_v.zero_()
             self._grad.zero_()
         self._reset_counters()
+
+    def _draw_variable(self, s):
+        p = self._params[s.name]
+        if s.kind == 'const':
+            if len(s.shape) == 2 and s.group == 'convb':       # [F, Mp]: keep the pad at zero
+                p.zero_()
+                p[:, :s.ref_shape[1]] = 0.2
+            else:
+                p.fill_(0.2)
+        elif s.kind == 'normal':
+            torch.nn.init.trunc_normal_(p, 0.0, 0.2, -0.4, 0.4)
+        else:   # 'he': variance_scaling_initializer(factor=2, FAN_IN, truncated normal)
+            std = math.sqrt(1.3 * 2.0 / s.fan_in)
+            torch.nn.init.trunc_normal_(p, 0.0, std, -2 * std, 2 * std)
 
     def _spec(self, name):
         return next(s for s in self._spec_list if s.name == name)
@@ -535,12 +540,7 @@ class base_model(object):
         if not self._fusable():
             self._grad.zero_()          # autograd accumulates into .grad there; the fused path writes every gradient
         else:
-            # the fused path WRITES each gradient; a variable that takes no gradient (requires_grad off) would keep
-            # the slice of an earlier step -- already all-reduced under data parallelism -- and Adam would apply it again
-            for name, p in self._params.items():
-                if not p.requires_grad:
-                    a, b = self._slices[name]
-                    self._grad[a:b].zero_()
+            self._zero_untrained_grads()
         if self._dp is not None:
             self._dp.begin_step()
         logits = self._inference_storage(x_storage, self.dropout)
@@ -572,6 +572,14 @@ class base_model(object):
                 loss_average = self._loss_ema * ema_correction
         self.training_mode = False
         return loss_average
+
+    def _zero_untrained_grads(self):
+        # the fused path WRITES each gradient; a variable that takes no gradient (requires_grad off) would keep
+        # the slice of an earlier step -- already all-reduced under data parallelism -- and Adam would apply it again
+        for name, p in self._params.items():
+            if not p.requires_grad:
+                a, b = self._slices[name]
+                self._grad[a:b].zero_()
 
     # ---------------------------------------------------------------- captured step (HIP graph)
 
@@ -1342,6 +1350,344 @@ class _LinearInto(torch.autograd.Function):
         return dx, None, None, None, None, None, None
 
 
+def _saver_checkpoint(ckp_path):
+    """The weights file a pretrained model's checkpoint directory names: line 1 of its Saver-format ``checkpoint`` file, line 2
+    where the file line 1 names is missing (:761-764)."""
+    lines = [line.rstrip('\n') for line in open(os.path.join(ckp_path, 'checkpoint'))]
+    name = lines[0].replace('"', '').split(' ')[-1].split('/')[-1]
+    if not os.path.isfile(ckp_path + name + '.pt') and len(lines) > 1:
+        name = lines[1].replace('"', '').split(' ')[-1].split('/')[-1]
+    return ckp_path + name + '.pt'
+
+
+def _level_sizes(sizes, p):
+    """Vertices of the graph level each conv layer filters on, from the vertex counts of all levels (the level advances by
+    log2(p), :462-469)."""
+    j, out = 0, []
+    for pp in p:
+        if j >= len(sizes):
+            raise ValueError('finetuning_cgcnn: %d Laplacians are too few for p = %s' % (len(sizes), list(p)))
+        out.append(int(sizes[j]))
+        j += int(np.log2(pp)) if pp > 1 else 0
+    return out
+
+
+class finetuning_cgcnn(cgcnn):
+    """Transfer learning on a pretrained ``cgcnn`` (:685-933): the graph-convolution trunk of a checkpoint of this package and a
+    new FC head on it, trained alone or together with the top conv layers.
+
+    * The trunk is read when the model is constructed, from ``checkpoint_dir + dir_name + '/model/'`` (plain string
+      concatenation, :756): the ``best.ckpt-<step>.pt`` that line 1 of the Saver-format ``checkpoint`` file names, or line 2
+      where that file is missing.  It is rebuilt from the file's architecture record (filter, brelu, pool, Laplacians, F, K, p,
+      channel, contraction).  ``L`` / ``F`` / ``K`` / ``p`` / ``channel`` must describe the same trunk (``ValueError``
+      otherwise; the reference trusts its meta-graph); ``filter`` / ``brelu`` / ``pool`` are the trunk's.  Trunks with
+      ``filter='chebyshev5'``, ``b1relu`` / ``b2relu`` and ``mpool1`` / ``apool1`` run; others raise ``NotImplementedError``.
+    * The head reads the bias-ReLU output of the LAST conv layer before its pooling (``conv6/bias_relu/Relu:0``, :793),
+      flattened as ``tf.reshape(conv, [N, M*F])``: element ``m*F + f`` is vertex m (the caller's order), filter f.
+      ``newfc{j}`` = ``fc(x, M[j])`` with ReLU, ``newlogits`` = ``fc(x, M[-1], relu=False)``; weights and biases are
+      L2-regularised.  The head never drops out: the reference builds it with ``dropout`` = 1 (``build_graph(flag_input=
+      False)`` sets it before ``inference`` runs, :204-210), whatever ``dropout`` says.
+    * ``flag_tuning=False`` (default): only the ``new*`` variables train.  ``flag_tuning=True`` also trains the conv layers
+      ``train_layers`` names -- by default the reference's ``conv4``, ``conv5``, ``conv6`` (:786) that exist.  Nothing below
+      the lowest trained layer takes a gradient; frozen variables are never written and have no optimizer moments.
+    * Loss: cross-entropy + ``regularization`` * sum of ``l2_loss`` over the ``new*`` variables only.  Optimizer (:895-933):
+      Nadam (``tf.contrib.opt.NadamOptimizer(0.001)``) when ``momentum != 0``, else gradient descent at the decayed rate; the
+      reported rate is ``cgcnn``'s.
+    * ``initial=None`` draws ``'normal'`` (the reference raises there).  ``fit()`` restarts from the state the constructor
+      produced -- a new head, the trained conv layers back at the checkpoint's values -- where the reference's ``op_init``
+      would redraw the restored trunk.  Its checkpoints go to this model's own ``dir_name``.
+    * Checkpoints hold every variable under its reference name and a complete architecture record: ``model_perf.predict``
+      rebuilds the model from its own directory, without the pretrained one.  No data parallelism."""
+
+    TUNED_LAYERS = ('conv4', 'conv5', 'conv6')          # the reference's train_layers (:786)
+    _SUPPORTED = {'filter': ('chebyshev5',), 'brelu': ('b1relu', 'b2relu'), 'pool': ('mpool1', 'apool1')}
+    _KEYWORDS = ('initial', 'num_epochs', 'learning_rate', 'decay_rate', 'decay_steps', 'momentum', 'regularization', 'dropout',
+                 'batch_size', 'eval_frequency', 'dir_name')
+
+    def __init__(self, config, checkpoint_dir, L, F, K, p, M, filter='chebyshev5', brelu='b1relu', pool='mpool1', initial=None,
+                 channel=1, num_epochs=20, learning_rate=0.1, decay_rate=0.95, decay_steps=None, momentum=0.9, regularization=0,
+                 dropout=0, batch_size=100, eval_frequency=200, dir_name='', flag_tuning=False, train_layers=None, verbose=True):
+        path = _saver_checkpoint(checkpoint_dir + dir_name + '/model/')
+        sd = torch.load(path, weights_only=True)
+        trunk = sd.get('architecture')
+        if not isinstance(trunk, dict) or trunk.get('class', 'cgcnn') != 'cgcnn':
+            raise ValueError('finetuning_cgcnn: %s is not a cgcnn checkpoint with an architecture record' % path)
+        want = {'F': list(trunk['F']), 'K': list(trunk['K']), 'p': list(trunk['p']), 'channel': trunk['channel']}
+        got = {'F': list(F), 'K': list(K), 'p': list(p), 'channel': channel}
+        for key in ('F', 'K', 'p', 'channel'):
+            if got[key] != want[key]:
+                raise ValueError('finetuning_cgcnn: %s = %s does not match the pretrained trunk in %s (%s = %s)'
+                                 % (key, got[key], path, key, want[key]))
+        mine = _level_sizes([Li.shape[0] for Li in L], got['p'])
+        theirs = _level_sizes([l['shape'][0] for l in trunk['L']], want['p'])
+        if mine != theirs:
+            raise ValueError('finetuning_cgcnn: the conv layers\' levels of L have %s vertices, those of the pretrained trunk in '
+                             '%s %s' % (mine, path, theirs))
+        self.checkpoint_dir = checkpoint_dir
+        self._setup(config, trunk, M, flag_tuning, train_layers, verbose, initial=initial, num_epochs=num_epochs,
+                    learning_rate=learning_rate, decay_rate=decay_rate, decay_steps=decay_steps, momentum=momentum,
+                    regularization=regularization, dropout=dropout, batch_size=batch_size, eval_frequency=eval_frequency,
+                    dir_name=dir_name)
+        self._load_trunk(sd, path)
+
+    def _setup(self, config, trunk, M, flag_tuning, train_layers, verbose, **kw):
+        """Builds the model on the trunk record ``trunk`` (a cgcnn architecture record, Laplacians included)."""
+        import scipy.sparse as sp
+        for key, ok in self._SUPPORTED.items():
+            if trunk[key] not in ok:
+                raise NotImplementedError("finetuning_cgcnn: the pretrained trunk has %s='%s'; fine-tuning runs on %s trunks "
+                                          "only" % (key, trunk[key], ' / '.join(ok)))
+        nl = len(trunk['p'])
+        layers = ['conv%d' % (i + 1) for i in range(nl)]
+        if train_layers is None:
+            train_layers = [n for n in self.TUNED_LAYERS if n in layers] if flag_tuning else []
+        elif not flag_tuning and list(train_layers):
+            raise ValueError('finetuning_cgcnn: train_layers = %s needs flag_tuning=True (without it the trunk is frozen)'
+                             % list(train_layers))
+        unknown = [n for n in train_layers if n not in layers]
+        if unknown:
+            raise ValueError('finetuning_cgcnn: train_layers %s are not conv layers of the trunk (%s)' % (unknown, layers))
+        self.fine_tuning = bool(flag_tuning)
+        self.train_layers = [n for n in layers if n in train_layers]
+        self._lowest = min([layers.index(n) for n in self.train_layers] or [nl])
+        self._trunk_arch = trunk
+        self._trunk_init = None
+        if kw.get('initial') is None:
+            kw['initial'] = 'normal'
+        Ls = [sp.csr_matrix((np.asarray(l['data']), np.asarray(l['indices']), np.asarray(l['indptr'])), shape=tuple(l['shape']))
+              for l in trunk['L']]
+        cgcnn.__init__(self, config, Ls, list(trunk['F']), list(trunk['K']), list(trunk['p']), list(M), filter=trunk['filter'],
+                       brelu=trunk['brelu'], pool=trunk['pool'], channel=trunk['channel'], verbose=verbose, **kw)
+        self.contraction = trunk.get('contraction', 'f32')
+        # the head's input: the top conv layer's output before its pooling, in that level's internal vertex order
+        self._M_top = int(self.L[-1].shape[0])
+        order = self._orders[-1] if self._orders else None
+        self._head_order = (torch.as_tensor(np.asarray(order, np.int32)).to(self.device)
+                            if order is not None and self.device.type == 'cuda' else None)
+
+    def _load_trunk(self, sd, path):
+        """The trunk's variables from the pretrained checkpoint, bit for bit; a device copy of the trained ones for fit()."""
+        trunk = [s for s in self._spec_list if s.group != 'head']
+        missing = [s.name for s in trunk if s.name not in sd]
+        if missing:
+            raise KeyError('finetuning_cgcnn: %s lacks the trunk variables %s' % (path, missing))
+        with torch.no_grad():
+            for s in trunk:
+                src = torch.as_tensor(np.asarray(sd[s.name], np.float32))
+                if tuple(src.shape) != tuple(s.ref_shape):
+                    raise ValueError('finetuning_cgcnn: %s in %s has shape %s, the trunk wants %s'
+                                     % (s.name, path, tuple(src.shape), tuple(s.ref_shape)))
+                if self.device.type != 'meta':
+                    self._ref_assign(self._params[s.name], s, src)
+        self._keep_trunk()
+
+    def _keep_trunk(self):
+        if self.device.type != 'meta':
+            self._trunk_init = self._flat[self._n_head:self._n_train].clone()
+
+    # ---------------------------------------------------------------- variables and layout
+
+    def _describe(self, M_0, F, K, p, M, brelu):
+        print('NN architecture (fine-tuning)')
+        print('  input: M_0 = {}'.format(M_0))
+        for i in range(len(p)):
+            print('  layer {0}: cgconv{0} ({1}): M = {2}, F = {3}, K = {4}, p = {5}'.format(
+                i + 1, 'trained' if 'conv%d' % (i + 1) in self.train_layers else 'fixed', self.L[i].shape[0], F[i], K[i], p[i]))
+        n_in = self.L[-1].shape[0] * F[-1]
+        for i, Mi in enumerate(M):
+            name = 'newlogits' if i == len(M) - 1 else 'newfc{}'.format(i + 1)
+            print('  layer {}: {}: weights {} * {}, biases {}'.format(len(p) + i + 1, name, n_in if i == 0 else M[i - 1], Mi, Mi))
+
+    def _weight_variable(self, shape, regularization=True):
+        # only the variables this model creates are regularised (:340-355): the trunk's conv weights are not
+        if self._scope and self._scope[0].startswith('conv'):
+            regularization = False
+        return super()._weight_variable(shape, regularization)
+
+    def _layout_key(self, spec):
+        # the head (regularised) first, then the trained conv layers, then the frozen ones: the trainable variables are one
+        # prefix of the flat buffer, the optimizer one launch over it
+        if spec.group == 'head':
+            return (0, 0)
+        return (1 if spec.name.split('/')[0] in self.train_layers else 2, 0 if spec.group == 'convw' else 1)
+
+    def build_graph(self, M_0, flag_input=True):
+        super().build_graph(M_0, flag_input)
+        self._trainable = [s.name for s in self._spec_list if s.group == 'head' or s.name.split('/')[0] in self.train_layers]
+        self._n_train = max(self._slices[n][1] for n in self._trainable)
+        if sum(self._slices[n][1] - self._slices[n][0] for n in self._trainable) != self._n_train:
+            raise AssertionError('flat layout assumes the trainable variables come first')
+        self._adam_m = torch.zeros(self._n_train, dtype=torch.float32, device=self.device)      # no moments for frozen ones
+        self._adam_v = torch.zeros(self._n_train, dtype=torch.float32, device=self.device)
+        for name, prm in self._params.items():
+            prm.requires_grad_(name in self._trainable)
+
+    def _init_variables(self):
+        """fit()'s restart: a new head, the trained conv layers back at the checkpoint's values, zero moments and step."""
+        if getattr(self, '_trunk_init', None) is None:
+            return super()._init_variables()          # (while the model is built: the trunk is loaded behind it)
+        self._reset_counters()
+        with torch.no_grad():
+            for s in self._spec_list:
+                if s.group == 'head':
+                    self._draw_variable(s)
+            self._flat[self._n_head:self._n_train].copy_(self._trunk_init)
+            self._adam_m.zero_()
+            self._adam_v.zero_()
+            self._grad[:self._n_train].zero_()
+        self._reset_counters()
+
+    def _zero_untrained_grads(self):
+        pass            # frozen variables' gradient slots are never written and never read
+
+    def state_dict(self):
+        """Every variable under its reference name and shape, the optimizer moments of the trained ones, the step counter and
+        the architecture record."""
+        sd = {'global_step': int(self.global_step), 'names': self.variables(), 'architecture': self._architecture()}
+        for name in self.variables():
+            sd[name] = self._ref_view(self._flat, name).detach().cpu().contiguous()
+        for name in self._trainable:
+            sd['adam_m/' + name] = self._ref_view(self._adam_m, name).cpu().contiguous()
+            sd['adam_v/' + name] = self._ref_view(self._adam_v, name).cpu().contiguous()
+        return sd
+
+    def load_state_dict(self, sd):
+        missing = [n for n in self.variables() if n not in sd]
+        if missing:
+            raise KeyError('checkpoint lacks variables %s' % missing)
+        with torch.no_grad():
+            for name in self.variables():
+                for prefix, flat in (('', self._flat), ('adam_m/', self._adam_m), ('adam_v/', self._adam_v)):
+                    if prefix + name not in sd or (prefix and name not in self._trainable):
+                        continue
+                    spec = self._spec(name)
+                    src = torch.as_tensor(np.asarray(sd[prefix + name], np.float32))
+                    if tuple(src.shape) != tuple(spec.ref_shape):
+                        raise ValueError('checkpoint variable %s%s has shape %s, the model wants %s'
+                                         % (prefix, name, tuple(src.shape), tuple(spec.ref_shape)))
+                    a, b = self._slices[name]
+                    self._ref_assign(flat[a:b].view(spec.shape), spec, src)
+        self.global_step = int(sd.get('global_step', 0))
+
+    def _architecture(self):
+        arch = {k: self._ctor[k] for k in self._KEYWORDS}
+        arch.update({'class': 'finetuning_cgcnn', 'trunk': self._trunk_arch, 'M': [int(m) for m in self.M],
+                     'flag_tuning': self.fine_tuning, 'train_layers': list(self.train_layers), 'contraction': self.contraction,
+                     'checkpoint_dir': getattr(self, 'checkpoint_dir', None)})
+        return arch
+
+    @classmethod
+    def from_checkpoint(cls, sd, config=None, **overrides):
+        """Rebuild a fine-tuned model from its own checkpoint (``state_dict()``); the pretrained one is not read.  ``fit()`` of
+        the result restarts its trained conv layers from this checkpoint's values."""
+        arch = dict(sd['architecture'])
+        if arch.pop('class', None) != 'finetuning_cgcnn':
+            raise ValueError('not a finetuning_cgcnn checkpoint')
+        trunk, M = arch.pop('trunk'), arch.pop('M')
+        flag_tuning, train_layers = arch.pop('flag_tuning'), arch.pop('train_layers')
+        contraction = arch.pop('contraction', 'f32')
+        checkpoint_dir = arch.pop('checkpoint_dir', None)
+        arch.update(overrides)
+        model = cls.__new__(cls)
+        model.checkpoint_dir = checkpoint_dir
+        model._setup(config, trunk, M, flag_tuning, train_layers, False, **arch)
+        model.contraction = contraction
+        model.load_state_dict(sd)
+        model._keep_trunk()
+        return model
+
+    # ---------------------------------------------------------------- network
+
+    def _inference(self, x, dropout):
+        if not x.is_meta:
+            return self._inference_storage(ops.plane_storage(x), dropout)
+        nl = len(self.p)
+        for i in range(nl):                             # build pass: the trunk's variables, then the head's
+            with self.variable_scope('conv{}'.format(i + 1)):
+                x = self.filter(x, self.L[i], self.F[i], self.K[i])
+                x = self.brelu(x)
+                if i + 1 < nl:
+                    x = self.pool(x, self.p[i])
+        N, M, F = x.shape
+        return self._head(torch.empty((N, M * F), device='meta'), dropout)
+
+    def _inference_storage(self, x, dropout):
+        """The trunk on the fused path -- the layers below the lowest trained one without autograd, the top layer without its
+        pooling -- then the head."""
+        x = self._to_internal(x)
+        nl = len(self.p)
+        B = x.shape[0]
+        per_vertex = getattr(self.brelu, '__func__', None) is cgcnn.b2relu
+        pool_kind = POOL_AVG if getattr(self.pool, '__func__', None) is cgcnn.apool1 else POOL_MAX
+        training = self.training_mode and torch.is_grad_enabled()
+        lo = self._lowest if training else nl
+        Wts = {}
+        if training:
+            fins = [x.shape[1]] + list(self.F[:-1])
+            idxs = [i for i in range(lo + 1, nl)
+                    if ops.dx_by_forward_shape(self.graphs[i], fins[i], self.K[i], self.F[i], self.contraction)]
+            if idxs:
+                outs = ops.reindex_weights_batch([self._params['conv%d/weights' % (i + 1)] for i in idxs],
+                                                 [(fins[i], self.K[i], self.F[i]) for i in idxs])
+                Wts = dict(zip(idxs, outs))
+        links = {i: ops.GateLink() for i in range(lo, nl - 1)}
+        stack = None
+        for i in range(nl):
+            g = self.graphs[i]
+            W = self._params['conv%d/weights' % (i + 1)]
+            b = self._params['conv%d/bias' % (i + 1)]
+            top = i + 1 == nl
+            out = next_stack = None
+            if not top and g.M // self.p[i] == self.graphs[i + 1].M:
+                next_stack = torch.empty((self.K[i + 1], B, self.F[i], self.graphs[i + 1].Mp), dtype=torch.float32,
+                                         device=x.device)
+                out = next_stack[0]
+            trained = i >= lo and W.requires_grad
+            with (contextlib.nullcontext() if i >= lo else torch.no_grad()):
+                x = ops.cheb_conv(x, W, b, g, self.K[i], 1 if top else self.p[i], pool_kind, True,
+                                  BIAS_VERTEX if per_vertex else BIAS_FILTER, stack=stack, out=out,
+                                  dW=W.grad if trained else None, dbias=b.grad if trained else None,
+                                  precision=self.contraction, pool_maps=None if top else self._pool_maps[i], Wt=Wts.get(i),
+                                  link_in=links.get(i - 1), link_out=links.get(i))
+            stack = next_stack
+        return self._head(x, dropout)
+
+    def _head(self, x, dropout):
+        """Planes of the top conv layer -> newfc1 (flatten + FC, ops.FlatFC) -> newfc2 ... -> newlogits, no dropout."""
+        for i, Mi in enumerate(self.M):
+            last = i + 1 == len(self.M)
+            with self.variable_scope('newlogits' if last else 'newfc{}'.format(i + 1)):
+                x = self._flat_fc(x, Mi, not last) if i == 0 else self.fc(x, Mi, relu=not last)
+        return x
+
+    def _flat_fc(self, x, Mout, relu):
+        if x.is_meta:
+            return self.fc(x, Mout, relu)
+        W = self._weight_variable([self._M_top * self.F[-1], Mout], regularization=True)
+        b = self._bias_variable([Mout], regularization=True)
+        direct = self.training_mode and torch.is_grad_enabled()
+        return ops.FlatFC.apply(x, W, b, self._head_order, self._M_top, relu, W.grad if direct else None,
+                                b.grad if direct else None)
+
+    def _apply_adam(self, grad_scale=1.0, lr_t=None, want_sq=False):
+        """The optimizer of :895-933 over the trainable prefix of the flat buffers: Nadam, or gradient descent at the decayed
+        rate when momentum == 0; returns the number of partial sums of squares (Nadam)."""
+        n, r = self._n_train, self._n_reg
+        if self.momentum == 0:
+            lr = self.training(None, self.learning_rate, self.decay_steps, self.decay_rate, self.momentum)
+            with torch.no_grad():
+                g = self._grad[:n] * grad_scale
+                g[:r] += self.regularization * self._flat[:r]
+                self._flat[:n] -= lr * g
+            return 0
+        if lr_t is None:
+            lr_t = self._adam_lr_t(self.global_step + 1)
+        if getattr(self, '_sq_part', None) is None:
+            self._sq_part = torch.zeros(4096, dtype=torch.float32, device=self.device)
+        return ops.nadam_step_sq_all(self._flat[:n], self._grad[:n], self._adam_m, self._adam_v, r, lr_t, self._sq_part,
+                                     0.9, 0.999, 1e-8, grad_scale, self.regularization)
+
+
 def get_best_checkpoint(best_checkpoint_dir, select_maximum_value=True):
     """Path of the best checkpoint according to the ``best_checkpoints`` index
     (checkmat.get_best_checkpoint, checkmat.py:121-138); the weights are in ``<path>.pt``."""
@@ -1391,7 +1737,9 @@ class model_perf(object):
         print(ckp_path + model_name + '.pt')
         sd = torch.load(ckp_path + model_name + '.pt', weights_only=True)
         if model is None:
-            model = cgcnn.from_checkpoint(sd, config=config, batch_size=batch_size)
+            arch = sd.get('architecture') or {}
+            cls = finetuning_cgcnn if arch.get('class') == 'finetuning_cgcnn' else cgcnn
+            model = cls.from_checkpoint(sd, config=config, batch_size=batch_size)
         else:
             model.load_state_dict(sd)
         test_labels = np.asarray(test_labels)

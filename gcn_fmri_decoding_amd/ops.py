@@ -1154,6 +1154,110 @@ def adam_step_sq_all(p, g, m, v, n_reg, lr_t, sq_partials, beta1=0.9, beta2=0.99
     return nparts
 
 
+def nadam_step_sq_all(p, g, m, v, n_reg, lr_t, sq_partials, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
+    """Nadam -- tf.contrib.opt.NadamOptimizer, TF's ApplyAdam with use_nesterov (finetuning_cgcnn, models_gcn.py:895-933) --
+    over ``p`` in one launch (chebgcn_nadam_step_sq_all): the first ``n_reg`` elements take the L2 term and leave the partial
+    sums of squares of their PRE-update values in ``sq_partials``, the rest plain Nadam.  ``lr_t``: a Python float, or a
+    one-element float32 device tensor read when the kernel runs (captured step).  Returns the number of partials."""
+    _require_cuda(p, g, m, v, sq_partials)
+    n = p.numel()
+    if not (g.numel() == m.numel() == v.numel() == n) or n == 0 or not (0 <= n_reg <= n):
+        raise ValueError('nadam_step_sq_all: size mismatch')
+    lib = _lib.lib()
+    nparts = lib.chebgcn_adam_partials(n)
+    if sq_partials.dtype != torch.float32 or sq_partials.numel() < nparts:
+        raise ValueError('nadam_step_sq_all: sq_partials needs %d float32' % nparts)
+    dev_lr = isinstance(lr_t, torch.Tensor)
+    if dev_lr and (lr_t.dtype != torch.float32 or lr_t.numel() != 1 or not lr_t.is_cuda):
+        raise ValueError('nadam_step_sq_all: a device lr_t must be one float32')
+    n_bytes = 28.0 * n          # reads p, g, m, v; writes p, m, v
+    _lib.check(_launch('nadam', n_bytes, 0.0, lambda: lib.chebgcn_nadam_step_sq_all(
+        _p(p), _p(g), _p(m), _p(v), n, int(n_reg), 0.0 if dev_lr else float(lr_t), _p(lr_t) if dev_lr else None, float(beta1),
+        float(beta2), float(eps), float(grad_scale), float(l2), _p(sq_partials), _stream())), 'nadam_step_sq_all')
+    return nparts
+
+
+def planes_to_rows(planes, M, order=None, ld=None):
+    """``tf.reshape(conv, [N, M*F])`` (models_gcn.py:805-806) of plane storage ``[B, F, Mp]``: ``[B, ld]`` rows (``ld``
+    defaults to M*F rounded up to 4; the columns past M*F are left unwritten), element ``m*F + f`` = vertex m (the caller's
+    order), filter f.  ``order``: int32 device tensor, internal position -> reference vertex, or None (planes in the caller's
+    order)."""
+    _require_cuda(planes)
+    B, F, Mp = planes.shape
+    if Mp != plane_stride(M) or not planes.is_contiguous():
+        raise ValueError('planes_to_rows: planes of %d vertices expected' % M)
+    ld = ld or ((M * F + 3) & ~3)
+    rows = torch.empty((B, ld), dtype=torch.float32, device=planes.device)
+    _lib.check(_launch('planes_to_rows', 8.0 * B * M * F, 0.0, lambda: _lib.lib().chebgcn_planes_to_rows(
+        _p(planes), _p(rows), _p(order), B, M, F, ld, _stream())), 'planes_to_rows')
+    return rows
+
+
+def rows_to_planes(rows, M, F, order=None):
+    """The adjoint of ``planes_to_rows``: ``[B, >= M*F]`` rows -> plane storage ``[B, F, Mp]``, zero in the pad."""
+    _require_cuda(rows)
+    B, ld = rows.shape
+    if ld < M * F or rows.stride(1) != 1 or rows.stride(0) != ld:
+        raise ValueError('rows_to_planes: rows of at least %d floats expected' % (M * F))
+    planes = torch.empty((B, F, plane_stride(M)), dtype=torch.float32, device=rows.device)
+    _lib.check(_launch('rows_to_planes', 8.0 * B * M * F, 0.0, lambda: _lib.lib().chebgcn_rows_to_planes(
+        _p(rows), _p(planes), _p(order), B, M, F, ld, _stream())), 'rows_to_planes')
+    return planes
+
+
+class FlatFC(torch.autograd.Function):
+    """The first head layer of ``finetuning_cgcnn``: ``act(reshape(x, [B, M*F]) @ W + b)`` on plane storage ``x`` [B, F, Mp]
+    of the top conv layer (models_gcn.py:805-806 and :744-750).  The flatten is chebgcn_planes_to_rows; the product runs on
+    the library's FC kernels at every inner size they serve (chebgcn_fc_fwd / chebgcn_fc_bwd called directly: the inner
+    size M*F is far beyond FC_BWD_MAX_INNER, which keeps cgcnn's own head where it is).  Backward WRITES dW / db into
+    ``gW`` / ``gb`` when they are given; the input gradient, where wanted, goes back to planes (chebgcn_rows_to_planes)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, order, M, relu, gW, gb):
+        _require_cuda(x, W, b)
+        B, F, Mp = x.shape
+        I, O = M * F, W.shape[1]
+        if tuple(W.shape) != (I, O) or tuple(b.shape) != (O,):
+            raise ValueError('FlatFC: weights [%d, O] and bias [O] expected' % I)
+        L = _lib.lib()
+        if not L.chebgcn_fc_fwd_supported(B, I, O):
+            raise ValueError('FlatFC: %d x %d x %d is outside the range of chebgcn_fc_fwd' % (B, I, O))
+        rows = planes_to_rows(x.contiguous(), M, order)
+        ld = rows.shape[1]
+        Wc, bc = W.detach().contiguous(), b.detach().contiguous()
+        y = torch.empty((B, O), dtype=torch.float32, device=x.device)
+        nws = L.chebgcn_fc_fwd_workspace(B, I, O)
+        ws = _workspace(nws, x.device, 'fc_fwd') if nws else None
+        _lib.check(_launch('fc_fwd', 4.0 * (B * I + I * O + B * O), 2.0 * B * I * O, lambda: L.chebgcn_fc_fwd(
+            _p(rows), ld, _p(Wc), _p(bc), _p(y), _p(ws), nws, B, I, O, 1 if relu else 0, _stream())), 'fc_fwd')
+        ctx.save_for_backward(rows, Wc, y if relu else None)
+        ctx.cfg, ctx.order, ctx.bufs = (B, M, F, I, O), order, (gW, gb)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, Wc, y = ctx.saved_tensors
+        B, M, F, I, O = ctx.cfg
+        gW, gb = ctx.bufs
+        g = g.contiguous()
+        need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dW = db = drows = None
+        if need_w:
+            dW = gW if gW is not None else torch.empty((I, O), dtype=torch.float32, device=g.device)
+            db = gb if gb is not None else torch.empty((O,), dtype=torch.float32, device=g.device)
+            _check_grad_buffer(dW, (I, O), 'dW')
+            _check_grad_buffer(db, (O,), 'db')
+        if ctx.needs_input_grad[0]:
+            drows = torch.empty(rows.shape, dtype=torch.float32, device=g.device)
+        ld = rows.shape[1]
+        if need_w or drows is not None:
+            _lib.check(_launch('fc_bwd', 4.0 * (B * I * (1 + (drows is not None)) + I * O * (1 + need_w) + B * O),
+                               2.0 * B * I * O * (need_w + (drows is not None)), lambda: _lib.lib().chebgcn_fc_bwd(
+                _p(rows), ld, _p(Wc), _p(g), _p(y), _p(dW), _p(db), _p(drows), ld, B, I, O, _stream())), 'fc_bwd')
+        dx = rows_to_planes(drows, M, F, ctx.order) if drows is not None else None
+        return (dx, None if gW is not None else dW, None if gb is not None else db, None, None, None, None, None)
+
+
 def adam_step_sq(p, g, m, v, lr_t, sq_partials, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
     """``adam_step`` that also leaves the per-workgroup partial sums of squares of the PRE-update ``p`` in ``sq_partials``
     (float32, at least ``adam_partials(n)`` elements): the L2 term of the loss without a pass of its own.  Returns the

@@ -369,6 +369,16 @@ int chebgcn_fc_fwd(const float* x, int64_t ldx, const float* W, const float* bia
 int chebgcn_fc_bwd(const float* x, int64_t ldx, const float* W, const float* g, const float* y, float* dW, float* db,
                    float* dx, int64_t lddx, int B, int I, int O, chebgcn_stream stream);
 
+/* The flatten of finetuning_cgcnn's head, tf.reshape(conv, [N, M*F]) (models_gcn.py:805-806), and its adjoint:
+ *   rows[b][m*F + f] = planes[b][f][v'],  order[v'] = m  (order: int32 [M], the level's internal vertex order -- internal
+ *   position -> reference vertex, a permutation; NULL: the identity).
+ * planes: [B][F][Mp(M)]; rows: [B] rows of stride ldr >= M*F floats (the columns [M*F, ldr) are not touched).
+ * chebgcn_rows_to_planes writes every position of the planes, zero in the pad. */
+int chebgcn_planes_to_rows(const float* planes, float* rows, const int32_t* order, int B, int M, int F, int64_t ldr,
+                           chebgcn_stream stream);
+int chebgcn_rows_to_planes(const float* rows, float* planes, const int32_t* order, int B, int M, int F, int64_t ldr,
+                           chebgcn_stream stream);
+
 /* The two scalars a captured training step reads from device memory -- Adam's step size lr_t of this step (models_gcn.py:296:
  * tf.train.AdamOptimizer's lr * sqrt(1 - b2^t) / (1 - b1^t)) and the read factor of the loss average (models_gcn.py:269-275) --,
  * written in one launch in front of the graph's replay: dst[0] = v0, dst[1] = v1. */
@@ -389,6 +399,14 @@ int chebgcn_adam_step_sq(float* p, const float* g, float* m, float* v, int64_t n
 int chebgcn_adam_step_sq_all(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_reg, float lr_t,
                              const float* lr_t_dev, float beta1, float beta2, float eps, float grad_scale, float l2,
                              float* sq_partials, chebgcn_stream stream);
+/* Nadam over one range of a model's variables in one launch: tf.contrib.opt.NadamOptimizer (finetuning_cgcnn, models_gcn.py:
+ * 895-933), i.e. TensorFlow's ApplyAdam with use_nesterov:  m += (1-b1)(g'-m);  v += (1-b2)(g'^2-v);
+ * p -= (g'(1-b1) + b1 m) lr_t / (sqrt(v)+eps).  Elements [0, n_reg) take the L2 term (g' = grad_scale g + l2 p) and leave the
+ * chebgcn_adam_partials(n) partial sums of squares of the PRE-update p in sq_partials (for chebgcn_loss_bookkeeping),
+ * elements [n_reg, n) plain Nadam; lr_t by value, or read from *lr_t_dev when that is not NULL.  Fixed-order sums. */
+int chebgcn_nadam_step_sq_all(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_reg, float lr_t,
+                              const float* lr_t_dev, float beta1, float beta2, float eps, float grad_scale, float l2,
+                              float* sq_partials, chebgcn_stream stream);
 int chebgcn_loss_bookkeeping(const float* cross_entropy, const float* sq_partials, int nparts, float half_reg, float* ema,
                              float decay, float corr, const float* corr_dev, float* loss_out, float* loss_average_out,
                              chebgcn_stream stream);
