@@ -104,6 +104,10 @@ SIGNATURES = {
     'chebgcn_spectral_mix_bwd_w': (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     'chebgcn_spectral_spline_expand': (_i, [_p, _p, _p, _i, _i, _i, _p]),
     'chebgcn_spectral_spline_expand_bwd': (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    'chebgcn_saliency_supported': (_i, [_i]),
+    'chebgcn_saliency_seed': (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _i, _p]),
+    'chebgcn_saliency_path': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    'chebgcn_saliency_reduce': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p]),
 }
 
 _lib = None

@@ -122,6 +122,8 @@ class base_model(object):
         # (shadow / (1 - 0.9^t): the first value is the loss).  Reporting only; the default follows TF >= 1.0, set
         # ``ema_zero_debias = True`` (or CHEBGCN_EMA_ZERO_DEBIAS=1) for the 0.12 reading.  Unverifiable here (no TensorFlow).
         self.ema_zero_debias = os.environ.get('CHEBGCN_EMA_ZERO_DEBIAS', '0') not in ('0', '', 'false', 'False')
+        # inside saliency(): the layers see their variables without gradient (no weight, bias-gradient or optimizer work)
+        self._saliency_pass = False
 
     # ---------------------------------------------------------------- run-time API
 
@@ -235,6 +237,162 @@ class base_model(object):
         # (the reference appends a 'time:' line only ``if sess is None``, which never holds there:
         # its local ``sess`` comes out of ``_get_session`` and is always a session, :88, :107-109)
         return string, accuracy, f1, loss
+
+    # ---------------------------------------------------------------- saliency maps
+
+    def saliency(self, data, target='predicted', score='logit', method='gradient', steps=32, baseline=None, batch_size=None,
+                 labels=None):
+        """Attribution of each window's class score to its inputs.  ``data``: ``[S, M, channel]`` as for ``predict`` (NumPy,
+        or a tensor from ``stage()``), in the caller's vertex order.  Returns ``(attr, target)``: float32 ``[S, M, channel]`` in
+        the order of ``data`` (fake vertices included) and the int64 class ``[S]`` each window was attributed to.
+
+        * ``target``: ``'predicted'`` (the window's own argmax, ``prediction()``'s tie rule), ``'label'`` (the int array
+          ``labels=`` ``[S]``), an int, or an int array ``[S]``; classes lie in ``[0, M[-1])``.
+        * ``score``: ``'logit'`` (z_c) or ``'logprob'`` (log softmax(z)_c).
+        * ``method``: ``'gradient'`` (ds/dx), ``'grad_x_input'`` (x * ds/dx), ``'integrated'`` ((x - x0) * the mean of ds/dx at
+          x0 + a_j (x - x0), a_j = (j + 1/2)/steps; ``baseline`` x0: None = zeros, or ``[M, channel]``; the class is decided at
+          x and held along the path).
+        * Dropout is off.  ``batch_size`` (default the model's): rows of one pass -- windows for the first two methods (the last
+          batch zero-padded like ``predict``), ``max(1, batch_size // steps)`` windows of ``steps`` rows each for
+          ``'integrated'``.
+
+        One pass per batch: the forward with the ReLU masks, then the training step's input-gradient kernels -- no weight or bias
+        gradient, no optimizer, nothing the model keeps is written."""
+        S, targets, _, base, bs = self._saliency_args(data, target, labels, score, method, steps, baseline, batch_size)
+        data_dev = self.stage(data)
+        M, C = data_dev.shape[1], data_dev.shape[2]
+        attr = torch.empty((S, M, C), dtype=torch.float32, device=self.device)
+        cls = torch.empty(S, dtype=torch.int64, device=self.device)
+        if targets is not None:
+            cls.copy_(torch.as_tensor(targets))
+        self._saliency_run(data_dev, cls if targets is not None else None, score, method, steps, base, bs, cls, attr)
+        return attr.cpu().numpy(), cls.cpu().numpy()
+
+    def saliency_maps(self, data, labels, absolute=False, score='logit', method='gradient', steps=32, baseline=None,
+                      batch_size=None):
+        """Per-class mean attribution: window w (target = its label) adds ``saliency``'s map -- ``|map|`` with ``absolute`` --
+        to the sum of class ``labels[w]``.  Returns ``(maps, counts)``: float64 ``[C, M, channel]`` (C = M[-1]; the mean, zero
+        for a class without windows) and int64 ``[C]``.  The sums run on the device in float64, windows in order within a
+        batch, batches in order; the per-window maps never leave the device."""
+        S, _, labels, base, bs = self._saliency_args(data, 'label', labels, score, method, steps, baseline, batch_size)
+        data_dev = self.stage(data)
+        M, C = data_dev.shape[1], data_dev.shape[2]
+        ncls = int(self.M[-1])
+        acc = torch.zeros((ncls, M, C), dtype=torch.float64, device=self.device)
+        labels_dev = torch.as_tensor(labels).to(self.device)
+        self._saliency_run(data_dev, labels_dev, score, method, steps, base, bs, None, None, absolute=absolute, acc=acc)
+        counts = np.bincount(labels, minlength=ncls).astype(np.int64)
+        maps = acc.cpu().numpy()
+        maps /= np.maximum(counts, 1)[:, None, None]         # in place, one pass (a class without windows stays 0)
+        return maps, counts
+
+    def _saliency_args(self, data, target, labels, score, method, steps, baseline, batch_size):
+        """Checks every argument of ``saliency`` / ``saliency_maps`` before any device work; returns (S, targets int64 [S] or
+        None for 'predicted', labels, baseline as a device tensor or None, batch size)."""
+        if score not in ops.SCORES:
+            raise ValueError('saliency: score must be one of %s, got %r' % (sorted(ops.SCORES), score))
+        if method not in ops.SALIENCY_METHODS:
+            raise ValueError('saliency: method must be one of %s, got %r' % (sorted(ops.SALIENCY_METHODS), method))
+        integrated = method == 'integrated'
+        if integrated and (isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= 65535):
+            raise ValueError('saliency: steps must be an int in [1, 65535], got %r' % (steps,))
+        bs = self.batch_size if batch_size is None else batch_size
+        if isinstance(bs, bool) or not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 65535:
+            raise ValueError('saliency: batch_size must be an int in [1, 65535], got %r' % (batch_size,))
+        shape = tuple(int(d) for d in data.shape)
+        want = (int(self._M0), int(self.channel))
+        if len(shape) != 3 or shape[1:] != want or shape[0] == 0:
+            raise ValueError('saliency: data must be [S, %d, %d] with S > 0, got %s' % (want + (shape,)))
+        from . import _lib
+        if not _lib.lib().chebgcn_saliency_supported(want[1]):
+            raise ValueError('saliency: %d channels are more than the saliency kernels serve (chebgcn_saliency_supported)'
+                             % want[1])
+        S, n_classes = shape[0], int(self.M[-1])
+
+        def classes(v, what):
+            a = np.asarray(v)
+            if a.shape != (S,) or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError('saliency: %s must be an int array of shape [%d], got %s %s' % (what, S, a.dtype, a.shape))
+            a = a.astype(np.int64)
+            if a.min() < 0 or a.max() >= n_classes:
+                raise ValueError('saliency: %s must lie in [0, %d); got %d ... %d' % (what, n_classes, a.min(), a.max()))
+            return a
+        if labels is not None:
+            labels = classes(labels, 'labels')
+        if isinstance(target, str):
+            if target == 'predicted':
+                targets = None
+            elif target == 'label':
+                if labels is None:
+                    raise ValueError("saliency: target='label' needs labels")
+                targets = labels
+            else:
+                raise ValueError("saliency: target must be 'predicted', 'label', an int or an int array, got %r" % target)
+        elif isinstance(target, (int, np.integer)) and not isinstance(target, bool):
+            if not 0 <= int(target) < n_classes:
+                raise ValueError('saliency: target %d is not a class in [0, %d)' % (int(target), n_classes))
+            targets = np.full(S, int(target), np.int64)
+        else:
+            targets = classes(target, 'target')
+        if baseline is not None:
+            baseline = np.asarray(baseline, np.float32)
+            if baseline.shape != want:
+                raise ValueError('saliency: baseline must be [%d, %d], got %s' % (want + (baseline.shape,)))
+        if self.device.type != 'cuda':
+            raise RuntimeError('saliency: the model has no device to run on (%s)' % self.device)
+        base = torch.as_tensor(baseline).to(self.device) if baseline is not None else None
+        return S, targets, labels, base, int(bs)
+
+    def _saliency_batch(self, data_dev, idx, R):
+        """The windows ``idx`` gathered into plane storage, zero-padded to ``R`` rows like ``predict``."""
+        x = self._gather(data_dev, idx).planes
+        if x.shape[0] < R:
+            pad = ops.plane_empty(R, x.shape[1], data_dev.shape[1], self.device, zero=True)
+            pad[:x.shape[0]] = x
+            x = pad
+        return x
+
+    def _saliency_run(self, data_dev, targets, score, method, steps, base, bs, cls, attr, absolute=False, acc=None):
+        """The passes of ``saliency`` / ``saliency_maps``: per batch, the forward with masks on inputs that need a gradient
+        and variables that do not, the seed, the input gradient (autograd over the library's layers), the reduction into
+        ``attr`` rows or the class sums ``acc`` (classes ``targets``)."""
+        S, M, C = data_dev.shape
+        integrated = method == 'integrated'
+        m = int(steps) if integrated else 1
+        wpp = max(1, bs // m) if integrated else bs
+        R = wpp * m
+        order = self._order_dev if self._order is not None else None
+        windows = torch.arange(S, dtype=torch.int32, device=self.device)
+        rows = torch.empty((wpp, M, C), dtype=torch.float32, device=self.device) if attr is None else None
+        was_training = self.training_mode
+        self.training_mode, self._saliency_pass = False, True
+        try:
+            if integrated and targets is None:
+                # the class is decided at x itself and held fixed along the path
+                with torch.no_grad():
+                    for begin in range(0, S, bs):
+                        end = min(begin + bs, S)
+                        logits = self._inference_storage(self.as_internal(self._saliency_batch(data_dev, windows[begin:end], bs)), 1)
+                        ops.saliency_seed(logits, None, 1, end - begin, score, cls_out=cls[begin:end], want_grad=False)
+                targets = cls
+            for begin in range(0, S, wpp):
+                end = min(begin + wpp, S)
+                nw, idx = end - begin, windows[begin:end]
+                if integrated:
+                    x = ops.saliency_path(data_dev, order, idx, base, R, m, M)
+                else:
+                    x = self._saliency_batch(data_dev, idx, R)
+                x.requires_grad_(True)
+                with torch.enable_grad():
+                    logits = self._inference_storage(self.as_internal(x), 1)
+                dz = ops.saliency_seed(logits, targets[begin:end] if targets is not None else None, m, nw * m, score,
+                                       cls_out=cls[begin:end] if targets is None else None)
+                dx, = torch.autograd.grad(logits, x, dz)
+                ops.saliency_reduce(dx, data_dev, order, idx, base, m, method, absolute,
+                                    attr[begin:end] if attr is not None else rows[:nw],
+                                    targets[begin:end] if acc is not None else None, acc)
+        finally:
+            self.training_mode, self._saliency_pass = was_training, False
 
     def fit(self, train_data, train_labels, val_data, val_labels, best_checkpoint_dir=None):
         """Mini-batch training loop (:112-184): ``int(num_epochs*S/batch)`` steps, samples
@@ -852,7 +1010,7 @@ class base_model(object):
         p = self._params[name]
         if tuple(p.shape) != tuple(shape):
             raise ValueError('variable %s has shape %s, requested %s' % (name, tuple(p.shape), tuple(shape)))
-        return p
+        return p.detach() if self._saliency_pass else p
 
     def _weight_variable(self, shape, regularization=True):
         """``tf.get_variable('weights', ...)`` in the current scope (:340-347)."""
@@ -1210,6 +1368,8 @@ class cgcnn(base_model):
         b = self._bias_variable([Mout], regularization=True)
         if x.is_meta:
             return torch.empty((N, Mout), device='meta')
+        if self._saliency_pass:
+            return ops.FCInputGrad.apply(x, W, b, relu)         # the input gradient alone, on the library's kernels
         if self.training_mode and torch.is_grad_enabled() and W.grad is not None and b.grad is not None:
             # training step: the layer writes its gradients straight into the flat gradient buffer (like the
             # conv layers do) -- no accumulate-into-.grad add per variable, no zeroing of the buffer
@@ -1276,6 +1436,8 @@ class cgcnn(base_model):
             g = self.graphs[i]
             W = self._params['conv%d/weights' % (i + 1)]
             b = self._params['conv%d/bias' % (i + 1)]
+            if self._saliency_pass:
+                W, b = W.detach(), b.detach()
             out = next_stack = None
             if i + 1 < nl and g.M // self.p[i] == self.graphs[i + 1].M:
                 next_stack = torch.empty((self.K[i + 1], B, self.F[i], self.graphs[i + 1].Mp), dtype=torch.float32,
@@ -1540,6 +1702,12 @@ class finetuning_cgcnn(cgcnn):
     def _zero_untrained_grads(self):
         pass            # frozen variables' gradient slots are never written and never read
 
+    def saliency(self, *args, **kwargs):
+        raise NotImplementedError('finetuning_cgcnn: saliency maps are not implemented for fine-tuned models (the frozen trunk '
+                                  'runs without autograd); they run on cgcnn')
+
+    saliency_maps = saliency
+
     def state_dict(self):
         """Every variable under its reference name and shape, the optimizer moments of the trained ones, the step counter and
         the architecture record."""
@@ -1722,15 +1890,10 @@ class model_perf(object):
         s.names.add(name)
         return s
 
-    def predict(s, ckp_path, test_data, test_labels, target_name=None, batch_size=128, trial_dura=17,
-                flag_starttr=False, sub_name=None, model=None, config=None):
-        """Restore a trained model from ``<ckp_path>/model/`` and score a dataset (:960-1088; call
-        site predict_states.py:102-108).  Like the reference it takes the checkpoint named on line 1
-        of the saver's ``checkpoint`` file (:968-969), pads the last batch with zeros, SUMS the batch
-        losses, and flattens the stacked logits before truncating them (:1022-1023).  The model is
-        rebuilt from the checkpoint's architecture record (the reference imports the TF meta-graph,
-        :979), or ``model`` is used.  Returns (pred_logits, pred_labels, pred_loss, test_acc)."""
-        import sklearn.metrics
+    @staticmethod
+    def _restore(ckp_path, batch_size, model=None, config=None):
+        """The model ``predict`` scores: the checkpoint named on line 2 of ``<ckp_path>/model/checkpoint``, rebuilt from its
+        architecture record, or loaded into ``model``."""
         ckp_path = str(ckp_path) + '/' + 'model/'
         lines = [line.rstrip('\n') for line in open(os.path.join(ckp_path, 'checkpoint'))]
         model_name = lines[1].replace('"', '').split(' ')[-1].split('/')[-1]
@@ -1742,6 +1905,25 @@ class model_perf(object):
             model = cls.from_checkpoint(sd, config=config, batch_size=batch_size)
         else:
             model.load_state_dict(sd)
+        return model
+
+    def saliency_maps(s, ckp_path, data, labels, target_name=None, batch_size=128, **kw):
+        """Per-class mean saliency maps (``base_model.saliency_maps``; ``kw``: its keywords) of the model ``predict`` would
+        restore from ``ckp_path``.  ``target_name`` is accepted for symmetry with ``predict`` and not used.  Returns
+        ``(maps, counts)``."""
+        model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
+        return model.saliency_maps(data, labels, **kw)
+
+    def predict(s, ckp_path, test_data, test_labels, target_name=None, batch_size=128, trial_dura=17,
+                flag_starttr=False, sub_name=None, model=None, config=None):
+        """Restore a trained model from ``<ckp_path>/model/`` and score a dataset (:960-1088; call
+        site predict_states.py:102-108).  Like the reference it takes the checkpoint named on line 1
+        of the saver's ``checkpoint`` file (:968-969), pads the last batch with zeros, SUMS the batch
+        losses, and flattens the stacked logits before truncating them (:1022-1023).  The model is
+        rebuilt from the checkpoint's architecture record (the reference imports the TF meta-graph,
+        :979), or ``model`` is used.  Returns (pred_logits, pred_labels, pred_loss, test_acc)."""
+        import sklearn.metrics
+        model = s._restore(ckp_path, batch_size, model, config)
         test_labels = np.asarray(test_labels)
         data_dev = model.stage(test_data)
         data_size = data_dev.shape[0]

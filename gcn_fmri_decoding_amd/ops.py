@@ -459,7 +459,7 @@ class ChebConv(torch.autograd.Function):
             _lib.check(_launch('contract_fwd', 4.0 * B * M * (Fin * K + 1), 2.0 * B * M * Fin * K * Fout,
                                lambda: lib.chebgcn_contract_fwd_mean(_p(stack), _p(Wc), _p(b), bias_kind, _p(y), _p(mask), B, M,
                                                                      Fin, K, Fout, _stream())), 'contract_fwd_mean')
-            ctx.save_for_backward(stack, Wc, None, mask)
+            ctx.save_for_backward(stack if ctx.needs_input_grad[1] else None, Wc, None, mask)
             ctx.fold, ctx.mean, ctx.fused = True, True, False
             ctx.graph, ctx.cfg = graph, (B, M, Fin, K, Fout, pool, pool_kind, int(relu), bias_kind)
             ctx.bias_shape = None if bias is None else tuple(bias.shape)
@@ -490,7 +490,7 @@ class ChebConv(torch.autograd.Function):
             sel = torch.empty(out.shape, dtype=torch.uint8, device=x.device) if wants_grad else None
             _lib.check(_launch('pool_gather_fwd', B * Fout * (4.0 * (M + Mo) + Mo), 0.0, lambda: lib.chebgcn_pool_gather_fwd(
                 _p(y_full), _p(maps[0]), _p(out), _p(sel), B, M, Fout, pool, pool_kind, int(relu), _stream())), 'pool_gather_fwd')
-            ctx.save_for_backward(stack, Wc, None, sel)
+            ctx.save_for_backward(stack if ctx.needs_input_grad[1] else None, Wc, None, sel)
             ctx.fold, ctx.mean, ctx.fused = False, False, False
             ctx.graph, ctx.cfg = graph, (B, M, Fin, K, Fout, pool, pool_kind, int(relu), bias_kind)
             ctx.bias_shape = None if bias is None else tuple(bias.shape)
@@ -513,7 +513,8 @@ class ChebConv(torch.autograd.Function):
         if b is not None and not b.is_contiguous():
             b = b.contiguous()
         contract_fwd_into(stack, Wc, b, bias_kind, out, argmax, B, M, Fin, K, Fout, pool, pool_kind, relu, precision)
-        ctx.save_for_backward(stack, Wc, None if (pool == 1 and relu) else out, argmax)
+        # the stack feeds the weight gradient alone: without one (saliency passes) it is not kept alive until the backward
+        ctx.save_for_backward(stack if ctx.needs_input_grad[1] else None, Wc, None if (pool == 1 and relu) else out, argmax)
         ctx.fold, ctx.mean, ctx.fused = fold, False, False
         ctx.graph, ctx.cfg = graph, (B, M, Fin, K, Fout, pool, pool_kind, int(relu), bias_kind)
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
@@ -1038,7 +1039,7 @@ class SpectralConv(torch.autograd.Function):
     """``filter_in_fourier`` (models_gcn.py:512-528) on plane storage: analysis, the per-frequency ``[Fout x Fin]`` mix,
     synthesis.  ``W``: ``[M, Fout, Fin]`` (``fourier``, :530-538), or, with the spline basis ``Bs [M, K]`` given, the
     ``[K, Fout*Fin]`` control weights the filter is expanded from (``spline``, :540-556).  Saves the analysed input for
-    the weight gradient; returns no input gradient where the input needs none."""
+    the weight gradient where one is wanted; returns no input gradient where the input needs none."""
 
     @staticmethod
     def forward(ctx, x, W, basis, Bs, M, Fout):
@@ -1051,7 +1052,7 @@ class SpectralConv(torch.autograd.Function):
         Wf = (spline_expand(Bs, Wd) if Bs is not None else Wd).view(M, Fout, Fin)
         xh = spectral_transform(x, basis, M, False)
         y = spectral_transform(spectral_mix(xh, Wf, M), basis, M, True)
-        ctx.save_for_backward(xh, Wf, basis, Bs)
+        ctx.save_for_backward(xh if ctx.needs_input_grad[1] else None, Wf, basis, Bs)
         ctx.M = M
         return y
 
@@ -1307,3 +1308,110 @@ def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0
         return
     _lib.check(_lib.lib().chebgcn_adam_step(_p(p), _p(g), _p(m), _p(v), n, float(lr_t), float(beta1), float(beta2),
                                             float(eps), float(grad_scale), float(l2), _stream()), 'adam_step')
+
+
+# ------------------------------------------------------------------------------------
+# saliency maps (base_model.saliency): the head without weight gradients and the three kernels of csrc/saliency.hip
+# ------------------------------------------------------------------------------------
+
+SCORES = {'logit': 0, 'logprob': 1}
+SALIENCY_METHODS = {'gradient': 0, 'grad_x_input': 1, 'integrated': 2}
+
+
+def _fc_rows(x):
+    """``x`` [B, I] as rows the library's FC kernels take (row stride a multiple of 4 floats, 16-byte aligned): itself where it
+    is such a view, else a copy into a buffer of that stride."""
+    B, I = x.shape
+    if x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= I and x.data_ptr() % 16 == 0:
+        return x
+    buf = torch.empty((B, (I + 3) & ~3), dtype=torch.float32, device=x.device)
+    buf[:, :I].copy_(x)
+    return buf[:, :I]
+
+
+class FCInputGrad(torch.autograd.Function):
+    """``act(x @ W + b)`` of the head whose backward forms the input gradient only (chebgcn_fc_bwd with dW = NULL): what a
+    saliency pass runs in place of the layer.  Both directions are the library's kernels at every size chebgcn_fc_fwd serves;
+    a size it does not serve raises."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, relu):
+        _require_cuda(x, W, b)
+        B, I = x.shape
+        O = W.shape[1]
+        L = _lib.lib()
+        if not L.chebgcn_fc_fwd_supported(B, I, O):
+            raise ValueError('saliency: the FC layer %d x %d x %d is outside the range of chebgcn_fc_fwd' % (B, I, O))
+        rows = _fc_rows(x.detach())
+        Wc, bc = W.detach().contiguous(), b.detach().contiguous()
+        y = torch.empty((B, O), dtype=torch.float32, device=x.device)
+        nws = L.chebgcn_fc_fwd_workspace(B, I, O)
+        ws = _workspace(nws, x.device, 'fc_fwd') if nws else None
+        _lib.check(_launch('fc_fwd', 4.0 * (B * I + I * O + B * O), 2.0 * B * I * O, lambda: L.chebgcn_fc_fwd(
+            _p(rows), rows.stride(0), _p(Wc), _p(bc), _p(y), _p(ws), nws, B, I, O, 1 if relu else 0, _stream())), 'fc_fwd')
+        ctx.save_for_backward(rows, Wc, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, Wc, y = ctx.saved_tensors
+        B, I = rows.shape
+        O = Wc.shape[1]
+        g = g.contiguous()
+        dx = torch.empty((B, I), dtype=torch.float32, device=g.device)
+        _lib.check(_launch('fc_bwd_x', 4.0 * (B * I + I * O + B * O), 2.0 * B * I * O, lambda: _lib.lib().chebgcn_fc_bwd(
+            _p(rows), rows.stride(0), _p(Wc), _p(g), _p(y), None, None, _p(dx), I, B, I, O, _stream())), 'fc_bwd_x')
+        return dx, None, None, None
+
+
+def saliency_seed(logits, targets, rep, nvalid, score, cls_out=None, want_grad=True):
+    """d score / d logits of ``logits [B, C]`` (chebgcn_saliency_seed): row r attributes ``targets[r // rep]`` (int64 device
+    tensor) or, with ``targets`` None, its own argmax; rows from ``nvalid`` get zeros.  Writes the attributed class of the
+    windows into ``cls_out`` (int64) when given.  Returns dlogits (None unless ``want_grad``)."""
+    _require_cuda(logits, targets, cls_out)
+    z = logits.detach().contiguous()
+    B, C = z.shape
+    for t, what in ((targets, 'targets'), (cls_out, 'cls_out')):
+        if t is not None and (t.dtype != torch.int64 or not t.is_contiguous() or t.numel() < (nvalid + rep - 1) // rep):
+            raise ValueError('saliency_seed: %s must be contiguous int64 with a value per window' % what)
+    dz = torch.empty_like(z) if want_grad else None
+    _lib.check(_launch('saliency_seed', 4.0 * 2 * B * C, 0.0, lambda: _lib.lib().chebgcn_saliency_seed(
+        _p(z), _p(targets), int(rep), int(nvalid), SCORES[score], _p(dz), _p(cls_out), B, C, _stream())), 'saliency_seed')
+    return dz
+
+
+def saliency_path(data, order, sample, baseline, R, steps, M):
+    """Plane storage ``[R, F, Mp]`` of the integrated-gradients path (chebgcn_saliency_path): row ``w*steps + j`` =
+    ``baseline + (j + 1/2)/steps * (data[sample[w]] - baseline)`` in the internal vertex order ``order`` (int32 device,
+    internal position -> vertex of ``data``, or None); zero rows behind the windows."""
+    _require_cuda(data, order, sample, baseline)
+    S, N, F = data.shape
+    nw = int(sample.numel())
+    out = torch.empty((int(R), F, plane_stride(M)), dtype=torch.float32, device=data.device)
+    _lib.check(_launch('saliency_path', 4.0 * F * (nw * N * (1 + (baseline is not None)) + R * plane_stride(M)), 0.0,
+                       lambda: _lib.lib().chebgcn_saliency_path(_p(data), _p(order), _p(sample), _p(baseline), _p(out), nw,
+                                                                int(steps), int(R), N, int(M), F, _stream())), 'saliency_path')
+    return out
+
+
+def saliency_reduce(dx, data, order, sample, baseline, steps, method, absolute, out, cls=None, acc=None):
+    """Input-gradient planes ``dx`` [>= nw*steps, F, Mp] (internal order) -> ``out`` [nw, M, F] in the caller's order (times
+    1, x or (x - x0)/steps; ``absolute``: |.|), and with ``acc`` (float64 [C, M, F]) the per-class sums of those rows over
+    the windows' classes ``cls`` (int64 [nw]) added to it (chebgcn_saliency_reduce)."""
+    _require_cuda(dx, data, order, sample, baseline, out, cls, acc)
+    nw, M, F = out.shape
+    if not out.is_contiguous() or dx.shape[1] != F or dx.shape[0] < nw * steps or not dx.is_contiguous():
+        raise ValueError('saliency_reduce: shapes of dx %s and out %s do not match' % (tuple(dx.shape), tuple(out.shape)))
+    if acc is not None and (acc.dtype != torch.float64 or not acc.is_contiguous() or tuple(acc.shape[1:]) != (M, F)
+                            or cls is None or cls.dtype != torch.int64 or cls.numel() != nw):
+        raise ValueError('saliency_reduce: acc float64 [C, %d, %d] with int64 cls [%d]' % (M, F, nw))
+    m = SALIENCY_METHODS[method]
+    # dx (the steps of every window), the rows written, x where the method reads it; the class sums read the rows again and
+    # update the float64 accumulator
+    nbytes = 4.0 * nw * M * F * (steps + 1 + (m > 0) + (m == 2 and baseline is not None))
+    if acc is not None:
+        nbytes += 4.0 * nw * M * F + 16.0 * acc.shape[0] * M * F
+    _lib.check(_launch('saliency_reduce', nbytes, 0.0, lambda: _lib.lib().chebgcn_saliency_reduce(
+        _p(dx), _p(data), _p(order), _p(sample), _p(baseline), nw, int(steps), M, F, m, int(bool(absolute)), _p(out), _p(cls),
+        int(acc.shape[0]) if acc is not None else 0, _p(acc), _stream())), 'saliency_reduce')
+    return out

@@ -484,6 +484,37 @@ int chebgcn_spectral_spline_expand(const float* Bs, const float* Wk, float* W, i
 int chebgcn_spectral_spline_expand_bwd(const float* Bs, const float* dW, float* dWk, int M, int K, int C,
                                        chebgcn_stream stream);
 
+/* ---- saliency maps: input gradients and integrated gradients of a trained model (models_gcn.base_model.saliency) -------
+ * The pass between these calls is the library's own forward (with ReLU masks) and the training step's input-gradient kernels.
+ *
+ * seed: the gradient of the attributed score wrt the logits, and the class it is attributed to.
+ *   logits, dlogits: [B][C] dense; row r attributes targets[r / rep] (int64, device), or where targets is NULL the row's own
+ *   first maximum (torch.argmax; a NaN counts as the largest value);  score CHEBGCN_SCORE_LOGIT: dlogits[r] = e_t,
+ *   CHEBGCN_SCORE_LOGPROB (log softmax(z)_t): e_t - softmax(z_r).  Rows r >= nvalid get dlogits 0.  cls_out (int64, or NULL):
+ *   cls_out[r / rep] = t for the rows r < nvalid with r % rep == 0.  dlogits may be NULL (the class alone).  A target outside
+ *   [0, C) gives a NaN row.
+ * path: the integrated-gradients path in plane storage.  x: [S][N][F] windows in row layout (device); perm: int32 [M] internal
+ *   position -> vertex of x (NULL: identity, M == N); sample: int32 [nw] rows of x; baseline: [N][F] or NULL (zeros);
+ *   out: [R][F][Mp(M)], R >= nw*steps:
+ *     out[w*steps + j][f][i] = x0 + a_j (x[sample[w]][perm[i]][f] - x0),  x0 = baseline[perm[i]][f],  a_j = (j + 1/2) / steps
+ *   rows from nw*steps and the pad [M, Mp) of every plane are 0.
+ * reduce: dx: [nw*steps][F][Mp(M)] input-gradient planes (internal order, perm as above, M == N); the steps of a window are
+ *   summed in order, g = sum_j dx[w*steps + j], and written in the caller's order to out [nw][M][F]:
+ *     CHEBGCN_SAL_GRADIENT g,  CHEBGCN_SAL_GRAD_X_INPUT x g,  CHEBGCN_SAL_INTEGRATED (x - x0) g / steps   (x = x[sample[w]],
+ *     x0 = baseline or 0), |.| when `absolute`.  With acc (float64 [ncls][M][F], device): acc[k] += the sum, windows in order,
+ *   of out[w] over the windows with cls[w] == k (int64 [nw]; other values are skipped).  Fixed-order sums throughout. */
+/* chebgcn_saliency_supported: 1 where path and reduce serve F channels (their LDS tiles: F <= 126), else 0.  Host only. */
+enum { CHEBGCN_SCORE_LOGIT = 0, CHEBGCN_SCORE_LOGPROB = 1 };
+int chebgcn_saliency_supported(int F);
+enum { CHEBGCN_SAL_GRADIENT = 0, CHEBGCN_SAL_GRAD_X_INPUT = 1, CHEBGCN_SAL_INTEGRATED = 2 };
+int chebgcn_saliency_seed(const float* logits, const int64_t* targets, int rep, int nvalid, int score, float* dlogits,
+                          int64_t* cls_out, int B, int C, chebgcn_stream stream);
+int chebgcn_saliency_path(const float* x, const int32_t* perm, const int32_t* sample, const float* baseline, float* out, int nw,
+                          int steps, int R, int N, int M, int F, chebgcn_stream stream);
+int chebgcn_saliency_reduce(const float* dx, const float* x, const int32_t* perm, const int32_t* sample, const float* baseline,
+                            int nw, int steps, int M, int F, int method, int absolute, float* out, const int64_t* cls, int ncls,
+                            double* acc, chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose
