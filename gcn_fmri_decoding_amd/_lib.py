@@ -108,6 +108,10 @@ SIGNATURES = {
     'chebgcn_saliency_seed': (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _i, _p]),
     'chebgcn_saliency_path': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     'chebgcn_saliency_reduce': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p]),
+    'chebgcn_occlusion_supported': (_i, [_i]),
+    'chebgcn_occlusion_rows': (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _p]),
+    'chebgcn_occlusion_score': (_i, [_p, _i64, _i, _i, _i, _i, _p, _i, _p, _p, _p]),
+    'chebgcn_occlusion_class_sums': (_i, [_p, _p, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

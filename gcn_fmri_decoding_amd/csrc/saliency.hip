@@ -15,12 +15,9 @@
 // plane <-> row change goes through an LDS tile of 64 vertices, as chebgcn_perm_data does.
 #include <algorithm>
 
-#include "common.h"
+#include "saliency_tile.h"
 
 namespace chebgcn {
-
-constexpr int SAL_T = 256;     // threads of the path / reduce workgroups
-constexpr int SAL_V = 64;      // vertices per tile
 
 // one thread per row of logits; C is small (the classes of the head)
 __global__ void __launch_bounds__(64)
@@ -73,37 +70,6 @@ saliency_seed_kernel(const float* __restrict__ z, const long long* __restrict__ 
     }
     const float inv = 1.f / s;
     for (int c = 0; c < C; ++c) drow[c] = c == t ? so * inv : -expf(row[c] - m) * inv;
-}
-
-// gathers the [F][64] tile of window row `src` (vertex nodes[q], N = none -> 0) into LDS, four loads in flight per thread
-__device__ __forceinline__ void gather_tile(const float* __restrict__ x, size_t src, const int* nodes, float* tile, int N, int F) {
-    for (int e0 = threadIdx.x; e0 < SAL_V * F; e0 += 4 * SAL_T) {
-        float v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int e = e0 + SAL_T * u, ec = e < SAL_V * F ? e : 0;
-            const int q = ec / F, f = ec - q * F;
-            const int node = nodes[q];
-            const float t = x[src + (size_t)(node < N ? node : 0) * F + f];
-            v[u] = node < N ? t : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int e = e0 + SAL_T * u;
-            if (e < SAL_V * F) {
-                const int q = e / F, f = e - q * F;
-                tile[f * (SAL_V + 1) + q] = v[u];
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void load_nodes(int* nodes, const int32_t* __restrict__ perm, int i0, int M, int N) {
-    if (threadIdx.x < SAL_V) {
-        const int i = i0 + threadIdx.x;
-        const int node = i < M ? (perm ? perm[i] : i) : N;
-        nodes[threadIdx.x] = node >= 0 && node < N ? node : N;
-    }
 }
 
 // block (vertex tile, window w): rows w*steps .. w*steps + steps - 1 of the output
@@ -215,6 +181,11 @@ saliency_class_sum_kernel(const float* __restrict__ rows, const long long* __res
     if (any && in) acc[k * NF + e] += s;
 }
 
+void launch_class_sum(const float* rows, const int64_t* cls, double* acc, int nw, long long NF, int ncls, hipStream_t stream) {
+    hipLaunchKernelGGL(saliency_class_sum_kernel, dim3((unsigned)((NF + SAL_T - 1) / SAL_T), ncls), dim3(SAL_T), 0, stream, rows,
+                       (const long long*)cls, acc, nw, NF);
+}
+
 }  // namespace chebgcn
 
 using namespace chebgcn;
@@ -277,8 +248,7 @@ extern "C" int chebgcn_saliency_reduce(const float* dx, const float* x, const in
     if (acc) {
         const long long NF = (long long)M * F;
         note_dispatch_more("saliency_class_sum_kernel");
-        hipLaunchKernelGGL(saliency_class_sum_kernel, dim3((unsigned)((NF + SAL_T - 1) / SAL_T), ncls), dim3(SAL_T), 0, stream,
-                           out, (const long long*)cls, acc, nw, NF);
+        launch_class_sum(out, cls, acc, nw, NF, ncls, stream);
     }
     CG_HIP(hipGetLastError());
     return CHEBGCN_OK;

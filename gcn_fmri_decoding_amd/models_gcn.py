@@ -122,7 +122,8 @@ class base_model(object):
         # (shadow / (1 - 0.9^t): the first value is the loss).  Reporting only; the default follows TF >= 1.0, set
         # ``ema_zero_debias = True`` (or CHEBGCN_EMA_ZERO_DEBIAS=1) for the 0.12 reading.  Unverifiable here (no TensorFlow).
         self.ema_zero_debias = os.environ.get('CHEBGCN_EMA_ZERO_DEBIAS', '0') not in ('0', '', 'false', 'False')
-        # inside saliency(): the layers see their variables without gradient (no weight, bias-gradient or optimizer work)
+        # inside saliency() / occlusion(): the layers see their variables without gradient (no weight, bias-gradient or
+        # optimizer work), and the head runs on the library's FC kernels at every size they serve (no vendor GEMM)
         self._saliency_pass = False
 
     # ---------------------------------------------------------------- run-time API
@@ -286,36 +287,37 @@ class base_model(object):
         maps /= np.maximum(counts, 1)[:, None, None]         # in place, one pass (a class without windows stays 0)
         return maps, counts
 
-    def _saliency_args(self, data, target, labels, score, method, steps, baseline, batch_size):
+    def _saliency_args(self, data, target, labels, score, method, steps, baseline, batch_size, who='saliency'):
         """Checks every argument of ``saliency`` / ``saliency_maps`` before any device work; returns (S, targets int64 [S] or
-        None for 'predicted', labels, baseline as a device tensor or None, batch size)."""
+        None for 'predicted', labels, baseline as a device tensor or None, batch size).  ``who`` names the caller in the
+        messages (``occlusion`` shares these checks)."""
         if score not in ops.SCORES:
-            raise ValueError('saliency: score must be one of %s, got %r' % (sorted(ops.SCORES), score))
+            raise ValueError(who + ': score must be one of %s, got %r' % (sorted(ops.SCORES), score))
         if method not in ops.SALIENCY_METHODS:
-            raise ValueError('saliency: method must be one of %s, got %r' % (sorted(ops.SALIENCY_METHODS), method))
+            raise ValueError(who + ': method must be one of %s, got %r' % (sorted(ops.SALIENCY_METHODS), method))
         integrated = method == 'integrated'
         if integrated and (isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= 65535):
-            raise ValueError('saliency: steps must be an int in [1, 65535], got %r' % (steps,))
+            raise ValueError(who + ': steps must be an int in [1, 65535], got %r' % (steps,))
         bs = self.batch_size if batch_size is None else batch_size
         if isinstance(bs, bool) or not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 65535:
-            raise ValueError('saliency: batch_size must be an int in [1, 65535], got %r' % (batch_size,))
+            raise ValueError(who + ': batch_size must be an int in [1, 65535], got %r' % (batch_size,))
         shape = tuple(int(d) for d in data.shape)
         want = (int(self._M0), int(self.channel))
         if len(shape) != 3 or shape[1:] != want or shape[0] == 0:
-            raise ValueError('saliency: data must be [S, %d, %d] with S > 0, got %s' % (want + (shape,)))
+            raise ValueError(who + ': data must be [S, %d, %d] with S > 0, got %s' % (want + (shape,)))
         from . import _lib
         if not _lib.lib().chebgcn_saliency_supported(want[1]):
-            raise ValueError('saliency: %d channels are more than the saliency kernels serve (chebgcn_saliency_supported)'
+            raise ValueError(who + ': %d channels are more than the saliency kernels serve (chebgcn_saliency_supported)'
                              % want[1])
         S, n_classes = shape[0], int(self.M[-1])
 
         def classes(v, what):
             a = np.asarray(v)
             if a.shape != (S,) or not np.issubdtype(a.dtype, np.integer):
-                raise ValueError('saliency: %s must be an int array of shape [%d], got %s %s' % (what, S, a.dtype, a.shape))
+                raise ValueError(who + ': %s must be an int array of shape [%d], got %s %s' % (what, S, a.dtype, a.shape))
             a = a.astype(np.int64)
             if a.min() < 0 or a.max() >= n_classes:
-                raise ValueError('saliency: %s must lie in [0, %d); got %d ... %d' % (what, n_classes, a.min(), a.max()))
+                raise ValueError(who + ': %s must lie in [0, %d); got %d ... %d' % (what, n_classes, a.min(), a.max()))
             return a
         if labels is not None:
             labels = classes(labels, 'labels')
@@ -324,22 +326,22 @@ class base_model(object):
                 targets = None
             elif target == 'label':
                 if labels is None:
-                    raise ValueError("saliency: target='label' needs labels")
+                    raise ValueError(who + ": target='label' needs labels")
                 targets = labels
             else:
-                raise ValueError("saliency: target must be 'predicted', 'label', an int or an int array, got %r" % target)
+                raise ValueError(who + ": target must be 'predicted', 'label', an int or an int array, got %r" % target)
         elif isinstance(target, (int, np.integer)) and not isinstance(target, bool):
             if not 0 <= int(target) < n_classes:
-                raise ValueError('saliency: target %d is not a class in [0, %d)' % (int(target), n_classes))
+                raise ValueError(who + ': target %d is not a class in [0, %d)' % (int(target), n_classes))
             targets = np.full(S, int(target), np.int64)
         else:
             targets = classes(target, 'target')
         if baseline is not None:
             baseline = np.asarray(baseline, np.float32)
             if baseline.shape != want:
-                raise ValueError('saliency: baseline must be [%d, %d], got %s' % (want + (baseline.shape,)))
+                raise ValueError(who + ': baseline must be [%d, %d], got %s' % (want + (baseline.shape,)))
         if self.device.type != 'cuda':
-            raise RuntimeError('saliency: the model has no device to run on (%s)' % self.device)
+            raise RuntimeError(who + ': the model has no device to run on (%s)' % self.device)
         base = torch.as_tensor(baseline).to(self.device) if baseline is not None else None
         return S, targets, labels, base, int(bs)
 
@@ -391,6 +393,112 @@ class base_model(object):
                 ops.saliency_reduce(dx, data_dev, order, idx, base, m, method, absolute,
                                     attr[begin:end] if attr is not None else rows[:nw],
                                     targets[begin:end] if acc is not None else None, acc)
+        finally:
+            self.training_mode, self._saliency_pass = was_training, False
+
+    # ---------------------------------------------------------------- occlusion maps
+
+    def occlusion(self, data, target='predicted', score='logit', groups=None, baseline=None, batch_size=None, labels=None):
+        """How much each window's class score falls when a group of its vertices is set to a baseline ("virtual lesion").
+        ``data``: ``[S, M, channel]`` as for ``predict`` (NumPy, or a tensor from ``stage()``), in the caller's vertex order.
+        Returns ``(drop, target)``: float32 ``[S, G]`` with ``drop[w, g] = s_c(x_w) - s_c(x_w with group g's vertices set to
+        the baseline)``, and the int64 class ``[S]`` each window was scored for.
+
+        * ``groups``: an int array ``[M]`` in the caller's order with values in ``[-1, G)``; ``-1`` never occludes a vertex, and
+          every id in ``[0, G)`` must occur.  ``None``: one group per vertex (``G = M``, fake vertices included).  In the
+          coarsening's tree order (``coarsening.perm_data`` data) ``groups = np.arange(M) >> j`` occludes the clusters of
+          level ``j``, ``2**j`` vertices each.
+        * ``baseline``: ``None`` (zeros) or ``[M, channel]`` in the caller's order.
+        * ``target``, ``labels``, ``score``: as for ``saliency``.  The class is decided on the unoccluded window and held for
+          all of its rows.
+        * Dropout is off.  ``batch_size`` (default the model's): forward rows of one pass.  Rows are (window, group) pairs,
+          ``G + 1`` per window (the window itself first), window-major: a pass may hold part of a window or several windows,
+          and the last one is zero-padded like ``predict``.  A call costs ``S * (G + 1)`` forward rows.
+
+        Only the inference kernels run, plus three small ones (chebgcn_occlusion_rows / _score, chebgcn_saliency_seed); nothing
+        the model keeps is written."""
+        S, targets, _, base, bs, gid, G = self._occlusion_args(data, target, labels, score, groups, baseline, batch_size)
+        data_dev = self.stage(data)
+        drop = torch.empty((S, G), dtype=torch.float32, device=self.device)
+        cls = torch.empty(S, dtype=torch.int64, device=self.device)
+        if targets is not None:
+            cls.copy_(torch.as_tensor(targets))
+        self._occlusion_run(data_dev, targets is None, score, gid, G, base, bs, cls, drop)
+        return drop.cpu().numpy(), cls.cpu().numpy()
+
+    def occlusion_maps(self, data, labels, score='logit', groups=None, baseline=None, batch_size=None):
+        """Per-class mean occlusion drop: window w (target = its label) adds its ``occlusion`` row to the sum of class
+        ``labels[w]``.  Returns ``(maps, counts)``: float64 ``[C, G]`` (C = M[-1]; the mean, zero for a class without windows)
+        and int64 ``[C]``.  The sums run on the device in float64, windows in order; the per-window table never leaves the
+        device."""
+        S, _, labels, base, bs, gid, G = self._occlusion_args(data, 'label', labels, score, groups, baseline, batch_size)
+        data_dev = self.stage(data)
+        ncls = int(self.M[-1])
+        drop = torch.empty((S, G), dtype=torch.float32, device=self.device)
+        cls = torch.as_tensor(labels).to(self.device)
+        self._occlusion_run(data_dev, False, score, gid, G, base, bs, cls, drop)
+        acc = torch.zeros((ncls, G), dtype=torch.float64, device=self.device)
+        ops.occlusion_class_sums(drop, cls, acc)
+        counts = np.bincount(labels, minlength=ncls).astype(np.int64)
+        maps = acc.cpu().numpy()
+        maps /= np.maximum(counts, 1)[:, None]
+        return maps, counts
+
+    def _occlusion_args(self, data, target, labels, score, groups, baseline, batch_size):
+        """Checks every argument of ``occlusion`` / ``occlusion_maps`` before any device work (``_saliency_args`` for the ones
+        they share); returns those of ``_saliency_args``, then the group of each internal position as int32 ``[Mp]`` on the
+        device (-1 on the pad) and G."""
+        M = int(self._M0)
+        if groups is None:
+            g = np.arange(M, dtype=np.int64)
+        else:
+            a = np.asarray(groups)
+            if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or a.shape != (M,):
+                raise ValueError('occlusion: groups must be an int array of shape [%d], got %s %s' % (M, a.dtype, a.shape))
+            g = a.astype(np.int64)
+            if g.min() < -1:
+                raise ValueError('occlusion: groups must lie in [-1, G) (-1: never occluded); got %d' % g.min())
+            if g.max() < 0:
+                raise ValueError('occlusion: groups holds no group (every entry is -1)')
+            empty = np.flatnonzero(np.bincount(g[g >= 0], minlength=int(g.max()) + 1) == 0)
+            if len(empty):
+                raise ValueError('occlusion: groups must use every id in [0, %d); %d of them occur nowhere (first %d)'
+                                 % (int(g.max()) + 1, len(empty), empty[0]))
+        G = int(g.max()) + 1
+        from . import _lib
+        if not _lib.lib().chebgcn_occlusion_supported(int(self.channel)):
+            raise ValueError('occlusion: %d channels are more than the occlusion kernels serve (chebgcn_occlusion_supported)'
+                             % int(self.channel))
+        S, targets, labels, base, bs = self._saliency_args(data, target, labels, score, 'gradient', 1, baseline, batch_size,
+                                                           who='occlusion')
+        internal = g[self._order] if self._order is not None else g
+        gid = np.full(ops.plane_stride(M), -1, np.int32)
+        gid[:M] = internal
+        return S, targets, labels, base, bs, torch.as_tensor(gid).to(self.device), G
+
+    def _occlusion_run(self, data_dev, predicted, score, gid, G, base, bs, cls, drop):
+        """The passes of ``occlusion`` / ``occlusion_maps``: per pass of ``bs`` rows, the rows in plane storage, the forward
+        (no autograd, the variables detached, the head on the library's kernels), the class of the windows whose own row is
+        in the pass (``predicted``: its argmax, else ``cls`` as given), and the drops into ``drop``."""
+        S, M, _ = data_dev.shape
+        G1 = G + 1
+        total = S * G1
+        order = self._order_dev if self._order is not None else None
+        ref = torch.empty(S, dtype=torch.float32, device=self.device)
+        was_training = self.training_mode
+        self.training_mode, self._saliency_pass = False, True
+        try:
+            with torch.no_grad():
+                for r0 in range(0, total, bs):
+                    x = ops.occlusion_rows(data_dev, order, gid, base, r0, bs, G, M)
+                    logits = self._inference_storage(self.as_internal(x), 1)
+                    if predicted:
+                        w = -(-r0 // G1)                    # the first window whose own row is in this pass
+                        off = w * G1 - r0
+                        if w < S and off < bs:
+                            ops.saliency_seed(logits[off:], None, G1, min(bs - off, total - w * G1), score, cls_out=cls[w:],
+                                              want_grad=False)
+                    ops.occlusion_score(logits, r0, G, cls, score, ref, drop)
         finally:
             self.training_mode, self._saliency_pass = was_training, False
 
@@ -1913,6 +2021,13 @@ class model_perf(object):
         ``(maps, counts)``."""
         model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
         return model.saliency_maps(data, labels, **kw)
+
+    def occlusion_maps(s, ckp_path, data, labels, target_name=None, batch_size=128, **kw):
+        """Per-class mean occlusion drops (``base_model.occlusion_maps``; ``kw``: its keywords) of the model ``predict`` would
+        restore from ``ckp_path``.  ``target_name`` is accepted for symmetry with ``predict`` and not used.  Returns
+        ``(maps, counts)``."""
+        model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
+        return model.occlusion_maps(data, labels, **kw)
 
     def predict(s, ckp_path, test_data, test_labels, target_name=None, batch_size=128, trial_dura=17,
                 flag_starttr=False, sub_name=None, model=None, config=None):

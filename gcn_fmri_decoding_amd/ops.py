@@ -1415,3 +1415,54 @@ def saliency_reduce(dx, data, order, sample, baseline, steps, method, absolute, 
         _p(dx), _p(data), _p(order), _p(sample), _p(baseline), nw, int(steps), M, F, m, int(bool(absolute)), _p(out), _p(cls),
         int(acc.shape[0]) if acc is not None else 0, _p(acc), _stream())), 'saliency_reduce')
     return out
+
+
+# ------------------------------------------------------------------------------------
+# occlusion maps (base_model.occlusion): the kernels of csrc/occlusion.hip around the inference layers
+# ------------------------------------------------------------------------------------
+
+def occlusion_rows(data, order, gid, baseline, r0, R, G, M):
+    """Plane storage ``[R, F, Mp]`` of rows ``r0 .. r0 + R - 1`` of an occlusion run (chebgcn_occlusion_rows): row r is window
+    ``r // (G + 1)`` of ``data`` with the vertices of group ``r % (G + 1) - 1`` set to ``baseline`` (slot 0: none), in the
+    internal vertex order ``order`` (int32 device, internal position -> vertex of ``data``, or None); ``gid``: int32 device
+    group of each internal position; zero rows past the last window."""
+    _require_cuda(data, order, gid, baseline)
+    S, N, F = data.shape
+    G1, Mp = int(G) + 1, plane_stride(M)
+    out = torch.empty((int(R), F, Mp), dtype=torch.float32, device=data.device)
+    windows = max(0, min(S - 1, (int(r0) + int(R) - 1) // G1) - int(r0) // G1 + 1)
+    nbytes = 4.0 * (F * (windows * N + (baseline is not None) * N + R * Mp) + M)
+    _lib.check(_launch('occlusion_rows', nbytes, 0.0, lambda: _lib.lib().chebgcn_occlusion_rows(
+        _p(data), _p(order), _p(gid), _p(baseline), _p(out), int(r0), int(R), S, int(G), N, int(M), F, _stream())),
+        'occlusion_rows')
+    return out
+
+
+def occlusion_score(logits, r0, G, cls, score, ref, drop):
+    """``drop[w, g]`` (float32 ``[S, G]``) of the rows whose logits ``[R, C]`` a pass from row ``r0`` formed, for the windows'
+    classes ``cls`` (int64 ``[S]``); ``ref`` (float32 ``[S]``) carries a window's own score to the passes after the one that
+    holds its row (chebgcn_occlusion_score)."""
+    _require_cuda(logits, cls, ref, drop)
+    z = logits.detach().contiguous()
+    R, C = z.shape
+    S = drop.shape[0]
+    if not (drop.is_contiguous() and drop.dtype == torch.float32 and drop.shape[1] == G and cls.dtype == torch.int64
+            and cls.is_contiguous() and cls.numel() == S and ref.dtype == torch.float32 and ref.numel() == S):
+        raise ValueError('occlusion_score: drop float32 [S, %d], cls int64 [S] and ref float32 [S]' % G)
+    _lib.check(_launch('occlusion_score', 4.0 * R * (2 * C + 2), 0.0, lambda: _lib.lib().chebgcn_occlusion_score(
+        _p(z), int(r0), R, S, int(G), C, _p(cls), SCORES[score], _p(ref), _p(drop), _stream())), 'occlusion_score')
+
+
+def occlusion_class_sums(drop, cls, acc):
+    """``acc[k] += `` the sum, windows in order, of the rows of ``drop`` [S, G] whose window has class k (``cls`` int64 [S],
+    ``acc`` float64 [C, G]; chebgcn_occlusion_class_sums)."""
+    _require_cuda(drop, cls, acc)
+    S, G = drop.shape
+    if not (drop.is_contiguous() and acc.is_contiguous() and acc.dtype == torch.float64 and acc.shape[1] == G
+            and cls.dtype == torch.int64 and cls.numel() == S):
+        raise ValueError('occlusion_class_sums: drop float32 [S, G], cls int64 [S], acc float64 [C, G]')
+    C = acc.shape[0]
+    _lib.check(_launch('occlusion_class_sums', 4.0 * S * G + 8.0 * C * S + 16.0 * C * G, 0.0,
+                       lambda: _lib.lib().chebgcn_occlusion_class_sums(_p(drop), _p(cls), S, G, C, _p(acc), _stream())),
+               'occlusion_class_sums')
+    return acc

@@ -515,6 +515,31 @@ int chebgcn_saliency_reduce(const float* dx, const float* x, const int32_t* perm
                             int nw, int steps, int M, int F, int method, int absolute, float* out, const int64_t* cls, int ncls,
                             double* acc, chebgcn_stream stream);
 
+/* ---- occlusion maps: score drops when vertex groups are set to a baseline (models_gcn.base_model.occlusion) ------------
+ * Rows are (window, group) pairs, window-major, G + 1 per window: row r is window w = r / (G + 1), slot j = r % (G + 1); slot 0
+ * is the window itself (group g = G, which no vertex has), slot j >= 1 occludes group g = j - 1.  Between rows and score runs
+ * the library's own forward.
+ *
+ * rows: rows r0 .. r0 + R - 1 in plane storage.  x: [S][N][F] windows in row layout (device); perm: int32 [M] internal position
+ *   -> vertex of x (NULL: identity, M == N); gid: int32 [M] (or longer) group of each internal position, -1 = never occluded;
+ *   baseline: [N][F] or NULL (zeros); out: [R][F][Mp(M)], 16-byte aligned:
+ *     out[r - r0][f][i] = gid[i] == g_r ? baseline[perm[i]][f] : x[w_r][perm[i]][f]
+ *   the pad [M, Mp) and the rows r >= S (G + 1) are 0.  R <= 65535.
+ * score: logits [R][C] of rows r0 .. r0 + R - 1; cls: int64 [S] class of each window (a class outside [0, C) gives NaN);
+ *   s = z_c (CHEBGCN_SCORE_LOGIT) or log softmax(z)_c (CHEBGCN_SCORE_LOGPROB, the maximum subtracted, classes summed in order).
+ *   A slot-0 row writes ref[w] = s; a row of slot j >= 1 writes drop[w][j - 1] = s(slot 0 of w) - s, its slot-0 row read from
+ *   logits when it lies in this call, else from ref[w] (written by an earlier call on the same stream).  ref: [S], drop: [S][G].
+ * class_sums: acc[k][g] += the sum, windows in order, of drop[w][g] over the windows with cls[w] == k (float64 [ncls][G];
+ *   other classes are skipped).  Fixed-order sums throughout; no atomics. */
+/* chebgcn_occlusion_supported: 1 where the row kernel serves F channels (its LDS tiles: F <= 125), else 0.  Host only. */
+int chebgcn_occlusion_supported(int F);
+int chebgcn_occlusion_rows(const float* x, const int32_t* perm, const int32_t* gid, const float* baseline, float* out, int64_t r0,
+                           int R, int S, int G, int N, int M, int F, chebgcn_stream stream);
+int chebgcn_occlusion_score(const float* logits, int64_t r0, int R, int S, int G, int C, const int64_t* cls, int score, float* ref,
+                            float* drop, chebgcn_stream stream);
+int chebgcn_occlusion_class_sums(const float* drop, const int64_t* cls, int S, int G, int ncls, double* acc,
+                                 chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose
