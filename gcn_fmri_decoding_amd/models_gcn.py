@@ -125,6 +125,9 @@ class base_model(object):
         # inside saliency() / occlusion(): the layers see their variables without gradient (no weight, bias-gradient or
         # optimizer work), and the head runs on the library's FC kernels at every size they serve (no vendor GEMM)
         self._saliency_pass = False
+        # inside gradcam(): the conv layer (index) whose output the input gradient stops at, and that output once a pass made it
+        self._cam_layer, self._cam_act = None, None
+        self._cam_orders = {}           # id(vertex order) -> (that order, its int32 device table)
 
     # ---------------------------------------------------------------- run-time API
 
@@ -287,10 +290,11 @@ class base_model(object):
         maps /= np.maximum(counts, 1)[:, None, None]         # in place, one pass (a class without windows stays 0)
         return maps, counts
 
-    def _saliency_args(self, data, target, labels, score, method, steps, baseline, batch_size, who='saliency'):
+    def _saliency_args(self, data, target, labels, score, method, steps, baseline, batch_size, who='saliency', channels=True):
         """Checks every argument of ``saliency`` / ``saliency_maps`` before any device work; returns (S, targets int64 [S] or
         None for 'predicted', labels, baseline as a device tensor or None, batch size).  ``who`` names the caller in the
-        messages (``occlusion`` shares these checks)."""
+        messages (``occlusion`` and ``gradcam`` share these checks); ``channels=False`` skips the channel limit of the saliency
+        kernels, which ``gradcam`` does not run."""
         if score not in ops.SCORES:
             raise ValueError(who + ': score must be one of %s, got %r' % (sorted(ops.SCORES), score))
         if method not in ops.SALIENCY_METHODS:
@@ -306,7 +310,7 @@ class base_model(object):
         if len(shape) != 3 or shape[1:] != want or shape[0] == 0:
             raise ValueError(who + ': data must be [S, %d, %d] with S > 0, got %s' % (want + (shape,)))
         from . import _lib
-        if not _lib.lib().chebgcn_saliency_supported(want[1]):
+        if channels and not _lib.lib().chebgcn_saliency_supported(want[1]):
             raise ValueError(who + ': %d channels are more than the saliency kernels serve (chebgcn_saliency_supported)'
                              % want[1])
         S, n_classes = shape[0], int(self.M[-1])
@@ -501,6 +505,109 @@ class base_model(object):
                     ops.occlusion_score(logits, r0, G, cls, score, ref, drop)
         finally:
             self.training_mode, self._saliency_pass = was_training, False
+
+    # ---------------------------------------------------------------- Grad-CAM maps
+
+    def gradcam(self, data, layer=None, target='predicted', score='logit', method='gradcam', relu=True, batch_size=None,
+                labels=None):
+        """Class activation maps of each window at a conv layer.  ``data``: ``[S, M, channel]`` as for ``predict`` (NumPy, or a
+        tensor from ``stage()``), in the caller's vertex order.  Returns ``(cam, target)``: float32 ``[S, M]`` at the input
+        resolution in the order of ``data`` (fake vertices included), and the int64 class ``[S]`` each window was scored for.
+
+        * ``layer``: ``'conv1'`` ... ``'conv<n>'``; ``None`` is the top conv layer.  Its activation ``A`` ``[F, N]`` is the
+          layer's output as the next stage reads it (after bias, ReLU and pooling; ``finetuning_cgcnn``'s top layer before its
+          pooling, as its flat head reads it) over the ``N`` vertices of that resolution, and ``G = ds/dA``.
+        * ``method``: ``'gradcam'`` (``cam_i = sum_f alpha_f A[f, i]``, ``alpha_f`` the mean of ``G[f]`` over the ``N``
+          vertices) or ``'grad_x_activation'`` (``cam_i = sum_f G[f, i] A[f, i]``).  ``relu``: ``max(0, cam)``.  At the top
+          layer of a ``cgcnn`` the head reads the feature mean, so ``G[f, i] = g_i / F`` is the same for every filter and
+          ``'gradcam'`` is ``ReLU(mean(alpha) * sum_f A[f, i])``: the per-vertex product is the map that stays informative there.
+        * Level vertex ``j`` (the coarsening's tree order) covers the input vertices ``[j P, (j + 1) P)``, ``P`` the product of
+          the pools up to the layer; each of them carries its value.
+        * ``target``, ``labels``, ``score``, ``batch_size``: as for ``saliency`` (``method='gradient'``).  Dropout is off.
+
+        One pass per batch: the layers up to ``layer`` without autograd, the layers above it, the head and the seed as a saliency
+        pass runs them (input-gradient kernels only), the gradient taken at the layer's output, then chebgcn_gradcam_weights /
+        _map.  Nothing the model keeps is written."""
+        S, targets, _, bs, li = self._gradcam_args(data, target, labels, score, layer, method, relu, batch_size)
+        data_dev = self.stage(data)
+        cam = torch.empty((S, data_dev.shape[1]), dtype=torch.float32, device=self.device)
+        cls = torch.empty(S, dtype=torch.int64, device=self.device)
+        if targets is not None:
+            cls.copy_(torch.as_tensor(targets))
+        self._gradcam_run(data_dev, cls if targets is not None else None, score, li, method, relu, bs, cls, cam)
+        return cam.cpu().numpy(), cls.cpu().numpy()
+
+    def gradcam_maps(self, data, labels, layer=None, score='logit', method='gradcam', relu=True, batch_size=None):
+        """Per-class mean Grad-CAM map: window w (target = its label) adds its ``gradcam`` row to the sum of class ``labels[w]``.
+        Returns ``(maps, counts)``: float64 ``[C, M]`` (C = M[-1]; the mean, zero for a class without windows) and int64 ``[C]``.
+        The sums run on the device in float64, windows in order; the per-window maps never leave the device."""
+        S, _, labels, bs, li = self._gradcam_args(data, 'label', labels, score, layer, method, relu, batch_size)
+        data_dev = self.stage(data)
+        ncls = int(self.M[-1])
+        cam = torch.empty((S, data_dev.shape[1]), dtype=torch.float32, device=self.device)
+        cls = torch.as_tensor(labels).to(self.device)
+        self._gradcam_run(data_dev, cls, score, li, method, relu, bs, None, cam)
+        acc = torch.zeros((ncls, data_dev.shape[1]), dtype=torch.float64, device=self.device)
+        ops.occlusion_class_sums(cam, cls, acc)
+        counts = np.bincount(labels, minlength=ncls).astype(np.int64)
+        maps = acc.cpu().numpy()
+        maps /= np.maximum(counts, 1)[:, None]
+        return maps, counts
+
+    def _gradcam_args(self, data, target, labels, score, layer, method, relu, batch_size):
+        """Checks every argument of ``gradcam`` / ``gradcam_maps`` before any device work (``_saliency_args`` for the ones they
+        share); returns (S, targets or None, labels, batch size, the layer's index)."""
+        nl = len(self.p)
+        names = ['conv%d' % (i + 1) for i in range(nl)]
+        if layer is None:
+            li = nl - 1
+        elif isinstance(layer, str) and layer in names:
+            li = names.index(layer)
+        else:
+            raise ValueError("gradcam: layer must be None or one of 'conv1' ... 'conv%d', got %r" % (nl, layer))
+        if not isinstance(method, str) or method not in ops.GRADCAM_METHODS:
+            raise ValueError('gradcam: method must be one of %s, got %r' % (sorted(ops.GRADCAM_METHODS), method))
+        if not isinstance(relu, (bool, np.bool_)):
+            raise ValueError('gradcam: relu must be True or False, got %r' % (relu,))
+        S, targets, labels, _, bs = self._saliency_args(data, target, labels, score, 'gradient', 1, None, batch_size,
+                                                        who='gradcam', channels=False)
+        return S, targets, labels, bs, li
+
+    def _gradcam_run(self, data_dev, targets, score, li, method, relu, bs, cls, cam):
+        """The passes of ``gradcam`` / ``gradcam_maps``: per batch of ``bs`` windows (the last one zero-padded), the forward
+        that stops autograd at layer ``li``'s output (``_cam_layer``; the layer leaves it in ``_cam_act``), the seed (classes
+        ``targets``, or the argmax written to ``cls``), the gradient at that output, the map rows of ``cam``."""
+        S, M, _ = data_dev.shape
+        N, P, order = self._cam_level(li)
+        windows = torch.arange(S, dtype=torch.int32, device=self.device)
+        was_training = self.training_mode
+        self.training_mode, self._saliency_pass, self._cam_layer = False, True, li
+        try:
+            for begin in range(0, S, bs):
+                end = min(begin + bs, S)
+                nw = end - begin
+                x = self._saliency_batch(data_dev, windows[begin:end], bs)
+                with torch.enable_grad():
+                    logits = self._inference_storage(self.as_internal(x), 1)
+                A, self._cam_act = self._cam_act, None
+                dz = ops.saliency_seed(logits, targets[begin:end] if targets is not None else None, 1, nw, score,
+                                       cls_out=cls[begin:end] if targets is None else None)
+                G, = torch.autograd.grad(logits, A, dz)
+                ops.gradcam_map(A, G, method, order, nw, N, P, relu, cam[begin:end])
+        finally:
+            self.training_mode, self._saliency_pass, self._cam_layer, self._cam_act = was_training, False, None, None
+
+    def _cam_tap(self, i, x):
+        """Inside a Grad-CAM pass: layer ``i``'s output ``x`` (plane storage), made the tensor the input gradient stops at."""
+        if i != self._cam_layer:
+            return x
+        x = x.detach().requires_grad_(True)
+        self._cam_act = x
+        return x
+
+    def _cam_grad_mode(self, i):
+        """Autograd for layer ``i`` inside a Grad-CAM pass: off up to the layer whose output the gradient stops at."""
+        return torch.no_grad() if (self._cam_layer is not None and i <= self._cam_layer) else contextlib.nullcontext()
 
     def fit(self, train_data, train_labels, val_data, val_labels, best_checkpoint_dir=None):
         """Mini-batch training loop (:112-184): ``int(num_epochs*S/batch)`` steps, samples
@@ -1274,12 +1381,11 @@ class cgcnn(base_model):
             nl = len(self.p)
             for i in range(nl):
                 if self.p[i] > 1:
-                    src = self._orders[i]
-                    dst = self._orders[i + 1] if i + 1 < nl else None      # the head reads the last pooled level in the reference's order
+                    src, dst = self._orders[i], self._output_order(i)
                     if src is not None or dst is not None:
                         self._pool_maps[i] = ops.pool_maps(int(self.p[i]), src, dst, self.L[i].shape[0], dev)
             # the order the LAST conv layer's output is in: what the first FC layer's rows follow
-            if self.p[-1] == 1 and self._orders[-1] is not None:
+            if self._output_order(nl - 1) is not None:
                 self._vtabs['head'] = self._vtabs[nl - 1]
             if self._orders[0] is not None:                 # the input level: staging and batches (InternalPlanes)
                 order = self._orders[0]
@@ -1304,6 +1410,27 @@ class cgcnn(base_model):
                           regularization=regularization, dropout=dropout, batch_size=batch_size,
                           eval_frequency=eval_frequency, dir_name=dir_name)
         self.build_graph((M_0, channel))
+
+    def _output_order(self, i):
+        """The internal order (internal position -> reference vertex, None: the reference's) conv layer ``i``'s output is in:
+        the next layer's level, or, behind the last layer, its own level when it does not pool (the head reads the last pooled
+        level in the reference's order)."""
+        if i + 1 < len(self.p):
+            return self._orders[i + 1]
+        return self._orders[i] if self.p[i] == 1 else None
+
+    def _cam_level(self, i):
+        """(N, P, order) of conv layer ``i``'s output for ``gradcam``: its vertices, the input vertices each one covers, and its
+        internal order as an int32 device table (None: the reference's)."""
+        N = int(self.L[i].shape[0]) // int(self.p[i])
+        return N, self._M0 // N, self._cam_order(self._output_order(i))
+
+    def _cam_order(self, order):
+        if order is None:
+            return None
+        if id(order) not in self._cam_orders:
+            self._cam_orders[id(order)] = (order, torch.as_tensor(np.asarray(order, np.int32)).to(self.device))
+        return self._cam_orders[id(order)][1]
 
     @property
     def contraction(self):
@@ -1502,10 +1629,12 @@ class cgcnn(base_model):
         """Layer loop + head (:658-682) on a logical [N, M, channel] tensor."""
         if x.is_meta or not self._fusable():
             for i in range(len(self.p)):
-                with self.variable_scope('conv{}'.format(i + 1)):
+                with self.variable_scope('conv{}'.format(i + 1)), self._cam_grad_mode(i):
                     x = self.filter(x, self.L[i], self.F[i], self.K[i])
                     x = self.brelu(x)
                     x = self.pool(x, self.p[i])
+                if i == self._cam_layer:
+                    x = ops.plane_view(self._cam_tap(i, ops.plane_storage(x)), x.shape[1])
             N, M, F = x.shape
             h = torch.empty((N, M), device='meta') if x.is_meta else ops.FeatureMean.apply(ops.plane_storage(x), int(M))
             return self._head(h, dropout)
@@ -1556,14 +1685,17 @@ class cgcnn(base_model):
             done = (lambda layer=i + 1: self._dp.layer_done(layer)) if (direct and self._dp is not None) else None
             # the last layer feeds tf.reduce_mean(x, -1) (:673) only: where the kernel can, it returns that mean and never
             # stores its own output; its gradients read one plane per window
-            mean = bool(i + 1 == nl and self.fuse_feature_mean and
+            # (a Grad-CAM pass at the top layer differentiates to its stored output: no fused mean there)
+            mean = bool(i + 1 == nl and self.fuse_feature_mean and self._cam_layer != i and
                         ops.conv_mean_supported(B, g.M, x.shape[1], self.K[i], self.F[i], self.p[i], True, self.contraction))
-            x = ops.cheb_conv(x, W, b, g, self.K[i], self.p[i], pool_kind, True,
-                              BIAS_VERTEX if per_vertex else BIAS_FILTER, stack=stack, out=out,
-                              dW=W.grad if direct else None, dbias=b.grad if direct else None,
-                              precision=self.contraction, done=done, mean=mean, pool_maps=self._pool_maps[i], Wt=Wts.get(i),
-                              link_in=links[i - 1] if (links and i > 0) else None,
-                              link_out=links[i] if (links and i + 1 < nl) else None)
+            with self._cam_grad_mode(i):
+                x = ops.cheb_conv(x, W, b, g, self.K[i], self.p[i], pool_kind, True,
+                                  BIAS_VERTEX if per_vertex else BIAS_FILTER, stack=stack, out=out,
+                                  dW=W.grad if direct else None, dbias=b.grad if direct else None,
+                                  precision=self.contraction, done=done, mean=mean, pool_maps=self._pool_maps[i], Wt=Wts.get(i),
+                                  link_in=links[i - 1] if (links and i > 0) else None,
+                                  link_out=links[i] if (links and i + 1 < nl) else None)
+            x = self._cam_tap(i, x)
             stack = next_stack
         M_last = self.graphs[-1].M // self.p[-1]
         if mean:
@@ -1816,6 +1948,12 @@ class finetuning_cgcnn(cgcnn):
 
     saliency_maps = saliency
 
+    def _cam_level(self, i):
+        if i + 1 < len(self.p):
+            return super()._cam_level(i)
+        N = self._M_top                                 # the head's input: the top layer before its pooling
+        return N, self._M0 // N, self._head_order
+
     def state_dict(self):
         """Every variable under its reference name and shape, the optimizer moments of the trained ones, the step counter and
         the architecture record."""
@@ -1912,6 +2050,8 @@ class finetuning_cgcnn(cgcnn):
             g = self.graphs[i]
             W = self._params['conv%d/weights' % (i + 1)]
             b = self._params['conv%d/bias' % (i + 1)]
+            if self._saliency_pass:
+                W, b = W.detach(), b.detach()
             top = i + 1 == nl
             out = next_stack = None
             if not top and g.M // self.p[i] == self.graphs[i + 1].M:
@@ -1919,12 +2059,16 @@ class finetuning_cgcnn(cgcnn):
                                          device=x.device)
                 out = next_stack[0]
             trained = i >= lo and W.requires_grad
-            with (contextlib.nullcontext() if i >= lo else torch.no_grad()):
+            # (a Grad-CAM pass: autograd from the layer above the one it stops at, on detached variables)
+            grad_mode = (self._cam_grad_mode(i) if self._cam_layer is not None else
+                         contextlib.nullcontext() if i >= lo else torch.no_grad())
+            with grad_mode:
                 x = ops.cheb_conv(x, W, b, g, self.K[i], 1 if top else self.p[i], pool_kind, True,
                                   BIAS_VERTEX if per_vertex else BIAS_FILTER, stack=stack, out=out,
                                   dW=W.grad if trained else None, dbias=b.grad if trained else None,
                                   precision=self.contraction, pool_maps=None if top else self._pool_maps[i], Wt=Wts.get(i),
                                   link_in=links.get(i - 1), link_out=links.get(i))
+            x = self._cam_tap(i, x)
             stack = next_stack
         return self._head(x, dropout)
 
@@ -1940,7 +2084,7 @@ class finetuning_cgcnn(cgcnn):
         if x.is_meta:
             return self.fc(x, Mout, relu)
         W = self._weight_variable([self._M_top * self.F[-1], Mout], regularization=True)
-        b = self._bias_variable([Mout], regularization=True)
+        b = self._bias_variable([Mout], regularization=True)           # (detached inside a saliency-style pass)
         direct = self.training_mode and torch.is_grad_enabled()
         return ops.FlatFC.apply(x, W, b, self._head_order, self._M_top, relu, W.grad if direct else None,
                                 b.grad if direct else None)
@@ -2028,6 +2172,13 @@ class model_perf(object):
         ``(maps, counts)``."""
         model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
         return model.occlusion_maps(data, labels, **kw)
+
+    def gradcam_maps(s, ckp_path, data, labels, target_name=None, batch_size=128, **kw):
+        """Per-class mean Grad-CAM maps (``base_model.gradcam_maps``; ``kw``: its keywords) of the model ``predict`` would
+        restore from ``ckp_path``.  ``target_name`` is accepted for symmetry with ``predict`` and not used.  Returns
+        ``(maps, counts)``."""
+        model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
+        return model.gradcam_maps(data, labels, **kw)
 
     def predict(s, ckp_path, test_data, test_labels, target_name=None, batch_size=128, trial_dura=17,
                 flag_starttr=False, sub_name=None, model=None, config=None):

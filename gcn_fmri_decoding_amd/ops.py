@@ -1466,3 +1466,41 @@ def occlusion_class_sums(drop, cls, acc):
                        lambda: _lib.lib().chebgcn_occlusion_class_sums(_p(drop), _p(cls), S, G, C, _p(acc), _stream())),
                'occlusion_class_sums')
     return acc
+
+
+# ------------------------------------------------------------------------------------
+# Grad-CAM maps (base_model.gradcam): the two kernels of csrc/gradcam.hip behind the pass that stops at a layer
+# ------------------------------------------------------------------------------------
+
+GRADCAM_METHODS = {'gradcam': 0, 'grad_x_activation': 1}
+
+
+def gradcam_map(A, G, method, order, nw, N, P, relu, out):
+    """Rows ``out`` [nw, N*P] (float32, the caller's input vertex order) of the windows' maps from a layer's activation ``A`` and
+    its gradient ``G`` (plane storage [>= nw, F, Mp(N)] in the level's internal order ``order``: int32 device, internal position
+    -> reference vertex, or None): 'gradcam' weighs the filters by the mean of G over the level's vertices
+    (chebgcn_gradcam_weights), 'grad_x_activation' takes G itself; chebgcn_gradcam_map sums over the filters, applies ReLU and
+    writes each level vertex to its P input vertices."""
+    _require_cuda(A, G, order, out)
+    A = A.detach()
+    G = G.detach()
+    A = A if A.is_contiguous() else A.contiguous()
+    G = G if G.is_contiguous() else G.contiguous()
+    B, F, Mp = A.shape
+    if (tuple(G.shape) != (B, F, Mp) or Mp != plane_stride(N) or B < nw or out.dtype != torch.float32
+            or not out.is_contiguous() or tuple(out.shape) != (nw, N * P)
+            or (order is not None and (order.dtype != torch.int32 or order.numel() != N))):
+        raise ValueError('gradcam_map: A and G [>= %d, F, %d], out float32 [%d, %d], order int32 [%d]'
+                         % (nw, plane_stride(N), nw, N * P, N))
+    L = _lib.lib()
+    alpha = None
+    if GRADCAM_METHODS[method] == 0:
+        alpha = torch.empty((nw, F), dtype=torch.float32, device=A.device)
+        _lib.check(_launch('gradcam_weights', 4.0 * nw * F * (N + 1), 0.0, lambda: L.chebgcn_gradcam_weights(
+            _p(G), nw, F, N, _p(alpha), _stream())), 'gradcam_weights')
+    # A (and G per vertex) over the level's vertices, the order table, the rows written
+    nbytes = 4.0 * (nw * F * N * (1 + (alpha is None)) + (N if order is not None else 0) + nw * N * P)
+    _lib.check(_launch('gradcam_map', nbytes, 2.0 * nw * F * N, lambda: L.chebgcn_gradcam_map(
+        _p(A), _p(G) if alpha is None else None, _p(alpha), _p(order), nw, F, N, P, int(bool(relu)), _p(out), N * P,
+        _stream())), 'gradcam_map')
+    return out

@@ -540,6 +540,20 @@ int chebgcn_occlusion_score(const float* logits, int64_t r0, int R, int S, int G
 int chebgcn_occlusion_class_sums(const float* drop, const int64_t* cls, int S, int G, int ncls, double* acc,
                                  chebgcn_stream stream);
 
+/* ---- Grad-CAM maps: class activation maps at a conv layer (models_gcn.base_model.gradcam) --------------------------------
+ * A: the layer's activation, G = ds/dA its gradient (the library's input-gradient kernels, stopped at the layer); both plane
+ * storage [>= nw][F][Mp(N)] over the N vertices of the layer's level in its internal order, 16-byte aligned.  Only the real
+ * positions i < N are read (the pad may hold anything).  Fixed-order sums throughout; no atomics.
+ *
+ * weights: alpha[r][f] = (1/N) sum_{i<N} G[r][f][i] for the rows r < nw (float32 [nw][F]; the sum in float64, in order).
+ * map: cam_i = sum_f alpha[r][f] A[r][f][i] (G NULL, alpha given: Grad-CAM) or sum_f G[r][f][i] A[r][f][i] (alpha NULL, G
+ *   given: gradient x activation), filters in order, max(0, .) when relu != 0.  order: int32 [N] internal position -> reference
+ *   vertex of the level (NULL: identity).  Reference vertex j covers the P (a power of two) input vertices [j P, (j + 1) P):
+ *     out[r * ldo + j P + q] = cam_i,  j = order[i],  q < P,  r < nw  (ldo >= N P; nothing else is written). */
+int chebgcn_gradcam_weights(const float* G, int nw, int F, int N, float* alpha, chebgcn_stream stream);
+int chebgcn_gradcam_map(const float* A, const float* G, const float* alpha, const int32_t* order, int nw, int F, int N, int P,
+                        int relu, float* out, int64_t ldo, chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose
