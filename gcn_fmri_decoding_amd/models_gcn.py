@@ -26,9 +26,11 @@ import numpy as np
 import torch
 import torch.nn.functional as Fnn
 
+from . import _lib
 from . import graph as graph_mod
 from . import ops
 from ._lib import BIAS_FILTER, BIAS_NONE, BIAS_VERTEX, POOL_AVG, POOL_MAX, plane_stride
+from .attribution import Attribution
 
 
 class _Spec:
@@ -86,8 +88,9 @@ class InternalPlanes(object):
         return self
 
 
-class base_model(object):
-    """Counterpart of ``base_model`` (:18-355): run-time interface + variable helpers."""
+class base_model(Attribution):
+    """Counterpart of ``base_model`` (:18-355): run-time interface + variable helpers.  The attribution maps (``saliency``,
+    ``occlusion``, ``gradcam`` and their ``*_maps``) come from ``attribution.Attribution``."""
 
     def __init__(self, config=None):
         self.regularizers = []          # names of L2-regularised variables (:345, :353)
@@ -113,6 +116,7 @@ class base_model(object):
         self._step_graph_on, self._sg, self._sg_warm = False, None, 0      # enable_step_graph()
         self._step_graph_user = None    # the caller's explicit enable_step_graph(True / False), None = never asked
         self._order = None              # internal vertex order of the INPUT level (cgcnn: graph.length_order), None = the caller's
+        self._order_dev = None          # ... as an int32 device table (what the gather kernels take)
         self._vtabs = {}                # per-variable vertex orders (_Spec.vkey -> index tables), empty = the caller's everywhere
         self.record_fit = False         # keep the sampled indices and the loss_average series of fit()
         # How the reported ``loss_average`` reads the 0.9-EMA of the loss (:269-275).  The reference calls
@@ -122,12 +126,9 @@ class base_model(object):
         # (shadow / (1 - 0.9^t): the first value is the loss).  Reporting only; the default follows TF >= 1.0, set
         # ``ema_zero_debias = True`` (or CHEBGCN_EMA_ZERO_DEBIAS=1) for the 0.12 reading.  Unverifiable here (no TensorFlow).
         self.ema_zero_debias = os.environ.get('CHEBGCN_EMA_ZERO_DEBIAS', '0') not in ('0', '', 'false', 'False')
-        # inside saliency() / occlusion(): the layers see their variables without gradient (no weight, bias-gradient or
-        # optimizer work), and the head runs on the library's FC kernels at every size they serve (no vendor GEMM)
-        self._saliency_pass = False
-        # inside gradcam(): the conv layer (index) whose output the input gradient stops at, and that output once a pass made it
-        self._cam_layer, self._cam_act = None, None
-        self._cam_orders = {}           # id(vertex order) -> (that order, its int32 device table)
+        # inside saliency() / occlusion() / gradcam(): the attribution.Pass the layers read -- they see their variables without
+        # gradient (no weight, bias-gradient or optimizer work), and the head runs on the library's FC kernels (no vendor GEMM)
+        self._pass = None
 
     # ---------------------------------------------------------------- run-time API
 
@@ -147,10 +148,19 @@ class base_model(object):
         S, M, C = data_dev.shape
         if out is None or tuple(out.shape) != (int(idx.numel()), C, ops.plane_stride(M)):
             out = ops.plane_empty(int(idx.numel()), C, M, self.device)
-        from . import _lib
-        _lib.check(_lib.lib().chebgcn_perm_data(ops._p(data_dev), ops._p(self._order_dev) if self._order is not None else None,
-                                                ops._p(idx), ops._p(out), int(idx.numel()), M, M, C, ops._stream()), 'perm_data')
+        _lib.check(_lib.lib().chebgcn_perm_data(ops._p(data_dev), ops._p(self._order_dev), ops._p(idx), ops._p(out),
+                                                int(idx.numel()), M, M, C, ops._stream()), 'perm_data')
         return self.as_internal(out)
+
+    def _gather_padded(self, data_dev, idx, R):
+        """The windows ``idx`` gathered like ``_gather`` and zero-padded to ``R`` rows, the way the reference pads the last
+        batch of a prediction (:50-54); the plain tensor, in the internal vertex order."""
+        x = self._gather(data_dev, idx).planes
+        if x.shape[0] < R:
+            pad = ops.plane_empty(R, x.shape[1], data_dev.shape[1], self.device, zero=True)
+            pad[:x.shape[0]] = x
+            x = pad
+        return x
 
     # ---- internal vertex order (cgcnn.vertex_order) -----------------------------------------------------------------
     def compose_perm(self, perm=None):
@@ -194,12 +204,8 @@ class base_model(object):
         try:
             for begin in range(0, size, self.batch_size):
                 end = min(begin + self.batch_size, size)
-                idx = np.arange(begin, end)
-                x = self._gather(data_dev, torch.as_tensor(idx, dtype=torch.int32).to(self.device))
-                if end - begin < self.batch_size:
-                    pad = ops.plane_empty(self.batch_size, x.shape[1], data_dev.shape[1], self.device, zero=True)
-                    pad[:end - begin] = x.planes
-                    x = self.as_internal(pad)
+                idx = torch.as_tensor(np.arange(begin, end), dtype=torch.int32).to(self.device)
+                x = self.as_internal(self._gather_padded(data_dev, idx, self.batch_size))
                 with torch.no_grad():
                     logits = self._inference_storage(x, 1)
                     batch_pred = self.prediction(logits)
@@ -241,373 +247,6 @@ class base_model(object):
         # (the reference appends a 'time:' line only ``if sess is None``, which never holds there:
         # its local ``sess`` comes out of ``_get_session`` and is always a session, :88, :107-109)
         return string, accuracy, f1, loss
-
-    # ---------------------------------------------------------------- saliency maps
-
-    def saliency(self, data, target='predicted', score='logit', method='gradient', steps=32, baseline=None, batch_size=None,
-                 labels=None):
-        """Attribution of each window's class score to its inputs.  ``data``: ``[S, M, channel]`` as for ``predict`` (NumPy,
-        or a tensor from ``stage()``), in the caller's vertex order.  Returns ``(attr, target)``: float32 ``[S, M, channel]`` in
-        the order of ``data`` (fake vertices included) and the int64 class ``[S]`` each window was attributed to.
-
-        * ``target``: ``'predicted'`` (the window's own argmax, ``prediction()``'s tie rule), ``'label'`` (the int array
-          ``labels=`` ``[S]``), an int, or an int array ``[S]``; classes lie in ``[0, M[-1])``.
-        * ``score``: ``'logit'`` (z_c) or ``'logprob'`` (log softmax(z)_c).
-        * ``method``: ``'gradient'`` (ds/dx), ``'grad_x_input'`` (x * ds/dx), ``'integrated'`` ((x - x0) * the mean of ds/dx at
-          x0 + a_j (x - x0), a_j = (j + 1/2)/steps; ``baseline`` x0: None = zeros, or ``[M, channel]``; the class is decided at
-          x and held along the path).
-        * Dropout is off.  ``batch_size`` (default the model's): rows of one pass -- windows for the first two methods (the last
-          batch zero-padded like ``predict``), ``max(1, batch_size // steps)`` windows of ``steps`` rows each for
-          ``'integrated'``.
-
-        One pass per batch: the forward with the ReLU masks, then the training step's input-gradient kernels -- no weight or bias
-        gradient, no optimizer, nothing the model keeps is written."""
-        S, targets, _, base, bs = self._saliency_args(data, target, labels, score, method, steps, baseline, batch_size)
-        data_dev = self.stage(data)
-        M, C = data_dev.shape[1], data_dev.shape[2]
-        attr = torch.empty((S, M, C), dtype=torch.float32, device=self.device)
-        cls = torch.empty(S, dtype=torch.int64, device=self.device)
-        if targets is not None:
-            cls.copy_(torch.as_tensor(targets))
-        self._saliency_run(data_dev, cls if targets is not None else None, score, method, steps, base, bs, cls, attr)
-        return attr.cpu().numpy(), cls.cpu().numpy()
-
-    def saliency_maps(self, data, labels, absolute=False, score='logit', method='gradient', steps=32, baseline=None,
-                      batch_size=None):
-        """Per-class mean attribution: window w (target = its label) adds ``saliency``'s map -- ``|map|`` with ``absolute`` --
-        to the sum of class ``labels[w]``.  Returns ``(maps, counts)``: float64 ``[C, M, channel]`` (C = M[-1]; the mean, zero
-        for a class without windows) and int64 ``[C]``.  The sums run on the device in float64, windows in order within a
-        batch, batches in order; the per-window maps never leave the device."""
-        S, _, labels, base, bs = self._saliency_args(data, 'label', labels, score, method, steps, baseline, batch_size)
-        data_dev = self.stage(data)
-        M, C = data_dev.shape[1], data_dev.shape[2]
-        ncls = int(self.M[-1])
-        acc = torch.zeros((ncls, M, C), dtype=torch.float64, device=self.device)
-        labels_dev = torch.as_tensor(labels).to(self.device)
-        self._saliency_run(data_dev, labels_dev, score, method, steps, base, bs, None, None, absolute=absolute, acc=acc)
-        counts = np.bincount(labels, minlength=ncls).astype(np.int64)
-        maps = acc.cpu().numpy()
-        maps /= np.maximum(counts, 1)[:, None, None]         # in place, one pass (a class without windows stays 0)
-        return maps, counts
-
-    def _saliency_args(self, data, target, labels, score, method, steps, baseline, batch_size, who='saliency', channels=True):
-        """Checks every argument of ``saliency`` / ``saliency_maps`` before any device work; returns (S, targets int64 [S] or
-        None for 'predicted', labels, baseline as a device tensor or None, batch size).  ``who`` names the caller in the
-        messages (``occlusion`` and ``gradcam`` share these checks); ``channels=False`` skips the channel limit of the saliency
-        kernels, which ``gradcam`` does not run."""
-        if score not in ops.SCORES:
-            raise ValueError(who + ': score must be one of %s, got %r' % (sorted(ops.SCORES), score))
-        if method not in ops.SALIENCY_METHODS:
-            raise ValueError(who + ': method must be one of %s, got %r' % (sorted(ops.SALIENCY_METHODS), method))
-        integrated = method == 'integrated'
-        if integrated and (isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= 65535):
-            raise ValueError(who + ': steps must be an int in [1, 65535], got %r' % (steps,))
-        bs = self.batch_size if batch_size is None else batch_size
-        if isinstance(bs, bool) or not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 65535:
-            raise ValueError(who + ': batch_size must be an int in [1, 65535], got %r' % (batch_size,))
-        shape = tuple(int(d) for d in data.shape)
-        want = (int(self._M0), int(self.channel))
-        if len(shape) != 3 or shape[1:] != want or shape[0] == 0:
-            raise ValueError(who + ': data must be [S, %d, %d] with S > 0, got %s' % (want + (shape,)))
-        from . import _lib
-        if channels and not _lib.lib().chebgcn_saliency_supported(want[1]):
-            raise ValueError(who + ': %d channels are more than the saliency kernels serve (chebgcn_saliency_supported)'
-                             % want[1])
-        S, n_classes = shape[0], int(self.M[-1])
-
-        def classes(v, what):
-            a = np.asarray(v)
-            if a.shape != (S,) or not np.issubdtype(a.dtype, np.integer):
-                raise ValueError(who + ': %s must be an int array of shape [%d], got %s %s' % (what, S, a.dtype, a.shape))
-            a = a.astype(np.int64)
-            if a.min() < 0 or a.max() >= n_classes:
-                raise ValueError(who + ': %s must lie in [0, %d); got %d ... %d' % (what, n_classes, a.min(), a.max()))
-            return a
-        if labels is not None:
-            labels = classes(labels, 'labels')
-        if isinstance(target, str):
-            if target == 'predicted':
-                targets = None
-            elif target == 'label':
-                if labels is None:
-                    raise ValueError(who + ": target='label' needs labels")
-                targets = labels
-            else:
-                raise ValueError(who + ": target must be 'predicted', 'label', an int or an int array, got %r" % target)
-        elif isinstance(target, (int, np.integer)) and not isinstance(target, bool):
-            if not 0 <= int(target) < n_classes:
-                raise ValueError(who + ': target %d is not a class in [0, %d)' % (int(target), n_classes))
-            targets = np.full(S, int(target), np.int64)
-        else:
-            targets = classes(target, 'target')
-        if baseline is not None:
-            baseline = np.asarray(baseline, np.float32)
-            if baseline.shape != want:
-                raise ValueError(who + ': baseline must be [%d, %d], got %s' % (want + (baseline.shape,)))
-        if self.device.type != 'cuda':
-            raise RuntimeError(who + ': the model has no device to run on (%s)' % self.device)
-        base = torch.as_tensor(baseline).to(self.device) if baseline is not None else None
-        return S, targets, labels, base, int(bs)
-
-    def _saliency_batch(self, data_dev, idx, R):
-        """The windows ``idx`` gathered into plane storage, zero-padded to ``R`` rows like ``predict``."""
-        x = self._gather(data_dev, idx).planes
-        if x.shape[0] < R:
-            pad = ops.plane_empty(R, x.shape[1], data_dev.shape[1], self.device, zero=True)
-            pad[:x.shape[0]] = x
-            x = pad
-        return x
-
-    def _saliency_run(self, data_dev, targets, score, method, steps, base, bs, cls, attr, absolute=False, acc=None):
-        """The passes of ``saliency`` / ``saliency_maps``: per batch, the forward with masks on inputs that need a gradient
-        and variables that do not, the seed, the input gradient (autograd over the library's layers), the reduction into
-        ``attr`` rows or the class sums ``acc`` (classes ``targets``)."""
-        S, M, C = data_dev.shape
-        integrated = method == 'integrated'
-        m = int(steps) if integrated else 1
-        wpp = max(1, bs // m) if integrated else bs
-        R = wpp * m
-        order = self._order_dev if self._order is not None else None
-        windows = torch.arange(S, dtype=torch.int32, device=self.device)
-        rows = torch.empty((wpp, M, C), dtype=torch.float32, device=self.device) if attr is None else None
-        was_training = self.training_mode
-        self.training_mode, self._saliency_pass = False, True
-        try:
-            if integrated and targets is None:
-                # the class is decided at x itself and held fixed along the path
-                with torch.no_grad():
-                    for begin in range(0, S, bs):
-                        end = min(begin + bs, S)
-                        logits = self._inference_storage(self.as_internal(self._saliency_batch(data_dev, windows[begin:end], bs)), 1)
-                        ops.saliency_seed(logits, None, 1, end - begin, score, cls_out=cls[begin:end], want_grad=False)
-                targets = cls
-            for begin in range(0, S, wpp):
-                end = min(begin + wpp, S)
-                nw, idx = end - begin, windows[begin:end]
-                if integrated:
-                    x = ops.saliency_path(data_dev, order, idx, base, R, m, M)
-                else:
-                    x = self._saliency_batch(data_dev, idx, R)
-                x.requires_grad_(True)
-                with torch.enable_grad():
-                    logits = self._inference_storage(self.as_internal(x), 1)
-                dz = ops.saliency_seed(logits, targets[begin:end] if targets is not None else None, m, nw * m, score,
-                                       cls_out=cls[begin:end] if targets is None else None)
-                dx, = torch.autograd.grad(logits, x, dz)
-                ops.saliency_reduce(dx, data_dev, order, idx, base, m, method, absolute,
-                                    attr[begin:end] if attr is not None else rows[:nw],
-                                    targets[begin:end] if acc is not None else None, acc)
-        finally:
-            self.training_mode, self._saliency_pass = was_training, False
-
-    # ---------------------------------------------------------------- occlusion maps
-
-    def occlusion(self, data, target='predicted', score='logit', groups=None, baseline=None, batch_size=None, labels=None):
-        """How much each window's class score falls when a group of its vertices is set to a baseline ("virtual lesion").
-        ``data``: ``[S, M, channel]`` as for ``predict`` (NumPy, or a tensor from ``stage()``), in the caller's vertex order.
-        Returns ``(drop, target)``: float32 ``[S, G]`` with ``drop[w, g] = s_c(x_w) - s_c(x_w with group g's vertices set to
-        the baseline)``, and the int64 class ``[S]`` each window was scored for.
-
-        * ``groups``: an int array ``[M]`` in the caller's order with values in ``[-1, G)``; ``-1`` never occludes a vertex, and
-          every id in ``[0, G)`` must occur.  ``None``: one group per vertex (``G = M``, fake vertices included).  In the
-          coarsening's tree order (``coarsening.perm_data`` data) ``groups = np.arange(M) >> j`` occludes the clusters of
-          level ``j``, ``2**j`` vertices each.
-        * ``baseline``: ``None`` (zeros) or ``[M, channel]`` in the caller's order.
-        * ``target``, ``labels``, ``score``: as for ``saliency``.  The class is decided on the unoccluded window and held for
-          all of its rows.
-        * Dropout is off.  ``batch_size`` (default the model's): forward rows of one pass.  Rows are (window, group) pairs,
-          ``G + 1`` per window (the window itself first), window-major: a pass may hold part of a window or several windows,
-          and the last one is zero-padded like ``predict``.  A call costs ``S * (G + 1)`` forward rows.
-
-        Only the inference kernels run, plus three small ones (chebgcn_occlusion_rows / _score, chebgcn_saliency_seed); nothing
-        the model keeps is written."""
-        S, targets, _, base, bs, gid, G = self._occlusion_args(data, target, labels, score, groups, baseline, batch_size)
-        data_dev = self.stage(data)
-        drop = torch.empty((S, G), dtype=torch.float32, device=self.device)
-        cls = torch.empty(S, dtype=torch.int64, device=self.device)
-        if targets is not None:
-            cls.copy_(torch.as_tensor(targets))
-        self._occlusion_run(data_dev, targets is None, score, gid, G, base, bs, cls, drop)
-        return drop.cpu().numpy(), cls.cpu().numpy()
-
-    def occlusion_maps(self, data, labels, score='logit', groups=None, baseline=None, batch_size=None):
-        """Per-class mean occlusion drop: window w (target = its label) adds its ``occlusion`` row to the sum of class
-        ``labels[w]``.  Returns ``(maps, counts)``: float64 ``[C, G]`` (C = M[-1]; the mean, zero for a class without windows)
-        and int64 ``[C]``.  The sums run on the device in float64, windows in order; the per-window table never leaves the
-        device."""
-        S, _, labels, base, bs, gid, G = self._occlusion_args(data, 'label', labels, score, groups, baseline, batch_size)
-        data_dev = self.stage(data)
-        ncls = int(self.M[-1])
-        drop = torch.empty((S, G), dtype=torch.float32, device=self.device)
-        cls = torch.as_tensor(labels).to(self.device)
-        self._occlusion_run(data_dev, False, score, gid, G, base, bs, cls, drop)
-        acc = torch.zeros((ncls, G), dtype=torch.float64, device=self.device)
-        ops.occlusion_class_sums(drop, cls, acc)
-        counts = np.bincount(labels, minlength=ncls).astype(np.int64)
-        maps = acc.cpu().numpy()
-        maps /= np.maximum(counts, 1)[:, None]
-        return maps, counts
-
-    def _occlusion_args(self, data, target, labels, score, groups, baseline, batch_size):
-        """Checks every argument of ``occlusion`` / ``occlusion_maps`` before any device work (``_saliency_args`` for the ones
-        they share); returns those of ``_saliency_args``, then the group of each internal position as int32 ``[Mp]`` on the
-        device (-1 on the pad) and G."""
-        M = int(self._M0)
-        if groups is None:
-            g = np.arange(M, dtype=np.int64)
-        else:
-            a = np.asarray(groups)
-            if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or a.shape != (M,):
-                raise ValueError('occlusion: groups must be an int array of shape [%d], got %s %s' % (M, a.dtype, a.shape))
-            g = a.astype(np.int64)
-            if g.min() < -1:
-                raise ValueError('occlusion: groups must lie in [-1, G) (-1: never occluded); got %d' % g.min())
-            if g.max() < 0:
-                raise ValueError('occlusion: groups holds no group (every entry is -1)')
-            empty = np.flatnonzero(np.bincount(g[g >= 0], minlength=int(g.max()) + 1) == 0)
-            if len(empty):
-                raise ValueError('occlusion: groups must use every id in [0, %d); %d of them occur nowhere (first %d)'
-                                 % (int(g.max()) + 1, len(empty), empty[0]))
-        G = int(g.max()) + 1
-        from . import _lib
-        if not _lib.lib().chebgcn_occlusion_supported(int(self.channel)):
-            raise ValueError('occlusion: %d channels are more than the occlusion kernels serve (chebgcn_occlusion_supported)'
-                             % int(self.channel))
-        S, targets, labels, base, bs = self._saliency_args(data, target, labels, score, 'gradient', 1, baseline, batch_size,
-                                                           who='occlusion')
-        internal = g[self._order] if self._order is not None else g
-        gid = np.full(ops.plane_stride(M), -1, np.int32)
-        gid[:M] = internal
-        return S, targets, labels, base, bs, torch.as_tensor(gid).to(self.device), G
-
-    def _occlusion_run(self, data_dev, predicted, score, gid, G, base, bs, cls, drop):
-        """The passes of ``occlusion`` / ``occlusion_maps``: per pass of ``bs`` rows, the rows in plane storage, the forward
-        (no autograd, the variables detached, the head on the library's kernels), the class of the windows whose own row is
-        in the pass (``predicted``: its argmax, else ``cls`` as given), and the drops into ``drop``."""
-        S, M, _ = data_dev.shape
-        G1 = G + 1
-        total = S * G1
-        order = self._order_dev if self._order is not None else None
-        ref = torch.empty(S, dtype=torch.float32, device=self.device)
-        was_training = self.training_mode
-        self.training_mode, self._saliency_pass = False, True
-        try:
-            with torch.no_grad():
-                for r0 in range(0, total, bs):
-                    x = ops.occlusion_rows(data_dev, order, gid, base, r0, bs, G, M)
-                    logits = self._inference_storage(self.as_internal(x), 1)
-                    if predicted:
-                        w = -(-r0 // G1)                    # the first window whose own row is in this pass
-                        off = w * G1 - r0
-                        if w < S and off < bs:
-                            ops.saliency_seed(logits[off:], None, G1, min(bs - off, total - w * G1), score, cls_out=cls[w:],
-                                              want_grad=False)
-                    ops.occlusion_score(logits, r0, G, cls, score, ref, drop)
-        finally:
-            self.training_mode, self._saliency_pass = was_training, False
-
-    # ---------------------------------------------------------------- Grad-CAM maps
-
-    def gradcam(self, data, layer=None, target='predicted', score='logit', method='gradcam', relu=True, batch_size=None,
-                labels=None):
-        """Class activation maps of each window at a conv layer.  ``data``: ``[S, M, channel]`` as for ``predict`` (NumPy, or a
-        tensor from ``stage()``), in the caller's vertex order.  Returns ``(cam, target)``: float32 ``[S, M]`` at the input
-        resolution in the order of ``data`` (fake vertices included), and the int64 class ``[S]`` each window was scored for.
-
-        * ``layer``: ``'conv1'`` ... ``'conv<n>'``; ``None`` is the top conv layer.  Its activation ``A`` ``[F, N]`` is the
-          layer's output as the next stage reads it (after bias, ReLU and pooling; ``finetuning_cgcnn``'s top layer before its
-          pooling, as its flat head reads it) over the ``N`` vertices of that resolution, and ``G = ds/dA``.
-        * ``method``: ``'gradcam'`` (``cam_i = sum_f alpha_f A[f, i]``, ``alpha_f`` the mean of ``G[f]`` over the ``N``
-          vertices) or ``'grad_x_activation'`` (``cam_i = sum_f G[f, i] A[f, i]``).  ``relu``: ``max(0, cam)``.  At the top
-          layer of a ``cgcnn`` the head reads the feature mean, so ``G[f, i] = g_i / F`` is the same for every filter and
-          ``'gradcam'`` is ``ReLU(mean(alpha) * sum_f A[f, i])``: the per-vertex product is the map that stays informative there.
-        * Level vertex ``j`` (the coarsening's tree order) covers the input vertices ``[j P, (j + 1) P)``, ``P`` the product of
-          the pools up to the layer; each of them carries its value.
-        * ``target``, ``labels``, ``score``, ``batch_size``: as for ``saliency`` (``method='gradient'``).  Dropout is off.
-
-        One pass per batch: the layers up to ``layer`` without autograd, the layers above it, the head and the seed as a saliency
-        pass runs them (input-gradient kernels only), the gradient taken at the layer's output, then chebgcn_gradcam_weights /
-        _map.  Nothing the model keeps is written."""
-        S, targets, _, bs, li = self._gradcam_args(data, target, labels, score, layer, method, relu, batch_size)
-        data_dev = self.stage(data)
-        cam = torch.empty((S, data_dev.shape[1]), dtype=torch.float32, device=self.device)
-        cls = torch.empty(S, dtype=torch.int64, device=self.device)
-        if targets is not None:
-            cls.copy_(torch.as_tensor(targets))
-        self._gradcam_run(data_dev, cls if targets is not None else None, score, li, method, relu, bs, cls, cam)
-        return cam.cpu().numpy(), cls.cpu().numpy()
-
-    def gradcam_maps(self, data, labels, layer=None, score='logit', method='gradcam', relu=True, batch_size=None):
-        """Per-class mean Grad-CAM map: window w (target = its label) adds its ``gradcam`` row to the sum of class ``labels[w]``.
-        Returns ``(maps, counts)``: float64 ``[C, M]`` (C = M[-1]; the mean, zero for a class without windows) and int64 ``[C]``.
-        The sums run on the device in float64, windows in order; the per-window maps never leave the device."""
-        S, _, labels, bs, li = self._gradcam_args(data, 'label', labels, score, layer, method, relu, batch_size)
-        data_dev = self.stage(data)
-        ncls = int(self.M[-1])
-        cam = torch.empty((S, data_dev.shape[1]), dtype=torch.float32, device=self.device)
-        cls = torch.as_tensor(labels).to(self.device)
-        self._gradcam_run(data_dev, cls, score, li, method, relu, bs, None, cam)
-        acc = torch.zeros((ncls, data_dev.shape[1]), dtype=torch.float64, device=self.device)
-        ops.occlusion_class_sums(cam, cls, acc)
-        counts = np.bincount(labels, minlength=ncls).astype(np.int64)
-        maps = acc.cpu().numpy()
-        maps /= np.maximum(counts, 1)[:, None]
-        return maps, counts
-
-    def _gradcam_args(self, data, target, labels, score, layer, method, relu, batch_size):
-        """Checks every argument of ``gradcam`` / ``gradcam_maps`` before any device work (``_saliency_args`` for the ones they
-        share); returns (S, targets or None, labels, batch size, the layer's index)."""
-        nl = len(self.p)
-        names = ['conv%d' % (i + 1) for i in range(nl)]
-        if layer is None:
-            li = nl - 1
-        elif isinstance(layer, str) and layer in names:
-            li = names.index(layer)
-        else:
-            raise ValueError("gradcam: layer must be None or one of 'conv1' ... 'conv%d', got %r" % (nl, layer))
-        if not isinstance(method, str) or method not in ops.GRADCAM_METHODS:
-            raise ValueError('gradcam: method must be one of %s, got %r' % (sorted(ops.GRADCAM_METHODS), method))
-        if not isinstance(relu, (bool, np.bool_)):
-            raise ValueError('gradcam: relu must be True or False, got %r' % (relu,))
-        S, targets, labels, _, bs = self._saliency_args(data, target, labels, score, 'gradient', 1, None, batch_size,
-                                                        who='gradcam', channels=False)
-        return S, targets, labels, bs, li
-
-    def _gradcam_run(self, data_dev, targets, score, li, method, relu, bs, cls, cam):
-        """The passes of ``gradcam`` / ``gradcam_maps``: per batch of ``bs`` windows (the last one zero-padded), the forward
-        that stops autograd at layer ``li``'s output (``_cam_layer``; the layer leaves it in ``_cam_act``), the seed (classes
-        ``targets``, or the argmax written to ``cls``), the gradient at that output, the map rows of ``cam``."""
-        S, M, _ = data_dev.shape
-        N, P, order = self._cam_level(li)
-        windows = torch.arange(S, dtype=torch.int32, device=self.device)
-        was_training = self.training_mode
-        self.training_mode, self._saliency_pass, self._cam_layer = False, True, li
-        try:
-            for begin in range(0, S, bs):
-                end = min(begin + bs, S)
-                nw = end - begin
-                x = self._saliency_batch(data_dev, windows[begin:end], bs)
-                with torch.enable_grad():
-                    logits = self._inference_storage(self.as_internal(x), 1)
-                A, self._cam_act = self._cam_act, None
-                dz = ops.saliency_seed(logits, targets[begin:end] if targets is not None else None, 1, nw, score,
-                                       cls_out=cls[begin:end] if targets is None else None)
-                G, = torch.autograd.grad(logits, A, dz)
-                ops.gradcam_map(A, G, method, order, nw, N, P, relu, cam[begin:end])
-        finally:
-            self.training_mode, self._saliency_pass, self._cam_layer, self._cam_act = was_training, False, None, None
-
-    def _cam_tap(self, i, x):
-        """Inside a Grad-CAM pass: layer ``i``'s output ``x`` (plane storage), made the tensor the input gradient stops at."""
-        if i != self._cam_layer:
-            return x
-        x = x.detach().requires_grad_(True)
-        self._cam_act = x
-        return x
-
-    def _cam_grad_mode(self, i):
-        """Autograd for layer ``i`` inside a Grad-CAM pass: off up to the layer whose output the gradient stops at."""
-        return torch.no_grad() if (self._cam_layer is not None and i <= self._cam_layer) else contextlib.nullcontext()
 
     def fit(self, train_data, train_labels, val_data, val_labels, best_checkpoint_dir=None):
         """Mini-batch training loop (:112-184): ``int(num_epochs*S/batch)`` steps, samples
@@ -1225,7 +864,7 @@ class base_model(object):
         p = self._params[name]
         if tuple(p.shape) != tuple(shape):
             raise ValueError('variable %s has shape %s, requested %s' % (name, tuple(p.shape), tuple(shape)))
-        return p.detach() if self._saliency_pass else p
+        return p.detach() if self._pass is not None else p
 
     def _weight_variable(self, shape, regularization=True):
         """``tf.get_variable('weights', ...)`` in the current scope (:340-347)."""
@@ -1337,6 +976,7 @@ class cgcnn(base_model):
         self.graphs = []
         self._orders = [None] * len(self.L)             # per conv layer: internal position -> reference vertex of its level
         self._pool_maps = [None] * len(self.L)
+        self._cam_tables = [None] * len(self.L)         # per conv layer: its output's order as an int32 device table (_cam_level)
         self._relabelled = False
         if self.device.type == 'cuda':
             force = self.vertex_order == 'length!'          # experiments: relabel even where no kernel gains from it
@@ -1423,14 +1063,10 @@ class cgcnn(base_model):
         """(N, P, order) of conv layer ``i``'s output for ``gradcam``: its vertices, the input vertices each one covers, and its
         internal order as an int32 device table (None: the reference's)."""
         N = int(self.L[i].shape[0]) // int(self.p[i])
-        return N, self._M0 // N, self._cam_order(self._output_order(i))
-
-    def _cam_order(self, order):
-        if order is None:
-            return None
-        if id(order) not in self._cam_orders:
-            self._cam_orders[id(order)] = (order, torch.as_tensor(np.asarray(order, np.int32)).to(self.device))
-        return self._cam_orders[id(order)][1]
+        order = self._output_order(i)
+        if order is not None and self._cam_tables[i] is None:       # (made on first use: most models never run a Grad-CAM pass)
+            self._cam_tables[i] = torch.as_tensor(np.asarray(order, np.int32)).to(self.device)
+        return N, self._M0 // N, self._cam_tables[i]
 
     @property
     def contraction(self):
@@ -1603,7 +1239,7 @@ class cgcnn(base_model):
         b = self._bias_variable([Mout], regularization=True)
         if x.is_meta:
             return torch.empty((N, Mout), device='meta')
-        if self._saliency_pass:
+        if self._pass is not None:
             return ops.FCInputGrad.apply(x, W, b, relu)         # the input gradient alone, on the library's kernels
         if self.training_mode and torch.is_grad_enabled() and W.grad is not None and b.grad is not None:
             # training step: the layer writes its gradients straight into the flat gradient buffer (like the
@@ -1628,13 +1264,14 @@ class cgcnn(base_model):
     def _inference(self, x, dropout):
         """Layer loop + head (:658-682) on a logical [N, M, channel] tensor."""
         if x.is_meta or not self._fusable():
+            ps = self._pass
             for i in range(len(self.p)):
-                with self.variable_scope('conv{}'.format(i + 1)), self._cam_grad_mode(i):
+                with self.variable_scope('conv{}'.format(i + 1)), ps.grad_mode(i) if ps is not None else contextlib.nullcontext():
                     x = self.filter(x, self.L[i], self.F[i], self.K[i])
                     x = self.brelu(x)
                     x = self.pool(x, self.p[i])
-                if i == self._cam_layer:
-                    x = ops.plane_view(self._cam_tap(i, ops.plane_storage(x)), x.shape[1])
+                if ps is not None and i == ps.layer:
+                    x = ops.plane_view(ps.tap(i, ops.plane_storage(x)), x.shape[1])
             N, M, F = x.shape
             h = torch.empty((N, M), device='meta') if x.is_meta else ops.FeatureMean.apply(ops.plane_storage(x), int(M))
             return self._head(h, dropout)
@@ -1655,7 +1292,7 @@ class cgcnn(base_model):
         B = x.shape[0]
         per_vertex = getattr(self.brelu, '__func__', None) is cgcnn.b2relu
         pool_kind = POOL_AVG if getattr(self.pool, '__func__', None) is cgcnn.apool1 else POOL_MAX
-        stack = None
+        stack, ps = None, self._pass                   # (ps: inside an attribution call, None otherwise)
         # training: the weights of every layer that forms its input gradient by the forward recurrence on dy (ops.dx_by_forward),
         # re-indexed in ONE launch here -- they are constant within the step -- instead of one launch per layer inside backward
         Wts = {}
@@ -1673,7 +1310,7 @@ class cgcnn(base_model):
             g = self.graphs[i]
             W = self._params['conv%d/weights' % (i + 1)]
             b = self._params['conv%d/bias' % (i + 1)]
-            if self._saliency_pass:
+            if ps is not None:
                 W, b = W.detach(), b.detach()
             out = next_stack = None
             if i + 1 < nl and g.M // self.p[i] == self.graphs[i + 1].M:
@@ -1686,16 +1323,17 @@ class cgcnn(base_model):
             # the last layer feeds tf.reduce_mean(x, -1) (:673) only: where the kernel can, it returns that mean and never
             # stores its own output; its gradients read one plane per window
             # (a Grad-CAM pass at the top layer differentiates to its stored output: no fused mean there)
-            mean = bool(i + 1 == nl and self.fuse_feature_mean and self._cam_layer != i and
+            mean = bool(i + 1 == nl and self.fuse_feature_mean and (ps is None or ps.layer != i) and
                         ops.conv_mean_supported(B, g.M, x.shape[1], self.K[i], self.F[i], self.p[i], True, self.contraction))
-            with self._cam_grad_mode(i):
+            with ps.grad_mode(i) if ps is not None else contextlib.nullcontext():
                 x = ops.cheb_conv(x, W, b, g, self.K[i], self.p[i], pool_kind, True,
                                   BIAS_VERTEX if per_vertex else BIAS_FILTER, stack=stack, out=out,
                                   dW=W.grad if direct else None, dbias=b.grad if direct else None,
                                   precision=self.contraction, done=done, mean=mean, pool_maps=self._pool_maps[i], Wt=Wts.get(i),
                                   link_in=links[i - 1] if (links and i > 0) else None,
                                   link_out=links[i] if (links and i + 1 < nl) else None)
-            x = self._cam_tap(i, x)
+            if ps is not None:
+                x = ps.tap(i, x)
             stack = next_stack
         M_last = self.graphs[-1].M // self.p[-1]
         if mean:
@@ -2045,12 +1683,13 @@ class finetuning_cgcnn(cgcnn):
                                                  [(fins[i], self.K[i], self.F[i]) for i in idxs])
                 Wts = dict(zip(idxs, outs))
         links = {i: ops.GateLink() for i in range(lo, nl - 1)}
-        stack = None
+        stack, ps = None, self._pass
+        stops = ps is not None and ps.layer is not None
         for i in range(nl):
             g = self.graphs[i]
             W = self._params['conv%d/weights' % (i + 1)]
             b = self._params['conv%d/bias' % (i + 1)]
-            if self._saliency_pass:
+            if ps is not None:
                 W, b = W.detach(), b.detach()
             top = i + 1 == nl
             out = next_stack = None
@@ -2060,15 +1699,15 @@ class finetuning_cgcnn(cgcnn):
                 out = next_stack[0]
             trained = i >= lo and W.requires_grad
             # (a Grad-CAM pass: autograd from the layer above the one it stops at, on detached variables)
-            grad_mode = (self._cam_grad_mode(i) if self._cam_layer is not None else
-                         contextlib.nullcontext() if i >= lo else torch.no_grad())
+            grad_mode = ps.grad_mode(i) if stops else contextlib.nullcontext() if i >= lo else torch.no_grad()
             with grad_mode:
                 x = ops.cheb_conv(x, W, b, g, self.K[i], 1 if top else self.p[i], pool_kind, True,
                                   BIAS_VERTEX if per_vertex else BIAS_FILTER, stack=stack, out=out,
                                   dW=W.grad if trained else None, dbias=b.grad if trained else None,
                                   precision=self.contraction, pool_maps=None if top else self._pool_maps[i], Wt=Wts.get(i),
                                   link_in=links.get(i - 1), link_out=links.get(i))
-            x = self._cam_tap(i, x)
+            if ps is not None:
+                x = ps.tap(i, x)
             stack = next_stack
         return self._head(x, dropout)
 
@@ -2084,7 +1723,7 @@ class finetuning_cgcnn(cgcnn):
         if x.is_meta:
             return self.fc(x, Mout, relu)
         W = self._weight_variable([self._M_top * self.F[-1], Mout], regularization=True)
-        b = self._bias_variable([Mout], regularization=True)           # (detached inside a saliency-style pass)
+        b = self._bias_variable([Mout], regularization=True)           # (detached inside an attribution pass)
         direct = self.training_mode and torch.is_grad_enabled()
         return ops.FlatFC.apply(x, W, b, self._head_order, self._M_top, relu, W.grad if direct else None,
                                 b.grad if direct else None)
@@ -2159,26 +1798,27 @@ class model_perf(object):
             model.load_state_dict(sd)
         return model
 
+    def _maps(s, method, ckp_path, data, labels, batch_size, kw):
+        model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
+        return getattr(model, method)(data, labels, **kw)
+
     def saliency_maps(s, ckp_path, data, labels, target_name=None, batch_size=128, **kw):
         """Per-class mean saliency maps (``base_model.saliency_maps``; ``kw``: its keywords) of the model ``predict`` would
         restore from ``ckp_path``.  ``target_name`` is accepted for symmetry with ``predict`` and not used.  Returns
         ``(maps, counts)``."""
-        model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
-        return model.saliency_maps(data, labels, **kw)
+        return s._maps('saliency_maps', ckp_path, data, labels, batch_size, kw)
 
     def occlusion_maps(s, ckp_path, data, labels, target_name=None, batch_size=128, **kw):
         """Per-class mean occlusion drops (``base_model.occlusion_maps``; ``kw``: its keywords) of the model ``predict`` would
         restore from ``ckp_path``.  ``target_name`` is accepted for symmetry with ``predict`` and not used.  Returns
         ``(maps, counts)``."""
-        model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
-        return model.occlusion_maps(data, labels, **kw)
+        return s._maps('occlusion_maps', ckp_path, data, labels, batch_size, kw)
 
     def gradcam_maps(s, ckp_path, data, labels, target_name=None, batch_size=128, **kw):
         """Per-class mean Grad-CAM maps (``base_model.gradcam_maps``; ``kw``: its keywords) of the model ``predict`` would
         restore from ``ckp_path``.  ``target_name`` is accepted for symmetry with ``predict`` and not used.  Returns
         ``(maps, counts)``."""
-        model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
-        return model.gradcam_maps(data, labels, **kw)
+        return s._maps('gradcam_maps', ckp_path, data, labels, batch_size, kw)
 
     def predict(s, ckp_path, test_data, test_labels, target_name=None, batch_size=128, trial_dura=17,
                 flag_starttr=False, sub_name=None, model=None, config=None):
@@ -2198,11 +1838,7 @@ class model_perf(object):
         for begin in range(0, data_size, batch_size):
             end = min([begin + batch_size, data_size])
             idx = torch.arange(begin, end, dtype=torch.int32, device=model.device)
-            x = model._gather(data_dev, idx)
-            if end - begin < batch_size:
-                pad = ops.plane_empty(batch_size, x.shape[1], data_dev.shape[1], model.device, zero=True)
-                pad[:end - begin] = x.planes
-                x = model.as_internal(pad)
+            x = model.as_internal(model._gather_padded(data_dev, idx, batch_size))
             batch_labels = np.zeros(batch_size, np.int64)
             batch_labels[:end - begin] = test_labels[begin:end]
             with torch.no_grad():

@@ -259,7 +259,7 @@ def test_model_state_untouched_and_next_step_bit_identical():
     torch.cuda.synchronize()
     assert _same(_state(a), before)
     assert a._sg is sg and a._step_graph_on and torch.equal(a.gradient('conv1/weights'), grad_view)
-    assert a._cam_layer is None and a._cam_act is None and not a._saliency_pass
+    assert a._pass is None
     for net in nets:
         xs = net._gather(net.stage(x), torch.arange(BS, dtype=torch.int32, device=DEV))
         net.train_step(xs, labels)

@@ -176,6 +176,28 @@ def test_model_level_of_each_layer():
     assert [net._cam_level(i) for i in range(3)] == [(M0, 1, None), (M0 // 2, 2, None), (M0 // 4, 4, None)]
 
 
+def test_a_pass_that_raises_leaves_no_pass_state():
+    """Whatever the body of an attribution pass does, ``training_mode`` comes back as it was and ``_pass`` is None again."""
+    Ls = graph_mod.synthetic_graph(64, k=4, levels=2, seed=1)[0]
+    net = models_gcn.cgcnn({'device': 'meta'}, Ls, [4, 4, 4], [3, 3, 3], [1, 2, 2], [8, 5], channel=2, batch_size=4,
+                           verbose=False)
+    assert net._pass is None and net.training_mode is False
+    for was_training in (True, False):
+        for layer in (None, 1):
+            net.training_mode = was_training
+            with pytest.raises(ZeroDivisionError):
+                with net._attribution_pass(layer) as ps:
+                    assert net._pass is ps and ps.layer == layer and ps.act is None
+                    assert net.training_mode is False
+                    1 / 0
+            assert net._pass is None and net.training_mode is was_training
+    # and a pass that ends normally
+    net.training_mode = True
+    with net._attribution_pass():
+        assert net._pass is not None and net.training_mode is False
+    assert net._pass is None and net.training_mode is True
+
+
 def _meta_model(channel=3):
     Ls = graph_mod.synthetic_graph(60, k=4, levels=0, seed=1)[0]
     return models_gcn.cgcnn({'device': 'meta'}, Ls * 2, [4, 4], [3, 3], [1, 1], [8, 5], channel=channel, batch_size=4,

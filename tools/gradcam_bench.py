@@ -26,19 +26,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
-from saliency_bench import build, instrumented, timed      # noqa: E402
+from saliency_bench import build, instrumented, kernel_shares, timed      # noqa: E402
 
 NEW = ('gradcam_weights', 'gradcam_map')
-
-
-def kernel_shares(fn):
-    kern = instrumented(fn)
-    total = sum(v['total_ms'] for v in kern.values())
-    new = {k: v for k, v in kern.items() if k.split(' | ')[0] in NEW}
-    return {'kernels_ms': total, 'new_kernels_ms': sum(v['total_ms'] for v in new.values()),
-            'new_share': sum(v['total_ms'] for v in new.values()) / total if total else 0.0,
-            'new': {k: {'launches': v['launches'], 'avg_ms': v['avg_ms'], 'bytes': v['bytes'], 'hbm_share': v['hbm_share']}
-                    for k, v in new.items()}}
 
 
 def main():
@@ -67,9 +57,9 @@ def main():
         r['maps_top_win_s'] = S / timed(lambda: net.gradcam_maps(data, labels, layer=top), args.reps)
         r['top_vs_saliency'] = r['gradcam_top_win_s'] / r['saliency_gradient_win_s']
         # one pass (one batch) of each: the kernel time and the new kernels' share of it
-        r['kernels_conv1'] = kernel_shares(lambda: net.gradcam(data[:B], 'conv1', batch_size=B))
-        r['kernels_top'] = kernel_shares(lambda: net.gradcam(data[:B], top, batch_size=B))
-        r['kernels_top_gxa'] = kernel_shares(lambda: net.gradcam(data[:B], top, method='grad_x_activation', batch_size=B))
+        r['kernels_conv1'] = kernel_shares(lambda: net.gradcam(data[:B], 'conv1', batch_size=B), NEW)
+        r['kernels_top'] = kernel_shares(lambda: net.gradcam(data[:B], top, batch_size=B), NEW)
+        r['kernels_top_gxa'] = kernel_shares(lambda: net.gradcam(data[:B], top, method='grad_x_activation', batch_size=B), NEW)
         r['kernels_saliency'] = sum(v['total_ms'] for v in instrumented(lambda: net.saliency(data[:B], batch_size=B)).values())
         res[shape] = r
         del net

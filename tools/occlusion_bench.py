@@ -26,18 +26,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
-from saliency_bench import build, instrumented, timed      # noqa: E402
+from saliency_bench import build, kernel_shares, timed     # noqa: E402
 
 NEW = ('occlusion_rows', 'occlusion_score', 'occlusion_class_sums', 'saliency_seed')
-
-
-def kernel_shares(fn):
-    kern = instrumented(fn)
-    total = sum(v['total_ms'] for v in kern.values())
-    new = {k: v for k, v in kern.items() if k.split(' | ')[0] in NEW}
-    return {'kernels_ms': total, 'new_kernels_ms': sum(v['total_ms'] for v in new.values()),
-            'new_share': sum(v['total_ms'] for v in new.values()) / total if total else 0.0,
-            'new': {k: {'launches': v['launches'], 'avg_ms': v['avg_ms'], 'hbm_share': v['hbm_share']} for k, v in new.items()}}
 
 
 def main():
@@ -69,8 +60,8 @@ def main():
         r['maps_rows_s'] = r['maps_win_s'] * (G + 1)
         # one call's kernels: a few windows (every pass alike), and the class sums once
         n = max(1, -(-4 * B // (G + 1)))
-        r['occlusion_kernels'] = kernel_shares(lambda: net.occlusion(data[:n], groups=groups))
-        r['maps_kernels'] = kernel_shares(lambda: net.occlusion_maps(data[:n], labels[:n], groups=groups))
+        r['occlusion_kernels'] = kernel_shares(lambda: net.occlusion(data[:n], groups=groups), NEW)
+        r['maps_kernels'] = kernel_shares(lambda: net.occlusion_maps(data[:n], labels[:n], groups=groups), NEW)
         if shape != 'atlas':
             nv = args.vertex_windows
             r['vertex_G'] = M

@@ -76,6 +76,17 @@ def instrumented(fn):
     return kern
 
 
+def kernel_shares(fn, names):
+    """One instrumented call: its kernel time, and the share and per-kernel figures of the launches called ``names``."""
+    kern = instrumented(fn)
+    total = sum(v['total_ms'] for v in kern.values())
+    new = {k: v for k, v in kern.items() if k.split(' | ')[0] in names}
+    return {'kernels_ms': total, 'new_kernels_ms': sum(v['total_ms'] for v in new.values()),
+            'new_share': sum(v['total_ms'] for v in new.values()) / total if total else 0.0,
+            'new': {k: {'launches': v['launches'], 'avg_ms': v['avg_ms'], 'bytes': v['bytes'], 'hbm_share': v['hbm_share']}
+                    for k, v in new.items()}}
+
+
 def host_profile(fn, batches):
     """One call under cProfile: wall ms per batch, ms per batch spent in Tensor.cpu (waiting for the device and copying the
     result), the top host functions by own time, and the allocator's counters over the call."""
