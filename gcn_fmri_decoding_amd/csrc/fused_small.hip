@@ -422,7 +422,8 @@ int fs_launch(const FusedArgs& a, int cus, hipStream_t stream) {
     const size_t lds = fs_lds(NW, PL, a.K);
     CG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fused_layer_kernel<NW, PL, ADJ, ML>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds));
-    static const std::string name = "fused_layer_kernel<" + std::to_string(NW) + "," + std::to_string(PL) + "," + (ADJ ? "true" : "false") + ">";
+    static const std::string name = "fused_layer_kernel<" + std::to_string(NW) + "," + std::to_string(PL) + "," + (ADJ ? "true" : "false") + "," +
+                                    std::to_string(ML) + ">";
     note_dispatch(name.c_str());
     constexpr int NS = 16 / PL;
     const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);

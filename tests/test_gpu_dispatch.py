@@ -668,9 +668,14 @@ def test_fused_atlas_layer_vs_oracle(ops, dev, lib, N, B, Fin, K, Fout, bias_kin
     out = torch.full((B, Fout, Mp), float('nan'), device=dev)
     mask = torch.zeros((B, Fout, Mp // 4), dtype=torch.uint8, device=dev)
     nw = 8 if Mp <= 256 else 12
+    # the fourth name parameter: operator entries per row held in registers, 16 where the longest row allows (a symmetric
+    # Laplacian: the rows of the transpose are as long)
+    longest = int(np.diff(graph.rescaled_laplacian_csr(L)[0]).max())
+    assert longest <= 20
+    ml = 16 if longest <= 16 else 20
     _lib.check(lib.chebgcn_fused_layer_fwd(g.handle, P(xs), P(Wd), P(bd), kind, P(stack), P(out), P(mask) if relu else None, P(ws), nws,
                                            B, Fin, K, Fout, int(relu), stream()), 'fused_layer_fwd')
-    want = 'fused_layer_kernel<%d,%d,false>' % (nw, 16 // split) + (' + fused_combine_kernel' if split == 2 else '')
+    want = 'fused_layer_kernel<%d,%d,false,%d>' % (nw, 16 // split, ml) + (' + fused_combine_kernel' if split == 2 else '')
     assert _lib.last_dispatch() == want, _lib.last_dispatch()
     got = {}
     o = out[:, :, :M].permute(0, 2, 1).cpu().numpy()
@@ -694,7 +699,7 @@ def test_fused_atlas_layer_vs_oracle(ops, dev, lib, N, B, Fin, K, Fout, bias_kin
     dx = torch.full((B, Fin, Mp), float('nan'), device=dev)
     _lib.check(lib.chebgcn_fused_layer_bwd_x(g.handle, P(dout), P(mask) if relu else None, P(Wd), P(dx), B, Fin, K, Fout, stream()),
                'fused_layer_bwd_x')
-    assert _lib.last_dispatch() == 'fused_layer_kernel<%d,%d,true>' % (nw, 16 // split)
+    assert _lib.last_dispatch() == 'fused_layer_kernel<%d,%d,true,%d>' % (nw, 16 // split, ml)
     d = dx[:, :, :M].permute(0, 2, 1).cpu().numpy()
     got['dx'] = np.abs(d - dx_ref).max() / np.abs(dx_ref).max()
     assert got['dx'] <= GREL, 'dx: %.3e' % got['dx']

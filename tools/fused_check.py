@@ -40,6 +40,9 @@ def main():
         relu = 1 if bias_kind else 0
         nws = lib.chebgcn_fused_layer_workspace(g.handle, B, Fin, K, Fout)
         ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
+        # fused_layer_kernel<waves, planes per lane, adjoint, row entries in registers> (a symmetric operator: one row length)
+        longest = int(np.diff(graph.rescaled_laplacian_csr(Ls[0])[0]).max())
+        kernel = 'fused_layer_kernel<%d,%d,%%s,%d>' % (8 if Mp <= 256 else 12, 8 if nws else 16, 16 if longest <= 16 else 20)
         # reference: the separate kernels
         stack_r = torch.full((K, B, Fin, Mp), float('nan'), device=dev)
         _lib.check(lib.chebgcn_recurrence_fwd(g.handle, P(x), P(stack_r), B, Fin, K, st), 'rec')
@@ -53,6 +56,7 @@ def main():
             _lib.check(lib.chebgcn_fused_layer_fwd(g.handle, P(x), P(W), P(bias), bias_kind, P(stack), P(out), P(mask) if relu else None, P(ws), nws,
                                                    B, Fin, K, Fout, relu, st), 'fused fwd')
             name = _lib.last_dispatch()
+            assert name == kernel % 'false' + (' + fused_combine_kernel' if nws else ''), name
             e = float((out[..., :M] - out_r[..., :M]).abs().max() / out_r[..., :M].abs().max())
             print('   fwd %s stack=%d: out rel err %.2e' % (name, with_stack, e), end='')
             assert e < 1e-5
@@ -79,6 +83,7 @@ def main():
         dx = torch.full((B, Fin, Mp), float('nan'), device=dev)
         _lib.check(lib.chebgcn_fused_layer_bwd_x(g.handle, P(dout), P(mask_r) if relu else None, P(W), P(dx), B, Fin, K, Fout, st), 'fused bwd')
         e = float((dx[..., :M] - dx_r[..., :M]).abs().max() / dx_r[..., :M].abs().max())
+        assert _lib.last_dispatch() == kernel % 'true', _lib.last_dispatch()
         print('   bwd %s: dx rel err %.2e' % (_lib.last_dispatch(), e), flush=True)
         assert e < 2e-5
 
