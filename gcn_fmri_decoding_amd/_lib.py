@@ -38,6 +38,8 @@ SIGNATURES = {
     'chebgcn_reindex_weights': (_i, [_p, _p, _i, _i, _i, _p]),
     'chebgcn_reindex_weights_batch': (_i, [_i, _p, _p, _p, _p, _p, _p]),
     'chebgcn_contract_fwd': (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    'chebgcn_contract_fwd_windows_supported': (_i, [_i, _i, _i, _i, _i, _i]),
+    'chebgcn_contract_fwd_windows': (_i, [_p, _i64, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     'chebgcn_contract_fwd_bf16_workspace': (C.c_size_t, [_i, _i, _i]),
     'chebgcn_contract_fwd_bf16': (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, C.c_size_t, _p]),
     'chebgcn_contract_bwd_x_bf16_workspace': (C.c_size_t, [_i, _i, _i]),

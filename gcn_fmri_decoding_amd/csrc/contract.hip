@@ -68,7 +68,8 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 // --------------------------------------------------------------------------------------
 constexpr int FWD_UNROLL = 8;
 
-template <int NT>
+// WIN (here and in the two kernels below): the operand planes of window b are a window of a longer stack (FwdArgs::starts)
+template <int NT, bool WIN = false>
 __global__ void __launch_bounds__(256, NT == 1 ? CG_LB_FWD : 1)
 contract_fwd_kernel(FwdArgs a) {
     const int lane = threadIdx.x & 63;
@@ -89,7 +90,7 @@ contract_fwd_kernel(FwdArgs a) {
 #pragma unroll
             for (int j = 0; j < 16; ++j) acc[t][r][j] = 0.f;
 
-    const float* base = a.stack + (size_t)b * a.Fin * a.Mp + (valid ? n0 : 0);
+    const float* base = a.stack + fwd_first_plane<WIN>(a, b) * a.Mp + (valid ? n0 : 0);
     const int npairs = (a.FinK + 1) >> 1;
     // this lane's reduction index kk = 2*i + h, tracked as (fin, k)
     int fin = h / a.K, k = h % a.K;
@@ -170,7 +171,7 @@ constexpr int RING = CG_FWD_RING;
 // LEAN: pool == 1, no out_K scatter (the launcher's choice): the row epilogue without the pooling variants
 // GATE (LEAN, no bias, no ReLU): the stored result gated by the mask a.gate -- the register slots that prefetch the bias rows
 // carry the mask byte of the lane's four vertices instead (FwdArgs::gate)
-template <bool LEAN, bool GATE = false>
+template <bool LEAN, bool GATE = false, bool WIN = false>
 __global__ void __launch_bounds__(256, CG_LB_RING)
 contract_fwd_ring_kernel(FwdArgs a, int nrows_pad) {
     extern __shared__ __align__(16) unsigned char ring_smem[];
@@ -211,7 +212,7 @@ contract_fwd_ring_kernel(FwdArgs a, int nrows_pad) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[r][j] = 0.f;
 
-    const float* base = a.stack + (size_t)b * a.Fin * a.Mp + (valid ? n0 : 0);
+    const float* base = a.stack + fwd_first_plane<WIN>(a, b) * a.Mp + (valid ? n0 : 0);
     const int rounds = nrows_pad / (2 * RING);
     float4 bv[RING];
     float av[RING];
@@ -329,6 +330,7 @@ contract_fwd_ring_kernel(FwdArgs a, int nrows_pad) {
 #ifndef CG_LB_SPLITK
 #define CG_LB_SPLITK 3
 #endif
+template <bool WIN = false>
 __global__ void __launch_bounds__(256, CG_LB_SPLITK)
 contract_fwd_splitk_kernel(FwdArgs a) {
     __shared__ float red[4][32][64];                   // [wave][accumulator register r*8 + (j & 7)][lane], rows j < 8 then j >= 8
@@ -345,7 +347,7 @@ contract_fwd_splitk_kernel(FwdArgs a) {
     for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[r][j] = 0.f;
-    const float* base = a.stack + (size_t)b * a.Fin * a.Mp + (valid ? n0 : 0);
+    const float* base = a.stack + fwd_first_plane<WIN>(a, b) * a.Mp + (valid ? n0 : 0);
     const int npairs = (a.FinK + 1) >> 1;
     const int fo = c < a.Fout ? c : a.Fout - 1;
     const float wz = c < a.Fout ? 1.f : 0.f;
@@ -1041,7 +1043,7 @@ extern "C" int chebgcn_contract_fwd(const float* stack, const float* W, const fl
     } else if (small_launch(B, M)) {
         dim3 grid((M + 127) / 128, B, 1);
         note_dispatch("contract_fwd_splitk_kernel");
-        hipLaunchKernelGGL(contract_fwd_splitk_kernel, grid, dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(contract_fwd_splitk_kernel<false>, grid, dim3(256), 0, stream, a);
     } else {
         dim3 grid(gx, B, 1);
 #if CG_FWD_RING
@@ -1120,6 +1122,74 @@ extern "C" int chebgcn_contract_fwd_gated(const float* stack, const float* W, co
     note_dispatch("contract_fwd_ring_kernel<gated>");
     hipLaunchKernelGGL((contract_fwd_ring_kernel<true, true>), dim3((M + 511) / 512, B, 1), dim3(256),
                        std::max((size_t)nrows_pad * 136, (size_t)lds_min), stream, a, nrows_pad);
+    CG_HIP(hipGetLastError());
+    return CHEBGCN_OK;
+}
+
+// ---- the forward contraction over windows of ONE longer stack (decoding a scan window by window) --------------------------------
+// The first layer's input folds time into the channels, and the recurrence acts on every channel plane on its own: T_k(L~) of
+// window b, channel c is T_k(L~) of the scan's time point starts[b] + c.  Overlapping windows share their time points, so the
+// stack is computed once over the scan ([K][T][Mp], chebgcn_recurrence_fwd with B = 1, Fin = T) and every window contracts its C
+// planes per slab out of it.  The kernels are the ones above with the first plane of a window read from a table
+// (fwd_first_plane): the same products in the same order, bit-identical to chebgcn_contract_fwd on the gathered stack.
+// Which arm serves a launch follows chebgcn_contract_fwd's rules for Fout <= 32, so that the two agree bit for bit at every shape.
+static const char* fwd_windows_arm(int B, int M, int C, int K, int Fout, int pool, int bias_kind) {
+    if (small_launch(B, M)) return "contract_fwd_windows_splitk_kernel";
+#if CG_FWD_RING
+    if ((size_t)ring_rows(C * K) * 136 <= 48 * 1024 && RING <= 8 && (bias_kind != CHEBGCN_BIAS_FILTER || Fout >= 4))
+        return pool == 1 ? "contract_fwd_windows_ring_kernel" : "contract_fwd_windows_ring_kernel<pool>";
+#endif
+    return "contract_fwd_windows_kernel<1>";
+}
+
+extern "C" int chebgcn_contract_fwd_windows_supported(int B, int M, int C, int K, int Fout, int pool) {
+    if (B <= 0 || M <= 0 || C <= 0 || K <= 0 || Fout <= 0 || Fout > 32 || B > 65535) return 0;
+    if ((int64_t)C * K > (1 << 20)) return 0;
+    return check_pool(pool, M);
+}
+
+extern "C" int chebgcn_contract_fwd_windows(const float* stack, int64_t T, const int32_t* starts, const float* W, const float* bias,
+                                            int bias_kind, float* out, uint8_t* argmax, int B, int M, int C, int K, int Fout,
+                                            int pool, int pool_kind, int relu, chebgcn_stream stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    CG_REQUIRE(stack && starts && W && out, "contract_fwd_windows: NULL argument");
+    CG_REQUIRE(B > 0 && M > 0 && C > 0 && K > 0 && Fout > 0, "contract_fwd_windows: bad shape");
+    CG_REQUIRE(B <= 65535, "contract_fwd_windows: B > 65535");
+    CG_REQUIRE(T >= C && T <= 0x7fffffff, "contract_fwd_windows: T=%lld must hold a window of C=%d time points", (long long)T, C);
+    CG_REQUIRE(check_pool(pool, M), "contract_fwd_windows: pool=%d must be a power of two <= 128 dividing M=%d", pool, M);
+    CG_REQUIRE(bias_kind == CHEBGCN_BIAS_NONE || bias, "contract_fwd_windows: bias_kind set but bias is NULL");
+    CG_REQUIRE(bias_kind >= 0 && bias_kind <= 2 && (pool_kind == 0 || pool_kind == 1), "contract_fwd_windows: bad kind");
+    CG_REQUIRE(!(pool_kind == CHEBGCN_POOL_AVG && relu && argmax && pool > 8),
+               "contract_fwd_windows: average pooling keeps a ReLU mask only for pool <= 8");
+    if (!chebgcn_contract_fwd_windows_supported(B, M, C, K, Fout, pool))
+        return fail(CHEBGCN_EUNSUPPORTED, "contract_fwd_windows: shape not served (chebgcn_contract_fwd_windows_supported)");
+    FwdArgs a;
+    a.stack = stack; a.W = W; a.bias = bias; a.out = out;
+    a.argmax = pool > 1 ? argmax : nullptr;
+    a.relu_mask = (pool == 1 && relu) ? argmax : nullptr;
+    a.B = B; a.M = M; a.Mp = plane_stride(M); a.Fin = C; a.K = K; a.Fout = Fout; a.FinK = C * K;
+    a.pool = pool; a.pool_kind = pool_kind; a.relu = relu; a.bias_kind = bias_kind;
+    a.Mo = M / pool; a.Mpo = plane_stride(a.Mo);
+    a.slab = (size_t)T * a.Mp;
+    a.starts = starts; a.T = (int)T;
+    const char* arm = fwd_windows_arm(B, M, C, K, Fout, pool, bias_kind);
+    note_dispatch(arm);
+    if (small_launch(B, M)) {
+        hipLaunchKernelGGL(contract_fwd_splitk_kernel<true>, dim3((M + 127) / 128, B, 1), dim3(256), 0, stream, a);
+        CG_HIP(hipGetLastError());
+        return CHEBGCN_OK;
+    }
+    dim3 grid((M + 511) / 512, B, 1);
+#if CG_FWD_RING
+    const int nrows_pad = ring_rows(a.FinK);
+    if ((size_t)nrows_pad * 136 <= 48 * 1024 && RING <= 8 && (bias_kind != CHEBGCN_BIAS_FILTER || Fout >= 4)) {
+        if (pool == 1) hipLaunchKernelGGL((contract_fwd_ring_kernel<true, false, true>), grid, dim3(256), (size_t)nrows_pad * 136, stream, a, nrows_pad);
+        else hipLaunchKernelGGL((contract_fwd_ring_kernel<false, false, true>), grid, dim3(256), (size_t)nrows_pad * 136, stream, a, nrows_pad);
+        CG_HIP(hipGetLastError());
+        return CHEBGCN_OK;
+    }
+#endif
+    hipLaunchKernelGGL((contract_fwd_kernel<1, true>), grid, dim3(256), 0, stream, a);
     CG_HIP(hipGetLastError());
     return CHEBGCN_OK;
 }

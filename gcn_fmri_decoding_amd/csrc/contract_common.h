@@ -36,7 +36,23 @@ struct FwdArgs {
     // [B][Fout][Mp/4] -- the result is stored as bit ? value : 0.  The kernel is then the last step of the gradient wrt a
     // layer's input in forward form, and the mask is the one the layer BELOW left: what is stored is that layer's dy
     const uint8_t* gate = nullptr;
+    // windows (the WIN instantiations of the forward kernels: chebgcn_contract_fwd_windows): the stack is [K][T][Mp], the planes
+    // of ONE long series, and window b's Fin operand planes per slab are the time points starts[b] .. starts[b] + Fin - 1 --
+    // `b * Fin` in the plane address becomes starts[b], slab = T * Mp.  int32 [B] on the device, 0 <= start <= T - Fin
+    const int32_t* starts = nullptr;
+    int T = 0;
 };
+
+// Index of window b's first operand plane inside a slab of the stack.  WIN: read from the table, held inside [0, T - Fin]
+// whatever the table says (the host checks it before the upload; a launch never leaves the stack).
+template <bool WIN>
+__device__ __forceinline__ size_t fwd_first_plane(const FwdArgs& a, int b) {
+    if (WIN) {
+        const int s = a.starts[b], hi = a.T - a.Fin;
+        return (size_t)(s < 0 ? 0 : s > hi ? hi : s);
+    }
+    return (size_t)b * a.Fin;
+}
 
 // Epilogue of one filter row for the four vertices n0..n0+3 held by lane c of a half-wave:
 // bias (models_gcn.py:619-629), ReLU, graph pooling over p consecutive vertices (:631-648),

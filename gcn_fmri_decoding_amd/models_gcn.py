@@ -31,6 +31,7 @@ from . import graph as graph_mod
 from . import ops
 from ._lib import BIAS_FILTER, BIAS_NONE, BIAS_VERTEX, POOL_AVG, POOL_MAX, plane_stride
 from .attribution import Attribution
+from .decode import Decode
 
 
 class _Spec:
@@ -88,9 +89,9 @@ class InternalPlanes(object):
         return self
 
 
-class base_model(Attribution):
+class base_model(Attribution, Decode):
     """Counterpart of ``base_model`` (:18-355): run-time interface + variable helpers.  The attribution maps (``saliency``,
-    ``occlusion``, ``gradcam`` and their ``*_maps``) come from ``attribution.Attribution``."""
+    ``occlusion``, ``gradcam`` and their ``*_maps``) come from ``attribution.Attribution``, ``decode_series`` from ``decode.Decode``."""
 
     def __init__(self, config=None):
         self.regularizers = []          # names of L2-regularised variables (:345, :353)
@@ -129,6 +130,8 @@ class base_model(Attribution):
         # inside saliency() / occlusion() / gradcam(): the attribution.Pass the layers read -- they see their variables without
         # gradient (no weight, bias-gradient or optimizer work), and the head runs on the library's FC kernels (no vendor GEMM)
         self._pass = None
+        # inside decode_series' shared path: the decode.Windows the first conv layer contracts its windows out of
+        self._windows = None
 
     # ---------------------------------------------------------------- run-time API
 
@@ -1287,9 +1290,10 @@ class cgcnn(base_model):
                                    "'length'), which the layer-by-layer path does not know: construct it with "
                                    "CHEBGCN_VERTEX_ORDER=reference to replace filter / brelu / pool methods")
             return self._inference(ops.plane_view(self._to_internal(x), self.L[0].shape[0]), dropout)
-        x = self._to_internal(x)
+        win = self._windows                            # (decode_series' shared path: layer 1 reads windows of a series' stack)
+        x = self._to_internal(x) if win is None else None
         nl = len(self.p)
-        B = x.shape[0]
+        B = x.shape[0] if win is None else win.B
         per_vertex = getattr(self.brelu, '__func__', None) is cgcnn.b2relu
         pool_kind = POOL_AVG if getattr(self.pool, '__func__', None) is cgcnn.apool1 else POOL_MAX
         stack, ps = None, self._pass                   # (ps: inside an attribution call, None otherwise)
@@ -1315,8 +1319,14 @@ class cgcnn(base_model):
             out = next_stack = None
             if i + 1 < nl and g.M // self.p[i] == self.graphs[i + 1].M:
                 next_stack = torch.empty((self.K[i + 1], B, self.F[i], self.graphs[i + 1].Mp), dtype=torch.float32,
-                                         device=x.device)
+                                         device=self.device)
                 out = next_stack[0]
+            if i == 0 and win is not None:
+                mean = False
+                x = ops.conv_windows(win, W, b, g, self.K[0], self.channel, self.p[0], pool_kind, True,
+                                     BIAS_VERTEX if per_vertex else BIAS_FILTER, out=out, pool_maps=self._pool_maps[0])
+                stack = next_stack
+                continue
             # training: the layer's gradients go straight into the flat (zeroed) gradient buffer
             direct = self.training_mode and W.grad is not None and b.grad is not None and torch.is_grad_enabled()
             done = (lambda layer=i + 1: self._dp.layer_done(layer)) if (direct and self._dp is not None) else None
@@ -1666,9 +1676,10 @@ class finetuning_cgcnn(cgcnn):
     def _inference_storage(self, x, dropout):
         """The trunk on the fused path -- the layers below the lowest trained one without autograd, the top layer without its
         pooling -- then the head."""
-        x = self._to_internal(x)
+        win = self._windows                            # (decode_series' shared path: see cgcnn._inference_storage)
+        x = self._to_internal(x) if win is None else None
         nl = len(self.p)
-        B = x.shape[0]
+        B = x.shape[0] if win is None else win.B
         per_vertex = getattr(self.brelu, '__func__', None) is cgcnn.b2relu
         pool_kind = POOL_AVG if getattr(self.pool, '__func__', None) is cgcnn.apool1 else POOL_MAX
         training = self.training_mode and torch.is_grad_enabled()
@@ -1695,8 +1706,14 @@ class finetuning_cgcnn(cgcnn):
             out = next_stack = None
             if not top and g.M // self.p[i] == self.graphs[i + 1].M:
                 next_stack = torch.empty((self.K[i + 1], B, self.F[i], self.graphs[i + 1].Mp), dtype=torch.float32,
-                                         device=x.device)
+                                         device=self.device)
                 out = next_stack[0]
+            if i == 0 and win is not None:
+                x = ops.conv_windows(win, W, b, g, self.K[0], self.channel, 1 if top else self.p[0], pool_kind, True,
+                                     BIAS_VERTEX if per_vertex else BIAS_FILTER, out=out,
+                                     pool_maps=None if top else self._pool_maps[0])
+                stack = next_stack
+                continue
             trained = i >= lo and W.requires_grad
             # (a Grad-CAM pass: autograd from the layer above the one it stops at, on detached variables)
             grad_mode = ps.grad_mode(i) if stops else contextlib.nullcontext() if i >= lo else torch.no_grad()
@@ -1819,6 +1836,12 @@ class model_perf(object):
         restore from ``ckp_path``.  ``target_name`` is accepted for symmetry with ``predict`` and not used.  Returns
         ``(maps, counts)``."""
         return s._maps('gradcam_maps', ckp_path, data, labels, batch_size, kw)
+
+    def decode_series(s, ckp_path, series, batch_size=128, **kw):
+        """``base_model.decode_series`` (``kw``: its keywords) of the model ``predict`` would restore from ``ckp_path``: the
+        logits (probabilities, labels) of every window of a scan, or of a list of runs."""
+        model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
+        return model.decode_series(series, **kw)
 
     def predict(s, ckp_path, test_data, test_labels, target_name=None, batch_size=128, trial_dura=17,
                 flag_starttr=False, sub_name=None, model=None, config=None):

@@ -924,6 +924,38 @@ def cheb_conv(x, W, bias, graph, K, pool=1, pool_kind=POOL_MAX, relu=False, bias
     return ChebConv.apply(x, W, bias, graph, K, pool, pool_kind, relu, bias_kind, bufs)
 
 
+def conv_windows(win, W, bias, graph, K, C, pool=1, pool_kind=POOL_MAX, relu=True, bias_kind=BIAS_NONE, out=None, pool_maps=None):
+    """The first conv layer of a batch of windows of ONE longer series (``decode.Windows``: the series' Chebyshev stack
+    ``[K, T, Mp]`` and the batch's window starts), forward only: chebgcn_contract_fwd_windows in place of ``cheb_conv``'s
+    recurrence + contraction -- the same products in the same order.  ``out`` / ``pool_maps``: as ``cheb_conv``."""
+    lib = _lib.lib()
+    _require_cuda(win.stack, win.starts, W, bias)
+    B, M, Mp = win.B, graph.M, graph.Mp
+    Fout = int(W.shape[1])
+    if tuple(win.stack.shape) != (K, win.T, Mp) or not win.stack.is_contiguous() or win.starts.dtype != torch.int32:
+        raise ValueError('conv_windows: stack [K, T, Mp] float32 and int32 starts expected')
+    if W.shape[0] != C * K:
+        raise ValueError('weight rows %d != C*K = %d' % (W.shape[0], C * K))
+    W = W.detach().contiguous()
+    b = bias.detach().contiguous() if bias is not None else None
+    maps = pool_maps if pool > 1 else None
+    cp = 1 if maps is not None else pool
+    Mo = M // pool
+    if out is None:
+        out = plane_empty(B, Fout, Mo, W.device)
+    elif tuple(out.shape) != (B, Fout, plane_stride(Mo)) or not out.is_contiguous():
+        raise ValueError('out buffer has the wrong shape')
+    y = plane_empty(B, Fout, M, W.device) if maps is not None else out
+    _lib.check(_launch('contract_fwd_windows', 4.0 * B * M * (C * K + Fout / cp), 2.0 * B * M * C * K * Fout,
+                       lambda: lib.chebgcn_contract_fwd_windows(_p(win.stack), win.T, _p(win.starts), _p(W), _p(b), bias_kind, _p(y),
+                                                                None, B, M, C, K, Fout, cp, pool_kind, int(relu), _stream())),
+               'contract_fwd_windows')
+    if maps is not None:
+        _lib.check(_launch('pool_gather_fwd', B * Fout * (4.0 * (M + Mo) + Mo), 0.0, lambda: lib.chebgcn_pool_gather_fwd(
+            _p(y), _p(maps[0]), _p(out), None, B, M, Fout, pool, pool_kind, int(relu), _stream())), 'pool_gather_fwd')
+    return out
+
+
 class BiasReluPool(torch.autograd.Function):
     """Standalone bias + ReLU + pooling (b1relu / b2relu / mpool1 / apool1 called on their
     own, models_gcn.py:619-648) on plane storage tensors."""

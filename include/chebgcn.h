@@ -157,6 +157,29 @@ int chebgcn_contract_fwd(const float* stack, const float* W, const float* bias, 
                          float* out, uint8_t* argmax, int B, int M, int Fin, int K, int Fout,
                          int pool, int pool_kind, int relu, chebgcn_stream stream);
 
+/* ---- the same contraction over WINDOWS of one longer stack (decoding a scan window by window: cgcnn.decode_series) ------
+ * The first layer's input folds time into the channels (x[b][m][c] = s[starts[b] + c][m]) and the recurrence acts on every
+ * channel plane on its own, so overlapping windows share their Chebyshev planes:
+ *   stack: [K][T][Mp(M)], what chebgcn_recurrence_fwd(g, s, stack, 1, T, K) leaves for the T time points of a scan;
+ *   starts: int32 [B] on the device; window b contracts the planes of the time points starts[b] .. starts[b] + C - 1:
+ *     y[b][o][m] = act( sum_{c<C, k<K} W[c*K + k][o] * stack[k][starts[b] + c][m] + bias ) -> pool over m
+ *   W, bias, out, argmax, pool, pool_kind, relu: exactly as chebgcn_contract_fwd with Fin = C.
+ * Every start must satisfy 0 <= start and start + C <= T: the CALLER checks the table before it uploads it (the library
+ * cannot read it without a synchronisation); a start outside that range is moved into it by the kernel, which therefore
+ * never reads outside the stack.  Overlapping, repeated and unsorted starts are fine.  Forward only.
+ * fp32 matrix instructions, Fout <= 32 (chebgcn_contract_fwd_windows_supported; CHEBGCN_EUNSUPPORTED otherwise).  Served: the
+ * three forward arms chebgcn_contract_fwd has for Fout <= 32, chosen by the same rules, reported by chebgcn_last_dispatch() as
+ *   contract_fwd_windows_splitk_kernel       small launches (ceil(M/512) * B < 2 * CUs), any pool
+ *   contract_fwd_windows_ring_kernel         big launches, pool == 1, C*K up to 352 rows (and Fout >= 4 with a per-filter bias)
+ *   contract_fwd_windows_ring_kernel<pool>   the same with pooling
+ *   contract_fwd_windows_kernel<1>           big launches beyond the ring kernel's shapes
+ * Same products in the same order as chebgcn_contract_fwd: BIT-IDENTICAL to it on the gathered [K][B][C][Mp] stack; with
+ * starts = {0, C, 2C, ...} and T = B*C the two read the very same memory. */
+int chebgcn_contract_fwd_windows_supported(int B, int M, int C, int K, int Fout, int pool);
+int chebgcn_contract_fwd_windows(const float* stack, int64_t T, const int32_t* starts, const float* W, const float* bias,
+                                 int bias_kind, float* out, uint8_t* argmax, int B, int M, int C, int K, int Fout, int pool,
+                                 int pool_kind, int relu, chebgcn_stream stream);
+
 /* ---- the same contraction on the bf16 matrix cores (wide layers: block_dura = 60, Fout = 256,
  * where the fp32-input MFMA is compute bound).  Same operands, epilogue and results layout as
  * chebgcn_contract_fwd; fp32 in HBM, converted in registers, fp32 accumulate.
