@@ -116,6 +116,9 @@ SIGNATURES = {
     'chebgcn_occlusion_class_sums': (_i, [_p, _p, _i, _i, _i, _p, _p]),
     'chebgcn_gradcam_weights': (_i, [_p, _i, _i, _i, _p, _p]),
     'chebgcn_gradcam_map': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i64, _p]),
+    'chebgcn_gather_windows': (_i, [_p, _i64, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    'chebgcn_window_stats_workspace': (C.c_size_t, [_i64, _i, _i]),
+    'chebgcn_window_stats': (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _i, _i, _p, C.c_size_t, _p]),
 }
 
 _lib = None

@@ -36,23 +36,24 @@ class Windows(object):
         return int(self.starts.numel())
 
 
-def window_starts(T, C, starts=None, stride=1):
+def window_starts(T, C, starts=None, stride=1, what='decode_series'):
     """The int64 starts of the windows of ``C`` time points decoded in a run of ``T``: ``starts`` as given (any order,
-    repeats allowed; every window must lie inside the run), else ``range(0, T - C + 1, stride)``.  ``ValueError`` otherwise."""
+    repeats allowed; every window must lie inside the run), else ``range(0, T - C + 1, stride)``.  ``ValueError`` otherwise
+    (``what`` names the calling method in the message)."""
     T, C = int(T), int(C)
     if T < C:
-        raise ValueError('decode_series: a run of T = %d time points is shorter than one window (C = %d)' % (T, C))
+        raise ValueError('%s: a run of T = %d time points is shorter than one window (C = %d)' % (what, T, C))
     if starts is None:
         if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
-            raise ValueError('decode_series: stride must be an int >= 1, got %r' % (stride,))
+            raise ValueError('%s: stride must be an int >= 1, got %r' % (what, stride))
         return np.arange(0, T - C + 1, int(stride), dtype=np.int64)
     a = np.asarray(starts)
     if a.ndim != 1 or a.size == 0 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
-        raise ValueError('decode_series: starts must be a non-empty 1-d int array, got %s %s' % (a.dtype, a.shape))
+        raise ValueError('%s: starts must be a non-empty 1-d int array, got %s %s' % (what, a.dtype, a.shape))
     a = a.astype(np.int64)
     if a.min() < 0 or a.max() + C > T:
-        raise ValueError('decode_series: every start must satisfy 0 <= start and start + %d <= T = %d; got %d ... %d'
-                         % (C, T, a.min(), a.max()))
+        raise ValueError('%s: every start must satisfy 0 <= start and start + %d <= T = %d; got %d ... %d'
+                         % (what, C, T, a.min(), a.max()))
     return a
 
 
@@ -83,23 +84,23 @@ class Decode(object):
 
     # ---------------------------------------------------------------- arguments
 
-    def _decode_args(self, series, starts, stride, scale, shift, share, batch_size, output):
+    def _decode_args(self, series, starts, stride, scale, shift, share, batch_size, output, what='decode_series'):
         """Everything that can be refused before device work.  Returns (runs as arrays / tensors, their starts, batch size,
-        scale, shift as float32 [M, C] or None, whether a list was given)."""
+        scale, shift as float32 [M, C] or None, whether a list was given).  ``what``: the public method the messages name."""
         if output not in OUTPUTS:
-            raise ValueError('decode_series: output must be one of %s, got %r' % (OUTPUTS, output))
+            raise ValueError('%s: output must be one of %s, got %r' % (what, OUTPUTS, output))
         if not (share is True or share is False or share == 'auto'):
-            raise ValueError("decode_series: share must be True, False or 'auto', got %r" % (share,))
+            raise ValueError("%s: share must be True, False or 'auto', got %r" % (what, share))
         bs = self.batch_size if batch_size is None else batch_size
         if isinstance(bs, bool) or not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 65535:
-            raise ValueError('decode_series: batch_size must be an int in [1, 65535], got %r' % (batch_size,))
+            raise ValueError('%s: batch_size must be an int in [1, 65535], got %r' % (what, batch_size))
         many = isinstance(series, (list, tuple))
         runs = list(series) if many else [series]
         if not runs:
-            raise ValueError('decode_series: series is an empty list')
+            raise ValueError('%s: series is an empty list' % what)
         if many and starts is not None:
             if not isinstance(starts, (list, tuple)) or len(starts) != len(runs) or any(np.ndim(s) == 0 for s in starts):
-                raise ValueError('decode_series: with a list of %d runs, starts must be a list of as many arrays' % len(runs))
+                raise ValueError('%s: with a list of %d runs, starts must be a list of as many arrays' % (what, len(runs)))
         per_run = list(starts) if (many and starts is not None) else [starts] * len(runs)
         M0, C = int(self._M0), int(self.channel)
         out_runs, out_starts = [], []
@@ -107,19 +108,19 @@ class Decode(object):
             if not isinstance(r, torch.Tensor):
                 r = np.asarray(r)
                 if not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
-                    raise ValueError('decode_series: series must be numeric, got %s' % r.dtype)
+                    raise ValueError('%s: series must be numeric, got %s' % (what, r.dtype))
             shape = tuple(int(d) for d in r.shape)
             if len(shape) != 2 or shape[1] != M0:
-                raise ValueError('decode_series: series must be [T, %d] (time points x vertices), got %s' % (M0, shape))
-            out_starts.append(window_starts(shape[0], C, st, stride))
+                raise ValueError('%s: series must be [T, %d] (time points x vertices), got %s' % (what, M0, shape))
+            out_starts.append(window_starts(shape[0], C, st, stride, what))
             out_runs.append(r)
 
-        def table(v, what):
+        def table(v, name):
             if v is None:
                 return None
             a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32)
             if a.shape != (M0, C):
-                raise ValueError('decode_series: %s must be [%d, %d] (vertices x channels), got %s' % (what, M0, C, a.shape))
+                raise ValueError('%s: %s must be [%d, %d] (vertices x channels), got %s' % (what, name, M0, C, a.shape))
             return a
         return out_runs, out_starts, int(bs), table(scale, 'scale'), table(shift, 'shift'), many
 
@@ -217,15 +218,15 @@ class Decode(object):
 
     # ---------------------------------------------------------------- device work
 
-    def _stage_series(self, run):
+    def _stage_series(self, run, out=None):
         """One run ``[T, M]`` -> its planes ``[T, Mp]`` on the device in the model's internal vertex order, fp32
-        (chebgcn_perm_data with one channel; the pad of every plane is zero)."""
+        (chebgcn_perm_data with one channel; the pad of every plane is zero).  ``out``: a ``[T, Mp]`` buffer to fill."""
         if isinstance(run, torch.Tensor):
             x = run.to(self.device, torch.float32).contiguous()
         else:
             x = torch.as_tensor(np.ascontiguousarray(run, np.float32)).to(self.device)
         T, M = x.shape
-        out = ops.plane_empty(T, 1, M, self.device)
+        out = ops.plane_empty(T, 1, M, self.device) if out is None else out.view(T, 1, -1)
         order = self._order_dev if self._order_dev is not None else torch.arange(M, dtype=torch.int32, device=self.device)
         for t0 in range(0, T, 32768):                                   # (the kernel's grid takes 65535 rows)
             ops.perm_data(x[t0:t0 + 32768].unsqueeze(2), order, out=out[t0:t0 + 32768])

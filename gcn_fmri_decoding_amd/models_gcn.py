@@ -32,6 +32,7 @@ from . import ops
 from ._lib import BIAS_FILTER, BIAS_NONE, BIAS_VERTEX, POOL_AVG, POOL_MAX, plane_stride
 from .attribution import Attribution
 from .decode import Decode
+from .series import Series, WindowSet
 
 
 class _Spec:
@@ -89,9 +90,10 @@ class InternalPlanes(object):
         return self
 
 
-class base_model(Attribution, Decode):
+class base_model(Attribution, Decode, Series):
     """Counterpart of ``base_model`` (:18-355): run-time interface + variable helpers.  The attribution maps (``saliency``,
-    ``occlusion``, ``gradcam`` and their ``*_maps``) come from ``attribution.Attribution``, ``decode_series`` from ``decode.Decode``."""
+    ``occlusion``, ``gradcam`` and their ``*_maps``) come from ``attribution.Attribution``, ``decode_series`` from ``decode.Decode``,
+    ``stage_windows`` / ``fit_series`` from ``series.Series``."""
 
     def __init__(self, config=None):
         self.regularizers = []          # names of L2-regularised variables (:345, :353)
@@ -138,7 +140,10 @@ class base_model(Attribution, Decode):
     def stage(self, data):
         """Copy a dataset ``[S, M, channel]`` (NumPy, any float dtype, or a torch tensor)
         to the device once, as fp32 in the reference's row layout.  ``fit``/``predict``
-        accept the staged tensor directly; batches are then gathered on the GPU."""
+        accept the staged tensor directly; batches are then gathered on the GPU.  A ``WindowSet`` (``stage_windows``) is
+        staged already and comes back unchanged."""
+        if isinstance(data, WindowSet):
+            return data
         if isinstance(data, torch.Tensor):
             return data.to(self.device, torch.float32).contiguous()
         if not isinstance(data, np.ndarray):
@@ -147,7 +152,10 @@ class base_model(Attribution, Decode):
 
     def _gather(self, data_dev, idx, out=None):
         """``data[idx]`` gathered on the GPU straight into plane storage [B, channel, Mp], in the model's internal vertex
-        order (replaces the host gather + feed of :142-146).  ``out``: a buffer of that shape (``step_inputs()``)."""
+        order (replaces the host gather + feed of :142-146).  ``out``: a buffer of that shape (``step_inputs()``).  The windows
+        of a ``WindowSet`` are cut out of its planes instead (chebgcn_gather_windows)."""
+        if isinstance(data_dev, WindowSet):
+            return data_dev.gather(self, idx, out)
         S, M, C = data_dev.shape
         if out is None or tuple(out.shape) != (int(idx.numel()), C, ops.plane_stride(M)):
             out = ops.plane_empty(int(idx.numel()), C, M, self.device)
@@ -311,6 +319,10 @@ class base_model(Attribution, Decode):
         for step in range(1, num_steps + 1):
             if len(indices) < self.batch_size:
                 indices.extend(np.random.permutation(n_train))
+                if isinstance(train_dev, WindowSet):
+                    starts = train_dev.refill()         # (fit_series(jitter=): this epoch's displaced starts, one upload)
+                    if self.record_fit:
+                        self.fit_log.setdefault('starts', []).append(starts.copy())
                 pool_dev = torch.as_tensor(np.asarray(indices, np.int32)).to(self.device)
                 pool_labels = labels_dev[pool_dev.long()]
                 pool_at = 0
@@ -753,7 +765,8 @@ class base_model(Attribution, Decode):
         """Checkpoint contents, keyed by the reference's variable names and in its shapes
         (``conv1/weights`` [Fin*K, Fout], ``conv1/bias`` [1, M, F] ...), the Adam moments under
         ``adam_m/<name>`` / ``adam_v/<name>`` (TF: ``<name>/Adam``, ``<name>/Adam_1``), and the step
-        counter.  Independent of the internal flat layout."""
+        counter; ``window_scaler`` ([2, M, channel]: scale, shift) when ``fit_series(standardize=True)`` fitted one.
+        Independent of the internal flat layout."""
         sd = {'global_step': int(self.global_step), 'names': self.variables()}
         arch = getattr(self, '_architecture', None)
         if arch is not None:
@@ -762,11 +775,11 @@ class base_model(Attribution, Decode):
             sd[name] = self._ref_view(self._flat, name).detach().cpu().contiguous()
             sd['adam_m/' + name] = self._ref_view(self._adam_m, name).cpu().contiguous()
             sd['adam_v/' + name] = self._ref_view(self._adam_v, name).cpu().contiguous()
-        return sd
+        return self._scaler_to_sd(sd)
 
     def load_state_dict(self, sd):
         """Restore by variable name; shapes are checked.  Optimizer state is optional (a file that
-        holds only variables -- e.g. converted from a TF checkpoint -- restores the weights)."""
+        holds only variables -- e.g. converted from a TF checkpoint -- restores the weights), and so is ``window_scaler``."""
         missing = [n for n in self.variables() if n not in sd]
         if missing:
             raise KeyError('checkpoint lacks variables %s' % missing)
@@ -783,6 +796,7 @@ class base_model(Attribution, Decode):
                     a, b = self._slices[name]
                     self._ref_assign(flat[a:b].view(spec.shape), spec, src)
         self.global_step = int(sd.get('global_step', 0))
+        self._scaler_from_sd(sd)
 
     def _save_best(self, accuracy, step, best, num_to_keep=3):
         """checkmat.BestCheckpointSaver.handle (checkmat.py:43-84, used at models_gcn.py:127, 175):
@@ -1611,7 +1625,7 @@ class finetuning_cgcnn(cgcnn):
         for name in self._trainable:
             sd['adam_m/' + name] = self._ref_view(self._adam_m, name).cpu().contiguous()
             sd['adam_v/' + name] = self._ref_view(self._adam_v, name).cpu().contiguous()
-        return sd
+        return self._scaler_to_sd(sd)
 
     def load_state_dict(self, sd):
         missing = [n for n in self.variables() if n not in sd]
@@ -1630,6 +1644,7 @@ class finetuning_cgcnn(cgcnn):
                     a, b = self._slices[name]
                     self._ref_assign(flat[a:b].view(spec.shape), spec, src)
         self.global_step = int(sd.get('global_step', 0))
+        self._scaler_from_sd(sd)
 
     def _architecture(self):
         arch = {k: self._ctor[k] for k in self._KEYWORDS}

@@ -268,6 +268,37 @@ def perm_data(x, perm, sample=None, out=None):
     return out
 
 
+def gather_windows(planes, rows, M, C, sample=None, scale=None, shift=None, out=None):
+    """Windows of a staged series (chebgcn_gather_windows): ``planes`` [Ttot, Mp] fp32 (internal vertex order, zero pad),
+    ``rows`` int64 device table of the windows' first rows, ``sample`` int32 device indices into it (None: all of them, in
+    order) -> storage [B, C, Mp]; ``scale`` / ``shift`` [C, Mp]: ``x * scale + shift`` in two roundings.  ``out``: a buffer of
+    that shape."""
+    _require_cuda(planes, rows, sample, scale, shift, out)
+    Ttot, Mp = planes.shape
+    B = int(rows.numel() if sample is None else sample.numel())
+    if out is None or tuple(out.shape) != (B, C, Mp) or not out.is_contiguous():
+        out = torch.empty((B, C, Mp), dtype=torch.float32, device=planes.device)
+    _lib.check(_launch('gather_windows', 8.0 * B * C * Mp, 0.0, lambda: _lib.lib().chebgcn_gather_windows(
+        _p(planes), Ttot, _p(rows), _p(sample), _p(scale), _p(shift), _p(out), B, M, C, _stream())), 'gather_windows')
+    return out
+
+
+def window_stats(planes, rows, M, C):
+    """Per (channel, vertex) statistics over the windows ``rows`` of a staged series (chebgcn_window_stats), none of them
+    built: ``(mean, var)`` float64 and ``(scale, shift)`` float32, all [C, Mp] on the device, internal vertex order."""
+    _require_cuda(planes, rows)
+    Ttot, Mp = planes.shape
+    dev = planes.device
+    mean, var = (torch.empty((C, Mp), dtype=torch.float64, device=dev) for _ in range(2))
+    scale, shift = (torch.empty((C, Mp), dtype=torch.float32, device=dev) for _ in range(2))
+    nbytes = int(_lib.lib().chebgcn_window_stats_workspace(Ttot, M, C))
+    ws = _workspace(nbytes, dev, 'window_stats')
+    _lib.check(_launch('window_stats', 4.0 * Ttot * Mp, 0.0, lambda: _lib.lib().chebgcn_window_stats(
+        _p(planes), Ttot, _p(rows), int(rows.numel()), _p(mean), _p(var), _p(scale), _p(shift), M, C, _p(ws), ws.numel(),
+        _stream())), 'window_stats')
+    return mean, var, scale, shift
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------

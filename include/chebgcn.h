@@ -577,6 +577,33 @@ int chebgcn_gradcam_weights(const float* G, int nw, int F, int N, float* alpha, 
 int chebgcn_gradcam_map(const float* A, const float* G, const float* alpha, const int32_t* order, int nw, int F, int N, int P,
                         int relu, float* out, int64_t ldo, chebgcn_stream stream);
 
+/* ---- training on scans: a dataset that IS windows of scans (models_gcn.base_model.stage_windows / fit_series) --------------
+ * series: [Ttot][Mp(M)] planes, every run of the dataset concatenated, in the model's internal vertex order, zero in the pad
+ * (what decode_series stages); rows: int64 [.] on the device, the global row of each window's first time point (run offset +
+ * start).  Window w is the model input x[w][c][m] = series[rows[w] + c][m], c < C: C consecutive planes, never stored per window.
+ * Every row must satisfy 0 <= row and row + C <= Ttot: the CALLER checks the table before it uploads it; a row outside that
+ * range is moved into it by the kernels (the rule of chebgcn_contract_fwd_windows), which never read outside the series.
+ *
+ * gather_windows: out[b][c][m] = series[rows[sample[b]] + c][m], [B][C][Mp]; sample: int32 [B] (device) indices into rows, or
+ *   NULL for the identity (as chebgcn_perm_data).  With scale / shift ([C][Mp], both or neither):  x * scale + shift  as a
+ *   rounded product followed by a rounded sum (never one fma: bit-identical to float32 NumPy).  The pad [M, Mp) of every
+ *   output plane is written as 0.  Bit-identical to chebgcn_perm_data on the windows cut on the host.  16-byte accesses;
+ *   series, tables and out 16-byte aligned; B <= 65535.  chebgcn_last_dispatch(): gather_windows_kernel<plain | tables>.
+ * window_stats: mean[c][m] and population variance var[c][m] (ddof = 0, sklearn's StandardScaler) of x[w][c][m] over the S
+ *   windows rows[0 .. S), float64 [C][Mp] (either may be NULL), and the float32 tables scale = 1/std, shift = -mean/std
+ *   ([C][Mp]; where the variance is 0: scale 1, shift -mean; the pad of all four is 0).  One pass over the series whatever the
+ *   overlap (a per-row count of the windows that start there, then  sum_u n[u - c] f(series[u][m])).  Float64 sums of the
+ *   deviations from series[0][m] in ascending row order inside chunks of 512 rows, chunks added in index order: no float
+ *   atomics, bit-identical from run to run and under any permutation of rows.  workspace: device scratch of at least
+ *   chebgcn_window_stats_workspace() bytes, 16-byte aligned.  chebgcn_last_dispatch(): window_count_kernel +
+ *   window_stats_partial_kernel + window_stats_finish_kernel. */
+int chebgcn_gather_windows(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* sample, const float* scale,
+                           const float* shift, float* out, int B, int M, int C, chebgcn_stream stream);
+size_t chebgcn_window_stats_workspace(int64_t Ttot, int M, int C);
+int chebgcn_window_stats(const float* series, int64_t Ttot, const int64_t* rows, int64_t S, double* mean, double* var,
+                         float* scale, float* shift, int M, int C, void* workspace, size_t workspace_bytes,
+                         chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose
