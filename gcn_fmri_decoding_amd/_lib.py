@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get('CHEBGCN_LIB') or os.path.join(_HERE, 'libchebgcn.so')
 
 BIAS_NONE, BIAS_FILTER, BIAS_VERTEX = 0, 1, 2
 POOL_MAX, POOL_AVG = 0, 1
+KNN_EUCLIDEAN, KNN_COSINE, KNN_CORRELATION, KNN_DOT = 0, 1, 2, 3
+KNN_KMAX = 32
 
 
 class ChebgcnError(RuntimeError):
@@ -119,6 +121,9 @@ SIGNATURES = {
     'chebgcn_gather_windows': (_i, [_p, _i64, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     'chebgcn_window_stats_workspace': (C.c_size_t, [_i64, _i, _i]),
     'chebgcn_window_stats': (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _i, _i, _p, C.c_size_t, _p]),
+    'chebgcn_knn_workspace': (C.c_size_t, [_i, _i, _i]),
+    'chebgcn_knn': (_i, [_p, _i, _i, _i, _i, _p, _p, _p, C.c_size_t, _p]),
+    'chebgcn_series_normalise': (_i, [_p, _i64, _p, _i, _i, _f, _p, _p]),
 }
 
 _lib = None

@@ -6,6 +6,9 @@ Laplacians) are uploaded to the GPU by ``ops.Graph``; ``fourier`` gives the dens
 of the spectral filters (``cgcnn`` with ``filter='fourier'`` / ``'spline'``).  Out of scope
 here and absent on purpose: ``plot_spectrum`` and the dense NumPy recurrence ``chebyshev``
 (the GPU kernel replaces it).
+
+The one stage that does run on the device is the neighbour search: ``knn_device`` and ``connectivity_graph`` (chebgcn_knn)
+return the same ``[N, k]`` tables as ``distance_sklearn_metrics`` without the N x N matrix; ``adjacency`` (N k work) stays here.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -43,6 +46,96 @@ def adjacency(dist, idx):
     flip = W.T > W
     W = W - W.multiply(flip) + W.T.multiply(flip)
     return sp.csr_matrix(W)
+
+
+KNN_METRICS = ('euclidean', 'cosine', 'correlation')
+KNN_KMAX = 32
+
+
+def _knn_check(N, k):
+    if int(k) != k or not 1 <= k <= KNN_KMAX:
+        raise ValueError('k = %r: 1 <= k <= %d neighbours are served on the device' % (k, KNN_KMAX))
+    if k >= N:
+        raise ValueError('k = %d neighbours need more than %d vertices' % (k, N))
+
+
+def _cuda_device(device):
+    import torch
+    if device is None:
+        return torch.device('cuda', torch.cuda.current_device())
+    return torch.device(device)
+
+
+def knn_device(z, k=4, metric='euclidean', device=None):
+    """``distance_sklearn_metrics`` on the device (chebgcn_knn), without the N x N matrix: ``z`` [N, D] features, ``metric``
+    'euclidean', 'cosine' or 'correlation'.  Returns (d float32 [N, k] ascending, idx int64 [N, k]) on the host, ready for
+    ``adjacency``.  Distances are computed in float64 from the float32 features and rounded once.
+
+    Differences from the reference function, both only where distances tie: vertex i itself is excluded by index (the reference
+    drops column 0 of the sorted row, which among coincident points may be another vertex), and equal distances order by
+    lower index.  A zero row under 'cosine' / a constant row under 'correlation' is at distance 1 from everything (sklearn
+    gives such rows distance 1 and NaN).  Bad arguments raise ``ValueError`` before the device is touched."""
+    if metric not in KNN_METRICS:
+        raise ValueError('knn_device: unknown metric %r (one of %s)' % (metric, ', '.join(KNN_METRICS)))
+    z = np.asarray(z)
+    if z.ndim != 2:
+        raise ValueError('knn_device: z must be [N, D], got shape %r' % (z.shape,))
+    N, D = z.shape
+    if D < 1:
+        raise ValueError('knn_device: no features')
+    _knn_check(N, k)
+    z = np.ascontiguousarray(z, dtype=np.float32)
+    if not np.isfinite(z).all():
+        raise ValueError('knn_device: z holds non-finite values')
+    import torch
+    from . import _lib, ops
+    dev = _cuda_device(device)
+    planes = np.zeros((D, _lib.plane_stride(N)), np.float32)
+    planes[:, :N] = z.T
+    with torch.cuda.device(dev):
+        d, idx = ops.knn(torch.as_tensor(planes).to(dev), N, int(k), KNN_METRICS.index(metric))
+        return d.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
+
+
+def connectivity_graph(series, k=8, device=None, return_sigma=False):
+    """Neighbours by functional connectivity, from the scans themselves: ``series`` is one ``[T, M]`` run or a list of runs
+    (any lengths >= 2, same M).  The runs are staged as ``[Ttot, Mp]`` planes in the caller's order, every run is centred and
+    scaled per vertex on the device (chebgcn_series_normalise), and the kNN kernels run on the Gram matrix of the result, which
+    is the mean over runs of the per-run Pearson correlation matrices r (never formed; a vertex constant in a run has
+    correlation 0 with everything in that run).  Returns (d, idx) with ``d = 1 - r`` float32 [M, k] ascending and idx int64,
+    as ``knn_device``; with ``return_sigma`` also the mean of the whole matrix r (diagonal included), the reference's kernel
+    width for its RSFC graph (model.py:126).  Tangent-space and partial correlation are out of scope."""
+    runs = [series] if isinstance(series, np.ndarray) and series.ndim == 2 else list(series)
+    if not runs:
+        raise ValueError('connectivity_graph: no runs')
+    runs = [np.asarray(r) for r in runs]
+    if any(r.ndim != 2 for r in runs):
+        raise ValueError('connectivity_graph: every run must be [T, M]')
+    M = runs[0].shape[1]
+    if any(r.shape[1] != M for r in runs):
+        raise ValueError('connectivity_graph: runs differ in the number of vertices')
+    if any(r.shape[0] < 2 for r in runs):
+        raise ValueError('connectivity_graph: a run needs at least two time points')
+    _knn_check(M, k)
+    runs = [np.ascontiguousarray(r, dtype=np.float32) for r in runs]
+    if not all(np.isfinite(r).all() for r in runs):
+        raise ValueError('connectivity_graph: series hold non-finite values')
+    import torch
+    from . import _lib, ops
+    dev = _cuda_device(device)
+    offs = np.concatenate([[0], np.cumsum([r.shape[0] for r in runs])]).astype(np.int64)
+    planes = np.zeros((int(offs[-1]), _lib.plane_stride(M)), np.float32)
+    for r, o in zip(runs, offs):
+        planes[o:o + r.shape[0], :M] = r
+    with torch.cuda.device(dev):
+        zn = ops.series_normalise(torch.as_tensor(planes).to(dev), torch.as_tensor(offs).to(dev), M,
+                                  scale=1.0 / np.sqrt(len(runs)))
+        d, idx = ops.knn(zn, M, int(k), _lib.KNN_DOT)
+        out = (d.cpu().numpy(), idx.cpu().numpy().astype(np.int64))
+        if return_sigma:
+            col = zn[:, :M].sum(dim=1, dtype=torch.float64)       # sum_ij r_ij = sum_t (sum_m zn[t][m])^2
+            out += (float((col * col).sum().item()) / (M * M),)
+    return out
 
 
 def replace_random_edges(A, noise_level):
@@ -180,14 +273,20 @@ def permute(L, order):
     return Lp
 
 
-def synthetic_graph(n_nodes=10000, k=8, levels=1, noise_level=0.01, seed=0, dtype=np.float32):
+def synthetic_graph(n_nodes=10000, k=8, levels=1, noise_level=0.01, seed=0, dtype=np.float32, knn='host'):
     """The seeded synthetic "brain" graph of the benchmark: kNN
     graph on uniform points in the unit cube, 1 % random edges, ``levels`` rounds of
     coarsening, one normalised Laplacian per level.  Returns (laplacians, perm, graphs).
+    ``knn='device'`` finds the neighbours with ``knn_device`` instead of the full distance matrix.
     """
     from . import coarsening
     z = np.random.RandomState(seed).rand(n_nodes, 3).astype(np.float32)
-    d, idx = distance_sklearn_metrics(z, k=k, metric='euclidean')
+    if knn == 'host':
+        d, idx = distance_sklearn_metrics(z, k=k, metric='euclidean')
+    elif knn == 'device':
+        d, idx = knn_device(z, k=k, metric='euclidean')
+    else:
+        raise ValueError("synthetic_graph: knn must be 'host' or 'device', not %r" % (knn,))
     A = adjacency(d, idx).astype(dtype)
     np.random.seed(seed)
     A = replace_random_edges(A, noise_level)

@@ -299,6 +299,48 @@ def window_stats(planes, rows, M, C):
     return mean, var, scale, shift
 
 
+def knn(planes, N, k, metric):
+    """The k nearest other vertices of every vertex (chebgcn_knn): ``planes`` [D, Np] fp32 feature-major planes on the device
+    (zero pad), ``metric`` one of ``_lib.KNN_*`` -> ``(dist float32 [N, k] ascending, idx int32 [N, k])`` on the device.  The
+    N x N matrix is never formed."""
+    _require_cuda(planes)
+    D, Np = planes.shape
+    if Np != plane_stride(N) or planes.dtype != torch.float32 or not planes.is_contiguous():
+        raise _lib.ChebgcnError('knn: planes must be contiguous float32 [D, plane_stride(N)]')
+    dev = planes.device
+    nbytes = int(_lib.lib().chebgcn_knn_workspace(N, D, k))
+    ws = _workspace(nbytes, dev, 'knn')
+    dist = torch.empty((N, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((N, k), dtype=torch.int32, device=dev)
+    _lib.check(_launch('knn', 4.0 * D * Np + 8.0 * N * k, 2.0 * N * N * D, lambda: _lib.lib().chebgcn_knn(
+        _p(planes), N, D, k, int(metric), _p(dist), _p(idx), _p(ws), ws.numel(), _stream())), 'knn')
+    return dist, idx
+
+
+def series_normalise(planes, run_offsets, M, scale=1.0, out=None):
+    """Every run of a staged series centred and scaled to norm ``scale`` per vertex inside that run
+    (chebgcn_series_normalise): ``planes`` [Ttot, Mp] fp32, ``run_offsets`` int64 [R + 1] on the device (run r = rows
+    [run_offsets[r], run_offsets[r + 1]), checked by the caller) -> [Ttot, Mp]; a vertex constant in a run is zero there."""
+    _require_cuda(planes, run_offsets, out)
+    if planes.dim() != 2 or planes.shape[1] != plane_stride(M) or planes.dtype != torch.float32 or not planes.is_contiguous():
+        raise _lib.ChebgcnError('series_normalise: planes must be contiguous float32 [Ttot, plane_stride(M)]')
+    Ttot, Mp = planes.shape
+    R = int(run_offsets.numel()) - 1
+    if run_offsets.dtype != torch.int64 or run_offsets.dim() != 1 or R < 1 or not run_offsets.is_contiguous():
+        raise _lib.ChebgcnError('series_normalise: run_offsets must be a contiguous int64 vector of R + 1 entries')
+    o = run_offsets.cpu().numpy()           # one small download: the kernel trusts the table, so it is checked here
+    if o[0] != 0 or o[-1] != Ttot or (np.diff(o) < 1).any():
+        raise _lib.ChebgcnError('series_normalise: run_offsets must ascend from 0 to Ttot')
+    if out is None:
+        out = torch.empty_like(planes)
+    elif (out.shape != planes.shape or out.dtype != torch.float32 or not out.is_contiguous()
+          or out.data_ptr() == planes.data_ptr()):
+        raise _lib.ChebgcnError('series_normalise: out must be a contiguous float32 tensor shaped like planes, not planes itself')
+    _lib.check(_launch('series_normalise', 16.0 * Ttot * Mp, 0.0, lambda: _lib.lib().chebgcn_series_normalise(
+        _p(planes), Ttot, _p(run_offsets), R, M, float(scale), _p(out), _stream())), 'series_normalise')
+    return out
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------

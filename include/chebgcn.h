@@ -604,6 +604,48 @@ int chebgcn_window_stats(const float* series, int64_t Ttot, const int64_t* rows,
                          float* scale, float* shift, int M, int C, void* workspace, size_t workspace_bytes,
                          chebgcn_stream stream);
 
+/* ---- kNN brain graphs on the device (graph.knn_device / graph.connectivity_graph) ------------------------------------------
+ * feat: [D][Np(N)] fp32, feature-major planes of N vertices (the staged-series layout with D = time; coordinates are
+ * transposed by the caller), zero in the pad.  For every vertex i the k nearest OTHER vertices under `metric`:
+ *   dist: float32 [N][k] ascending;  idx: int32 [N][k].  Vertex i itself is excluded BY INDEX (the reference drops column 0 of
+ *   the sorted row instead, graph.py:14: where points coincide that can drop another vertex and keep i as its own neighbour at
+ *   distance 0; everywhere else the two agree).  Equal distances order by lower index first.
+ *   EUCLIDEAN    |a - b|
+ *   COSINE       1 - a.b / (|a| |b|)
+ *   CORRELATION  cosine of the rows centred over d
+ *   DOT          1 - a.b, rows taken as prepared by the caller (the output of chebgcn_series_normalise with scale =
+ *                1/sqrt(R): 1 - the mean over runs of the per-run Pearson correlation)
+ *                (arms by D like every metric: a series of at most 8 time points in all runs the direct arm)
+ *   A zero-norm row under COSINE and a constant row under CORRELATION have similarity 0 (distance 1) to everything: never NaN.
+ *   Features must be finite (the caller checks).
+ * Served: 1 <= k <= 32 (CHEBGCN_EUNSUPPORTED beyond) and k < N (CHEBGCN_EINVAL), checked before any launch.
+ * Arms (chebgcn_last_dispatch(): knn_prep_kernel + <arm> + knn_merge_refine_kernel):
+ *   knn_direct_kernel<whole | split>  D <= 8: differences / products on the vector ALU, a thread per query;
+ *   knn_gram_kernel<whole | split>    D > 8: the Gram tile on v_mfma_f32_32x32x2_f32 (any D: odd, not a multiple of the
+ *                                     eight-feature loop turn), a wave per 32 queries, lists of candidates in LDS;
+ *   <split>: fewer query blocks than CUs, the candidate range is cut into up to 8 pieces with their own partial lists.
+ * Selection runs on float32 keys with k + 8 candidates kept per query; the k returned distances are recomputed from the
+ * features with float64 accumulators in ascending d (never the cancelling Gram form) and rounded once to float32.  Prep sums
+ * (means, norms) are float64 in ascending d.  No float atomics, every order fixed: two calls give bit-identical outputs.
+ * workspace: device scratch of at least chebgcn_knn_workspace() bytes (0 = shape not served), 16-byte aligned, as is feat.
+ *
+ * series_normalise: series [Ttot][Mp(M)] = R runs concatenated, run r = rows [run_offsets[r], run_offsets[r + 1]) (int64
+ *   [R + 1] on the device, ascending, run_offsets[R] = Ttot: the CALLER checks the table).  out[t][m] = (series[t][m] - mean)
+ *   / norm * scale, mean and norm of vertex m inside ITS run (float64, ascending t); a vertex constant in a run is all zeros
+ *   there, the pad is zero.  With scale = 1 the Gram matrix of out over t, divided by R, is the mean over runs of the per-run
+ *   Pearson correlation matrices; neither is ever formed.  chebgcn_last_dispatch(): series_normalise_kernel. */
+enum {
+    CHEBGCN_KNN_EUCLIDEAN = 0,
+    CHEBGCN_KNN_COSINE = 1,
+    CHEBGCN_KNN_CORRELATION = 2,
+    CHEBGCN_KNN_DOT = 3
+};
+size_t chebgcn_knn_workspace(int N, int D, int k);
+int chebgcn_knn(const float* feat, int N, int D, int k, int metric, float* dist_out, int32_t* idx_out, void* workspace,
+                size_t workspace_bytes, chebgcn_stream stream);
+int chebgcn_series_normalise(const float* series, int64_t Ttot, const int64_t* run_offsets, int R, int M, float scale,
+                             float* out, chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose
