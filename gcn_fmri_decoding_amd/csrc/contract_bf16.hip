@@ -10,6 +10,11 @@
 // passes = 3: each operand split x = hi + lo (two bf16) and  hi*hi + hi*lo + lo*hi accumulated
 //             (the lo*lo term, 2^-16 relative, is dropped)   -> ~fp32-grade results at three
 //             times the matrix work, which is still below the HBM time of the op.
+//             Reductions of at most CG_BF16_LOLO_KSTEPS k-steps (Fin*K <= 32) accumulate lo*lo as well: a sum of a few
+//             products does not average the dropped term away -- four products per output, 3.5 million outputs: 1.07e-5 of
+//             max |y| without it (the arithmetic itself, in float64), 0.80e-5 with it, against the 1e-5 every contraction is
+//             held to -- and such a launch is bound by its result stores, not by its matrix work
+//             (tests/test_gpu_contract_pool_epilogue.py).
 //
 // Mapping.  A workgroup = 128 consecutive vertices of one window x 256 filters; wave w owns
 // filters 64w..64w+63 (two 32-row MFMA tiles) for all 128 vertices.  As in contract.hip the
@@ -152,6 +157,10 @@ struct Bf16Cfg {
     static_assert(!RING_BIAS || (NDMA0 <= 8 && NDMA1 <= 8) || STAGE >= 16384 + 1024, "padding DMAs of a bias stage leave the stage");
 };
 
+#ifndef CG_BF16_LOLO_KSTEPS
+#define CG_BF16_LOLO_KSTEPS 2
+#endif
+
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int PASSES, int NW, bool X16 = false, int NVT = 1>
@@ -165,6 +174,7 @@ contract_fwd_bf16_kernel(FwdArgs a, const __bf16* __restrict__ Wp, int nks, int 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 31, g = lane >> 5;
     const size_t lo_part = (size_t)nks * FoutP * 16;                     // bf16 elements between the hi and lo image
+    const bool lolo = PASSES == 3 && nks <= CG_BF16_LOLO_KSTEPS;         // short reductions keep the lo*lo term (uniform)
 
     // work item = (filter group of 64 NWF, window, 128 NVT vertices), walked with the pipeline running (ntm = tiles of 128 NVT).
     // XCD-aware order: workgroup w runs on XCD w % 8 (round-robin dispatch); XCD x takes the vertex tiles x, x + 8, ... for
@@ -396,6 +406,10 @@ contract_fwd_bf16_kernel(FwdArgs a, const __bf16* __restrict__ Wp, int nks, int 
                     bh[i] = (__bf16)v;
                     if (PASSES == 3) bl[i] = (__bf16)(v - (float)bh[i]);
                 }
+                }
+                if (lolo) {
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) acc[t][r] = mfma_bf16(al[t], bl, acc[t][r]);
                 }
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
