@@ -119,6 +119,7 @@ SIGNATURES = {
     'chebgcn_gradcam_weights': (_i, [_p, _i, _i, _i, _p, _p]),
     'chebgcn_gradcam_map': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i64, _p]),
     'chebgcn_gather_windows': (_i, [_p, _i64, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    'chebgcn_gather_windows_mix': (_i, [_p, _i64, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _p]),
     'chebgcn_window_stats_workspace': (C.c_size_t, [_i64, _i, _i]),
     'chebgcn_window_stats': (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p, _i, _i, _p, C.c_size_t, _p]),
     'chebgcn_knn_workspace': (C.c_size_t, [_i, _i, _i]),

@@ -6,6 +6,9 @@
 //
 //   gather:  out[b][c][m] = x[rows[sample[b]]][c][m]  (* scale[c][m] + shift[c][m], two roundings), [B][C][Mp], pad zero:
 //            a contiguous copy of C * Mp floats per window, 16 bytes per lane.
+//   mix:     out[b][c][m] = (sum_{j < cnt[w]} series[rows[w][j] + c][m]) / cnt[w],  w = sample[b]: a window that is the mean of
+//            up to 16 source windows (class balancing: a re-drawn copy at cnt = 1, a synthetic window above), float32 adds in
+//            ascending j, one rounded division, then the tables: cnt + 1 windows of HBM traffic per output window.
 //   stats:   mean / population variance over the S windows for every (c, m), without building a window: with n[t] = how many
 //            windows start at row t,  sum_w f(x[w][c][m]) = sum_u n[u - c] f(series[u][m]):  ONE pass over the series, every
 //            plane read once per group of 8 channels however much the windows overlap.  Sums run in float64 on the deviations
@@ -68,6 +71,96 @@ gather_windows_kernel(const float* __restrict__ series, long long last_row, cons
             dst[e] = r;
         }
     }
+}
+
+// ---- the mix gather: an output window is the mean of n <= GWM_MAX source windows (series.balance_plan) ------------------------
+// One window's n is the same for every thread of its blocks, so the kernel branches ONCE on it into a body whose source count
+// is a compile-time constant: the n loads of a piece are straight-line code, all issued before the first add (a per-load
+// "j < n" test would make the compiler wait for every load on its own).  Pieces in flight per thread: n * U float4s <= 16.
+constexpr int GWM_MAX = 16;
+
+template <bool Tables, int N>
+__device__ __forceinline__ void mix_pieces(const float4* __restrict__ series4, long long last_row,
+                                           const long long* __restrict__ rw, const float* __restrict__ scale,
+                                           const float* __restrict__ shift, float4* __restrict__ dst, int M, int Mq, int CMq) {
+    constexpr int U = N <= 4 ? GW_U : (N <= 8 ? GW_U / 2 : GW_U / 4);
+    const float4* src[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) src[j] = series4 + clamp_row(rw[j], last_row) * Mq;
+    for (int p = 0; p < GW_U / U; ++p) {
+        const int e0 = blockIdx.x * (GW_T * GW_U) + p * (GW_T * U) + threadIdx.x;
+        float4 v[N][U], a[U], s[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * GW_T;
+            if (e < CMq) {
+#pragma unroll
+                for (int j = 0; j < N; ++j) v[j][u] = src[j][e];
+                if (Tables) {
+                    a[u] = reinterpret_cast<const float4*>(scale)[e];
+                    s[u] = reinterpret_cast<const float4*>(shift)[e];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * GW_T;
+            if (e < CMq) {
+                float4 r = v[0][u];
+#pragma unroll
+                for (int j = 1; j < N; ++j) {           // float32 adds in ascending j
+                    r.x = __fadd_rn(r.x, v[j][u].x);
+                    r.y = __fadd_rn(r.y, v[j][u].y);
+                    r.z = __fadd_rn(r.z, v[j][u].z);
+                    r.w = __fadd_rn(r.w, v[j][u].w);
+                }
+                if (N > 1) {                            // one correctly rounded division (n = 1: the plain gather's bits)
+                    r.x = __fdiv_rn(r.x, (float)N);
+                    r.y = __fdiv_rn(r.y, (float)N);
+                    r.z = __fdiv_rn(r.z, (float)N);
+                    r.w = __fdiv_rn(r.w, (float)N);
+                }
+                if (Tables) {                           // after the mean; a rounded product, then a rounded sum
+                    r.x = __fadd_rn(__fmul_rn(r.x, a[u].x), s[u].x);
+                    r.y = __fadd_rn(__fmul_rn(r.y, a[u].y), s[u].y);
+                    r.z = __fadd_rn(__fmul_rn(r.z, a[u].z), s[u].z);
+                    r.w = __fadd_rn(__fmul_rn(r.w, a[u].w), s[u].w);
+                }
+                const int m = 4 * (e % Mq);
+                if (m + 3 >= M) {
+                    if (m >= M) r.x = 0.f;
+                    if (m + 1 >= M) r.y = 0.f;
+                    if (m + 2 >= M) r.z = 0.f;
+                    r.w = 0.f;
+                }
+                dst[e] = r;
+            }
+        }
+    }
+}
+
+// block (piece of the window's C * Mp/4 float4s, window b); rows [.][smax], cnt [.]: a count outside [1, smax] is clamped into it
+template <bool Tables>
+__global__ void __launch_bounds__(GW_T)
+gather_windows_mix_kernel(const float* __restrict__ series, long long last_row, const long long* __restrict__ rows,
+                          const int32_t* __restrict__ cnt, int smax, const int32_t* __restrict__ sample,
+                          const float* __restrict__ scale, const float* __restrict__ shift, float* __restrict__ out, int M, int Mq,
+                          int CMq) {
+    const int b = blockIdx.y;
+    const long long w = sample ? sample[b] : b;
+    int n = cnt[w];
+    n = n < 1 ? 1 : (n > smax ? smax : n);
+    const long long* rw = rows + w * smax;
+    const float4* series4 = reinterpret_cast<const float4*>(series);
+    float4* dst = reinterpret_cast<float4*>(out) + (long long)b * CMq;
+#define CG_MIX_CASE(N) case N: mix_pieces<Tables, N>(series4, last_row, rw, scale, shift, dst, M, Mq, CMq); break;
+    switch (n) {
+        CG_MIX_CASE(1) CG_MIX_CASE(2) CG_MIX_CASE(3) CG_MIX_CASE(4) CG_MIX_CASE(5) CG_MIX_CASE(6) CG_MIX_CASE(7) CG_MIX_CASE(8)
+        CG_MIX_CASE(9) CG_MIX_CASE(10) CG_MIX_CASE(11) CG_MIX_CASE(12) CG_MIX_CASE(13) CG_MIX_CASE(14) CG_MIX_CASE(15)
+        CG_MIX_CASE(16)
+    }
+#undef CG_MIX_CASE
+    static_assert(GWM_MAX == 16, "one case per source count");
 }
 
 // n[lead + row] += 1 per window (integer adds: the counts do not depend on the order of arrival).  lead = C - 1 + WS_CG zeros in
@@ -203,6 +296,33 @@ extern "C" int chebgcn_gather_windows(const float* series, int64_t Ttot, const i
         note_dispatch("gather_windows_kernel<plain>");
         hipLaunchKernelGGL(gather_windows_kernel<false>, grid, dim3(GW_T), 0, (hipStream_t)stream_, series,
                            (long long)(Ttot - C), (const long long*)rows, sample, scale, shift, out, M, Mq, CMq);
+    }
+    CG_HIP(hipGetLastError());
+    return CHEBGCN_OK;
+}
+
+extern "C" int chebgcn_gather_windows_mix(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* cnt, int smax,
+                                          const int32_t* sample, const float* scale, const float* shift, float* out, int B, int M,
+                                          int C, chebgcn_stream stream_) {
+    CG_REQUIRE(series && rows && out, "gather_windows_mix: NULL argument");
+    CG_REQUIRE(cnt, "gather_windows_mix: NULL cnt (the number of sources of every window)");
+    CG_REQUIRE(smax >= 1 && smax <= GWM_MAX, "gather_windows_mix: smax = %d, must be in [1, %d]", smax, GWM_MAX);
+    CG_REQUIRE((scale != nullptr) == (shift != nullptr), "gather_windows_mix: scale and shift come together (both or neither)");
+    CG_REQUIRE(B > 0 && B <= 65535 && M > 0 && C > 0 && (int64_t)C * plane_stride(M) / 4 <= 0x7fffffffLL / 2,
+               "gather_windows_mix: bad shape (B = %d, M = %d, C = %d)", B, M, C);
+    CG_REQUIRE(Ttot >= C, "gather_windows_mix: a series of %lld time points holds no window of %d", (long long)Ttot, C);
+    CG_REQUIRE((((uintptr_t)series | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
+               "gather_windows_mix: series, tables and out must be 16-byte aligned");
+    const int Mq = plane_stride(M) / 4, CMq = C * Mq;
+    dim3 grid((CMq + GW_T * GW_U - 1) / (GW_T * GW_U), B);
+    if (scale) {
+        note_dispatch("gather_windows_mix_kernel<tables>");
+        hipLaunchKernelGGL(gather_windows_mix_kernel<true>, grid, dim3(GW_T), 0, (hipStream_t)stream_, series,
+                           (long long)(Ttot - C), (const long long*)rows, cnt, smax, sample, scale, shift, out, M, Mq, CMq);
+    } else {
+        note_dispatch("gather_windows_mix_kernel<plain>");
+        hipLaunchKernelGGL(gather_windows_mix_kernel<false>, grid, dim3(GW_T), 0, (hipStream_t)stream_, series,
+                           (long long)(Ttot - C), (const long long*)rows, cnt, smax, sample, scale, shift, out, M, Mq, CMq);
     }
     CG_HIP(hipGetLastError());
     return CHEBGCN_OK;

@@ -323,6 +323,8 @@ class base_model(Attribution, Decode, Series):
                     starts = train_dev.refill()         # (fit_series(jitter=): this epoch's displaced starts, one upload)
                     if self.record_fit:
                         self.fit_log.setdefault('starts', []).append(starts.copy())
+                        if train_dev.sources is not None:       # (fit_series(sampling=): this epoch's plan)
+                            self.fit_log.setdefault('sources', []).append(tuple(a.copy() for a in train_dev.sources))
                 pool_dev = torch.as_tensor(np.asarray(indices, np.int32)).to(self.device)
                 pool_labels = labels_dev[pool_dev.long()]
                 pool_at = 0

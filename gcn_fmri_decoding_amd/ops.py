@@ -283,6 +283,27 @@ def gather_windows(planes, rows, M, C, sample=None, scale=None, shift=None, out=
     return out
 
 
+def gather_windows_mix(planes, rows, cnt, M, C, sample=None, scale=None, shift=None, out=None, sources=None):
+    """Windows that are means of source windows (chebgcn_gather_windows_mix): ``rows`` int64 [S', smax] and ``cnt`` int32 [S']
+    device tables (window ``w`` is the mean of the ``cnt[w]`` windows that start at ``rows[w, :cnt[w]]``: float32 adds in that
+    order, one rounded division, then the tables), otherwise ``gather_windows``.  ``sources``: the mean ``cnt`` of the
+    windows gathered, for the launch log's byte count (None: ``smax``)."""
+    _require_cuda(planes, rows, cnt, sample, scale, shift, out)
+    Ttot, Mp = planes.shape
+    if rows.dim() != 2 or cnt.dim() != 1 or rows.shape[0] != cnt.shape[0] or rows.dtype != torch.int64 \
+            or cnt.dtype != torch.int32 or not rows.is_contiguous() or not cnt.is_contiguous():
+        raise _lib.ChebgcnError('gather_windows_mix: rows must be contiguous int64 [S, smax] and cnt int32 [S]')
+    smax = int(rows.shape[1])
+    B = int(cnt.numel() if sample is None else sample.numel())
+    if out is None or tuple(out.shape) != (B, C, Mp) or not out.is_contiguous():
+        out = torch.empty((B, C, Mp), dtype=torch.float32, device=planes.device)
+    nsrc = float(smax if sources is None else sources)
+    _lib.check(_launch('gather_windows_mix', 4.0 * (nsrc + 1) * B * C * Mp, 0.0, lambda: _lib.lib().chebgcn_gather_windows_mix(
+        _p(planes), Ttot, _p(rows), _p(cnt), smax, _p(sample), _p(scale), _p(shift), _p(out), B, M, C, _stream())),
+        'gather_windows_mix')
+    return out
+
+
 def window_stats(planes, rows, M, C):
     """Per (channel, vertex) statistics over the windows ``rows`` of a staged series (chebgcn_window_stats), none of them
     built: ``(mean, var)`` float64 and ``(scale, shift)`` float32, all [C, Mp] on the device, internal vertex order."""

@@ -7,7 +7,9 @@ on the stack, every split transformed): a time point is stored once per window t
 outside the model.  Here the series is stored once (``channel`` x less memory at stride 1), ``fit`` / ``predict`` /
 ``evaluate`` take the set wherever they take an array, the scaler's tables come from one pass over the series
 (chebgcn_window_stats) in exactly the form ``decode_series(scale=, shift=)`` takes, and moving a window a few TRs inside its
-trial is a new row table, not a new array."""
+trial is a new row table, not a new array.  Balancing unbalanced classes (the reference's ``sampling``) is a table as well:
+``balance_plan`` says which original windows every extra window is the mean of, and chebgcn_gather_windows_mix forms them
+batch by batch."""
 import numpy as np
 import torch
 
@@ -43,11 +45,99 @@ def jitter_rows(rows, lo, hi, jitter, rng):
     return np.clip(rows + d, lo, hi)
 
 
+SAMPLING_MAX = 16              # sources of one synthetic window at most (the mix gather holds them in registers)
+
+
+def check_sampling(sampling, what, least=0):
+    """``sampling`` as an int in ``[least, SAMPLING_MAX]``; a bool, a non-int or a value outside is a ``ValueError``."""
+    if isinstance(sampling, bool) or not isinstance(sampling, (int, np.integer)) or not least <= sampling <= SAMPLING_MAX:
+        raise ValueError('%s: sampling must be an int in [%d, %d], got %r' % (what, least, SAMPLING_MAX, sampling))
+    return int(sampling)
+
+
+def _int_vector(a, name, what, n=None):
+    a = np.asarray(a)
+    if a.ndim != 1 or a.dtype.kind not in 'iu' or (n is not None and len(a) != n):
+        raise ValueError('%s: %s must be a 1-D int array%s, got %s %s'
+                         % (what, name, '' if n is None else ' of %d entries' % n, a.dtype, a.shape))
+    return a.astype(np.int64)
+
+
+def check_balance_args(what, labels, S, sampling, seed, groups, nruns, resample):
+    """The arguments of ``WindowSet.balance`` / ``fit_series(sampling=...)``, refused with a ``ValueError`` or returned as
+    ``(labels int64 [S], one group id per run int64 [nruns])``."""
+    check_sampling(sampling, what)
+    labels = _int_vector(labels, 'labels', what, S)
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 32:
+        raise ValueError('%s: the sampling seed must be an int in [0, 2**32), got %r' % (what, seed))
+    if not isinstance(resample, (bool, np.bool_)):
+        raise ValueError('%s: resample must be a bool, got %r' % (what, resample))
+    if groups is None:
+        return labels, np.arange(nruns, dtype=np.int64)
+    return labels, _int_vector(groups, 'the sampling groups (one id per run)', what, nruns)
+
+
+def balance_plan(labels, groups, sampling, rng):
+    """Which windows top up the small classes of an unbalanced set: ``(src, cnt, new_labels)``.
+
+    ``labels`` int ``[S]``, ``groups`` int ``[S]`` (the scan, or subject, of every window), ``sampling`` an int in [1, 16],
+    ``rng`` a ``np.random.RandomState`` (the global NumPy stream is never touched).  With ``n_c`` windows of class ``c`` and
+    ``n_max`` the largest class, a class with ``2 n_c <= n_max`` gets ``n_c * (n_max // n_c - 1)`` extra windows, every other
+    class none.  Window ``w`` of the balanced set is the mean of the ``cnt[w]`` windows ``src[w, :cnt[w]]``:
+
+    * the originals keep the indices ``0 .. S-1`` (``cnt = 1``, ``src[w, 0] = w``); the extra windows follow, classes in
+      ascending label order; ``new_labels`` ``[S']`` are the labels of all of them;
+    * ``sampling == 1``: an extra window is ONE window of its class, drawn uniformly with replacement;
+    * ``sampling >= 2``: per extra window, groups are drawn uniformly with replacement and all windows of class ``c`` of the
+      drawn group appended, in window order, to a pool (a group without any adds nothing, a group drawn twice adds twice) until
+      the pool holds at least ``sampling`` windows; the sources are ``sampling`` entries of the pool, drawn uniformly with
+      replacement -- a synthetic window, the mean of same-class windows of a few scans.
+
+    ``src`` is int64 ``[S', max(1, sampling)]`` (entries past ``cnt`` repeat entry 0), ``cnt`` int32 ``[S']``."""
+    what = 'balance_plan'
+    sampling = check_sampling(sampling, what, least=1)
+    labels = _int_vector(labels, 'labels', what)
+    groups = _int_vector(groups, 'groups', what, len(labels))
+    S = len(labels)
+    if S == 0:
+        raise ValueError('%s: labels is empty' % what)
+    smax = max(1, sampling)
+    classes, counts = np.unique(labels, return_counts=True)                # ascending labels
+    n_max = int(counts.max())
+    group_ids = np.unique(groups)
+    src = [np.repeat(np.arange(S, dtype=np.int64)[:, None], smax, axis=1)]
+    new_labels = [labels]
+    for c, n_c in zip(classes.tolist(), counts.tolist()):
+        extra = n_c * (n_max // n_c - 1) if 2 * n_c <= n_max else 0
+        if extra == 0:
+            continue
+        own = np.flatnonzero(labels == c)                                  # window order
+        if sampling == 1:
+            rows = own[rng.randint(0, n_c, size=extra)][:, None]
+        else:
+            of_group = [own[groups[own] == g] for g in group_ids]
+            rows = np.empty((extra, sampling), np.int64)
+            for x in range(extra):
+                pool, n = [], 0
+                while n < sampling:
+                    t = of_group[rng.randint(0, len(group_ids))]
+                    pool.append(t)
+                    n += len(t)
+                rows[x] = np.concatenate(pool)[rng.randint(0, n, size=sampling)]
+        src.append(rows)
+        new_labels.append(np.full(extra, c, np.int64))
+    src = np.concatenate(src)
+    cnt = np.ones(len(src), np.int32)
+    cnt[S:] = sampling
+    return src, cnt, np.concatenate(new_labels).astype(labels.dtype)
+
+
 class WindowSet(object):
     """``S`` windows of ``channel`` time points over staged runs: ``planes`` ``[Ttot, Mp]`` (every run concatenated, the owner's
     internal vertex order, zero pad), ``rows`` the int64 device table of first rows, optionally the ``[channel, Mp]`` device
     tables of a normalisation ``x * scale + shift``.  ``len()`` and ``shape == (S, M, channel)`` are those of the array it
-    stands for."""
+    stands for.  After ``balance()`` the set stands for ``S' >= S`` windows: the originals and, behind them, the windows
+    that top up the small classes, each the mean of ``cnt`` source windows (``sources``)."""
 
     def __init__(self, owner, planes, run_lengths, run_starts, M, C):
         self.owner, self.planes = owner, planes
@@ -62,6 +152,8 @@ class WindowSet(object):
         self.scaler = None              # the same as NumPy [M, C] in the caller's order
         self.stats = None               # fit_scaler(): (mean, var) float64 [M, C] in the caller's order
         self.jitter, self.jitter_rng = 0, None
+        self.plan = None                # balance(): dict(src, cnt, labels, groups, sampling, resample, rng)
+        self.mix_rows_host = self.mix_rows = self.mix_cnt = None   # [S', smax] first rows of every source; device: int64 / int32
 
     def __len__(self):
         return self.shape[0]
@@ -75,6 +167,8 @@ class WindowSet(object):
     def nbytes(self):
         """Device bytes of the set: planes, row table, tables."""
         n = self.planes.numel() * 4 + self.rows.numel() * 8
+        if self.plan is not None:
+            n += self.mix_rows.numel() * 8 + self.mix_cnt.numel() * 4
         return n + (sum(t.numel() * 4 for t in self.tables) if self.tables is not None else 0)
 
     # ---------------------------------------------------------------- tables
@@ -125,19 +219,34 @@ class WindowSet(object):
 
     def gather(self, model, idx, out=None):
         """The windows ``idx`` (int32 device indices; None: all) as ``InternalPlanes`` ``[B, channel, Mp]`` of ``model``
-        (chebgcn_gather_windows), straight into ``out`` when that has the shape."""
+        (chebgcn_gather_windows; of a balanced set chebgcn_gather_windows_mix), straight into ``out`` when that has the
+        shape."""
         if model is not self.owner and not model._same_order(self.owner):
             raise ValueError('this WindowSet is staged in the internal vertex order of another model')
         S, M, C = self.shape
         scale, shift = self.tables if self.tables is not None else (None, None)
+        if self.plan is not None:
+            return model.as_internal(ops.gather_windows_mix(self.planes, self.mix_rows, self.mix_cnt, M, C, idx, scale, shift,
+                                                            out, sources=self.plan['cnt'].mean()))
         return model.as_internal(ops.gather_windows(self.planes, self.rows, M, C, idx, scale, shift, out))
 
     def materialise(self):
         """The ``[S, M, channel]`` float32 array the set stands for, in the caller's vertex order, as the model sees it (the
-        tables applied, in float32 like the kernel: a rounded product, then a rounded sum)."""
+        tables applied, in float32 like the kernel: a rounded product, then a rounded sum).  Of a balanced set: the ``S'``
+        windows, the sources added in float32 in their order and divided once by ``cnt``, then the tables."""
         S, M, C = self.shape
         series = self._caller_order(self.planes)                                        # [M, Ttot]
-        x = series[:, self.rows_host[:, None] + np.arange(C)[None, :]]                 # [M, S, C]
+        if self.plan is None:
+            x = series[:, self.rows_host[:, None] + np.arange(C)[None, :]]             # [M, S, C]
+        else:
+            cnt = self.plan['cnt']
+            x = series[:, self.mix_rows_host[:, 0, None] + np.arange(C)[None, :]]
+            for j in range(1, self.mix_rows_host.shape[1]):
+                more = cnt > j
+                if more.any():
+                    x[:, more] = x[:, more] + series[:, self.mix_rows_host[more, j, None] + np.arange(C)[None, :]]
+            mixed = cnt > 1
+            x[:, mixed] = x[:, mixed] / cnt[mixed].astype(np.float32)[None, :, None]
         x = np.ascontiguousarray(x.transpose(1, 0, 2))
         if self.scaler is not None:
             x = (x * self.scaler[0][None]).astype(np.float32) + self.scaler[1][None]
@@ -149,18 +258,101 @@ class WindowSet(object):
         """Upload another row table (same length) into the device table in place."""
         self.rows_host = np.asarray(rows_host, np.int64).copy()
         self.rows.copy_(torch.as_tensor(self.rows_host))
+        if self.plan is not None:
+            self._upload_mix(None)
 
     def refill(self):
         """Called by ``fit`` each time it refills its index deque (once per epoch): with ``jitter > 0`` every window's start
-        is redrawn around its undisplaced one and the table uploaded, once.  Returns the starts now in use."""
+        is redrawn around its undisplaced one and the table uploaded, once.  Returns the starts now in use.
+
+        Of a balanced set the originals are displaced exactly as without the plan (the same ``jitter_rng`` draws, the same
+        rows); then, out of the balancing stream, the plan is redrawn when ``resample`` is set and, with ``jitter > 0``, every
+        source entry of the extra windows gets a displacement of its own, clipped to the source's run; the ``[S', smax]``
+        table is uploaded once."""
+        if self.plan is None:
+            if self.jitter:
+                self.set_rows(jitter_rows(self.base_rows, self.lo, self.hi, self.jitter, self.jitter_rng))
+            return self.starts
+        plan = self.plan
+        changed = False
         if self.jitter:
-            self.set_rows(jitter_rows(self.base_rows, self.lo, self.hi, self.jitter, self.jitter_rng))
+            self.rows_host = jitter_rows(self.base_rows, self.lo, self.hi, self.jitter, self.jitter_rng)
+            changed = True
+        if plan['resample']:
+            src, cnt, _ = balance_plan(plan['labels'], plan['groups'], plan['sampling'], plan['rng'])
+            assert np.array_equal(cnt, plan['cnt'])                    # the counts depend on the labels alone
+            plan['src'] = src
+            changed = True
+        extra = None
+        if self.jitter:
+            e = plan['src'][self.shape_base[0]:]
+            extra = jitter_rows(self.base_rows[e], self.lo[e], self.hi[e], self.jitter, plan['rng'])
+        if changed:
+            self._upload_mix(extra)
         return self.starts
 
     def reset_rows(self):
         self.jitter, self.jitter_rng = 0, None
         if not np.array_equal(self.rows_host, self.base_rows):
             self.set_rows(self.base_rows)
+        elif self.plan is not None:
+            self._upload_mix(None)
+
+    # ---------------------------------------------------------------- balanced classes
+
+    @property
+    def shape_base(self):
+        """``(S, M, channel)`` of the originals, whatever plan is installed."""
+        return (int(len(self.base_rows)),) + self.shape[1:]
+
+    @property
+    def sources(self):
+        """``(src, cnt)`` of the plan in use (``balance_plan``), None without one."""
+        return None if self.plan is None else (self.plan['src'], self.plan['cnt'])
+
+    def _upload_mix(self, extra_rows):
+        """The ``[S', smax]`` table of first rows: the originals at their rows in use (every entry), the extra windows at
+        ``extra_rows`` (None: their sources' undisplaced rows); one upload."""
+        src = self.plan['src']
+        S = len(self.base_rows)
+        tab = np.empty(src.shape, np.int64)
+        tab[:S] = self.rows_host[:, None]
+        tab[S:] = self.base_rows[src[S:]] if extra_rows is None else extra_rows
+        self.mix_rows_host = tab
+        if self.mix_rows is None or tuple(self.mix_rows.shape) != tab.shape:
+            self.mix_rows = torch.as_tensor(tab).to(self.planes.device)
+            self.mix_cnt = torch.as_tensor(self.plan['cnt']).to(self.planes.device)
+        else:
+            self.mix_rows.copy_(torch.as_tensor(tab))
+
+    def balance(self, labels, sampling, seed=0, groups=None, resample=False):
+        """Top up the small classes (``balance_plan``): installs the plan and returns the ``S'`` labels of the balanced set.
+        Afterwards ``len()`` and ``shape[0]`` are ``S'``, ``gather()`` runs chebgcn_gather_windows_mix, ``materialise()``
+        returns the ``S'`` windows and ``sources`` is ``(src, cnt)``; ``starts`` stays the ``S`` originals' starts.
+
+        ``labels``: one int per original window.  ``sampling``: 1 re-draws windows of a small class, ``n >= 2`` (at most 16)
+        forms every extra window as the mean of ``n`` same-class windows of randomly drawn groups; 0 removes the plan.
+        ``groups``: one int id PER RUN -- the runs of one subject form one group; None: every run is its own.  ``seed``
+        starts the balancing stream ``np.random.RandomState(seed)``, which every later draw of the plan comes out of (the
+        global NumPy stream is never touched).  ``resample``: ``refill()`` redraws the plan (once per epoch of ``fit``);
+        the labels do not change with it.  Arguments are refused (``ValueError``) before anything touches the device."""
+        sampling = check_sampling(sampling, 'balance')
+        S = len(self.base_rows)
+        if sampling == 0:
+            if self.plan is not None:
+                self.plan = self.mix_rows_host = self.mix_rows = self.mix_cnt = None
+                self.shape = (S,) + self.shape[1:]
+                self.rows.copy_(torch.as_tensor(self.rows_host))      # (displaced originals were uploaded in the mix table only)
+            return None if labels is None else np.asarray(labels).copy()
+        labels, run_groups = check_balance_args('balance', labels, S, sampling, seed, groups, len(self.run_starts), resample)
+        groups = np.repeat(run_groups, [len(s) for s in self.run_starts])
+        rng = np.random.RandomState(int(seed))
+        src, cnt, new_labels = balance_plan(labels, groups, sampling, rng)
+        self.plan = dict(src=src, cnt=cnt, labels=labels, groups=groups, sampling=sampling, resample=bool(resample), rng=rng)
+        self.shape = (int(len(src)),) + self.shape[1:]
+        self.mix_rows = self.mix_cnt = None
+        self._upload_mix(None)
+        return new_labels
 
 
 class Series(object):
@@ -197,7 +389,8 @@ class Series(object):
         return self._stage_window_set(runs, run_starts, scale, shift, 'stage_windows')
 
     def fit_series(self, train_series, train_starts, train_labels, val_series, val_starts, val_labels, standardize=False,
-                   jitter=0, jitter_seed=0, best_checkpoint_dir=None):
+                   jitter=0, jitter_seed=0, best_checkpoint_dir=None, sampling=0, sampling_seed=0, sampling_groups=None,
+                   resample=False):
         """``fit`` on scans: both splits are staged as ``WindowSet``s (``stage_windows``' rules; labels one per window, runs in
         order, the starts of a run in the caller's order) and ``fit`` runs on them; returns what ``fit`` returns.
 
@@ -208,7 +401,18 @@ class Series(object):
           displaced by an integer from ``[-j, j]`` drawn out of ``np.random.RandomState(jitter_seed)`` and clipped so that the
           window stays inside its run.  Labels, validation windows and the scaler (fitted on the undisplaced windows) are
           unaffected; the global NumPy stream sees exactly the draws of ``fit``.  With ``record_fit``, ``fit_log['starts']``
-          holds the starts of every refill."""
+          holds the starts of every refill.
+        * ``sampling = n > 0``: the classes of the TRAINING set are balanced (``WindowSet.balance``, ``balance_plan``): every
+          class with at most half the windows of the largest is topped up, with re-drawn windows of its own at ``n = 1`` and
+          with synthetic windows at ``n >= 2`` (at most 16), each the mean of ``n`` same-class windows of randomly drawn groups
+          (``sampling_groups``: one id per training run, e.g. its subject; None: every run its own), formed batch by batch
+          on the device (chebgcn_gather_windows_mix).  The scaler is fitted before, on the originals.  All draws come out of
+          ``np.random.RandomState(sampling_seed)``; ``resample`` redraws the plan at every refill; with ``jitter`` the
+          originals move exactly as without balancing and every source of an extra window gets a displacement of its own out
+          of the balancing stream.  ``fit`` then runs on ``S'`` windows; with ``record_fit``, ``fit_log['sources']`` holds
+          ``(src, cnt)`` of every refill.  ``sampling = 0`` is the training without any of this, on the same kernels as
+          before.  Under ``dist.DataParallel`` the ranks' ``S'`` may differ (they depend on each shard's labels); ``fit``'s
+          check of equal training-set sizes then fires -- balance shards that come out equal, or balance before sharding."""
         what = 'fit_series'
         if isinstance(jitter, bool) or not isinstance(jitter, (int, np.integer)) or jitter < 0:
             raise ValueError('fit_series: jitter must be an int >= 0, got %r' % (jitter,))
@@ -221,6 +425,9 @@ class Series(object):
             if np.ndim(labels) != 1 or len(labels) != n:
                 raise ValueError('fit_series: %s_labels must be one label per window (%d), got shape %s'
                                  % (name, n, np.shape(labels)))
+        if check_sampling(sampling, what):
+            train_labels, _ = check_balance_args(what, train_labels, len(train_labels), sampling, sampling_seed,
+                                                 sampling_groups, len(tr[0]), resample)
         ws_train = self._stage_window_set(tr[0], tr[1], None, None, what)
         ws_val = self._stage_window_set(va[0], va[1], None, None, what)
         self.window_scaler = None
@@ -229,9 +436,12 @@ class Series(object):
             ws_val.share_tables(ws_train)
         ws_train.jitter, ws_train.jitter_rng = int(jitter), np.random.RandomState(int(jitter_seed))
         try:
+            if sampling:
+                train_labels = ws_train.balance(train_labels, sampling, sampling_seed, sampling_groups, resample)
             return self.fit(ws_train, train_labels, ws_val, val_labels, best_checkpoint_dir)
         finally:
             ws_train.reset_rows()
+            ws_train.balance(None, 0)
 
     # ---------------------------------------------------------------- checkpoints
 

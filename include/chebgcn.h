@@ -589,6 +589,15 @@ int chebgcn_gradcam_map(const float* A, const float* G, const float* alpha, cons
  *   rounded product followed by a rounded sum (never one fma: bit-identical to float32 NumPy).  The pad [M, Mp) of every
  *   output plane is written as 0.  Bit-identical to chebgcn_perm_data on the windows cut on the host.  16-byte accesses;
  *   series, tables and out 16-byte aligned; B <= 65535.  chebgcn_last_dispatch(): gather_windows_kernel<plain | tables>.
+ * gather_windows_mix: a window that is the MEAN of several source windows (class balancing, series.balance_plan).  rows: int64
+ *   [.][smax], cnt: int32 [.] (device), 1 <= smax <= 16; with w = sample ? sample[b] : b and n = cnt[w]
+ *     out[b][c][m] = ( sum_{j < n} series[rows[w][j] + c][m] ) / n     (then * scale[c][m] + shift[c][m], as above).
+ *   The sum is formed in float32 in ascending j, followed by ONE correctly rounded float32 division by (float)n, then the
+ *   rounded product and the rounded sum of the tables: every result is reproducible bit for bit in float32 NumPy, and a window
+ *   with n == 1 is bit-identical to gather_windows on rows[w][0].  A count outside [1, smax] is clamped into it (it is never a
+ *   trip count taken from memory unchecked); every row is clamped like gather_windows' rows.  Pad, alignment and B as
+ *   gather_windows.  Traffic: (n + 1) windows per output window.  chebgcn_last_dispatch():
+ *   gather_windows_mix_kernel<plain | tables>.
  * window_stats: mean[c][m] and population variance var[c][m] (ddof = 0, sklearn's StandardScaler) of x[w][c][m] over the S
  *   windows rows[0 .. S), float64 [C][Mp] (either may be NULL), and the float32 tables scale = 1/std, shift = -mean/std
  *   ([C][Mp]; where the variance is 0: scale 1, shift -mean; the pad of all four is 0).  One pass over the series whatever the
@@ -599,6 +608,9 @@ int chebgcn_gradcam_map(const float* A, const float* G, const float* alpha, cons
  *   window_stats_partial_kernel + window_stats_finish_kernel. */
 int chebgcn_gather_windows(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* sample, const float* scale,
                            const float* shift, float* out, int B, int M, int C, chebgcn_stream stream);
+int chebgcn_gather_windows_mix(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* cnt, int smax,
+                               const int32_t* sample, const float* scale, const float* shift, float* out, int B, int M, int C,
+                               chebgcn_stream stream);
 size_t chebgcn_window_stats_workspace(int64_t Ttot, int M, int C);
 int chebgcn_window_stats(const float* series, int64_t Ttot, const int64_t* rows, int64_t S, double* mean, double* var,
                          float* scale, float* shift, int M, int C, void* workspace, size_t workspace_bytes,
