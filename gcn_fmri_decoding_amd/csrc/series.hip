@@ -163,6 +163,225 @@ gather_windows_mix_kernel(const float* __restrict__ series, long long last_row, 
     static_assert(GWM_MAX == 16, "one case per source count");
 }
 
+// ---- the indexed gather: a window is a LIST of rows (events.match_events) ------------------------------------------------------
+// idx [S][Cin], Cin = C * fold: channel c of window s is the mean of the fold rows idx[s][f * C + c] (a trial padded by
+// repeating its last volume, a chunk that straddles a rest period, TRstep sub-windows), and an output window the mean of n such
+// windows (src [.][smax], cnt [.]: series.balance_plan's indices into idx; src == NULL: window w is its own single source).  A
+// plane is still Mp contiguous floats, so the loads stay 16 bytes per lane and coalesced: only the row of a (window, channel)
+// comes from the table -- one 8-byte load that a whole plane's lanes share.  Like the mix gather the kernel branches ONCE per
+// workgroup on (fold, n) into a body whose counts are compile-time constants and whose fold * n loads of a piece are all
+// issued before the first add; counts without a body of their own take the generic loop.  Every window index is clamped into
+// [0, S - 1] and every row into [0, Ttot - 1]: nothing read from memory is an address or a trip count unchecked.
+constexpr int GWI_MAX = 16;             // fold and n at most
+
+__device__ __forceinline__ float4 add4(float4 a, float4 b) {
+    return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
+}
+__device__ __forceinline__ float4 div4(float4 a, float d) {
+    return make_float4(__fdiv_rn(a.x, d), __fdiv_rn(a.y, d), __fdiv_rn(a.z, d), __fdiv_rn(a.w, d));
+}
+
+// the tables (a rounded product, then a rounded sum), the zero pad, the store
+template <bool Tables>
+__device__ __forceinline__ void finish_piece(float4 r, float4 a, float4 s, int q, int M, float4* __restrict__ dst) {
+    if (Tables) {
+        r.x = __fadd_rn(__fmul_rn(r.x, a.x), s.x);
+        r.y = __fadd_rn(__fmul_rn(r.y, a.y), s.y);
+        r.z = __fadd_rn(__fmul_rn(r.z, a.z), s.z);
+        r.w = __fadd_rn(__fmul_rn(r.w, a.w), s.w);
+    }
+    const int m = 4 * q;
+    if (m + 3 >= M) {
+        if (m >= M) r.x = 0.f;
+        if (m + 1 >= M) r.y = 0.f;
+        if (m + 2 >= M) r.z = 0.f;
+        r.w = 0.f;
+    }
+    *dst = r;
+}
+
+struct IndexedArgs {
+    const float4* series4;
+    long long last_row;                 // Ttot - 1
+    const long long* idx;               // [S][Cin]
+    long long last_win;                 // S - 1
+    int Cin, C, M, Mq, CMq;
+};
+
+// sw[j]: the (clamped) source windows of this workgroup's output window
+template <bool Tables, int FOLD, int N>
+__device__ __forceinline__ void indexed_pieces(const IndexedArgs& A, const long long* sw, const float* __restrict__ scale,
+                                               const float* __restrict__ shift, float4* __restrict__ dst) {
+    constexpr int L = FOLD * N;
+    constexpr int U = L <= 4 ? GW_U : (L <= 8 ? GW_U / 2 : GW_U / 4);
+    const long long* ir[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) ir[j] = A.idx + sw[j] * A.Cin;
+    for (int p = 0; p < GW_U / U; ++p) {
+        const int e0 = blockIdx.x * (GW_T * GW_U) + p * (GW_T * U) + threadIdx.x;
+        float4 v[N][FOLD][U], a[U], s[U];
+        int q[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * GW_T;
+            if (e < A.CMq) {
+                const int c = e / A.Mq;
+                q[u] = e - c * A.Mq;
+#pragma unroll
+                for (int j = 0; j < N; ++j)
+#pragma unroll
+                    for (int f = 0; f < FOLD; ++f)
+                        v[j][f][u] = A.series4[clamp_row(ir[j][f * A.C + c], A.last_row) * A.Mq + q[u]];
+                if (Tables) {
+                    a[u] = reinterpret_cast<const float4*>(scale)[e];
+                    s[u] = reinterpret_cast<const float4*>(shift)[e];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * GW_T;
+            if (e < A.CMq) {
+                float4 r;
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    float4 w = v[j][0][u];
+#pragma unroll
+                    for (int f = 1; f < FOLD; ++f) w = add4(w, v[j][f][u]);         // float32 adds in ascending f
+                    if (FOLD > 1) w = div4(w, (float)FOLD);                        // one rounded division per level
+                    r = j == 0 ? w : add4(r, w);                                   // ... in ascending j
+                }
+                if (N > 1) r = div4(r, (float)N);
+                finish_piece<Tables>(r, a[u], s[u], q[u], A.M, dst + e);
+            }
+        }
+    }
+}
+
+// any (fold, n) in [1, 16]^2, one piece at a time
+template <bool Tables>
+__device__ __forceinline__ void indexed_pieces_any(const IndexedArgs& A, int fold, int n, const long long* __restrict__ srcw,
+                                                   long long w, const float* __restrict__ scale, const float* __restrict__ shift,
+                                                   float4* __restrict__ dst) {
+    for (int u = 0; u < GW_U; ++u) {
+        const int e = blockIdx.x * (GW_T * GW_U) + u * GW_T + threadIdx.x;
+        if (e >= A.CMq) continue;
+        const int c = e / A.Mq, q = e - c * A.Mq;
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f), a = r, s = r;
+        if (Tables) {
+            a = reinterpret_cast<const float4*>(scale)[e];
+            s = reinterpret_cast<const float4*>(shift)[e];
+        }
+        for (int j = 0; j < n; ++j) {
+            const long long sj = srcw ? clamp_row(srcw[j], A.last_win) : w;
+            const long long* ir = A.idx + sj * A.Cin + c;
+            float4 x = A.series4[clamp_row(ir[0], A.last_row) * A.Mq + q];
+            for (int f = 1; f < fold; ++f) x = add4(x, A.series4[clamp_row(ir[(long long)f * A.C], A.last_row) * A.Mq + q]);
+            if (fold > 1) x = div4(x, (float)fold);
+            r = j == 0 ? x : add4(r, x);
+        }
+        if (n > 1) r = div4(r, (float)n);
+        finish_piece<Tables>(r, a, s, q, A.M, dst + e);
+    }
+}
+
+// block (piece of the window's C * Mp/4 float4s, window b).  W: the windows sample[] may name (the rows of src / cnt; S without)
+template <bool Tables>
+__global__ void __launch_bounds__(GW_T)
+gather_windows_indexed_kernel(IndexedArgs A, int fold, const long long* __restrict__ src, const int32_t* __restrict__ cnt,
+                              long long last_w, int smax, const int32_t* __restrict__ sample, const float* __restrict__ scale,
+                              const float* __restrict__ shift, float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const long long w = clamp_row(sample ? (long long)sample[b] : (long long)b, last_w);
+    int n = 1;
+    if (src) {
+        n = cnt[w];
+        n = n < 1 ? 1 : (n > smax ? smax : n);
+    }
+    const long long* srcw = src ? src + w * smax : nullptr;
+    float4* dst = reinterpret_cast<float4*>(out) + (long long)b * A.CMq;
+    long long sw[8];
+#define CG_IDX_CASE(FOLD, N)                                                                                 \
+    case FOLD * 32 + N: {                                                                                    \
+        _Pragma("unroll") for (int j = 0; j < N; ++j) sw[j] = srcw ? clamp_row(srcw[j], A.last_win) : w;     \
+        indexed_pieces<Tables, FOLD, N>(A, sw, scale, shift, dst);                                           \
+    } break;
+    switch (fold * 32 + n) {
+        CG_IDX_CASE(1, 1) CG_IDX_CASE(1, 2) CG_IDX_CASE(1, 3) CG_IDX_CASE(1, 4)
+        CG_IDX_CASE(1, 5) CG_IDX_CASE(1, 6) CG_IDX_CASE(1, 7) CG_IDX_CASE(1, 8)
+        CG_IDX_CASE(2, 1) CG_IDX_CASE(2, 2) CG_IDX_CASE(2, 3) CG_IDX_CASE(2, 4)
+        CG_IDX_CASE(3, 1) CG_IDX_CASE(4, 1)
+        default: indexed_pieces_any<Tables>(A, fold, n, srcw, w, scale, shift, dst);
+    }
+#undef CG_IDX_CASE
+}
+
+// ---- the statistics of indexed windows -----------------------------------------------------------------------------------------
+// Windows that are lists of rows have no "count of the windows that start here": the values the scaler sees are the FOLDED ones
+// the gather forms in float32, so the kernel forms them the same way, window by window.  block (tile of 2 * WS_T vertices x
+// channel c, chunk g of `chunk` windows): part[g][k][c][m] as window_stats_partial_kernel writes it, windows in ascending
+// order; window_stats_finish_kernel adds the chunks in index order.
+constexpr int WSI_CHUNKS = 32;          // chunks at most (a chunk's partials are 2 * C * Mp doubles)
+constexpr int WSI_MIN = 16;             // windows of a chunk at least
+
+template <int FOLD>                     // 0: any fold
+__global__ void __launch_bounds__(WS_T)
+window_stats_indexed_partial_kernel(const float* __restrict__ series, long long last_row, const long long* __restrict__ idx,
+                                    long long S, int Cin, int fold_, int C, int Mp, long long chunk, double* __restrict__ part) {
+    const int c = blockIdx.x % C, tile = blockIdx.x / C;
+    const int m = 2 * (tile * WS_T + threadIdx.x);
+    const int g = blockIdx.y;
+    if (m >= Mp) return;
+    const int fold = FOLD ? FOLD : fold_;
+    const long long w0 = (long long)g * chunk, w1 = min(w0 + chunk, S);
+    const float2 base = *reinterpret_cast<const float2*>(series + m);
+    const double k0 = (double)base.x, k1 = (double)base.y;
+    double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
+    for (long long wb = w0; wb < w1; wb += 4) {
+        float2 x[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const long long* ir = idx + min(wb + i, w1 - 1) * Cin + c;
+            x[i] = *reinterpret_cast<const float2*>(series + clamp_row(ir[0], last_row) * Mp + m);
+            if (FOLD == 2) {
+                const float2 y = *reinterpret_cast<const float2*>(series + clamp_row(ir[C], last_row) * Mp + m);
+                x[i].x = __fdiv_rn(__fadd_rn(x[i].x, y.x), 2.f);
+                x[i].y = __fdiv_rn(__fadd_rn(x[i].y, y.y), 2.f);
+            } else if (FOLD == 0) {
+                for (int f = 1; f < fold; ++f) {
+                    const float2 y = *reinterpret_cast<const float2*>(series + clamp_row(ir[(long long)f * C], last_row) * Mp + m);
+                    x[i].x = __fadd_rn(x[i].x, y.x);
+                    x[i].y = __fadd_rn(x[i].y, y.y);
+                }
+                if (fold > 1) {
+                    x[i].x = __fdiv_rn(x[i].x, (float)fold);
+                    x[i].y = __fdiv_rn(x[i].y, (float)fold);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (wb + i < w1) {
+                const double d0 = (double)x[i].x - k0, d1 = (double)x[i].y - k1;
+                s1[0] += d0;
+                s1[1] += d1;
+                s2[0] = fma(d0, d0, s2[0]);
+                s2[1] = fma(d1, d1, s2[1]);
+            }
+        }
+    }
+    const size_t slab = (size_t)C * Mp, o = (size_t)c * Mp + m;
+    double* p = part + (size_t)g * 2 * slab;
+    *reinterpret_cast<double2*>(p + o) = make_double2(s1[0], s1[1]);
+    *reinterpret_cast<double2*>(p + slab + o) = make_double2(s2[0], s2[1]);
+}
+
+static inline long long wsi_chunk(int64_t S) {
+    const long long c = (S + WSI_CHUNKS - 1) / WSI_CHUNKS;
+    return c < WSI_MIN ? WSI_MIN : c;
+}
+static inline int wsi_chunks(int64_t S) { return (int)((S + wsi_chunk(S) - 1) / wsi_chunk(S)); }
+
 // n[lead + row] += 1 per window (integer adds: the counts do not depend on the order of arrival).  lead = C - 1 + WS_CG zeros in
 // front and 4 behind: n[lead + u - c] is in bounds for every row u < Ttot + 3 and every channel c < C + WS_CG - 1 the partial
 // kernel's unrolled loads touch
@@ -356,6 +575,88 @@ extern "C" int chebgcn_window_stats(const float* series, int64_t Ttot, const int
     const int tiles = (Mp / 2 + WS_T - 1) / WS_T;
     hipLaunchKernelGGL(window_stats_partial_kernel, dim3(tiles * ncg, G), dim3(WS_T), 0, stream, series, (long long)Ttot, cnt, C,
                        Mp, ncg, part);
+    CG_HIP(hipGetLastError());
+    note_dispatch_more("window_stats_finish_kernel");
+    const size_t slab = (size_t)C * Mp;
+    hipLaunchKernelGGL(window_stats_finish_kernel, dim3((unsigned)((slab + WS_T - 1) / WS_T)), dim3(WS_T), 0, stream, series, part,
+                       G, (long long)S, M, Mp, C, mean, var, scale, shift);
+    CG_HIP(hipGetLastError());
+    return CHEBGCN_OK;
+}
+
+extern "C" int chebgcn_gather_windows_indexed(const float* series, int64_t Ttot, const int64_t* idx, int64_t S, int Cin, int fold,
+                                              const int64_t* src, const int32_t* cnt, int64_t W, int smax, const int32_t* sample,
+                                              const float* scale, const float* shift, float* out, int B, int M, int C,
+                                              chebgcn_stream stream_) {
+    CG_REQUIRE(series && idx && out, "gather_windows_indexed: NULL argument");
+    CG_REQUIRE((src != nullptr) == (cnt != nullptr), "gather_windows_indexed: src and cnt come together (both or neither)");
+    CG_REQUIRE(!src || (smax >= 1 && smax <= GWI_MAX && W >= 1), "gather_windows_indexed: smax = %d, must be in [1, %d], W = %lld",
+               smax, GWI_MAX, (long long)W);
+    CG_REQUIRE(fold >= 1 && fold <= GWI_MAX, "gather_windows_indexed: fold = %d, must be in [1, %d]", fold, GWI_MAX);
+    CG_REQUIRE((scale != nullptr) == (shift != nullptr), "gather_windows_indexed: scale and shift come together (both or neither)");
+    CG_REQUIRE(B > 0 && B <= 65535 && M > 0 && C > 0 && (int64_t)C * plane_stride(M) / 4 <= 0x7fffffffLL / 2,
+               "gather_windows_indexed: bad shape (B = %d, M = %d, C = %d)", B, M, C);
+    CG_REQUIRE((int64_t)Cin == (int64_t)C * fold, "gather_windows_indexed: Cin = %d is not C * fold = %d * %d", Cin, C, fold);
+    CG_REQUIRE(S >= 1 && Ttot >= 1, "gather_windows_indexed: S = %lld windows of a series of %lld time points", (long long)S,
+               (long long)Ttot);
+    CG_REQUIRE((((uintptr_t)series | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
+               "gather_windows_indexed: series, tables and out must be 16-byte aligned");
+    IndexedArgs A;
+    A.series4 = reinterpret_cast<const float4*>(series);
+    A.last_row = (long long)Ttot - 1;
+    A.idx = (const long long*)idx;
+    A.last_win = (long long)S - 1;
+    A.Cin = Cin;
+    A.C = C;
+    A.M = M;
+    A.Mq = plane_stride(M) / 4;
+    A.CMq = C * A.Mq;
+    const long long last_w = (src ? (long long)W : (long long)S) - 1;
+    dim3 grid((A.CMq + GW_T * GW_U - 1) / (GW_T * GW_U), B);
+    if (scale) {
+        note_dispatch("gather_windows_indexed_kernel<tables>");
+        hipLaunchKernelGGL(gather_windows_indexed_kernel<true>, grid, dim3(GW_T), 0, (hipStream_t)stream_, A, fold,
+                           (const long long*)src, cnt, last_w, smax, sample, scale, shift, out);
+    } else {
+        note_dispatch("gather_windows_indexed_kernel<plain>");
+        hipLaunchKernelGGL(gather_windows_indexed_kernel<false>, grid, dim3(GW_T), 0, (hipStream_t)stream_, A, fold,
+                           (const long long*)src, cnt, last_w, smax, sample, scale, shift, out);
+    }
+    CG_HIP(hipGetLastError());
+    return CHEBGCN_OK;
+}
+
+extern "C" size_t chebgcn_window_stats_indexed_workspace(int64_t S, int M, int C) {
+    if (S <= 0 || M <= 0 || C <= 0 || S > 0x7fffffffLL) return 0;
+    return (size_t)wsi_chunks(S) * 2 * C * plane_stride(M) * sizeof(double);
+}
+
+extern "C" int chebgcn_window_stats_indexed(const float* series, int64_t Ttot, const int64_t* idx, int64_t S, int Cin, int fold,
+                                            double* mean, double* var, float* scale, float* shift, int M, int C, void* workspace,
+                                            size_t workspace_bytes, chebgcn_stream stream_) {
+    CG_REQUIRE(series && idx && scale && shift && workspace, "window_stats_indexed: NULL argument");
+    CG_REQUIRE(S > 0 && S <= 0x7fffffffLL && M > 0 && C > 0 && Ttot >= 1, "window_stats_indexed: bad shape");
+    CG_REQUIRE(fold >= 1 && fold <= GWI_MAX, "window_stats_indexed: fold = %d, must be in [1, %d]", fold, GWI_MAX);
+    CG_REQUIRE((int64_t)Cin == (int64_t)C * fold, "window_stats_indexed: Cin = %d is not C * fold = %d * %d", Cin, C, fold);
+    CG_REQUIRE(workspace_bytes >= chebgcn_window_stats_indexed_workspace(S, M, C),
+               "window_stats_indexed: workspace of %zu bytes, %zu needed", workspace_bytes,
+               chebgcn_window_stats_indexed_workspace(S, M, C));
+    CG_REQUIRE((((uintptr_t)series | (uintptr_t)workspace) & 15) == 0,
+               "window_stats_indexed: series and workspace must be 16-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int Mp = plane_stride(M), G = wsi_chunks(S);
+    const int tiles = (Mp / 2 + WS_T - 1) / WS_T;
+    CG_REQUIRE((int64_t)tiles * C <= 0x7fffffffLL, "window_stats_indexed: bad shape");
+    double* part = (double*)workspace;
+    const dim3 grid(tiles * C, G);
+    note_dispatch("window_stats_indexed_partial_kernel");
+#define CG_WSI(FOLD)                                                                                                         \
+    hipLaunchKernelGGL(window_stats_indexed_partial_kernel<FOLD>, grid, dim3(WS_T), 0, stream, series, (long long)Ttot - 1,  \
+                       (const long long*)idx, (long long)S, Cin, fold, C, Mp, wsi_chunk(S), part)
+    if (fold == 1) CG_WSI(1);
+    else if (fold == 2) CG_WSI(2);
+    else CG_WSI(0);
+#undef CG_WSI
     CG_HIP(hipGetLastError());
     note_dispatch_more("window_stats_finish_kernel");
     const size_t slab = (size_t)C * Mp;

@@ -320,6 +320,61 @@ def window_stats(planes, rows, M, C):
     return mean, var, scale, shift
 
 
+def _index_table(idx, M, C, fold, what):
+    if idx.dim() != 2 or idx.dtype != torch.int64 or not idx.is_contiguous() or idx.shape[0] < 1 \
+            or isinstance(fold, bool) or not isinstance(fold, (int, np.integer)) or not 1 <= fold <= 16 \
+            or idx.shape[1] != int(C) * int(fold):
+        raise _lib.ChebgcnError('%s: idx must be contiguous int64 [S, C * fold] with fold in [1, 16] (C = %r, fold = %r, got %s %s)'
+                                % (what, C, fold, idx.dtype, tuple(idx.shape)))
+    return int(idx.shape[0]), int(idx.shape[1])
+
+
+def gather_windows_indexed(planes, idx, M, C, fold=1, src=None, cnt=None, sample=None, scale=None, shift=None, out=None,
+                           sources=None):
+    """Windows that are lists of rows (chebgcn_gather_windows_indexed): ``idx`` int64 [S, C * fold] device table of rows of
+    ``planes`` (channel ``c`` of window ``s`` is the float32 mean of the rows ``idx[s, f * C + c]``), ``src`` int64 [S', smax] /
+    ``cnt`` int32 [S'] (both or neither): output window ``w`` is the mean of the ``cnt[w]`` windows ``src[w, :cnt[w]]`` of
+    ``idx``; ``sample`` int32 device indices (None: all, in order) -> storage [B, C, Mp], then the tables like
+    ``gather_windows``.  ``sources``: the mean ``cnt`` of the windows gathered, for the launch log's byte count."""
+    _require_cuda(planes, idx, src, cnt, sample, scale, shift, out)
+    Ttot, Mp = planes.shape
+    S, Cin = _index_table(idx, M, C, fold, 'gather_windows_indexed')
+    if (src is None) != (cnt is None):
+        raise _lib.ChebgcnError('gather_windows_indexed: src and cnt come together (both or neither)')
+    W, smax = S, 1
+    if src is not None:
+        if src.dim() != 2 or cnt.dim() != 1 or src.shape[0] != cnt.shape[0] or src.dtype != torch.int64 \
+                or cnt.dtype != torch.int32 or not src.is_contiguous() or not cnt.is_contiguous():
+            raise _lib.ChebgcnError('gather_windows_indexed: src must be contiguous int64 [S, smax] and cnt int32 [S]')
+        W, smax = int(src.shape[0]), int(src.shape[1])
+    B = int(W if sample is None else sample.numel())
+    if out is None or tuple(out.shape) != (B, C, Mp) or not out.is_contiguous():
+        out = torch.empty((B, C, Mp), dtype=torch.float32, device=planes.device)
+    nsrc = float(fold) * float((smax if src is not None else 1) if sources is None else sources)
+    _lib.check(_launch('gather_windows_indexed', 4.0 * (nsrc + 1) * B * C * Mp, 0.0,
+                       lambda: _lib.lib().chebgcn_gather_windows_indexed(
+                           _p(planes), Ttot, _p(idx), S, Cin, int(fold), _p(src), _p(cnt), W, smax, _p(sample), _p(scale),
+                           _p(shift), _p(out), B, M, C, _stream())), 'gather_windows_indexed')
+    return out
+
+
+def window_stats_indexed(planes, idx, M, C, fold=1):
+    """``window_stats`` over windows that are lists of rows (chebgcn_window_stats_indexed; ``idx`` as in
+    ``gather_windows_indexed``): the statistics of the folded float32 values the gather forms."""
+    _require_cuda(planes, idx)
+    Ttot, Mp = planes.shape
+    S, Cin = _index_table(idx, M, C, fold, 'window_stats_indexed')
+    dev = planes.device
+    mean, var = (torch.empty((C, Mp), dtype=torch.float64, device=dev) for _ in range(2))
+    scale, shift = (torch.empty((C, Mp), dtype=torch.float32, device=dev) for _ in range(2))
+    nbytes = int(_lib.lib().chebgcn_window_stats_indexed_workspace(S, M, C))
+    ws = _workspace(nbytes, dev, 'window_stats_indexed')
+    _lib.check(_launch('window_stats_indexed', 4.0 * S * Cin * Mp, 0.0, lambda: _lib.lib().chebgcn_window_stats_indexed(
+        _p(planes), Ttot, _p(idx), S, Cin, int(fold), _p(mean), _p(var), _p(scale), _p(shift), M, C, _p(ws), ws.numel(),
+        _stream())), 'window_stats_indexed')
+    return mean, var, scale, shift
+
+
 def knn(planes, N, k, metric):
     """The k nearest other vertices of every vertex (chebgcn_knn): ``planes`` [D, Np] fp32 feature-major planes on the device
     (zero pad), ``metric`` one of ``_lib.KNN_*`` -> ``(dist float32 [N, k] ascending, idx int32 [N, k])`` on the device.  The

@@ -9,7 +9,8 @@ outside the model.  Here the series is stored once (``channel`` x less memory at
 (chebgcn_window_stats) in exactly the form ``decode_series(scale=, shift=)`` takes, and moving a window a few TRs inside its
 trial is a new row table, not a new array.  Balancing unbalanced classes (the reference's ``sampling``) is a table as well:
 ``balance_plan`` says which original windows every extra window is the mean of, and chebgcn_gather_windows_mix forms them
-batch by batch."""
+batch by batch.  ``EventWindowSet`` is the set whose windows are lists of rows rather than one contiguous piece (the windows of
+an event design, ``events.match_events``): ``stage_windows(index=)`` / ``stage_events`` / ``fit_events``."""
 import numpy as np
 import torch
 
@@ -355,6 +356,142 @@ class WindowSet(object):
         return new_labels
 
 
+class EventWindowSet(WindowSet):
+    """A ``WindowSet`` whose windows are LISTS of rows (``stage_windows(index=, fold=)``, ``stage_events``): ``index`` is the
+    int64 device table ``[S, channel * fold]`` of global rows, channel ``c`` of window ``s`` the float32 mean of the rows
+    ``index[s, f * channel + c]`` (chebgcn_gather_windows_indexed).  Everything a ``WindowSet`` does but displacement:
+    ``jitter`` raises a ``ValueError`` -- a displaced window leaves its trial.  ``balance()`` needs no row table of its own:
+    the plan's sources are indices into ``index``."""
+
+    def __init__(self, owner, planes, run_lengths, run_index, M, C, fold):
+        self.owner, self.planes = owner, planes
+        self.run_lengths = [int(t) for t in run_lengths]
+        self.run_index = [np.asarray(i, np.int64) for i in run_index]
+        self.run_starts = self.run_index                # (balance(): one entry per run, as many items as the run has windows)
+        self.fold = int(fold)
+        offs = np.concatenate([[0], np.cumsum(self.run_lengths)[:-1]]).astype(np.int64)
+        self.index_host = np.ascontiguousarray(np.concatenate([i + o for i, o in zip(self.run_index, offs)]), np.int64)
+        self.offsets = np.repeat(offs, [len(i) for i in self.run_index])
+        self.base_rows = self.rows_host = self.index_host[:, 0]    # (len(): the number of originals)
+        self.index = torch.as_tensor(self.index_host).to(planes.device)
+        self.shape = (int(len(self.index_host)), int(M), int(C))
+        self.tables = self.scaler = self.stats = None
+        self.plan = None
+        self.mix_src = self.mix_cnt = None              # balance(): [S', smax] int64 indices into index / int32, device
+
+    jitter_rng = None
+
+    @property
+    def jitter(self):
+        return 0
+
+    @jitter.setter
+    def jitter(self, j):
+        if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or j != 0:
+            raise ValueError('jitter: the windows of an event design cannot be displaced (a displaced window leaves its '
+                             'trial), got jitter = %r' % (j,))
+
+    @property
+    def starts(self):
+        """The rows every window reads, inside its run: ``[S, channel * fold]``."""
+        return self.index_host - self.offsets[:, None]
+
+    @property
+    def nbytes(self):
+        n = self.planes.numel() * 4 + self.index.numel() * 8
+        if self.plan is not None:
+            n += self.mix_src.numel() * 8 + self.mix_cnt.numel() * 4
+        return n + (sum(t.numel() * 4 for t in self.tables) if self.tables is not None else 0)
+
+    def fit_scaler(self):
+        """``WindowSet.fit_scaler`` over the folded values of the ``S`` ORIGINAL windows, as the gather forms them in float32
+        (chebgcn_window_stats_indexed), whatever plan is installed."""
+        S, M, C = self.shape
+        mean, var, scale, shift = ops.window_stats_indexed(self.planes, self.index, M, C, self.fold)
+        self.tables = (scale, shift)
+        self.scaler = (self._caller_order(scale), self._caller_order(shift))
+        self.stats = (self._caller_order(mean), self._caller_order(var))
+        return self.scaler
+
+    def gather(self, model, idx, out=None):
+        """``WindowSet.gather`` on chebgcn_gather_windows_indexed (of a balanced set: with the plan's sources)."""
+        if model is not self.owner and not model._same_order(self.owner):
+            raise ValueError('this WindowSet is staged in the internal vertex order of another model')
+        S, M, C = self.shape
+        scale, shift = self.tables if self.tables is not None else (None, None)
+        sources = None if self.plan is None else self.plan['cnt'].mean()
+        return model.as_internal(ops.gather_windows_indexed(self.planes, self.index, M, C, self.fold, self.mix_src, self.mix_cnt,
+                                                            idx, scale, shift, out, sources=sources))
+
+    def materialise(self):
+        """``WindowSet.materialise``: every level in float32 like the kernel -- the ``fold`` pieces added in ascending order
+        and divided once, the sources likewise, then the tables."""
+        S, M, C = self.shape
+        series = self._caller_order(self.planes)                                        # [M, Ttot]
+        piece = series[:, self.index_host[:, :C]]                                       # [M, S, C]
+        for f in range(1, self.fold):
+            piece = piece + series[:, self.index_host[:, f * C:(f + 1) * C]]
+        if self.fold > 1:
+            piece = piece / np.float32(self.fold)
+        if self.plan is None:
+            x = piece
+        else:
+            src, cnt = self.plan['src'], self.plan['cnt']
+            x = piece[:, src[:, 0]]
+            for j in range(1, src.shape[1]):
+                more = cnt > j
+                if more.any():
+                    x[:, more] = x[:, more] + piece[:, src[more, j]]
+            mixed = cnt > 1
+            x[:, mixed] = x[:, mixed] / cnt[mixed].astype(np.float32)[None, :, None]
+        x = np.ascontiguousarray(x.transpose(1, 0, 2))
+        if self.scaler is not None:
+            x = (x * self.scaler[0][None]).astype(np.float32) + self.scaler[1][None]
+        return x.astype(np.float32, copy=False)
+
+    def set_rows(self, rows_host):
+        raise ValueError('set_rows: the windows of an event design cannot be displaced')
+
+    def refill(self):
+        """Called by ``fit`` once per epoch: redraws the plan when ``resample`` is set.  Returns the rows in use."""
+        plan = self.plan
+        if plan is not None and plan['resample']:
+            src, cnt, _ = balance_plan(plan['labels'], plan['groups'], plan['sampling'], plan['rng'])
+            assert np.array_equal(cnt, plan['cnt'])
+            plan['src'] = src
+            self._upload_mix(None)
+        return self.starts
+
+    def reset_rows(self):
+        pass
+
+    def _upload_mix(self, extra_rows):
+        src = self.plan['src']
+        if self.mix_src is None or tuple(self.mix_src.shape) != src.shape:
+            self.mix_src = torch.as_tensor(np.ascontiguousarray(src)).to(self.planes.device)
+            self.mix_cnt = torch.as_tensor(self.plan['cnt']).to(self.planes.device)
+        else:
+            self.mix_src.copy_(torch.as_tensor(np.ascontiguousarray(src)))
+
+    def balance(self, labels, sampling, seed=0, groups=None, resample=False):
+        """``WindowSet.balance``; the sources are indices into the set's own table."""
+        sampling = check_sampling(sampling, 'balance')
+        S = len(self.index_host)
+        if sampling == 0:
+            self.plan = self.mix_src = self.mix_cnt = None
+            self.shape = (S,) + self.shape[1:]
+            return None if labels is None else np.asarray(labels).copy()
+        labels, run_groups = check_balance_args('balance', labels, S, sampling, seed, groups, len(self.run_index), resample)
+        groups = np.repeat(run_groups, [len(i) for i in self.run_index])
+        rng = np.random.RandomState(int(seed))
+        src, cnt, new_labels = balance_plan(labels, groups, sampling, rng)
+        self.plan = dict(src=src, cnt=cnt, labels=labels, groups=groups, sampling=sampling, resample=bool(resample), rng=rng)
+        self.shape = (int(len(src)),) + self.shape[1:]
+        self.mix_src = self.mix_cnt = None
+        self._upload_mix(None)
+        return new_labels
+
+
 class Series(object):
     """``stage_windows`` / ``fit_series`` of ``base_model``.  Uses the model's ``_decode_args`` / ``_stage_series`` /
     ``_scale_tables`` (decode.Decode), its sizes and ``fit``."""
@@ -379,14 +516,158 @@ class Series(object):
             off += T
         return WindowSet(self, planes, lengths, run_starts, M0, C).set_tables(scale, shift)
 
-    def stage_windows(self, series, starts=None, scale=None, shift=None):
+    def _check_runs(self, series, what):
+        """``series`` as a list of ``[T, M]`` runs (the checks of ``_decode_args`` that do not involve starts)."""
+        runs = list(series) if isinstance(series, (list, tuple)) else [series]
+        if not runs:
+            raise ValueError('%s: series is an empty list' % what)
+        M0 = int(self._M0)
+        out = []
+        for r in runs:
+            if not isinstance(r, torch.Tensor):
+                r = np.asarray(r)
+                if not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
+                    raise ValueError('%s: series must be numeric, got %s' % (what, r.dtype))
+            shape = tuple(int(d) for d in r.shape)
+            if len(shape) != 2 or shape[1] != M0 or shape[0] < 1:
+                raise ValueError('%s: series must be [T, %d] (time points x vertices), got %s' % (what, M0, shape))
+            out.append(r)
+        return out
+
+    def _index_args(self, series, index, fold, scale, shift, what):
+        """The arguments of ``stage_windows(index=)``, refused or returned as ``(runs, one int64 [S_r, Cin] table per run,
+        fold, scale, shift)``."""
+        runs = self._check_runs(series, what)
+        M0, C = int(self._M0), int(self.channel)
+        if isinstance(fold, bool) or not isinstance(fold, (int, np.integer)) or not 1 <= fold <= 16:
+            raise ValueError('%s: fold must be an int in [1, 16], got %r' % (what, fold))
+        many = isinstance(series, (list, tuple))
+        tables = list(index) if (many and isinstance(index, (list, tuple))) else [index]
+        if len(tables) != len(runs) or (many and not isinstance(index, (list, tuple))):
+            raise ValueError('%s: index must hold one [S_r, %d] table per run (%d runs)' % (what, C * fold, len(runs)))
+        out = []
+        for r, t in zip(runs, tables):
+            a = np.asarray(t)
+            if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != C * fold or a.dtype == np.bool_ \
+                    or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError('%s: every index table must be a non-empty int array [S_r, channel * fold = %d * %d], got %s %s'
+                                 % (what, C, fold, a.dtype, a.shape))
+            a = a.astype(np.int64)
+            T = int(r.shape[0])
+            if a.min() < 0 or a.max() >= T:
+                raise ValueError('%s: every row of an index table must satisfy 0 <= row < T = %d; got %d ... %d'
+                                 % (what, T, a.min(), a.max()))
+            out.append(a)
+
+        def table(v, name):
+            if v is None:
+                return None
+            a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32)
+            if a.shape != (M0, C):
+                raise ValueError('%s: %s must be [%d, %d] (vertices x channels), got %s' % (what, name, M0, C, a.shape))
+            return a
+        if (scale is None) != (shift is None):
+            raise ValueError('%s: scale and shift come together (both or neither)' % what)
+        return runs, out, int(fold), table(scale, 'scale'), table(shift, 'shift')
+
+    def _stage_event_set(self, runs, run_index, fold, scale, shift, what):
+        if self.device.type != 'cuda':
+            raise RuntimeError('%s: the model has no device to run on (%s)' % (what, self.device))
+        M0, C = int(self._M0), int(self.channel)
+        lengths = [int(r.shape[0]) for r in runs]
+        planes = torch.empty((sum(lengths), ops.plane_stride(M0)), dtype=torch.float32, device=self.device)
+        off = 0
+        for r, T in zip(runs, lengths):
+            self._stage_series(r, out=planes[off:off + T])
+            off += T
+        return EventWindowSet(self, planes, lengths, run_index, M0, C, fold).set_tables(scale, shift)
+
+    def stage_windows(self, series, starts=None, scale=None, shift=None, index=None, fold=1):
         """A ``WindowSet``: the windows ``x[v][c] = series[start + c][v]`` of one ``[T, M]`` run or a list of runs (``starts``:
         an array per run; any order, repeats allowed; None: every window, stride 1 -- ``decode_series``' rules), staged on
         the device once as planes.  ``fit`` / ``predict`` / ``evaluate`` / ``model_perf.test`` / ``model_perf.predict`` take
         it wherever they take ``[S, M, channel]`` data.  ``scale`` / ``shift`` ``[M, channel]``: every window is seen as
-        ``x * scale + shift``.  Arguments are refused (``ValueError``) before anything touches the device."""
+        ``x * scale + shift``.  Arguments are refused (``ValueError``) before anything touches the device.
+
+        ``index`` (instead of ``starts``): one int table ``[S_r, channel * fold]`` per run -- a window is a LIST of rows of its
+        run, ``x[v][c] = mean_f series[index[s, f * channel + c]][v]`` (rows may repeat, decrease or skip; ``fold`` in
+        [1, 16]).  Returns an ``EventWindowSet`` (``events.match_events`` produces such tables; ``stage_events``)."""
+        if index is not None:
+            if starts is not None:
+                raise ValueError('stage_windows: starts and index are mutually exclusive')
+            runs, run_index, fold, scale, shift = self._index_args(series, index, fold, scale, shift, 'stage_windows')
+            return self._stage_event_set(runs, run_index, fold, scale, shift, 'stage_windows')
+        if not (fold == 1 and not isinstance(fold, bool)):
+            raise ValueError('stage_windows: fold goes with index (windows cut by starts have fold = 1), got %r' % (fold,))
         runs, run_starts, scale, shift = self._window_args(series, starts, scale, shift, 'stage_windows')
         return self._stage_window_set(runs, run_starts, scale, shift, 'stage_windows')
+
+    def _event_args(self, series, label_runs, target_name, block_dura, match_kw, what):
+        """``stage_events``' arguments matched and checked: ``(runs kept, their index tables, fold, labels int64 [S], kept)``."""
+        from . import events
+        runs = self._check_runs(series, what)
+        many = isinstance(series, (list, tuple))
+        if not many:
+            label_runs = [label_runs]
+        try:
+            ev = events.match_events(label_runs, target_name, block_dura, **match_kw)
+        except (TypeError, ValueError) as e:            # (TypeError: a keyword match_events does not take, jitter= among them)
+            raise ValueError('%s: %s' % (what, e))
+        if len(label_runs) != len(runs):
+            raise ValueError('%s: %d runs but %d event designs' % (what, len(runs), len(label_runs)))
+        for r, names in zip(runs, label_runs):
+            if int(r.shape[0]) != len(names):
+                raise ValueError('%s: a run of %d time points with a design of %d entries' % (what, int(r.shape[0]), len(names)))
+        if ev.channel != int(self.channel):
+            raise ValueError('%s: the model has channel = %d, block_dura // TRstep = %d // %d = %d'
+                             % (what, int(self.channel), ev.block_dura, ev.fold, ev.channel))
+        if not ev.kept:
+            raise ValueError('%s: no run yields a window (no trial of %r of at least block_dura = %d TRs?)'
+                             % (what, list(target_name), ev.block_dura))
+        if len(ev.classes) > int(self.M[-1]):
+            raise ValueError('%s: %d conditions but the model has %d classes' % (what, len(ev.classes), int(self.M[-1])))
+        return [runs[k] for k in ev.kept], ev.index, ev.fold, np.concatenate(ev.labels), ev.kept
+
+    def stage_events(self, series, label_runs, target_name, block_dura, **match_kw):
+        """``(window_set, labels)`` of an event design: ``events.match_events(label_runs, target_name, block_dura,
+        **match_kw)`` (the reference's ``matching_fmri_data_to_trials_event``; ``match_kw``: ``start_trial``, ``hrf_delay``,
+        ``flag_event``, ``TRstep``, ``rest``) decides which rows every window reads, and the runs that yield windows are
+        staged as an ``EventWindowSet``.  ``series``: one ``[T, M]`` run with one design, or a list of runs with a list of
+        designs, each as long as its run.  ``labels``: int64, one per window, codes into ``sorted(set(target_name))``.  The
+        model's ``channel`` must equal ``block_dura // TRstep`` (``ValueError``)."""
+        runs, run_index, fold, labels, _ = self._event_args(series, label_runs, target_name, block_dura, match_kw,
+                                                            'stage_events')
+        return self._stage_event_set(runs, run_index, fold, None, None, 'stage_events'), labels
+
+    def fit_events(self, train_series, train_label_runs, val_series, val_label_runs, target_name, block_dura, standardize=False,
+                   sampling=0, seed=0, groups=None, best_checkpoint_dir=None, **match_kw):
+        """``fit`` on event designs: both splits go through ``stage_events`` and ``fit`` runs on the two sets; returns what
+        ``fit`` returns.  ``fit_series``' rules: with ``standardize`` the scaler is fitted on the training set's ORIGINAL
+        windows (their folded values, chebgcn_window_stats_indexed) before balancing, the validation set takes the training
+        tables, and ``model.window_scaler`` goes into the checkpoints; ``sampling = n > 0`` balances the training classes
+        (``WindowSet.balance``; ``seed`` starts the balancing stream, ``groups``: one id per training run GIVEN -- runs that
+        yield no window are dropped from it like from the set; None: every run its own)."""
+        what = 'fit_events'
+        tr = self._event_args(train_series, train_label_runs, target_name, block_dura, match_kw, what)
+        va = self._event_args(val_series, val_label_runs, target_name, block_dura, match_kw, what)
+        train_labels, val_labels = tr[3], va[3]
+        if check_sampling(sampling, what):
+            if groups is not None:
+                n_given = len(train_series) if isinstance(train_series, (list, tuple)) else 1
+                groups = _int_vector(groups, 'the sampling groups (one id per run)', what, n_given)[tr[4]]
+            check_balance_args(what, train_labels, len(train_labels), sampling, seed, groups, len(tr[0]), False)
+        ws_train = self._stage_event_set(tr[0], tr[1], tr[2], None, None, what)
+        ws_val = self._stage_event_set(va[0], va[1], va[2], None, None, what)
+        self.window_scaler = None
+        if standardize:
+            self.window_scaler = ws_train.fit_scaler()
+            ws_val.share_tables(ws_train)
+        try:
+            if sampling:
+                train_labels = ws_train.balance(train_labels, sampling, seed, groups)
+            return self.fit(ws_train, train_labels, ws_val, val_labels, best_checkpoint_dir)
+        finally:
+            ws_train.balance(None, 0)
 
     def fit_series(self, train_series, train_starts, train_labels, val_series, val_starts, val_labels, standardize=False,
                    jitter=0, jitter_seed=0, best_checkpoint_dir=None, sampling=0, sampling_seed=0, sampling_groups=None,

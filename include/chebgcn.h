@@ -605,7 +605,29 @@ int chebgcn_gradcam_map(const float* A, const float* G, const float* alpha, cons
  *   deviations from series[0][m] in ascending row order inside chunks of 512 rows, chunks added in index order: no float
  *   atomics, bit-identical from run to run and under any permutation of rows.  workspace: device scratch of at least
  *   chebgcn_window_stats_workspace() bytes, 16-byte aligned.  chebgcn_last_dispatch(): window_count_kernel +
- *   window_stats_partial_kernel + window_stats_finish_kernel. */
+ *   window_stats_partial_kernel + window_stats_finish_kernel.
+ *
+ * Windows that are LISTS of rows (events.match_events: a trial padded by repeating its last volume, a chunk that straddles a rest
+ * period, the mean of TRstep sub-windows).  idx: int64 [S][Cin] (device), Cin = C * fold, rows of the concatenated planes;
+ * channel c of window s is the mean of the fold rows idx[s][f * C + c], f < fold:
+ *     piece(s)[c][m] = ( series[idx[s][0 * C + c]][m] + ... + series[idx[s][(fold - 1) * C + c]][m] ) / fold.
+ * gather_windows_indexed: src int64 [W][smax] with cnt int32 [W] (both or neither; series.balance_plan's indices INTO idx,
+ *   1 <= smax <= 16; NULL: every window is its own single source and W is ignored).  With w = sample ? sample[b] : b,
+ *   n = cnt[w] (1 without src):
+ *     out[b][c][m] = ( piece(src[w][0]) + ... + piece(src[w][n - 1]) ) / n     (then * scale[c][m] + shift[c][m]).
+ *   Float32 adds (round to nearest) in ascending order at both levels; each level takes ONE correctly rounded division, and
+ *   only when its count is above 1; the tables apply as a rounded product followed by a rounded sum, never one fma: bit for
+ *   bit reproducible in float32 NumPy, equal to gather_windows on contiguous rows at fold = 1 without src, and to
+ *   gather_windows_mix with src.  fold must lie in [1, 16] (and Cin == C * fold); n is clamped into [1, smax]; w is clamped
+ *   into [0, W - 1] (without src: [0, S - 1]), every entry of src into [0, S - 1] and every row into [0, Ttot - 1]: nothing
+ *   read from memory is an address or a trip count unchecked.  Pad, alignment and B as gather_windows.  Traffic:
+ *   (fold * n + 1) windows per output window.  chebgcn_last_dispatch(): gather_windows_indexed_kernel<plain | tables>.
+ * window_stats_indexed: what window_stats computes, over piece(s), s < S -- the folded values as the gather forms them in
+ *   float32, before the tables and without sources (what the reference's scaler sees, utils.py:573).  Float64 sums of the
+ *   deviations from series[0][m]; one workgroup sums a chunk of windows in ascending order (chunks of max(16, ceil(S / 32))
+ *   windows), chunks are added in index order: no float atomics, bit-identical from run to run.  workspace: at least
+ *   chebgcn_window_stats_indexed_workspace() bytes, 16-byte aligned.  chebgcn_last_dispatch():
+ *   window_stats_indexed_partial_kernel + window_stats_finish_kernel. */
 int chebgcn_gather_windows(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* sample, const float* scale,
                            const float* shift, float* out, int B, int M, int C, chebgcn_stream stream);
 int chebgcn_gather_windows_mix(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* cnt, int smax,
@@ -615,6 +637,14 @@ size_t chebgcn_window_stats_workspace(int64_t Ttot, int M, int C);
 int chebgcn_window_stats(const float* series, int64_t Ttot, const int64_t* rows, int64_t S, double* mean, double* var,
                          float* scale, float* shift, int M, int C, void* workspace, size_t workspace_bytes,
                          chebgcn_stream stream);
+int chebgcn_gather_windows_indexed(const float* series, int64_t Ttot, const int64_t* idx, int64_t S, int Cin, int fold,
+                                   const int64_t* src, const int32_t* cnt, int64_t W, int smax, const int32_t* sample,
+                                   const float* scale, const float* shift, float* out, int B, int M, int C,
+                                   chebgcn_stream stream);
+size_t chebgcn_window_stats_indexed_workspace(int64_t S, int M, int C);
+int chebgcn_window_stats_indexed(const float* series, int64_t Ttot, const int64_t* idx, int64_t S, int Cin, int fold,
+                                 double* mean, double* var, float* scale, float* shift, int M, int C, void* workspace,
+                                 size_t workspace_bytes, chebgcn_stream stream);
 
 /* ---- kNN brain graphs on the device (graph.knn_device / graph.connectivity_graph) ------------------------------------------
  * feat: [D][Np(N)] fp32, feature-major planes of N vertices (the staged-series layout with D = time; coordinates are
