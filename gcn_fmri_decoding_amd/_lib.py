@@ -13,6 +13,7 @@ BIAS_NONE, BIAS_FILTER, BIAS_VERTEX = 0, 1, 2
 POOL_MAX, POOL_AVG = 0, 1
 KNN_EUCLIDEAN, KNN_COSINE, KNN_CORRELATION, KNN_DOT = 0, 1, 2, 3
 KNN_KMAX = 32
+PARCEL_MEAN, PARCEL_SUM = 0, 1
 
 
 class ChebgcnError(RuntimeError):
@@ -128,6 +129,9 @@ SIGNATURES = {
     'chebgcn_knn_workspace': (C.c_size_t, [_i, _i, _i]),
     'chebgcn_knn': (_i, [_p, _i, _i, _i, _i, _p, _p, _p, C.c_size_t, _p]),
     'chebgcn_series_normalise': (_i, [_p, _i64, _p, _i, _i, _f, _p, _p]),
+    'chebgcn_parcellate_query': (_i, [_i]),
+    'chebgcn_parcellate': (_i, [_p, _i64, _p, _p, _i64, _p, _p, _i64, _i64, _i, _i, _i, _p]),
+    'chebgcn_parcel_expand': (_i, [_p, _p, _p, _i64, _i, _i, _f, _p]),
 }
 
 _lib = None

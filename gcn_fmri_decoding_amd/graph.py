@@ -99,16 +99,22 @@ def knn_device(z, k=4, metric='euclidean', device=None):
 
 def connectivity_graph(series, k=8, device=None, return_sigma=False):
     """Neighbours by functional connectivity, from the scans themselves: ``series`` is one ``[T, M]`` run or a list of runs
-    (any lengths >= 2, same M).  The runs are staged as ``[Ttot, Mp]`` planes in the caller's order, every run is centred and
+    (any lengths >= 2, same M; NumPy arrays, or torch tensors such as ``Parcellation.reduce`` returns, which are staged on the
+    device without a host round trip and give the same result as their ``.cpu().numpy()``).
+    The runs are staged as ``[Ttot, Mp]`` planes in the caller's order, every run is centred and
     scaled per vertex on the device (chebgcn_series_normalise), and the kNN kernels run on the Gram matrix of the result, which
     is the mean over runs of the per-run Pearson correlation matrices r (never formed; a vertex constant in a run has
     correlation 0 with everything in that run).  Returns (d, idx) with ``d = 1 - r`` float32 [M, k] ascending and idx int64,
     as ``knn_device``; with ``return_sigma`` also the mean of the whole matrix r (diagonal included), the reference's kernel
     width for its RSFC graph (model.py:126).  Tangent-space and partial correlation are out of scope."""
-    runs = [series] if isinstance(series, np.ndarray) and series.ndim == 2 else list(series)
+    def is_tensor(r):
+        return type(r).__module__.split('.')[0] == 'torch'
+
+    runs = [series] if (isinstance(series, np.ndarray) or is_tensor(series)) and series.ndim == 2 else list(series)
     if not runs:
         raise ValueError('connectivity_graph: no runs')
-    runs = [np.asarray(r) for r in runs]
+    on_device = any(is_tensor(r) for r in runs)
+    runs = [r if is_tensor(r) else np.asarray(r) for r in runs]
     if any(r.ndim != 2 for r in runs):
         raise ValueError('connectivity_graph: every run must be [T, M]')
     M = runs[0].shape[1]
@@ -117,16 +123,23 @@ def connectivity_graph(series, k=8, device=None, return_sigma=False):
     if any(r.shape[0] < 2 for r in runs):
         raise ValueError('connectivity_graph: a run needs at least two time points')
     _knn_check(M, k)
-    runs = [np.ascontiguousarray(r, dtype=np.float32) for r in runs]
-    if not all(np.isfinite(r).all() for r in runs):
+    runs = [r if is_tensor(r) else np.ascontiguousarray(r, dtype=np.float32) for r in runs]
+    if not all(np.isfinite(r).all() for r in runs if not is_tensor(r)):
         raise ValueError('connectivity_graph: series hold non-finite values')
     import torch
     from . import _lib, ops
     dev = _cuda_device(device)
     offs = np.concatenate([[0], np.cumsum([r.shape[0] for r in runs])]).astype(np.int64)
-    planes = np.zeros((int(offs[-1]), _lib.plane_stride(M)), np.float32)
-    for r, o in zip(runs, offs):
-        planes[o:o + r.shape[0], :M] = r
+    if on_device:                       # tensors (Parcellation.reduce gives them on the device) are staged where they lie
+        planes = torch.zeros((int(offs[-1]), _lib.plane_stride(M)), dtype=torch.float32, device=dev)
+        for r, o in zip(runs, offs):
+            planes[o:o + r.shape[0], :M] = (r if is_tensor(r) else torch.as_tensor(r)).to(dev, torch.float32)
+        if not bool(torch.isfinite(planes).all()):
+            raise ValueError('connectivity_graph: series hold non-finite values')
+    else:
+        planes = np.zeros((int(offs[-1]), _lib.plane_stride(M)), np.float32)
+        for r, o in zip(runs, offs):
+            planes[o:o + r.shape[0], :M] = r
     with torch.cuda.device(dev):
         zn = ops.series_normalise(torch.as_tensor(planes).to(dev), torch.as_tensor(offs).to(dev), M,
                                   scale=1.0 / np.sqrt(len(runs)))

@@ -417,6 +417,75 @@ def series_normalise(planes, run_offsets, M, scale=1.0, out=None):
     return out
 
 
+def parcellate_geometry():
+    """The constants of the parcellation kernels (chebgcn_parcellate_query), so that callers and tests follow the tile:
+    ``tile`` floats of x a workgroup holds per chunk (a chunk is ``tile // rows`` vertices of every row), ``rows`` the row tile of
+    the rows4 arm, ``wide_T`` the rows from which it runs, ``regions_per_pass``, ``max_grid`` workgroups of a launch,
+    ``expand_grid_rows`` and ``expand_vec`` of the expand kernel."""
+    q = _lib.lib().chebgcn_parcellate_query
+    return {'tile': q(0), 'rows': q(1), 'wide_T': q(2), 'regions_per_pass': q(3), 'max_grid': q(4), 'expand_grid_rows': q(5),
+            'expand_vec': q(6)}
+
+
+def _rows_of(t, n, what):
+    """Row stride (elements) of a 2-D float32 device tensor whose rows are contiguous over ``n`` values."""
+    if t.dim() != 2 or t.shape[1] != n or t.dtype != torch.float32 or (n > 1 and t.stride(1) != 1):
+        raise _lib.ChebgcnError('%s must be float32 [rows, %d] with contiguous rows' % (what, n))
+    ld = int(t.stride(0)) if t.shape[0] > 1 else n
+    if ld < n:
+        raise _lib.ChebgcnError('%s: a row stride of %d elements is less than the %d values of a row' % (what, ld, n))
+    return ld
+
+
+def parcellate(x, ptr, idx, R, w=None, mode=_lib.PARCEL_MEAN, out=None):
+    """A vertex-level run reduced to regions (chebgcn_parcellate): ``x`` float32 [T, V] on the device, rows contiguous (any row
+    stride >= V: a view of some columns of a wider tensor is taken as it is), ``ptr`` int32 [R + 1] / ``idx`` int32 [nnz] the
+    regions' member lists on the device (ascending inside a region; the caller checks them, the kernel trusts them), ``w``
+    float32 [V] or None -> ``out`` float32 [T, R] (given: any row stride >= R).  Sums run in ascending member order, one
+    rounded division: see include/chebgcn.h."""
+    _require_cuda(x, ptr, idx, w, out)
+    if x.dim() != 2:
+        raise _lib.ChebgcnError('parcellate: x must be [T, V]')
+    T, V = int(x.shape[0]), int(x.shape[1])
+    ldx = _rows_of(x, V, 'parcellate: x')
+    if (ptr.dtype != torch.int32 or idx.dtype != torch.int32 or ptr.dim() != 1 or idx.dim() != 1 or ptr.numel() != R + 1
+            or not ptr.is_contiguous() or not idx.is_contiguous()):
+        raise _lib.ChebgcnError('parcellate: ptr / idx must be contiguous int32 vectors of R + 1 / nnz entries')
+    if w is not None and (w.dtype != torch.float32 or w.shape != (V,) or not w.is_contiguous()):
+        raise _lib.ChebgcnError('parcellate: w must be a contiguous float32 vector of V entries')
+    if out is None:
+        out = torch.empty((T, R), dtype=torch.float32, device=x.device)
+    elif out.shape[0] != T:
+        raise _lib.ChebgcnError('parcellate: out has %d rows, x has %d' % (out.shape[0], T))
+    ldo = _rows_of(out, R, 'parcellate: out')
+    if T == 0:
+        return out
+    _lib.check(_launch('parcellate', 4.0 * T * V + 4.0 * T * R, float(T) * idx.numel(), lambda: _lib.lib().chebgcn_parcellate(
+        _p(x), ldx, _p(ptr), _p(idx), idx.numel(), _p(w), _p(out), ldo, T, V, int(R), int(mode), _stream())), 'parcellate')
+    return out
+
+
+def parcel_expand(maps, region_of, fill=0.0, out=None):
+    """Region maps back on the vertices (chebgcn_parcel_expand): ``maps`` float32 [B, R] and ``region_of`` int32 [V] (-1:
+    background) on the device, both contiguous -> ``out`` float32 [B, V], ``out[b, v] = maps[b, region_of[v]]`` or ``fill``."""
+    _require_cuda(maps, region_of, out)
+    if maps.dim() != 2 or maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise _lib.ChebgcnError('parcel_expand: maps must be contiguous float32 [B, R]')
+    if region_of.dim() != 1 or region_of.dtype != torch.int32 or not region_of.is_contiguous():
+        raise _lib.ChebgcnError('parcel_expand: region_of must be a contiguous int32 vector')
+    B, R = maps.shape
+    V = int(region_of.numel())
+    if out is None:
+        out = torch.empty((B, V), dtype=torch.float32, device=maps.device)
+    elif out.shape != (B, V) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.ChebgcnError('parcel_expand: out must be contiguous float32 [B, V]')
+    if B == 0:
+        return out
+    _lib.check(_launch('parcel_expand', 4.0 * B * V + 4.0 * V + 4.0 * B * R, 0.0, lambda: _lib.lib().chebgcn_parcel_expand(
+        _p(maps), _p(region_of), _p(out), B, R, V, float(fill), _stream())), 'parcel_expand')
+    return out
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------

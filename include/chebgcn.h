@@ -688,6 +688,40 @@ int chebgcn_knn(const float* feat, int N, int D, int k, int metric, float* dist_
 int chebgcn_series_normalise(const float* series, int64_t Ttot, const int64_t* run_offsets, int R, int M, float scale,
                              float* out, chebgcn_stream stream);
 
+/* ---- parcellation: vertex-level scans reduced to atlas regions, and back (parcellation.Parcellation) --------------------------
+ * parcellate: x float32, T rows of V values with row stride ldx >= V (elements; the offset t * ldx is 64-bit), vertex fastest;
+ *   the member lists of the R regions in CSR form, ptr int32 [R + 1] and idx int32 [nnz] (device), members ASCENDING inside a
+ *   region, every vertex at most once (nnz <= V); w float32 [V] per-vertex weights or NULL.  out float32 [T][R], row stride ldo.
+ *     MEAN  out[t][r] = (sum_j x[t][idx[j]]) / n_r              with w:  (sum_j w[idx[j]] * x[t][idx[j]]) / (sum_j w[idx[j]])
+ *     SUM   the numerator alone.
+ *   Float32 throughout, round to nearest: acc = 0, then acc = acc + term for j = ptr[r], ptr[r] + 1, ... one after the other
+ *   (a weighted term is a product rounded on its own, never an fma), the denominator of the weighted mean summed in the same
+ *   order, ONE correctly rounded division at the end.  The order is a function of (ptr, idx) alone -- not of T, of the row a
+ *   value stands in, of the launch geometry or of how the caller cuts the rows into calls: bit for bit reproducible in float32
+ *   NumPy (parcellation.Parcellation.reduce_host) and from call to call.  No float atomics.  A region without members gives
+ *   0 (SUM) or NaN (MEAN); a non-finite value reaches its own (t, r) only.  The lists are trusted (the caller checks them);
+ *   an entry that does not ascend is skipped, ptr is clamped into [0, nnz]: nothing read from memory is an address unchecked.
+ *   R <= 65535, V <= 2^30; x, w, out 4-byte aligned (any ldx: a row need not start on 16 bytes).  R above the regions of one
+ *   pass (chebgcn_parcellate_query(3)) sweeps x once per pass.
+ *   chebgcn_last_dispatch(): parcellate_kernel<rows1 | rows4, plain | weighted> -- rows4 (a workgroup owns 4 rows) from
+ *   T >= chebgcn_parcellate_query(2) rows, rows1 below (more workgroups).
+ * parcel_expand: out[b][v] = maps[b][region_of[v]], or `fill` where region_of[v] is outside [0, R) (-1: background); maps
+ *   float32 [B][R], region_of int32 [V] (16-byte aligned), out float32 [B][V], all contiguous.
+ *   chebgcn_last_dispatch(): parcel_expand_kernel.
+ * parcellate_query: constants of the kernels, for callers and tests that must follow the tile -- 0 floats of x a workgroup holds
+ *   per chunk (a chunk is that many / row tile vertices), 1 the row tile of rows4, 2 the rows from which rows4 runs, 3 regions
+ *   per pass, 4 most workgroups of a parcellate launch (beyond: a workgroup loops), 5 most map rows of an expand grid, 6
+ *   vertices per thread of expand; -1 for anything else. */
+enum {
+    CHEBGCN_PARCEL_MEAN = 0,
+    CHEBGCN_PARCEL_SUM = 1
+};
+int chebgcn_parcellate_query(int what);
+int chebgcn_parcellate(const float* x, int64_t ldx, const int32_t* ptr, const int32_t* idx, int64_t nnz, const float* w, float* out,
+                       int64_t ldo, int64_t T, int V, int R, int mode, chebgcn_stream stream);
+int chebgcn_parcel_expand(const float* maps, const int32_t* region_of, float* out, int64_t B, int R, int V, float fill,
+                          chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose

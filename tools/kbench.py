@@ -3,6 +3,7 @@
 
     python tools/kbench.py [--B 64 256] [--fin 32] [--fout 32] [--K 5] [--iters 20]
                            [--kernels recurrence_fwd ...]
+    python tools/kbench.py --parcellate [--iters 20] [--json out.json]      # the parcellation leg alone
 
 Times each C-ABI entry point with HIP events on the launch stream and prints achieved
 algorithmic GB/s (SURVEY.md 8d byte counts) and the fraction of the 8 TB/s HBM roofline.
@@ -18,8 +19,115 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def synthetic_atlas(V=91282, R=360, cortex=59412, seed=0, scattered=False):
+    """Labels shaped like a cortical atlas on grayordinates: the first ``cortex`` vertices belong to R parcels in runs of 1..32
+    consecutive indices drawn from a pool of 12 parcels that drifts along V (a parcel is local but not contiguous), the rest
+    (subcortex) is background.  ``scattered``: every cortical vertex an independent uniform draw instead."""
+    rs = np.random.RandomState(seed)
+    lab = np.zeros(V, np.int64)
+    if scattered:
+        lab[:cortex] = rs.randint(1, R + 1, size=cortex)
+    else:
+        v = 0
+        while v < cortex:
+            n = int(rs.randint(1, 33))
+            centre = v * R // cortex
+            lab[v:min(v + n, cortex)] = 1 + (centre + int(rs.randint(-6, 6))) % R
+            v += n
+    lab[:R] = np.arange(1, R + 1)           # every parcel exists
+    return lab
+
+
+def parcellate_leg(args):
+    """ops.parcellate on device-resident runs of HCP size against what the parent commit could do -- torch's index_add_ on the
+    device, np.add.reduceat on label-sorted columns on the host -- and Parcellation.reduce end to end from host memory."""
+    import time
+    import torch
+    from gcn_fmri_decoding_amd import Parcellation, _lib, ops
+    dev = torch.device('cuda:0')
+    results = []
+
+    def timeit(fn, iters):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        for s, e in evs:
+            s.record()
+            fn()
+            e.record()
+        torch.cuda.synchronize()
+        ms = sorted(s.elapsed_time(e) for s, e in evs)
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    def wall(fn, reps):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        ts.sort()
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    def note(name, T, atlas, t, nbytes):
+        med, lo, hi = t
+        r = {'leg': name, 'T': T, 'atlas': atlas, 'median_ms': med, 'min_ms': lo, 'max_ms': hi, 'GBps': nbytes / med / 1e6,
+             'frac_hbm': nbytes / med / 1e6 / 8000.0}
+        results.append(r)
+        print('%-28s T=%-5d %-9s %9.3f ms (min %8.3f, max %8.3f)  %7.0f GB/s  %5.1f%% of 8 TB/s'
+              % (name, T, atlas, med, lo, hi, r['GBps'], 100 * r['frac_hbm']), flush=True)
+
+    V, R = 91282, 360
+    for atlas in ('local', 'scattered'):
+        P = Parcellation(synthetic_atlas(V, R, scattered=atlas == 'scattered'))
+        ptr, idx, region_of, _ = P._tables(dev)
+        kept = torch.as_tensor(P.idx.astype(np.int64)).to(dev)
+        reg_kept = region_of[kept].long()
+        counts = torch.as_tensor(P.counts.astype(np.float32)).to(dev)
+        wts = torch.rand(V, device=dev) + 0.5
+        for T in (1200, 284):
+            torch.manual_seed(T)
+            x = torch.randn(T, V, device=dev) + 100.0 * (2 * torch.rand(V, device=dev) - 1)
+            out = torch.empty(T, R, device=dev)
+            nbytes = 4.0 * T * V + 4.0 * T * R
+            note('parcellate', T, atlas, timeit(lambda: ops.parcellate(x, ptr, idx, R, out=out), args.iters), nbytes)
+            print('   ', _lib.last_dispatch())
+            if atlas == 'local':
+                note('parcellate weighted', T, atlas, timeit(lambda: ops.parcellate(x, ptr, idx, R, w=wts, out=out), args.iters),
+                     nbytes)
+
+                def torch_way():
+                    return torch.zeros(T, R, device=dev).index_add_(1, reg_kept, x[:, kept]) / counts
+                note('torch index_add_', T, atlas, timeit(torch_way, args.iters), nbytes)
+                ref = torch_way()
+                got = ops.parcellate(x, ptr, idx, R)
+                print('    max |kernel - torch| = %.3e' % float((got - ref).abs().max()))
+    # the host baseline and the end-to-end call from host memory, T = 1200
+    P = Parcellation(synthetic_atlas(V, R))
+    T = 1200
+    xh = (np.random.RandomState(1).randn(T, V) + 100.0).astype(np.float32)
+    nbytes = 4.0 * T * V + 4.0 * T * R
+    order = P.idx.astype(np.int64)
+    starts = P.ptr[:-1].astype(np.int64)
+
+    def host_way():
+        return np.add.reduceat(xh[:, order], starts, axis=1) / P.counts.astype(np.float32)
+    note('host np.add.reduceat', T, 'local', wall(host_way, 3), nbytes)
+    note('reduce, pageable host array', T, 'local', wall(lambda: P.reduce(xh), 5), nbytes)
+    xp = torch.as_tensor(xh).pin_memory()
+    note('reduce, pinned host tensor', T, 'local', wall(lambda: P.reduce(xp), 5), nbytes)
+    xd = torch.as_tensor(xh).to(dev)
+    note('reduce, device tensor', T, 'local', wall(lambda: P.reduce(xd), 5), nbytes)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--parcellate', action='store_true', help='the parcellation leg alone (ops.parcellate at HCP size)')
     ap.add_argument('--B', type=int, nargs='+', default=[64, 256])
     ap.add_argument('--fin', type=int, default=32)
     ap.add_argument('--fout', type=int, default=32)
@@ -40,6 +148,8 @@ def main():
     ap.add_argument('--stagger', type=int, default=0, help='chebgcn_tune(4, x): start stagger override (x-1 eighths), 0 = automatic')
     ap.add_argument('--wide', type=int, default=0, help='chebgcn_tune(3, x): 1 = 1024-thread recurrence shape')
     args = ap.parse_args()
+    if args.parcellate:
+        return parcellate_leg(args)
 
     import torch
     import bench
