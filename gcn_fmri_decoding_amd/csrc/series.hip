@@ -27,6 +27,34 @@ constexpr int WS_ROWS = 512;            // series rows of one chunk (a chunk's p
 
 __device__ __forceinline__ long long clamp_row(long long r, long long last) { return r < 0 ? 0 : (r > last ? last : r); }
 
+// ---- what the gathers do to a piece (16 bytes of a window): float32 adds and divisions of one rounding each, then the epilogue ---
+__device__ __forceinline__ float4 add4(float4 a, float4 b) {
+    return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
+}
+__device__ __forceinline__ float4 div4(float4 a, float d) {
+    return make_float4(__fdiv_rn(a.x, d), __fdiv_rn(a.y, d), __fdiv_rn(a.z, d), __fdiv_rn(a.w, d));
+}
+
+// the tables (a rounded product, then a rounded sum: never one fma), the zero pad (the pad of an output plane is zero whatever
+// the operands hold there), the store
+template <bool Tables>
+__device__ __forceinline__ void finish_piece(float4 r, float4 a, float4 s, int q, int M, float4* __restrict__ dst) {
+    if (Tables) {
+        r.x = __fadd_rn(__fmul_rn(r.x, a.x), s.x);
+        r.y = __fadd_rn(__fmul_rn(r.y, a.y), s.y);
+        r.z = __fadd_rn(__fmul_rn(r.z, a.z), s.z);
+        r.w = __fadd_rn(__fmul_rn(r.w, a.w), s.w);
+    }
+    const int m = 4 * q;
+    if (m + 3 >= M) {
+        if (m >= M) r.x = 0.f;
+        if (m + 1 >= M) r.y = 0.f;
+        if (m + 2 >= M) r.z = 0.f;
+        r.w = 0.f;
+    }
+    *dst = r;
+}
+
 // block (piece of the window's C * Mp/4 float4s, window b)
 template <bool Tables>
 __global__ void __launch_bounds__(GW_T)
@@ -53,23 +81,7 @@ gather_windows_kernel(const float* __restrict__ series, long long last_row, cons
 #pragma unroll
     for (int u = 0; u < GW_U; ++u) {
         const int e = e0 + u * GW_T;
-        if (e < CMq) {
-            float4 r = v[u];
-            if (Tables) {               // a rounded product, then a rounded sum: never one fma
-                r.x = __fadd_rn(__fmul_rn(r.x, a[u].x), s[u].x);
-                r.y = __fadd_rn(__fmul_rn(r.y, a[u].y), s[u].y);
-                r.z = __fadd_rn(__fmul_rn(r.z, a[u].z), s[u].z);
-                r.w = __fadd_rn(__fmul_rn(r.w, a[u].w), s[u].w);
-            }
-            const int m = 4 * (e % Mq);
-            if (m + 3 >= M) {           // the pad of an output plane is zero whatever the operands hold there
-                if (m >= M) r.x = 0.f;
-                if (m + 1 >= M) r.y = 0.f;
-                if (m + 2 >= M) r.z = 0.f;
-                r.w = 0.f;
-            }
-            dst[e] = r;
-        }
+        if (e < CMq) finish_piece<Tables>(v[u], a[u], s[u], e % Mq, M, dst + e);
     }
 }
 
@@ -108,32 +120,9 @@ __device__ __forceinline__ void mix_pieces(const float4* __restrict__ series4, l
             if (e < CMq) {
                 float4 r = v[0][u];
 #pragma unroll
-                for (int j = 1; j < N; ++j) {           // float32 adds in ascending j
-                    r.x = __fadd_rn(r.x, v[j][u].x);
-                    r.y = __fadd_rn(r.y, v[j][u].y);
-                    r.z = __fadd_rn(r.z, v[j][u].z);
-                    r.w = __fadd_rn(r.w, v[j][u].w);
-                }
-                if (N > 1) {                            // one correctly rounded division (n = 1: the plain gather's bits)
-                    r.x = __fdiv_rn(r.x, (float)N);
-                    r.y = __fdiv_rn(r.y, (float)N);
-                    r.z = __fdiv_rn(r.z, (float)N);
-                    r.w = __fdiv_rn(r.w, (float)N);
-                }
-                if (Tables) {                           // after the mean; a rounded product, then a rounded sum
-                    r.x = __fadd_rn(__fmul_rn(r.x, a[u].x), s[u].x);
-                    r.y = __fadd_rn(__fmul_rn(r.y, a[u].y), s[u].y);
-                    r.z = __fadd_rn(__fmul_rn(r.z, a[u].z), s[u].z);
-                    r.w = __fadd_rn(__fmul_rn(r.w, a[u].w), s[u].w);
-                }
-                const int m = 4 * (e % Mq);
-                if (m + 3 >= M) {
-                    if (m >= M) r.x = 0.f;
-                    if (m + 1 >= M) r.y = 0.f;
-                    if (m + 2 >= M) r.z = 0.f;
-                    r.w = 0.f;
-                }
-                dst[e] = r;
+                for (int j = 1; j < N; ++j) r = add4(r, v[j][u]);           // float32 adds in ascending j
+                if (N > 1) r = div4(r, (float)N);       // one correctly rounded division (n = 1: the plain gather's bits)
+                finish_piece<Tables>(r, a[u], s[u], e % Mq, M, dst + e);    // the tables come after the mean
             }
         }
     }
@@ -173,32 +162,6 @@ gather_windows_mix_kernel(const float* __restrict__ series, long long last_row, 
 // issued before the first add; counts without a body of their own take the generic loop.  Every window index is clamped into
 // [0, S - 1] and every row into [0, Ttot - 1]: nothing read from memory is an address or a trip count unchecked.
 constexpr int GWI_MAX = 16;             // fold and n at most
-
-__device__ __forceinline__ float4 add4(float4 a, float4 b) {
-    return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
-}
-__device__ __forceinline__ float4 div4(float4 a, float d) {
-    return make_float4(__fdiv_rn(a.x, d), __fdiv_rn(a.y, d), __fdiv_rn(a.z, d), __fdiv_rn(a.w, d));
-}
-
-// the tables (a rounded product, then a rounded sum), the zero pad, the store
-template <bool Tables>
-__device__ __forceinline__ void finish_piece(float4 r, float4 a, float4 s, int q, int M, float4* __restrict__ dst) {
-    if (Tables) {
-        r.x = __fadd_rn(__fmul_rn(r.x, a.x), s.x);
-        r.y = __fadd_rn(__fmul_rn(r.y, a.y), s.y);
-        r.z = __fadd_rn(__fmul_rn(r.z, a.z), s.z);
-        r.w = __fadd_rn(__fmul_rn(r.w, a.w), s.w);
-    }
-    const int m = 4 * q;
-    if (m + 3 >= M) {
-        if (m >= M) r.x = 0.f;
-        if (m + 1 >= M) r.y = 0.f;
-        if (m + 2 >= M) r.z = 0.f;
-        r.w = 0.f;
-    }
-    *dst = r;
-}
 
 struct IndexedArgs {
     const float4* series4;
@@ -491,6 +454,43 @@ static inline size_t ws_count_bytes(int64_t Ttot, int C) {
 }
 static inline int ws_chunks(int64_t Ttot) { return (int)((Ttot + WS_ROWS - 1) / WS_ROWS); }
 
+// the checks the three gather entries share (name: the entry's, as its messages spell it), and their grid
+static int gather_args(const char* name, const void* series, const void* table, const void* out, const float* scale,
+                       const float* shift, int B, int M, int C) {
+    CG_REQUIRE(series && table && out, "%s: NULL argument", name);
+    CG_REQUIRE((scale != nullptr) == (shift != nullptr), "%s: scale and shift come together (both or neither)", name);
+    CG_REQUIRE(B > 0 && B <= 65535 && M > 0 && C > 0 && (int64_t)C * plane_stride(M) / 4 <= 0x7fffffffLL / 2,
+               "%s: bad shape (B = %d, M = %d, C = %d)", name, B, M, C);
+    CG_REQUIRE((((uintptr_t)series | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
+               "%s: series, tables and out must be 16-byte aligned", name);
+    return CHEBGCN_OK;
+}
+static inline dim3 gather_grid(int CMq, int B) { return dim3((CMq + GW_T * GW_U - 1) / (GW_T * GW_U), B); }
+
+// KERNEL<true> with tables, KERNEL<false> without, under its dispatch name; needs scale, grid and stream_ in scope
+#define CG_LAUNCH_GATHER(KERNEL, ...)                                                                                 \
+    do {                                                                                                              \
+        if (scale) {                                                                                                  \
+            note_dispatch(#KERNEL "<tables>");                                                                        \
+            hipLaunchKernelGGL(KERNEL<true>, grid, dim3(GW_T), 0, (hipStream_t)stream_, __VA_ARGS__);                 \
+        } else {                                                                                                      \
+            note_dispatch(#KERNEL "<plain>");                                                                         \
+            hipLaunchKernelGGL(KERNEL<false>, grid, dim3(GW_T), 0, (hipStream_t)stream_, __VA_ARGS__);                \
+        }                                                                                                             \
+        CG_HIP(hipGetLastError());                                                                                    \
+    } while (0)
+
+// the last launch of both statistics entries: the chunks' partials into the four tables
+static int stats_finish(const float* series, const double* part, int G, int64_t S, int M, int Mp, int C, double* mean,
+                        double* var, float* scale, float* shift, hipStream_t stream) {
+    note_dispatch_more("window_stats_finish_kernel");
+    const size_t slab = (size_t)C * Mp;
+    hipLaunchKernelGGL(window_stats_finish_kernel, dim3((unsigned)((slab + WS_T - 1) / WS_T)), dim3(WS_T), 0, stream, series, part,
+                       G, (long long)S, M, Mp, C, mean, var, scale, shift);
+    CG_HIP(hipGetLastError());
+    return CHEBGCN_OK;
+}
+
 }  // namespace chebgcn
 
 using namespace chebgcn;
@@ -498,52 +498,26 @@ using namespace chebgcn;
 extern "C" int chebgcn_gather_windows(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* sample,
                                       const float* scale, const float* shift, float* out, int B, int M, int C,
                                       chebgcn_stream stream_) {
-    CG_REQUIRE(series && rows && out, "gather_windows: NULL argument");
-    CG_REQUIRE((scale != nullptr) == (shift != nullptr), "gather_windows: scale and shift come together (both or neither)");
-    CG_REQUIRE(B > 0 && B <= 65535 && M > 0 && C > 0 && (int64_t)C * plane_stride(M) / 4 <= 0x7fffffffLL / 2,
-               "gather_windows: bad shape (B = %d, M = %d, C = %d)", B, M, C);
+    if (int rc = gather_args("gather_windows", series, rows, out, scale, shift, B, M, C)) return rc;
     CG_REQUIRE(Ttot >= C, "gather_windows: a series of %lld time points holds no window of %d", (long long)Ttot, C);
-    CG_REQUIRE((((uintptr_t)series | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
-               "gather_windows: series, tables and out must be 16-byte aligned");
     const int Mq = plane_stride(M) / 4, CMq = C * Mq;
-    dim3 grid((CMq + GW_T * GW_U - 1) / (GW_T * GW_U), B);
-    if (scale) {
-        note_dispatch("gather_windows_kernel<tables>");
-        hipLaunchKernelGGL(gather_windows_kernel<true>, grid, dim3(GW_T), 0, (hipStream_t)stream_, series,
-                           (long long)(Ttot - C), (const long long*)rows, sample, scale, shift, out, M, Mq, CMq);
-    } else {
-        note_dispatch("gather_windows_kernel<plain>");
-        hipLaunchKernelGGL(gather_windows_kernel<false>, grid, dim3(GW_T), 0, (hipStream_t)stream_, series,
-                           (long long)(Ttot - C), (const long long*)rows, sample, scale, shift, out, M, Mq, CMq);
-    }
-    CG_HIP(hipGetLastError());
+    const dim3 grid = gather_grid(CMq, B);
+    CG_LAUNCH_GATHER(gather_windows_kernel, series, (long long)(Ttot - C), (const long long*)rows, sample, scale, shift, out, M, Mq,
+                     CMq);
     return CHEBGCN_OK;
 }
 
 extern "C" int chebgcn_gather_windows_mix(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* cnt, int smax,
                                           const int32_t* sample, const float* scale, const float* shift, float* out, int B, int M,
                                           int C, chebgcn_stream stream_) {
-    CG_REQUIRE(series && rows && out, "gather_windows_mix: NULL argument");
+    if (int rc = gather_args("gather_windows_mix", series, rows, out, scale, shift, B, M, C)) return rc;
     CG_REQUIRE(cnt, "gather_windows_mix: NULL cnt (the number of sources of every window)");
     CG_REQUIRE(smax >= 1 && smax <= GWM_MAX, "gather_windows_mix: smax = %d, must be in [1, %d]", smax, GWM_MAX);
-    CG_REQUIRE((scale != nullptr) == (shift != nullptr), "gather_windows_mix: scale and shift come together (both or neither)");
-    CG_REQUIRE(B > 0 && B <= 65535 && M > 0 && C > 0 && (int64_t)C * plane_stride(M) / 4 <= 0x7fffffffLL / 2,
-               "gather_windows_mix: bad shape (B = %d, M = %d, C = %d)", B, M, C);
     CG_REQUIRE(Ttot >= C, "gather_windows_mix: a series of %lld time points holds no window of %d", (long long)Ttot, C);
-    CG_REQUIRE((((uintptr_t)series | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
-               "gather_windows_mix: series, tables and out must be 16-byte aligned");
     const int Mq = plane_stride(M) / 4, CMq = C * Mq;
-    dim3 grid((CMq + GW_T * GW_U - 1) / (GW_T * GW_U), B);
-    if (scale) {
-        note_dispatch("gather_windows_mix_kernel<tables>");
-        hipLaunchKernelGGL(gather_windows_mix_kernel<true>, grid, dim3(GW_T), 0, (hipStream_t)stream_, series,
-                           (long long)(Ttot - C), (const long long*)rows, cnt, smax, sample, scale, shift, out, M, Mq, CMq);
-    } else {
-        note_dispatch("gather_windows_mix_kernel<plain>");
-        hipLaunchKernelGGL(gather_windows_mix_kernel<false>, grid, dim3(GW_T), 0, (hipStream_t)stream_, series,
-                           (long long)(Ttot - C), (const long long*)rows, cnt, smax, sample, scale, shift, out, M, Mq, CMq);
-    }
-    CG_HIP(hipGetLastError());
+    const dim3 grid = gather_grid(CMq, B);
+    CG_LAUNCH_GATHER(gather_windows_mix_kernel, series, (long long)(Ttot - C), (const long long*)rows, cnt, smax, sample, scale,
+                     shift, out, M, Mq, CMq);
     return CHEBGCN_OK;
 }
 
@@ -576,31 +550,21 @@ extern "C" int chebgcn_window_stats(const float* series, int64_t Ttot, const int
     hipLaunchKernelGGL(window_stats_partial_kernel, dim3(tiles * ncg, G), dim3(WS_T), 0, stream, series, (long long)Ttot, cnt, C,
                        Mp, ncg, part);
     CG_HIP(hipGetLastError());
-    note_dispatch_more("window_stats_finish_kernel");
-    const size_t slab = (size_t)C * Mp;
-    hipLaunchKernelGGL(window_stats_finish_kernel, dim3((unsigned)((slab + WS_T - 1) / WS_T)), dim3(WS_T), 0, stream, series, part,
-                       G, (long long)S, M, Mp, C, mean, var, scale, shift);
-    CG_HIP(hipGetLastError());
-    return CHEBGCN_OK;
+    return stats_finish(series, part, G, S, M, Mp, C, mean, var, scale, shift, stream);
 }
 
 extern "C" int chebgcn_gather_windows_indexed(const float* series, int64_t Ttot, const int64_t* idx, int64_t S, int Cin, int fold,
                                               const int64_t* src, const int32_t* cnt, int64_t W, int smax, const int32_t* sample,
                                               const float* scale, const float* shift, float* out, int B, int M, int C,
                                               chebgcn_stream stream_) {
-    CG_REQUIRE(series && idx && out, "gather_windows_indexed: NULL argument");
+    if (int rc = gather_args("gather_windows_indexed", series, idx, out, scale, shift, B, M, C)) return rc;
     CG_REQUIRE((src != nullptr) == (cnt != nullptr), "gather_windows_indexed: src and cnt come together (both or neither)");
     CG_REQUIRE(!src || (smax >= 1 && smax <= GWI_MAX && W >= 1), "gather_windows_indexed: smax = %d, must be in [1, %d], W = %lld",
                smax, GWI_MAX, (long long)W);
     CG_REQUIRE(fold >= 1 && fold <= GWI_MAX, "gather_windows_indexed: fold = %d, must be in [1, %d]", fold, GWI_MAX);
-    CG_REQUIRE((scale != nullptr) == (shift != nullptr), "gather_windows_indexed: scale and shift come together (both or neither)");
-    CG_REQUIRE(B > 0 && B <= 65535 && M > 0 && C > 0 && (int64_t)C * plane_stride(M) / 4 <= 0x7fffffffLL / 2,
-               "gather_windows_indexed: bad shape (B = %d, M = %d, C = %d)", B, M, C);
     CG_REQUIRE((int64_t)Cin == (int64_t)C * fold, "gather_windows_indexed: Cin = %d is not C * fold = %d * %d", Cin, C, fold);
     CG_REQUIRE(S >= 1 && Ttot >= 1, "gather_windows_indexed: S = %lld windows of a series of %lld time points", (long long)S,
                (long long)Ttot);
-    CG_REQUIRE((((uintptr_t)series | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
-               "gather_windows_indexed: series, tables and out must be 16-byte aligned");
     IndexedArgs A;
     A.series4 = reinterpret_cast<const float4*>(series);
     A.last_row = (long long)Ttot - 1;
@@ -612,17 +576,8 @@ extern "C" int chebgcn_gather_windows_indexed(const float* series, int64_t Ttot,
     A.Mq = plane_stride(M) / 4;
     A.CMq = C * A.Mq;
     const long long last_w = (src ? (long long)W : (long long)S) - 1;
-    dim3 grid((A.CMq + GW_T * GW_U - 1) / (GW_T * GW_U), B);
-    if (scale) {
-        note_dispatch("gather_windows_indexed_kernel<tables>");
-        hipLaunchKernelGGL(gather_windows_indexed_kernel<true>, grid, dim3(GW_T), 0, (hipStream_t)stream_, A, fold,
-                           (const long long*)src, cnt, last_w, smax, sample, scale, shift, out);
-    } else {
-        note_dispatch("gather_windows_indexed_kernel<plain>");
-        hipLaunchKernelGGL(gather_windows_indexed_kernel<false>, grid, dim3(GW_T), 0, (hipStream_t)stream_, A, fold,
-                           (const long long*)src, cnt, last_w, smax, sample, scale, shift, out);
-    }
-    CG_HIP(hipGetLastError());
+    const dim3 grid = gather_grid(A.CMq, B);
+    CG_LAUNCH_GATHER(gather_windows_indexed_kernel, A, fold, (const long long*)src, cnt, last_w, smax, sample, scale, shift, out);
     return CHEBGCN_OK;
 }
 
@@ -658,10 +613,5 @@ extern "C" int chebgcn_window_stats_indexed(const float* series, int64_t Ttot, c
     else CG_WSI(0);
 #undef CG_WSI
     CG_HIP(hipGetLastError());
-    note_dispatch_more("window_stats_finish_kernel");
-    const size_t slab = (size_t)C * Mp;
-    hipLaunchKernelGGL(window_stats_finish_kernel, dim3((unsigned)((slab + WS_T - 1) / WS_T)), dim3(WS_T), 0, stream, series, part,
-                       G, (long long)S, M, Mp, C, mean, var, scale, shift);
-    CG_HIP(hipGetLastError());
-    return CHEBGCN_OK;
+    return stats_finish(series, part, G, S, M, Mp, C, mean, var, scale, shift, stream);
 }

@@ -57,6 +57,36 @@ def window_starts(T, C, starts=None, stride=1, what='decode_series'):
     return a
 
 
+def run_list(series, what):
+    """``series``, one run or a list of runs, as a non-empty list."""
+    runs = list(series) if isinstance(series, (list, tuple)) else [series]
+    if not runs:
+        raise ValueError('%s: series is an empty list' % what)
+    return runs
+
+
+def check_run(r, M0, what, least=0):
+    """One run as a numeric ``[T, M0]`` array or tensor of at least ``least`` time points, else a ``ValueError``."""
+    if not isinstance(r, torch.Tensor):
+        r = np.asarray(r)
+        if not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
+            raise ValueError('%s: series must be numeric, got %s' % (what, r.dtype))
+    shape = tuple(int(d) for d in r.shape)
+    if len(shape) != 2 or shape[1] != M0 or shape[0] < least:
+        raise ValueError('%s: series must be [T, %d] (time points x vertices), got %s' % (what, M0, shape))
+    return r
+
+
+def check_table(v, name, M0, C, what):
+    """A ``scale`` / ``shift`` table as float32 ``[M0, C]`` (None stays None), else a ``ValueError``."""
+    if v is None:
+        return None
+    a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32)
+    if a.shape != (M0, C):
+        raise ValueError('%s: %s must be [%d, %d] (vertices x channels), got %s' % (what, name, M0, C, a.shape))
+    return a
+
+
 def chunk_plan(starts, T, C, chunk_T):
     """How a run is cut when its stack may hold ``chunk_T >= C`` time points: a list of ``(t0, t1, idx)`` -- the chunk covers
     the time points ``[t0, t1)``, consecutive chunks overlap by ``C - 1``, and ``idx`` are the positions in ``starts`` of the
@@ -95,9 +125,7 @@ class Decode(object):
         if isinstance(bs, bool) or not isinstance(bs, (int, np.integer)) or not 1 <= bs <= 65535:
             raise ValueError('%s: batch_size must be an int in [1, 65535], got %r' % (what, batch_size))
         many = isinstance(series, (list, tuple))
-        runs = list(series) if many else [series]
-        if not runs:
-            raise ValueError('%s: series is an empty list' % what)
+        runs = run_list(series, what)
         if many and starts is not None:
             if not isinstance(starts, (list, tuple)) or len(starts) != len(runs) or any(np.ndim(s) == 0 for s in starts):
                 raise ValueError('%s: with a list of %d runs, starts must be a list of as many arrays' % (what, len(runs)))
@@ -105,24 +133,11 @@ class Decode(object):
         M0, C = int(self._M0), int(self.channel)
         out_runs, out_starts = [], []
         for r, st in zip(runs, per_run):
-            if not isinstance(r, torch.Tensor):
-                r = np.asarray(r)
-                if not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
-                    raise ValueError('%s: series must be numeric, got %s' % (what, r.dtype))
-            shape = tuple(int(d) for d in r.shape)
-            if len(shape) != 2 or shape[1] != M0:
-                raise ValueError('%s: series must be [T, %d] (time points x vertices), got %s' % (what, M0, shape))
-            out_starts.append(window_starts(shape[0], C, st, stride, what))
+            r = check_run(r, M0, what)
+            out_starts.append(window_starts(r.shape[0], C, st, stride, what))
             out_runs.append(r)
-
-        def table(v, name):
-            if v is None:
-                return None
-            a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32)
-            if a.shape != (M0, C):
-                raise ValueError('%s: %s must be [%d, %d] (vertices x channels), got %s' % (what, name, M0, C, a.shape))
-            return a
-        return out_runs, out_starts, int(bs), table(scale, 'scale'), table(shift, 'shift'), many
+        scale, shift = check_table(scale, 'scale', M0, C, what), check_table(shift, 'shift', M0, C, what)
+        return out_runs, out_starts, int(bs), scale, shift, many
 
     def _shared_refusal(self, B, scaled):
         """None where the shared path serves this model, else why not."""

@@ -268,6 +268,32 @@ def perm_data(x, perm, sample=None, out=None):
     return out
 
 
+def _windows_out(out, n, sample, C, planes):
+    """``(B, out)`` of a gather of ``sample`` (None: all ``n``) windows: ``out`` where it is contiguous ``[B, C, Mp]``, else new."""
+    shape = (int(n if sample is None else sample.numel()), C, planes.shape[1])
+    if out is None or tuple(out.shape) != shape or not out.is_contiguous():
+        out = torch.empty(shape, dtype=torch.float32, device=planes.device)
+    return shape[0], out
+
+
+def _mix_tables(tab, cnt, what, name):
+    """``(S', smax)`` of the tables of a plan: ``tab`` contiguous int64 ``[S', smax]``, ``cnt`` int32 ``[S']``."""
+    if tab.dim() != 2 or cnt.dim() != 1 or tab.shape[0] != cnt.shape[0] or tab.dtype != torch.int64 \
+            or cnt.dtype != torch.int32 or not tab.is_contiguous() or not cnt.is_contiguous():
+        raise _lib.ChebgcnError('%s: %s must be contiguous int64 [S, smax] and cnt int32 [S]' % (what, name))
+    return int(tab.shape[0]), int(tab.shape[1])
+
+
+def _stats_launch(what, planes, M, C, nbytes, traffic, entry, *head):
+    """What the statistics entries share: the outputs ``mean, var`` float64 and ``scale, shift`` float32, ``[C, Mp]`` each, the
+    workspace, and the launch ``entry(*head, mean, var, scale, shift, M, C, workspace, its bytes, stream)``."""
+    kinds = (torch.float64, torch.float64, torch.float32, torch.float32)
+    outs = tuple(torch.empty((C, planes.shape[1]), dtype=dt, device=planes.device) for dt in kinds)
+    ws = _workspace(int(nbytes), planes.device, what)
+    _lib.check(_launch(what, traffic, 0.0, lambda: entry(*head, *map(_p, outs), M, C, _p(ws), ws.numel(), _stream())), what)
+    return outs
+
+
 def gather_windows(planes, rows, M, C, sample=None, scale=None, shift=None, out=None):
     """Windows of a staged series (chebgcn_gather_windows): ``planes`` [Ttot, Mp] fp32 (internal vertex order, zero pad),
     ``rows`` int64 device table of the windows' first rows, ``sample`` int32 device indices into it (None: all of them, in
@@ -275,9 +301,7 @@ def gather_windows(planes, rows, M, C, sample=None, scale=None, shift=None, out=
     that shape."""
     _require_cuda(planes, rows, sample, scale, shift, out)
     Ttot, Mp = planes.shape
-    B = int(rows.numel() if sample is None else sample.numel())
-    if out is None or tuple(out.shape) != (B, C, Mp) or not out.is_contiguous():
-        out = torch.empty((B, C, Mp), dtype=torch.float32, device=planes.device)
+    B, out = _windows_out(out, rows.numel(), sample, C, planes)
     _lib.check(_launch('gather_windows', 8.0 * B * C * Mp, 0.0, lambda: _lib.lib().chebgcn_gather_windows(
         _p(planes), Ttot, _p(rows), _p(sample), _p(scale), _p(shift), _p(out), B, M, C, _stream())), 'gather_windows')
     return out
@@ -290,13 +314,8 @@ def gather_windows_mix(planes, rows, cnt, M, C, sample=None, scale=None, shift=N
     windows gathered, for the launch log's byte count (None: ``smax``)."""
     _require_cuda(planes, rows, cnt, sample, scale, shift, out)
     Ttot, Mp = planes.shape
-    if rows.dim() != 2 or cnt.dim() != 1 or rows.shape[0] != cnt.shape[0] or rows.dtype != torch.int64 \
-            or cnt.dtype != torch.int32 or not rows.is_contiguous() or not cnt.is_contiguous():
-        raise _lib.ChebgcnError('gather_windows_mix: rows must be contiguous int64 [S, smax] and cnt int32 [S]')
-    smax = int(rows.shape[1])
-    B = int(cnt.numel() if sample is None else sample.numel())
-    if out is None or tuple(out.shape) != (B, C, Mp) or not out.is_contiguous():
-        out = torch.empty((B, C, Mp), dtype=torch.float32, device=planes.device)
+    W, smax = _mix_tables(rows, cnt, 'gather_windows_mix', 'rows')
+    B, out = _windows_out(out, W, sample, C, planes)
     nsrc = float(smax if sources is None else sources)
     _lib.check(_launch('gather_windows_mix', 4.0 * (nsrc + 1) * B * C * Mp, 0.0, lambda: _lib.lib().chebgcn_gather_windows_mix(
         _p(planes), Ttot, _p(rows), _p(cnt), smax, _p(sample), _p(scale), _p(shift), _p(out), B, M, C, _stream())),
@@ -309,15 +328,9 @@ def window_stats(planes, rows, M, C):
     built: ``(mean, var)`` float64 and ``(scale, shift)`` float32, all [C, Mp] on the device, internal vertex order."""
     _require_cuda(planes, rows)
     Ttot, Mp = planes.shape
-    dev = planes.device
-    mean, var = (torch.empty((C, Mp), dtype=torch.float64, device=dev) for _ in range(2))
-    scale, shift = (torch.empty((C, Mp), dtype=torch.float32, device=dev) for _ in range(2))
-    nbytes = int(_lib.lib().chebgcn_window_stats_workspace(Ttot, M, C))
-    ws = _workspace(nbytes, dev, 'window_stats')
-    _lib.check(_launch('window_stats', 4.0 * Ttot * Mp, 0.0, lambda: _lib.lib().chebgcn_window_stats(
-        _p(planes), Ttot, _p(rows), int(rows.numel()), _p(mean), _p(var), _p(scale), _p(shift), M, C, _p(ws), ws.numel(),
-        _stream())), 'window_stats')
-    return mean, var, scale, shift
+    lib = _lib.lib()
+    return _stats_launch('window_stats', planes, M, C, lib.chebgcn_window_stats_workspace(Ttot, M, C), 4.0 * Ttot * Mp,
+                         lib.chebgcn_window_stats, _p(planes), Ttot, _p(rows), int(rows.numel()))
 
 
 def _index_table(idx, M, C, fold, what):
@@ -341,15 +354,8 @@ def gather_windows_indexed(planes, idx, M, C, fold=1, src=None, cnt=None, sample
     S, Cin = _index_table(idx, M, C, fold, 'gather_windows_indexed')
     if (src is None) != (cnt is None):
         raise _lib.ChebgcnError('gather_windows_indexed: src and cnt come together (both or neither)')
-    W, smax = S, 1
-    if src is not None:
-        if src.dim() != 2 or cnt.dim() != 1 or src.shape[0] != cnt.shape[0] or src.dtype != torch.int64 \
-                or cnt.dtype != torch.int32 or not src.is_contiguous() or not cnt.is_contiguous():
-            raise _lib.ChebgcnError('gather_windows_indexed: src must be contiguous int64 [S, smax] and cnt int32 [S]')
-        W, smax = int(src.shape[0]), int(src.shape[1])
-    B = int(W if sample is None else sample.numel())
-    if out is None or tuple(out.shape) != (B, C, Mp) or not out.is_contiguous():
-        out = torch.empty((B, C, Mp), dtype=torch.float32, device=planes.device)
+    W, smax = (S, 1) if src is None else _mix_tables(src, cnt, 'gather_windows_indexed', 'src')
+    B, out = _windows_out(out, W, sample, C, planes)
     nsrc = float(fold) * float((smax if src is not None else 1) if sources is None else sources)
     _lib.check(_launch('gather_windows_indexed', 4.0 * (nsrc + 1) * B * C * Mp, 0.0,
                        lambda: _lib.lib().chebgcn_gather_windows_indexed(
@@ -364,15 +370,9 @@ def window_stats_indexed(planes, idx, M, C, fold=1):
     _require_cuda(planes, idx)
     Ttot, Mp = planes.shape
     S, Cin = _index_table(idx, M, C, fold, 'window_stats_indexed')
-    dev = planes.device
-    mean, var = (torch.empty((C, Mp), dtype=torch.float64, device=dev) for _ in range(2))
-    scale, shift = (torch.empty((C, Mp), dtype=torch.float32, device=dev) for _ in range(2))
-    nbytes = int(_lib.lib().chebgcn_window_stats_indexed_workspace(S, M, C))
-    ws = _workspace(nbytes, dev, 'window_stats_indexed')
-    _lib.check(_launch('window_stats_indexed', 4.0 * S * Cin * Mp, 0.0, lambda: _lib.lib().chebgcn_window_stats_indexed(
-        _p(planes), Ttot, _p(idx), S, Cin, int(fold), _p(mean), _p(var), _p(scale), _p(shift), M, C, _p(ws), ws.numel(),
-        _stream())), 'window_stats_indexed')
-    return mean, var, scale, shift
+    lib = _lib.lib()
+    return _stats_launch('window_stats_indexed', planes, M, C, lib.chebgcn_window_stats_indexed_workspace(S, M, C),
+                         4.0 * S * Cin * Mp, lib.chebgcn_window_stats_indexed, _p(planes), Ttot, _p(idx), S, Cin, int(fold))
 
 
 def knn(planes, N, k, metric):

@@ -1,21 +1,47 @@
-"""Training on scans: ``WindowSet`` is a dataset that IS windows of scans -- the runs staged once as planes, the windows an
-int64 table of first rows, cut (and scaled) on the device batch by batch -- and ``Series`` carries ``stage_windows`` /
-``fit_series`` and is a base of ``models_gcn.base_model``.
+"""Training on scans: a ``WindowSet`` is a dataset that IS windows of scans -- the runs staged once as planes, the windows a
+device table, cut (and scaled) on the device batch by batch -- and ``Series`` carries ``stage_windows`` / ``fit_series`` /
+``stage_events`` / ``fit_events`` and is a base of ``models_gcn.base_model``.
 
 The reference builds ``[S, M, channel]`` on the host (utils.py: the windows cut with NumPy, stacked, an NDStandardScaler fitted
 on the stack, every split transformed): a time point is stored once per window that holds it, and the normalisation lives
 outside the model.  Here the series is stored once (``channel`` x less memory at stride 1), ``fit`` / ``predict`` /
 ``evaluate`` take the set wherever they take an array, the scaler's tables come from one pass over the series
-(chebgcn_window_stats) in exactly the form ``decode_series(scale=, shift=)`` takes, and moving a window a few TRs inside its
-trial is a new row table, not a new array.  Balancing unbalanced classes (the reference's ``sampling``) is a table as well:
-``balance_plan`` says which original windows every extra window is the mean of, and chebgcn_gather_windows_mix forms them
-batch by batch.  ``EventWindowSet`` is the set whose windows are lists of rows rather than one contiguous piece (the windows of
-an event design, ``events.match_events``): ``stage_windows(index=)`` / ``stage_events`` / ``fit_events``."""
+(chebgcn_window_stats) in exactly the form ``decode_series(scale=, shift=)`` takes.  Balancing unbalanced classes (the
+reference's ``sampling``) is a table as well: ``balance_plan`` says which original windows every extra window is the mean of,
+and the mix gathers form them batch by batch.
+
+``WindowSet`` holds what every set does -- tables and scaler, the owner check of ``gather``, ``balance``, ``materialise``,
+``nbytes`` -- and two kinds say how a window is cut.  ``StartWindowSet``: ``channel`` consecutive rows from an int64 table of
+first rows (``stage_windows(starts=)``, ``fit_series``); moving a window a few TRs inside its trial is a new row table, not a
+new array, and only this kind can be displaced.  ``EventWindowSet``: a list of rows per window, ``fold`` of them averaged per
+channel (the windows of an event design, ``events.match_events``: ``stage_windows(index=)`` / ``stage_events`` /
+``fit_events``)."""
 import numpy as np
 import torch
 
 from . import ops
-from .decode import window_starts          # noqa: F401  (the validation stage_windows shares with decode_series)
+from .decode import check_run, check_table, run_list, window_starts    # (the validation shared with decode_series)  # noqa: F401
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _both_or_neither(scale, shift, what):
+    if (scale is None) != (shift is None):
+        raise ValueError('%s: scale and shift come together (both or neither)' % what)
+
+
+def check_jitter(jitter, what=''):
+    if not _is_int(jitter) or jitter < 0:
+        raise ValueError('%sjitter must be an int >= 0, got %r' % (what, jitter))
+    return int(jitter)
+
+
+def check_seed(seed, name, what):
+    if not _is_int(seed) or not 0 <= seed < 2 ** 32:
+        raise ValueError('%s: %s must be an int in [0, 2**32), got %r' % (what, name, seed))
+    return int(seed)
 
 
 def row_table(run_lengths, run_starts, C):
@@ -38,11 +64,10 @@ def jitter_rows(rows, lo, hi, jitter, rng):
     ``np.random.RandomState``; the global NumPy stream is never touched), clipped to ``[lo, hi]`` so that the window stays
     inside its own run.  ``jitter = 0`` draws nothing and returns the rows."""
     rows = np.asarray(rows, np.int64)
-    if isinstance(jitter, bool) or not isinstance(jitter, (int, np.integer)) or jitter < 0:
-        raise ValueError('jitter must be an int >= 0, got %r' % (jitter,))
+    jitter = check_jitter(jitter)
     if jitter == 0:
         return rows.copy()
-    d = rng.randint(-int(jitter), int(jitter) + 1, size=rows.shape).astype(np.int64)
+    d = rng.randint(-jitter, jitter + 1, size=rows.shape).astype(np.int64)
     return np.clip(rows + d, lo, hi)
 
 
@@ -51,7 +76,7 @@ SAMPLING_MAX = 16              # sources of one synthetic window at most (the mi
 
 def check_sampling(sampling, what, least=0):
     """``sampling`` as an int in ``[least, SAMPLING_MAX]``; a bool, a non-int or a value outside is a ``ValueError``."""
-    if isinstance(sampling, bool) or not isinstance(sampling, (int, np.integer)) or not least <= sampling <= SAMPLING_MAX:
+    if not _is_int(sampling) or not least <= sampling <= SAMPLING_MAX:
         raise ValueError('%s: sampling must be an int in [%d, %d], got %r' % (what, least, SAMPLING_MAX, sampling))
     return int(sampling)
 
@@ -69,8 +94,7 @@ def check_balance_args(what, labels, S, sampling, seed, groups, nruns, resample)
     ``(labels int64 [S], one group id per run int64 [nruns])``."""
     check_sampling(sampling, what)
     labels = _int_vector(labels, 'labels', what, S)
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 32:
-        raise ValueError('%s: the sampling seed must be an int in [0, 2**32), got %r' % (what, seed))
+    check_seed(seed, 'the sampling seed', what)
     if not isinstance(resample, (bool, np.bool_)):
         raise ValueError('%s: resample must be a bool, got %r' % (what, resample))
     if groups is None:
@@ -134,43 +158,37 @@ def balance_plan(labels, groups, sampling, rng):
 
 
 class WindowSet(object):
-    """``S`` windows of ``channel`` time points over staged runs: ``planes`` ``[Ttot, Mp]`` (every run concatenated, the owner's
-    internal vertex order, zero pad), ``rows`` the int64 device table of first rows, optionally the ``[channel, Mp]`` device
+    """``S`` windows of ``channel`` time points over staged runs, the machinery both kinds of set share: ``planes``
+    ``[Ttot, Mp]`` (every run concatenated, the owner's internal vertex order, zero pad), optionally the ``[channel, Mp]`` device
     tables of a normalisation ``x * scale + shift``.  ``len()`` and ``shape == (S, M, channel)`` are those of the array it
     stands for.  After ``balance()`` the set stands for ``S' >= S`` windows: the originals and, behind them, the windows
-    that top up the small classes, each the mean of ``cnt`` source windows (``sources``)."""
+    that top up the small classes, each the mean of ``cnt`` source windows (``sources``).
 
-    def __init__(self, owner, planes, run_lengths, run_starts, M, C):
+    A kind names each original by an int64 KEY (``_keys()``: its first row, or its place in the index table) and says how keys
+    become windows on the host (``_originals``) and on the device (``_gather``, ``_stats``), and what the mix table of a plan
+    holds (``_mix_table``: ``[S', smax]`` keys)."""
+
+    def __init__(self, owner, planes, run_lengths, run_windows, M, C):
         self.owner, self.planes = owner, planes
         self.run_lengths = [int(t) for t in run_lengths]
-        self.run_starts = [np.asarray(s, np.int64) for s in run_starts]
-        self.base_rows, self.lo, self.hi = row_table(self.run_lengths, self.run_starts, C)
-        self.offsets = self.lo.copy()                   # run offset of every window: start = row - offset
-        self.rows_host = self.base_rows.copy()
-        self.rows = torch.as_tensor(self.rows_host).to(planes.device)
-        self.shape = (int(len(self.base_rows)), int(M), int(C))
+        self.run_windows = [int(n) for n in run_windows]                # windows of every run
+        offs = np.concatenate([[0], np.cumsum(self.run_lengths)[:-1]]).astype(np.int64)
+        self.offsets = np.repeat(offs, self.run_windows)                # run offset of every window: start = row - offset
+        self.shape = self.shape_base = (int(sum(self.run_windows)), int(M), int(C))   # shape_base: the originals', whatever plan
         self.tables = None              # (scale, shift) device [C, Mp], internal order
         self.scaler = None              # the same as NumPy [M, C] in the caller's order
         self.stats = None               # fit_scaler(): (mean, var) float64 [M, C] in the caller's order
-        self.jitter, self.jitter_rng = 0, None
         self.plan = None                # balance(): dict(src, cnt, labels, groups, sampling, resample, rng)
-        self.mix_rows_host = self.mix_rows = self.mix_cnt = None   # [S', smax] first rows of every source; device: int64 / int32
+        self.mix_rows_host = self.mix_rows = self.mix_cnt = None   # [S', smax] keys of every source; device: int64 / int32
 
     def __len__(self):
         return self.shape[0]
 
     @property
-    def starts(self):
-        """The start of every window inside its run, as currently in use (after a displacement: the displaced ones)."""
-        return self.rows_host - self.offsets
-
-    @property
     def nbytes(self):
-        """Device bytes of the set: planes, row table, tables."""
-        n = self.planes.numel() * 4 + self.rows.numel() * 8
-        if self.plan is not None:
-            n += self.mix_rows.numel() * 8 + self.mix_cnt.numel() * 4
-        return n + (sum(t.numel() * 4 for t in self.tables) if self.tables is not None else 0)
+        """Device bytes of the set: every device tensor it holds (planes, row or index table, mix tables) and the tables."""
+        held = [t for t in vars(self).values() if isinstance(t, torch.Tensor)] + list(self.tables or ())
+        return sum(t.numel() * t.element_size() for t in held)
 
     # ---------------------------------------------------------------- tables
 
@@ -188,8 +206,7 @@ class WindowSet(object):
     def set_tables(self, scale, shift):
         """Install a normalisation: ``scale`` / ``shift`` ``[M, channel]`` in the caller's vertex order (what ``fit_scaler``
         and ``decode_series`` use), both or neither."""
-        if (scale is None) != (shift is None):
-            raise ValueError('stage_windows: scale and shift come together (both or neither)')
+        _both_or_neither(scale, shift, 'stage_windows')
         if scale is None:
             self.tables = self.scaler = None
             return self
@@ -204,13 +221,13 @@ class WindowSet(object):
         return self
 
     def fit_scaler(self):
-        """Mean and population variance of every (vertex, channel) over the set's windows, none of them built
-        (chebgcn_window_stats), installed on the set as ``scale = 1/std``, ``shift = -mean/std`` (a zero variance: 1 and
-        ``-mean``, like sklearn's StandardScaler).  Returns ``(scale, shift)`` as ``[M, channel]`` float32 in the caller's
-        vertex order; ``stats`` keeps ``(mean, var)`` in float64.  Always computed on the undisplaced windows."""
-        S, M, C = self.shape
-        rows = torch.as_tensor(self.base_rows).to(self.planes.device)
-        mean, var, scale, shift = ops.window_stats(self.planes, rows, M, C)
+        """Mean and population variance of every (vertex, channel) over the set's ``S`` ORIGINAL windows, none of them built
+        (chebgcn_window_stats; of windows that are lists of rows chebgcn_window_stats_indexed, over the folded values as the
+        gather forms them in float32), installed on the set as ``scale = 1/std``, ``shift = -mean/std`` (a zero variance: 1
+        and ``-mean``, like sklearn's StandardScaler).  Returns ``(scale, shift)`` as ``[M, channel]`` float32 in the caller's
+        vertex order; ``stats`` keeps ``(mean, var)`` in float64.  Always computed on the undisplaced windows, whatever plan
+        is installed."""
+        mean, var, scale, shift = self._stats()
         self.tables = (scale, shift)
         self.scaler = (self._caller_order(scale), self._caller_order(shift))
         self.stats = (self._caller_order(mean), self._caller_order(var))
@@ -220,32 +237,28 @@ class WindowSet(object):
 
     def gather(self, model, idx, out=None):
         """The windows ``idx`` (int32 device indices; None: all) as ``InternalPlanes`` ``[B, channel, Mp]`` of ``model``
-        (chebgcn_gather_windows; of a balanced set chebgcn_gather_windows_mix), straight into ``out`` when that has the
-        shape."""
+        (chebgcn_gather_windows, of a balanced set chebgcn_gather_windows_mix; of windows that are lists of rows
+        chebgcn_gather_windows_indexed either way), straight into ``out`` when that has the shape."""
         if model is not self.owner and not model._same_order(self.owner):
             raise ValueError('this WindowSet is staged in the internal vertex order of another model')
-        S, M, C = self.shape
         scale, shift = self.tables if self.tables is not None else (None, None)
-        if self.plan is not None:
-            return model.as_internal(ops.gather_windows_mix(self.planes, self.mix_rows, self.mix_cnt, M, C, idx, scale, shift,
-                                                            out, sources=self.plan['cnt'].mean()))
-        return model.as_internal(ops.gather_windows(self.planes, self.rows, M, C, idx, scale, shift, out))
+        sources = None if self.plan is None else self.plan['cnt'].mean()
+        return model.as_internal(self._gather(idx, scale, shift, out, sources))
 
     def materialise(self):
-        """The ``[S, M, channel]`` float32 array the set stands for, in the caller's vertex order, as the model sees it (the
-        tables applied, in float32 like the kernel: a rounded product, then a rounded sum).  Of a balanced set: the ``S'``
-        windows, the sources added in float32 in their order and divided once by ``cnt``, then the tables."""
-        S, M, C = self.shape
+        """The ``[S, M, channel]`` float32 array the set stands for, in the caller's vertex order, as the model sees it: every
+        level in float32 like the kernels -- the originals as their kind cuts them, of a balanced set the ``S'`` windows, the
+        sources added in their order and divided once by ``cnt``, then the tables (a rounded product, then a rounded sum)."""
         series = self._caller_order(self.planes)                                        # [M, Ttot]
         if self.plan is None:
-            x = series[:, self.rows_host[:, None] + np.arange(C)[None, :]]             # [M, S, C]
+            x = self._originals(series, self._keys())                                   # [M, S, C]
         else:
-            cnt = self.plan['cnt']
-            x = series[:, self.mix_rows_host[:, 0, None] + np.arange(C)[None, :]]
-            for j in range(1, self.mix_rows_host.shape[1]):
+            tab, cnt = self.mix_rows_host, self.plan['cnt']
+            x = self._originals(series, tab[:, 0])
+            for j in range(1, tab.shape[1]):
                 more = cnt > j
                 if more.any():
-                    x[:, more] = x[:, more] + series[:, self.mix_rows_host[more, j, None] + np.arange(C)[None, :]]
+                    x[:, more] = x[:, more] + self._originals(series, tab[more, j])
             mixed = cnt > 1
             x[:, mixed] = x[:, mixed] / cnt[mixed].astype(np.float32)[None, :, None]
         x = np.ascontiguousarray(x.transpose(1, 0, 2))
@@ -253,82 +266,46 @@ class WindowSet(object):
             x = (x * self.scaler[0][None]).astype(np.float32) + self.scaler[1][None]
         return x.astype(np.float32, copy=False)
 
-    # ---------------------------------------------------------------- displaced starts
-
-    def set_rows(self, rows_host):
-        """Upload another row table (same length) into the device table in place."""
-        self.rows_host = np.asarray(rows_host, np.int64).copy()
-        self.rows.copy_(torch.as_tensor(self.rows_host))
-        if self.plan is not None:
-            self._upload_mix(None)
-
-    def refill(self):
-        """Called by ``fit`` each time it refills its index deque (once per epoch): with ``jitter > 0`` every window's start
-        is redrawn around its undisplaced one and the table uploaded, once.  Returns the starts now in use.
-
-        Of a balanced set the originals are displaced exactly as without the plan (the same ``jitter_rng`` draws, the same
-        rows); then, out of the balancing stream, the plan is redrawn when ``resample`` is set and, with ``jitter > 0``, every
-        source entry of the extra windows gets a displacement of its own, clipped to the source's run; the ``[S', smax]``
-        table is uploaded once."""
-        if self.plan is None:
-            if self.jitter:
-                self.set_rows(jitter_rows(self.base_rows, self.lo, self.hi, self.jitter, self.jitter_rng))
-            return self.starts
-        plan = self.plan
-        changed = False
-        if self.jitter:
-            self.rows_host = jitter_rows(self.base_rows, self.lo, self.hi, self.jitter, self.jitter_rng)
-            changed = True
-        if plan['resample']:
-            src, cnt, _ = balance_plan(plan['labels'], plan['groups'], plan['sampling'], plan['rng'])
-            assert np.array_equal(cnt, plan['cnt'])                    # the counts depend on the labels alone
-            plan['src'] = src
-            changed = True
-        extra = None
-        if self.jitter:
-            e = plan['src'][self.shape_base[0]:]
-            extra = jitter_rows(self.base_rows[e], self.lo[e], self.hi[e], self.jitter, plan['rng'])
-        if changed:
-            self._upload_mix(extra)
-        return self.starts
-
-    def reset_rows(self):
-        self.jitter, self.jitter_rng = 0, None
-        if not np.array_equal(self.rows_host, self.base_rows):
-            self.set_rows(self.base_rows)
-        elif self.plan is not None:
-            self._upload_mix(None)
-
     # ---------------------------------------------------------------- balanced classes
-
-    @property
-    def shape_base(self):
-        """``(S, M, channel)`` of the originals, whatever plan is installed."""
-        return (int(len(self.base_rows)),) + self.shape[1:]
 
     @property
     def sources(self):
         """``(src, cnt)`` of the plan in use (``balance_plan``), None without one."""
         return None if self.plan is None else (self.plan['src'], self.plan['cnt'])
 
-    def _upload_mix(self, extra_rows):
-        """The ``[S', smax]`` table of first rows: the originals at their rows in use (every entry), the extra windows at
-        ``extra_rows`` (None: their sources' undisplaced rows); one upload."""
-        src = self.plan['src']
-        S = len(self.base_rows)
-        tab = np.empty(src.shape, np.int64)
-        tab[:S] = self.rows_host[:, None]
-        tab[S:] = self.base_rows[src[S:]] if extra_rows is None else extra_rows
-        self.mix_rows_host = tab
+    def _upload_mix(self, extra=None):
+        """The ``[S', smax]`` mix table of the plan in use (``_mix_table``; ``extra``: rows of the extra windows that are not
+        their sources' undisplaced ones), in one upload."""
+        tab = self.mix_rows_host = np.ascontiguousarray(self._mix_table(extra))
         if self.mix_rows is None or tuple(self.mix_rows.shape) != tab.shape:
             self.mix_rows = torch.as_tensor(tab).to(self.planes.device)
             self.mix_cnt = torch.as_tensor(self.plan['cnt']).to(self.planes.device)
         else:
             self.mix_rows.copy_(torch.as_tensor(tab))
 
+    def _redraw(self):
+        """The plan drawn again out of its stream where ``resample`` asks for it; says whether it was."""
+        plan = self.plan
+        if plan is None or not plan['resample']:
+            return False
+        src, cnt, _ = balance_plan(plan['labels'], plan['groups'], plan['sampling'], plan['rng'])
+        assert np.array_equal(cnt, plan['cnt'])                        # the counts depend on the labels alone
+        plan['src'] = src
+        return True
+
+    def refill(self):
+        """Called by ``fit`` each time it refills its index deque (once per epoch): redraws the plan when ``resample`` is
+        set, one upload.  Returns the starts (rows) in use."""
+        if self._redraw():
+            self._upload_mix()
+        return self.starts
+
+    def _plan_removed(self):
+        pass
+
     def balance(self, labels, sampling, seed=0, groups=None, resample=False):
         """Top up the small classes (``balance_plan``): installs the plan and returns the ``S'`` labels of the balanced set.
-        Afterwards ``len()`` and ``shape[0]`` are ``S'``, ``gather()`` runs chebgcn_gather_windows_mix, ``materialise()``
+        Afterwards ``len()`` and ``shape[0]`` are ``S'``, ``gather()`` forms the means on the device, ``materialise()``
         returns the ``S'`` windows and ``sources`` is ``(src, cnt)``; ``starts`` stays the ``S`` originals' starts.
 
         ``labels``: one int per original window.  ``sampling``: 1 re-draws windows of a small class, ``n >= 2`` (at most 16)
@@ -338,48 +315,120 @@ class WindowSet(object):
         global NumPy stream is never touched).  ``resample``: ``refill()`` redraws the plan (once per epoch of ``fit``);
         the labels do not change with it.  Arguments are refused (``ValueError``) before anything touches the device."""
         sampling = check_sampling(sampling, 'balance')
-        S = len(self.base_rows)
         if sampling == 0:
             if self.plan is not None:
                 self.plan = self.mix_rows_host = self.mix_rows = self.mix_cnt = None
-                self.shape = (S,) + self.shape[1:]
-                self.rows.copy_(torch.as_tensor(self.rows_host))      # (displaced originals were uploaded in the mix table only)
+                self.shape = self.shape_base
+                self._plan_removed()
             return None if labels is None else np.asarray(labels).copy()
-        labels, run_groups = check_balance_args('balance', labels, S, sampling, seed, groups, len(self.run_starts), resample)
-        groups = np.repeat(run_groups, [len(s) for s in self.run_starts])
+        labels, run_groups = check_balance_args('balance', labels, self.shape_base[0], sampling, seed, groups,
+                                                len(self.run_windows), resample)
+        groups = np.repeat(run_groups, self.run_windows)
         rng = np.random.RandomState(int(seed))
         src, cnt, new_labels = balance_plan(labels, groups, sampling, rng)
         self.plan = dict(src=src, cnt=cnt, labels=labels, groups=groups, sampling=sampling, resample=bool(resample), rng=rng)
         self.shape = (int(len(src)),) + self.shape[1:]
         self.mix_rows = self.mix_cnt = None
-        self._upload_mix(None)
+        self._upload_mix()
         return new_labels
 
 
+class StartWindowSet(WindowSet):
+    """The ``WindowSet`` of ``stage_windows(starts=)``: a window is ``channel`` CONSECUTIVE rows, ``rows`` the int64 device
+    table of first rows, and the only kind that can be displaced (``jitter``: every window moved a few TRs inside its run, a
+    new row table, not a new array).  The mix table of a plan holds the first rows of every source."""
+
+    def __init__(self, owner, planes, run_lengths, run_starts, M, C):
+        run_starts = [np.asarray(s, np.int64) for s in run_starts]
+        WindowSet.__init__(self, owner, planes, run_lengths, [len(s) for s in run_starts], M, C)
+        self.base_rows, self.lo, self.hi = row_table(self.run_lengths, run_starts, C)
+        self.rows_host = self.base_rows.copy()
+        self.rows = torch.as_tensor(self.rows_host).to(planes.device)
+        self.jitter, self.jitter_rng = 0, None
+
+    @property
+    def starts(self):
+        """The start of every window inside its run, as currently in use (after a displacement: the displaced ones)."""
+        return self.rows_host - self.offsets
+
+    def _keys(self):
+        return self.rows_host
+
+    def _originals(self, series, rows):
+        return series[:, rows[:, None] + np.arange(self.shape[2])[None, :]]
+
+    def _stats(self):
+        rows = torch.as_tensor(self.base_rows).to(self.planes.device)
+        return ops.window_stats(self.planes, rows, *self.shape[1:])
+
+    def _gather(self, idx, scale, shift, out, sources):
+        M, C = self.shape[1:]
+        if self.plan is not None:
+            return ops.gather_windows_mix(self.planes, self.mix_rows, self.mix_cnt, M, C, idx, scale, shift, out, sources=sources)
+        return ops.gather_windows(self.planes, self.rows, M, C, idx, scale, shift, out)
+
+    def _mix_table(self, extra):
+        """The originals at their rows in use (every entry), the extra windows at ``extra`` (None: their sources'
+        undisplaced rows)."""
+        src, S = self.plan['src'], self.shape_base[0]
+        tab = np.empty(src.shape, np.int64)
+        tab[:S] = self.rows_host[:, None]
+        tab[S:] = self.base_rows[src[S:]] if extra is None else extra
+        return tab
+
+    def _plan_removed(self):
+        self.rows.copy_(torch.as_tensor(self.rows_host))              # (displaced originals were uploaded in the mix table only)
+
+    # ---------------------------------------------------------------- displaced starts
+
+    def set_rows(self, rows_host):
+        """Upload another row table (same length) into the device table in place."""
+        self.rows_host = np.asarray(rows_host, np.int64).copy()
+        self.rows.copy_(torch.as_tensor(self.rows_host))
+        if self.plan is not None:
+            self._upload_mix()
+
+    def refill(self):
+        """``WindowSet.refill``; with ``jitter > 0`` every window's start is redrawn around its undisplaced one and the table
+        uploaded, once.  Returns the starts now in use.
+
+        Of a balanced set the originals are displaced exactly as without the plan (the same ``jitter_rng`` draws, the same
+        rows); then, out of the balancing stream, the plan is redrawn when ``resample`` is set and, with ``jitter > 0``, every
+        source entry of the extra windows gets a displacement of its own, clipped to the source's run; the ``[S', smax]``
+        table is uploaded once."""
+        if not self.jitter:
+            return WindowSet.refill(self)
+        rows = jitter_rows(self.base_rows, self.lo, self.hi, self.jitter, self.jitter_rng)
+        if self.plan is None:
+            self.set_rows(rows)
+            return self.starts
+        self.rows_host = rows
+        self._redraw()
+        e = self.plan['src'][self.shape_base[0]:]
+        self._upload_mix(jitter_rows(self.base_rows[e], self.lo[e], self.hi[e], self.jitter, self.plan['rng']))
+        return self.starts
+
+    def reset_rows(self):
+        self.jitter, self.jitter_rng = 0, None
+        if not np.array_equal(self.rows_host, self.base_rows):
+            self.set_rows(self.base_rows)
+        elif self.plan is not None:
+            self._upload_mix()
+
+
 class EventWindowSet(WindowSet):
-    """A ``WindowSet`` whose windows are LISTS of rows (``stage_windows(index=, fold=)``, ``stage_events``): ``index`` is the
+    """The ``WindowSet`` whose windows are LISTS of rows (``stage_windows(index=, fold=)``, ``stage_events``): ``index`` is the
     int64 device table ``[S, channel * fold]`` of global rows, channel ``c`` of window ``s`` the float32 mean of the rows
-    ``index[s, f * channel + c]`` (chebgcn_gather_windows_indexed).  Everything a ``WindowSet`` does but displacement:
-    ``jitter`` raises a ``ValueError`` -- a displaced window leaves its trial.  ``balance()`` needs no row table of its own:
-    the plan's sources are indices into ``index``."""
+    ``index[s, f * channel + c]`` (chebgcn_gather_windows_indexed).  It cannot be displaced: ``jitter`` and ``set_rows`` raise
+    a ``ValueError`` -- a displaced window leaves its trial.  The mix table of a plan holds the plan's sources themselves:
+    they are places in ``index``."""
 
     def __init__(self, owner, planes, run_lengths, run_index, M, C, fold):
-        self.owner, self.planes = owner, planes
-        self.run_lengths = [int(t) for t in run_lengths]
-        self.run_index = [np.asarray(i, np.int64) for i in run_index]
-        self.run_starts = self.run_index                # (balance(): one entry per run, as many items as the run has windows)
+        run_index = [np.asarray(i, np.int64) for i in run_index]
+        WindowSet.__init__(self, owner, planes, run_lengths, [len(i) for i in run_index], M, C)
         self.fold = int(fold)
-        offs = np.concatenate([[0], np.cumsum(self.run_lengths)[:-1]]).astype(np.int64)
-        self.index_host = np.ascontiguousarray(np.concatenate([i + o for i, o in zip(self.run_index, offs)]), np.int64)
-        self.offsets = np.repeat(offs, [len(i) for i in self.run_index])
-        self.base_rows = self.rows_host = self.index_host[:, 0]    # (len(): the number of originals)
+        self.index_host = np.ascontiguousarray(np.concatenate(run_index) + self.offsets[:, None], np.int64)
         self.index = torch.as_tensor(self.index_host).to(planes.device)
-        self.shape = (int(len(self.index_host)), int(M), int(C))
-        self.tables = self.scaler = self.stats = None
-        self.plan = None
-        self.mix_src = self.mix_cnt = None              # balance(): [S', smax] int64 indices into index / int32, device
-
-    jitter_rng = None
 
     @property
     def jitter(self):
@@ -387,124 +436,55 @@ class EventWindowSet(WindowSet):
 
     @jitter.setter
     def jitter(self, j):
-        if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or j != 0:
+        if not _is_int(j) or j != 0:
             raise ValueError('jitter: the windows of an event design cannot be displaced (a displaced window leaves its '
                              'trial), got jitter = %r' % (j,))
+
+    def set_rows(self, rows_host):
+        raise ValueError('set_rows: the windows of an event design cannot be displaced')
 
     @property
     def starts(self):
         """The rows every window reads, inside its run: ``[S, channel * fold]``."""
         return self.index_host - self.offsets[:, None]
 
-    @property
-    def nbytes(self):
-        n = self.planes.numel() * 4 + self.index.numel() * 8
-        if self.plan is not None:
-            n += self.mix_src.numel() * 8 + self.mix_cnt.numel() * 4
-        return n + (sum(t.numel() * 4 for t in self.tables) if self.tables is not None else 0)
+    def _keys(self):
+        return np.arange(self.shape_base[0])
 
-    def fit_scaler(self):
-        """``WindowSet.fit_scaler`` over the folded values of the ``S`` ORIGINAL windows, as the gather forms them in float32
-        (chebgcn_window_stats_indexed), whatever plan is installed."""
-        S, M, C = self.shape
-        mean, var, scale, shift = ops.window_stats_indexed(self.planes, self.index, M, C, self.fold)
-        self.tables = (scale, shift)
-        self.scaler = (self._caller_order(scale), self._caller_order(shift))
-        self.stats = (self._caller_order(mean), self._caller_order(var))
-        return self.scaler
-
-    def gather(self, model, idx, out=None):
-        """``WindowSet.gather`` on chebgcn_gather_windows_indexed (of a balanced set: with the plan's sources)."""
-        if model is not self.owner and not model._same_order(self.owner):
-            raise ValueError('this WindowSet is staged in the internal vertex order of another model')
-        S, M, C = self.shape
-        scale, shift = self.tables if self.tables is not None else (None, None)
-        sources = None if self.plan is None else self.plan['cnt'].mean()
-        return model.as_internal(ops.gather_windows_indexed(self.planes, self.index, M, C, self.fold, self.mix_src, self.mix_cnt,
-                                                            idx, scale, shift, out, sources=sources))
-
-    def materialise(self):
-        """``WindowSet.materialise``: every level in float32 like the kernel -- the ``fold`` pieces added in ascending order
-        and divided once, the sources likewise, then the tables."""
-        S, M, C = self.shape
-        series = self._caller_order(self.planes)                                        # [M, Ttot]
-        piece = series[:, self.index_host[:, :C]]                                       # [M, S, C]
+    def _originals(self, series, which):
+        """The ``fold`` pieces added in ascending order and divided once."""
+        C, idx = self.shape[2], self.index_host[which]
+        piece = series[:, idx[:, :C]]                                                   # [M, S, C]
         for f in range(1, self.fold):
-            piece = piece + series[:, self.index_host[:, f * C:(f + 1) * C]]
-        if self.fold > 1:
-            piece = piece / np.float32(self.fold)
-        if self.plan is None:
-            x = piece
-        else:
-            src, cnt = self.plan['src'], self.plan['cnt']
-            x = piece[:, src[:, 0]]
-            for j in range(1, src.shape[1]):
-                more = cnt > j
-                if more.any():
-                    x[:, more] = x[:, more] + piece[:, src[more, j]]
-            mixed = cnt > 1
-            x[:, mixed] = x[:, mixed] / cnt[mixed].astype(np.float32)[None, :, None]
-        x = np.ascontiguousarray(x.transpose(1, 0, 2))
-        if self.scaler is not None:
-            x = (x * self.scaler[0][None]).astype(np.float32) + self.scaler[1][None]
-        return x.astype(np.float32, copy=False)
+            piece = piece + series[:, idx[:, f * C:(f + 1) * C]]
+        return piece / np.float32(self.fold) if self.fold > 1 else piece
 
-    def set_rows(self, rows_host):
-        raise ValueError('set_rows: the windows of an event design cannot be displaced')
+    def _stats(self):
+        return ops.window_stats_indexed(self.planes, self.index, *self.shape[1:], self.fold)
 
-    def refill(self):
-        """Called by ``fit`` once per epoch: redraws the plan when ``resample`` is set.  Returns the rows in use."""
-        plan = self.plan
-        if plan is not None and plan['resample']:
-            src, cnt, _ = balance_plan(plan['labels'], plan['groups'], plan['sampling'], plan['rng'])
-            assert np.array_equal(cnt, plan['cnt'])
-            plan['src'] = src
-            self._upload_mix(None)
-        return self.starts
+    def _gather(self, idx, scale, shift, out, sources):
+        M, C = self.shape[1:]
+        return ops.gather_windows_indexed(self.planes, self.index, M, C, self.fold, self.mix_rows, self.mix_cnt, idx, scale,
+                                          shift, out, sources=sources)
 
-    def reset_rows(self):
-        pass
-
-    def _upload_mix(self, extra_rows):
-        src = self.plan['src']
-        if self.mix_src is None or tuple(self.mix_src.shape) != src.shape:
-            self.mix_src = torch.as_tensor(np.ascontiguousarray(src)).to(self.planes.device)
-            self.mix_cnt = torch.as_tensor(self.plan['cnt']).to(self.planes.device)
-        else:
-            self.mix_src.copy_(torch.as_tensor(np.ascontiguousarray(src)))
-
-    def balance(self, labels, sampling, seed=0, groups=None, resample=False):
-        """``WindowSet.balance``; the sources are indices into the set's own table."""
-        sampling = check_sampling(sampling, 'balance')
-        S = len(self.index_host)
-        if sampling == 0:
-            self.plan = self.mix_src = self.mix_cnt = None
-            self.shape = (S,) + self.shape[1:]
-            return None if labels is None else np.asarray(labels).copy()
-        labels, run_groups = check_balance_args('balance', labels, S, sampling, seed, groups, len(self.run_index), resample)
-        groups = np.repeat(run_groups, [len(i) for i in self.run_index])
-        rng = np.random.RandomState(int(seed))
-        src, cnt, new_labels = balance_plan(labels, groups, sampling, rng)
-        self.plan = dict(src=src, cnt=cnt, labels=labels, groups=groups, sampling=sampling, resample=bool(resample), rng=rng)
-        self.shape = (int(len(src)),) + self.shape[1:]
-        self.mix_src = self.mix_cnt = None
-        self._upload_mix(None)
-        return new_labels
+    def _mix_table(self, extra):
+        return self.plan['src']
 
 
 class Series(object):
-    """``stage_windows`` / ``fit_series`` of ``base_model``.  Uses the model's ``_decode_args`` / ``_stage_series`` /
-    ``_scale_tables`` (decode.Decode), its sizes and ``fit``."""
+    """``stage_windows`` / ``fit_series`` / ``stage_events`` / ``fit_events`` of ``base_model``.  Uses the model's
+    ``_decode_args`` / ``_stage_series`` / ``_scale_tables`` (decode.Decode), its sizes and ``fit``."""
 
     window_scaler = None            # (scale, shift) [M, channel] fitted by fit_series(standardize=True), else None
 
     def _window_args(self, series, starts, scale, shift, what):
         runs, run_starts, _, scale, shift, _ = self._decode_args(series, starts, 1, scale, shift, 'auto', None, 'logits', what)
-        if (scale is None) != (shift is None):
-            raise ValueError('%s: scale and shift come together (both or neither)' % what)
+        _both_or_neither(scale, shift, what)
         return runs, run_starts, scale, shift
 
-    def _stage_window_set(self, runs, run_starts, scale, shift, what):
+    def _stage_set(self, what, kind, runs, cut, scale=None, shift=None, **more):
+        """The runs staged as planes and the set ``kind`` (a ``WindowSet`` class) over them; ``cut``: per run the starts or
+        the index table of its windows."""
         if self.device.type != 'cuda':
             raise RuntimeError('%s: the model has no device to run on (%s)' % (what, self.device))
         M0, C = int(self._M0), int(self.channel)
@@ -514,32 +494,18 @@ class Series(object):
         for r, T in zip(runs, lengths):
             self._stage_series(r, out=planes[off:off + T])
             off += T
-        return WindowSet(self, planes, lengths, run_starts, M0, C).set_tables(scale, shift)
+        return kind(self, planes, lengths, cut, M0, C, **more).set_tables(scale, shift)
 
     def _check_runs(self, series, what):
-        """``series`` as a list of ``[T, M]`` runs (the checks of ``_decode_args`` that do not involve starts)."""
-        runs = list(series) if isinstance(series, (list, tuple)) else [series]
-        if not runs:
-            raise ValueError('%s: series is an empty list' % what)
-        M0 = int(self._M0)
-        out = []
-        for r in runs:
-            if not isinstance(r, torch.Tensor):
-                r = np.asarray(r)
-                if not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
-                    raise ValueError('%s: series must be numeric, got %s' % (what, r.dtype))
-            shape = tuple(int(d) for d in r.shape)
-            if len(shape) != 2 or shape[1] != M0 or shape[0] < 1:
-                raise ValueError('%s: series must be [T, %d] (time points x vertices), got %s' % (what, M0, shape))
-            out.append(r)
-        return out
+        """``series`` as a list of ``[T, M]`` runs of at least one time point each (``decode.check_run``)."""
+        return [check_run(r, int(self._M0), what, least=1) for r in run_list(series, what)]
 
     def _index_args(self, series, index, fold, scale, shift, what):
         """The arguments of ``stage_windows(index=)``, refused or returned as ``(runs, one int64 [S_r, Cin] table per run,
         fold, scale, shift)``."""
         runs = self._check_runs(series, what)
         M0, C = int(self._M0), int(self.channel)
-        if isinstance(fold, bool) or not isinstance(fold, (int, np.integer)) or not 1 <= fold <= 16:
+        if not _is_int(fold) or not 1 <= fold <= 16:
             raise ValueError('%s: fold must be an int in [1, 16], got %r' % (what, fold))
         many = isinstance(series, (list, tuple))
         tables = list(index) if (many and isinstance(index, (list, tuple))) else [index]
@@ -558,29 +524,8 @@ class Series(object):
                 raise ValueError('%s: every row of an index table must satisfy 0 <= row < T = %d; got %d ... %d'
                                  % (what, T, a.min(), a.max()))
             out.append(a)
-
-        def table(v, name):
-            if v is None:
-                return None
-            a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32)
-            if a.shape != (M0, C):
-                raise ValueError('%s: %s must be [%d, %d] (vertices x channels), got %s' % (what, name, M0, C, a.shape))
-            return a
-        if (scale is None) != (shift is None):
-            raise ValueError('%s: scale and shift come together (both or neither)' % what)
-        return runs, out, int(fold), table(scale, 'scale'), table(shift, 'shift')
-
-    def _stage_event_set(self, runs, run_index, fold, scale, shift, what):
-        if self.device.type != 'cuda':
-            raise RuntimeError('%s: the model has no device to run on (%s)' % (what, self.device))
-        M0, C = int(self._M0), int(self.channel)
-        lengths = [int(r.shape[0]) for r in runs]
-        planes = torch.empty((sum(lengths), ops.plane_stride(M0)), dtype=torch.float32, device=self.device)
-        off = 0
-        for r, T in zip(runs, lengths):
-            self._stage_series(r, out=planes[off:off + T])
-            off += T
-        return EventWindowSet(self, planes, lengths, run_index, M0, C, fold).set_tables(scale, shift)
+        _both_or_neither(scale, shift, what)
+        return runs, out, int(fold), check_table(scale, 'scale', M0, C, what), check_table(shift, 'shift', M0, C, what)
 
     def stage_windows(self, series, starts=None, scale=None, shift=None, index=None, fold=1):
         """A ``WindowSet``: the windows ``x[v][c] = series[start + c][v]`` of one ``[T, M]`` run or a list of runs (``starts``:
@@ -592,15 +537,16 @@ class Series(object):
         ``index`` (instead of ``starts``): one int table ``[S_r, channel * fold]`` per run -- a window is a LIST of rows of its
         run, ``x[v][c] = mean_f series[index[s, f * channel + c]][v]`` (rows may repeat, decrease or skip; ``fold`` in
         [1, 16]).  Returns an ``EventWindowSet`` (``events.match_events`` produces such tables; ``stage_events``)."""
+        what = 'stage_windows'
         if index is not None:
             if starts is not None:
                 raise ValueError('stage_windows: starts and index are mutually exclusive')
-            runs, run_index, fold, scale, shift = self._index_args(series, index, fold, scale, shift, 'stage_windows')
-            return self._stage_event_set(runs, run_index, fold, scale, shift, 'stage_windows')
+            runs, run_index, fold, scale, shift = self._index_args(series, index, fold, scale, shift, what)
+            return self._stage_set(what, EventWindowSet, runs, run_index, scale, shift, fold=fold)
         if not (fold == 1 and not isinstance(fold, bool)):
             raise ValueError('stage_windows: fold goes with index (windows cut by starts have fold = 1), got %r' % (fold,))
-        runs, run_starts, scale, shift = self._window_args(series, starts, scale, shift, 'stage_windows')
-        return self._stage_window_set(runs, run_starts, scale, shift, 'stage_windows')
+        runs, run_starts, scale, shift = self._window_args(series, starts, scale, shift, what)
+        return self._stage_set(what, StartWindowSet, runs, run_starts, scale, shift)
 
     def _event_args(self, series, label_runs, target_name, block_dura, match_kw, what):
         """``stage_events``' arguments matched and checked: ``(runs kept, their index tables, fold, labels int64 [S], kept)``."""
@@ -637,7 +583,7 @@ class Series(object):
         model's ``channel`` must equal ``block_dura // TRstep`` (``ValueError``)."""
         runs, run_index, fold, labels, _ = self._event_args(series, label_runs, target_name, block_dura, match_kw,
                                                             'stage_events')
-        return self._stage_event_set(runs, run_index, fold, None, None, 'stage_events'), labels
+        return self._stage_set('stage_events', EventWindowSet, runs, run_index, fold=fold), labels
 
     def fit_events(self, train_series, train_label_runs, val_series, val_label_runs, target_name, block_dura, standardize=False,
                    sampling=0, seed=0, groups=None, best_checkpoint_dir=None, **match_kw):
@@ -656,17 +602,25 @@ class Series(object):
                 n_given = len(train_series) if isinstance(train_series, (list, tuple)) else 1
                 groups = _int_vector(groups, 'the sampling groups (one id per run)', what, n_given)[tr[4]]
             check_balance_args(what, train_labels, len(train_labels), sampling, seed, groups, len(tr[0]), False)
-        ws_train = self._stage_event_set(tr[0], tr[1], tr[2], None, None, what)
-        ws_val = self._stage_event_set(va[0], va[1], va[2], None, None, what)
+        ws_train = self._stage_set(what, EventWindowSet, tr[0], tr[1], fold=tr[2])
+        ws_val = self._stage_set(what, EventWindowSet, va[0], va[1], fold=va[2])
+        return self._fit_sets(ws_train, train_labels, ws_val, val_labels, standardize, best_checkpoint_dir,
+                              (sampling, seed, groups))
+
+    def _fit_sets(self, ws_train, train_labels, ws_val, val_labels, standardize, best_checkpoint_dir, plan):
+        """The tail of ``fit_series`` / ``fit_events``: the scaler fitted on the training originals and shared, the classes
+        balanced (``plan``: ``balance``'s arguments from ``sampling`` on), ``fit``; the training set left as it was staged."""
         self.window_scaler = None
         if standardize:
             self.window_scaler = ws_train.fit_scaler()
             ws_val.share_tables(ws_train)
         try:
-            if sampling:
-                train_labels = ws_train.balance(train_labels, sampling, seed, groups)
+            if plan[0]:
+                train_labels = ws_train.balance(train_labels, *plan)
             return self.fit(ws_train, train_labels, ws_val, val_labels, best_checkpoint_dir)
         finally:
+            if ws_train.jitter:
+                ws_train.reset_rows()
             ws_train.balance(None, 0)
 
     def fit_series(self, train_series, train_starts, train_labels, val_series, val_starts, val_labels, standardize=False,
@@ -695,10 +649,8 @@ class Series(object):
           before.  Under ``dist.DataParallel`` the ranks' ``S'`` may differ (they depend on each shard's labels); ``fit``'s
           check of equal training-set sizes then fires -- balance shards that come out equal, or balance before sharding."""
         what = 'fit_series'
-        if isinstance(jitter, bool) or not isinstance(jitter, (int, np.integer)) or jitter < 0:
-            raise ValueError('fit_series: jitter must be an int >= 0, got %r' % (jitter,))
-        if isinstance(jitter_seed, bool) or not isinstance(jitter_seed, (int, np.integer)) or not 0 <= jitter_seed < 2 ** 32:
-            raise ValueError('fit_series: jitter_seed must be an int in [0, 2**32), got %r' % (jitter_seed,))
+        check_jitter(jitter, 'fit_series: ')
+        check_seed(jitter_seed, 'jitter_seed', what)
         tr = self._window_args(train_series, train_starts, None, None, what)
         va = self._window_args(val_series, val_starts, None, None, what)
         for (runs, run_starts, _, _), labels, name in ((tr, train_labels, 'train'), (va, val_labels, 'val')):
@@ -709,20 +661,11 @@ class Series(object):
         if check_sampling(sampling, what):
             train_labels, _ = check_balance_args(what, train_labels, len(train_labels), sampling, sampling_seed,
                                                  sampling_groups, len(tr[0]), resample)
-        ws_train = self._stage_window_set(tr[0], tr[1], None, None, what)
-        ws_val = self._stage_window_set(va[0], va[1], None, None, what)
-        self.window_scaler = None
-        if standardize:
-            self.window_scaler = ws_train.fit_scaler()
-            ws_val.share_tables(ws_train)
+        ws_train = self._stage_set(what, StartWindowSet, tr[0], tr[1])
+        ws_val = self._stage_set(what, StartWindowSet, va[0], va[1])
         ws_train.jitter, ws_train.jitter_rng = int(jitter), np.random.RandomState(int(jitter_seed))
-        try:
-            if sampling:
-                train_labels = ws_train.balance(train_labels, sampling, sampling_seed, sampling_groups, resample)
-            return self.fit(ws_train, train_labels, ws_val, val_labels, best_checkpoint_dir)
-        finally:
-            ws_train.reset_rows()
-            ws_train.balance(None, 0)
+        return self._fit_sets(ws_train, train_labels, ws_val, val_labels, standardize, best_checkpoint_dir,
+                              (sampling, sampling_seed, sampling_groups, resample))
 
     # ---------------------------------------------------------------- checkpoints
 
