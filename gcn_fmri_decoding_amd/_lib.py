@@ -117,6 +117,10 @@ SIGNATURES = {
     'chebgcn_occlusion_rows': (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _p]),
     'chebgcn_occlusion_score': (_i, [_p, _i64, _i, _i, _i, _i, _p, _i, _p, _p, _p]),
     'chebgcn_occlusion_class_sums': (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    'chebgcn_shapley_supported': (_i, [_i]),
+    'chebgcn_shapley_rows': (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p]),
+    'chebgcn_shapley_score': (_i, [_p, _i64, _i, _i, _i, _i, _i, _p, _i, _p, _p]),
+    'chebgcn_shapley_reduce': (_i, [_p, _p, _i, _i, _i, _p, _p]),
     'chebgcn_gradcam_weights': (_i, [_p, _i, _i, _i, _p, _p]),
     'chebgcn_gradcam_map': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i64, _p]),
     'chebgcn_gather_windows': (_i, [_p, _i64, _p, _p, _p, _p, _p, _i, _i, _i, _p]),

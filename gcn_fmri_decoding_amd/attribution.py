@@ -1,12 +1,24 @@
-"""Attribution maps of a model: ``saliency`` (input gradients), ``occlusion`` (score drops under masked vertex groups) and
-``gradcam`` (class activation maps at a conv layer), each with its per-class mean ``*_maps``.  ``Attribution`` carries the six
-methods and is a base of ``models_gcn.base_model``; ``Pass`` is what the model's layers see while one of them runs."""
+"""Attribution maps of a model: ``saliency`` (input gradients), ``occlusion`` (score drops under masked vertex groups),
+``shapley`` (sampled Shapley values of vertex groups) and ``gradcam`` (class activation maps at a conv layer), each with its
+per-class mean ``*_maps``.  ``Attribution`` carries the eight methods and is a base of ``models_gcn.base_model``; ``Pass`` is
+what the model's layers see while one of them runs."""
 import contextlib
 
 import numpy as np
 import torch
 
 from . import _lib, ops
+
+
+def shapley_permutations(G, P, antithetic, seed):
+    """The permutations of a ``shapley`` call: int32 ``[P, G]``, row p the order in which permutation p reveals the G groups.
+    Drawn one after the other by ``np.random.RandomState(seed).permutation(G)`` (NumPy's global stream is not touched); with
+    ``antithetic`` only the even rows are drawn and row 2i + 1 is row 2i reversed."""
+    rs = np.random.RandomState(seed)
+    perms = np.empty((P, G), np.int32)
+    for p in range(P):
+        perms[p] = perms[p - 1, ::-1] if antithetic and p % 2 else rs.permutation(G)
+    return perms
 
 
 class Pass(object):
@@ -236,35 +248,45 @@ class Attribution(object):
         device."""
         return self._class_means(*self._occlusion_run(data, 'label', labels, score, groups, baseline, batch_size))
 
-    def _occlusion_args(self, data, target, labels, score, groups, baseline, batch_size):
-        """Checks every argument of ``occlusion`` / ``occlusion_maps`` before any device work: its own (groups, the channel
-        limit of the occlusion kernels), then the shared ones (``_pass_args``); returns those of ``_pass_args``, then the group
-        of each internal position as int32 ``[Mp]`` on the device (-1 on the pad) and G."""
+    def _group_args(self, who, groups, outside):
+        """Checks ``groups`` of ``occlusion`` / ``shapley`` (``who`` names the caller in the messages, ``outside`` says what -1
+        means to it); returns the group of each vertex in the caller's order as int64 ``[M]`` and G."""
         M = int(self._M0)
         if groups is None:
             g = np.arange(M, dtype=np.int64)
         else:
             a = np.asarray(groups)
             if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer) or a.shape != (M,):
-                raise ValueError('occlusion: groups must be an int array of shape [%d], got %s %s' % (M, a.dtype, a.shape))
+                raise ValueError(who + ': groups must be an int array of shape [%d], got %s %s' % (M, a.dtype, a.shape))
             g = a.astype(np.int64)
             if g.min() < -1:
-                raise ValueError('occlusion: groups must lie in [-1, G) (-1: never occluded); got %d' % g.min())
+                raise ValueError(who + ': groups must lie in [-1, G) (-1: %s); got %d' % (outside, g.min()))
             if g.max() < 0:
-                raise ValueError('occlusion: groups holds no group (every entry is -1)')
+                raise ValueError(who + ': groups holds no group (every entry is -1)')
             empty = np.flatnonzero(np.bincount(g[g >= 0], minlength=int(g.max()) + 1) == 0)
             if len(empty):
-                raise ValueError('occlusion: groups must use every id in [0, %d); %d of them occur nowhere (first %d)'
+                raise ValueError(who + ': groups must use every id in [0, %d); %d of them occur nowhere (first %d)'
                                  % (int(g.max()) + 1, len(empty), empty[0]))
-        G = int(g.max()) + 1
+        return g, int(g.max()) + 1
+
+    def _group_table(self, g):
+        """The groups ``g`` of ``_group_args`` as the kernels take them: the group of each internal position, int32 ``[Mp]`` on
+        the device, -1 on the pad."""
+        M = int(self._M0)
+        gid = np.full(ops.plane_stride(M), -1, np.int32)
+        gid[:M] = g[self._order] if self._order is not None else g
+        return torch.as_tensor(gid).to(self.device)
+
+    def _occlusion_args(self, data, target, labels, score, groups, baseline, batch_size):
+        """Checks every argument of ``occlusion`` / ``occlusion_maps`` before any device work: its own (groups, the channel
+        limit of the occlusion kernels), then the shared ones (``_pass_args``); returns those of ``_pass_args``, then the group
+        of each internal position as int32 ``[Mp]`` on the device (-1 on the pad) and G."""
+        g, G = self._group_args('occlusion', groups, 'never occluded')
         if not _lib.lib().chebgcn_occlusion_supported(int(self.channel)):
             raise ValueError('occlusion: %d channels are more than the occlusion kernels serve (chebgcn_occlusion_supported)'
                              % int(self.channel))
         shared = self._pass_args('occlusion', data, target, labels, score, batch_size, baseline)
-        internal = g[self._order] if self._order is not None else g
-        gid = np.full(ops.plane_stride(M), -1, np.int32)
-        gid[:M] = internal
-        return shared + (torch.as_tensor(gid).to(self.device), G)
+        return shared + (self._group_table(g), G)
 
     def _occlusion_run(self, data, target, labels, score, groups, baseline, batch_size):
         """The passes of ``occlusion`` / ``occlusion_maps``: per pass of ``bs`` rows, the rows in plane storage, the forward
@@ -292,6 +314,106 @@ class Attribution(object):
                                           want_grad=False)
                 ops.occlusion_score(logits, r0, G, cls, score, ref, drop)
         return drop, cls, labels
+
+    # ---------------------------------------------------------------- Shapley maps
+
+    def shapley(self, data, target='predicted', score='logit', groups=None, baseline=None, permutations=16, antithetic=True,
+                seed=0, batch_size=None, labels=None):
+        """How each window's class score is shared among groups of its vertices: sampled Shapley values.  ``data``:
+        ``[S, M, channel]`` as for ``predict`` (NumPy, or a tensor from ``stage()``), in the caller's vertex order.  Returns
+        ``(phi, target)``: float32 ``[S, G]`` and the int64 class ``[S]`` each window was scored for.
+
+        A permutation of the G groups defines G + 1 rows: row j holds the window's own values on the vertices of the
+        permutation's first j groups (and of group -1) and the baseline elsewhere -- row 0 is the baseline window, row G the
+        window itself.  ``phi[w, g]`` is the mean over the permutations of ``s_c(row pos(g) + 1) - s_c(row pos(g))``, ``pos(g)``
+        the position of g in the permutation.  Every window's row sums to ``s_c(x_w) - s_c(baseline window)``, whatever the
+        permutations; where ``occlusion`` shows a drop near zero for each of several redundant groups, these share what
+        they carry together.
+
+        * ``groups``, ``baseline``, ``target``, ``labels``, ``score``: as for ``occlusion`` (a vertex of group -1 always keeps
+          its own value).  At most 4096 groups: use parcels or networks, not vertices.
+        * ``permutations``: P in [1, 4096], drawn by ``shapley_permutations(G, P, antithetic, seed)`` and shared by every
+          window of the call; ``antithetic``: permutation 2i + 1 is the reverse of permutation 2i (an odd P leaves the last one
+          unpaired); ``seed``: an int in [0, 2**32).  A call is bit-reproducible.
+        * Dropout is off.  ``batch_size`` (default the model's): forward rows of one pass.  Rows are (window, permutation,
+          prefix) triples in that order: a pass may hold part of a window or several windows, and the last one is zero-padded
+          like ``predict``.  A call costs ``S * P * (G + 1)`` forward rows, and ``S`` more under ``'predicted'`` (the class is
+          decided by one plain forward over the windows first).
+
+        Only the inference kernels run, plus four small ones (chebgcn_shapley_rows / _score / _reduce, chebgcn_saliency_seed);
+        nothing the model keeps is written."""
+        phi, cls, _ = self._shapley_run(data, target, labels, score, groups, baseline, permutations, antithetic, seed, batch_size)
+        return phi.cpu().numpy(), cls.cpu().numpy()
+
+    def shapley_maps(self, data, labels, score='logit', groups=None, baseline=None, permutations=16, antithetic=True, seed=0,
+                     batch_size=None):
+        """Per-class mean Shapley values: window w (target = its label) adds its ``shapley`` row to the sum of class
+        ``labels[w]``.  Returns ``(maps, counts)``: float64 ``[C, G]`` (C = M[-1]; the mean, zero for a class without windows)
+        and int64 ``[C]``.  The sums run on the device in float64, windows in order; the per-window table never leaves the
+        device."""
+        return self._class_means(*self._shapley_run(data, 'label', labels, score, groups, baseline, permutations, antithetic,
+                                                    seed, batch_size))
+
+    def _shapley_args(self, data, target, labels, score, groups, baseline, permutations, antithetic, seed, batch_size):
+        """Checks every argument of ``shapley`` / ``shapley_maps`` before any device work: its own (permutations, antithetic,
+        seed), the groups (as ``occlusion`` checks them, then the limits of the Shapley kernels), then the shared ones
+        (``_pass_args``); returns those of ``_pass_args``, then the group of each internal position as int32 ``[Mp]`` on the
+        device (-1 on the pad), G and the rank table int32 ``[P, G]`` on the device (the inverse of the permutations)."""
+        def whole(v, lo, hi):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and lo <= v < hi
+        if not whole(permutations, 1, 4097):
+            raise ValueError('shapley: permutations must be an int in [1, 4096], got %r' % (permutations,))
+        if not isinstance(antithetic, (bool, np.bool_)):
+            raise ValueError('shapley: antithetic must be True or False, got %r' % (antithetic,))
+        if not whole(seed, 0, 2 ** 32):
+            raise ValueError('shapley: seed must be an int in [0, 2**32), got %r' % (seed,))
+        g, G = self._group_args('shapley', groups, 'outside the game')
+        P = int(permutations)
+        if G > 4096:
+            raise ValueError('shapley: groups holds %d groups, more than the 4096 it serves (use parcels, not vertices)' % G)
+        if P * (G + 1) >= 2 ** 31:
+            raise ValueError('shapley: permutations * (G + 1) = %d rows per window, the limit is 2**31 - 1' % (P * (G + 1)))
+        if not _lib.lib().chebgcn_shapley_supported(int(self.channel)):
+            raise ValueError('shapley: %d channels are more than the Shapley kernels serve (chebgcn_shapley_supported)'
+                             % int(self.channel))
+        shared = self._pass_args('shapley', data, target, labels, score, batch_size, baseline)
+        perms = shapley_permutations(G, P, bool(antithetic), int(seed))
+        rank = np.empty_like(perms)
+        np.put_along_axis(rank, perms, np.arange(G, dtype=np.int32)[None, :], axis=1)
+        return shared + (self._group_table(g), G, torch.as_tensor(rank).to(self.device))
+
+    def _shapley_run(self, data, target, labels, score, groups, baseline, permutations, antithetic, seed, batch_size):
+        """The passes of ``shapley`` / ``shapley_maps``.  Under 'predicted', first one plain forward over the windows for their
+        classes.  Then, per pass of ``bs`` consecutive rows: the rows in plane storage, the forward (no autograd, the variables
+        detached, the head on the library's kernels), the scores into the table ``[windows, P, G + 1]``; one reduction once the
+        table is complete.  A table above ``ops.SHAPLEY_TABLE_BYTES`` is run over as many windows at a time as fit.  Nothing
+        waits for the device.  Returns (phi float32 ``[S, G]``, the classes int64 ``[S]``, labels), on the device."""
+        S, targets, labels, bs, base, gid, G, rank = self._shapley_args(data, target, labels, score, groups, baseline,
+                                                                        permutations, antithetic, seed, batch_size)
+        data_dev = self.stage(data)
+        M = data_dev.shape[1]
+        cls = self._class_vector(S, targets)
+        P = rank.shape[0]
+        per = P * (G + 1)
+        order = self._order_dev
+        phi = torch.empty((S, G), dtype=torch.float32, device=self.device)
+        chunk = min(S, max(1, ops.SHAPLEY_TABLE_BYTES // (4 * per)))
+        table = torch.empty((chunk, P, G + 1), dtype=torch.float32, device=self.device)
+        with self._attribution_pass(), torch.no_grad():
+            if targets is None:
+                windows = torch.arange(S, dtype=torch.int32, device=self.device)
+                for begin in range(0, S, bs):
+                    end = min(begin + bs, S)
+                    logits = self._inference_storage(self.as_internal(self._gather_padded(data_dev, windows[begin:end], bs)), 1)
+                    ops.saliency_seed(logits, None, 1, end - begin, score, cls_out=cls[begin:end], want_grad=False)
+            for w0 in range(0, S, chunk):
+                w1 = min(w0 + chunk, S)
+                for r0 in range(0, (w1 - w0) * per, bs):
+                    x = ops.shapley_rows(data_dev[w0:w1], order, gid, rank, base, r0, bs, M)
+                    logits = self._inference_storage(self.as_internal(x), 1)
+                    ops.shapley_score(logits, r0, cls[w0:w1], score, table[:w1 - w0])
+                ops.shapley_reduce(table[:w1 - w0], rank, phi[w0:w1])
+        return phi, cls, labels
 
     # ---------------------------------------------------------------- Grad-CAM maps
 

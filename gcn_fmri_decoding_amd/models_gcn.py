@@ -92,8 +92,8 @@ class InternalPlanes(object):
 
 class base_model(Attribution, Decode, Series):
     """Counterpart of ``base_model`` (:18-355): run-time interface + variable helpers.  The attribution maps (``saliency``,
-    ``occlusion``, ``gradcam`` and their ``*_maps``) come from ``attribution.Attribution``, ``decode_series`` from ``decode.Decode``,
-    ``stage_windows`` / ``fit_series`` from ``series.Series``."""
+    ``occlusion``, ``shapley``, ``gradcam`` and their ``*_maps``) come from ``attribution.Attribution``, ``decode_series`` from
+    ``decode.Decode``, ``stage_windows`` / ``fit_series`` from ``series.Series``."""
 
     def __init__(self, config=None):
         self.regularizers = []          # names of L2-regularised variables (:345, :353)
@@ -129,8 +129,9 @@ class base_model(Attribution, Decode, Series):
         # (shadow / (1 - 0.9^t): the first value is the loss).  Reporting only; the default follows TF >= 1.0, set
         # ``ema_zero_debias = True`` (or CHEBGCN_EMA_ZERO_DEBIAS=1) for the 0.12 reading.  Unverifiable here (no TensorFlow).
         self.ema_zero_debias = os.environ.get('CHEBGCN_EMA_ZERO_DEBIAS', '0') not in ('0', '', 'false', 'False')
-        # inside saliency() / occlusion() / gradcam(): the attribution.Pass the layers read -- they see their variables without
-        # gradient (no weight, bias-gradient or optimizer work), and the head runs on the library's FC kernels (no vendor GEMM)
+        # inside saliency() / occlusion() / shapley() / gradcam(): the attribution.Pass the layers read -- they see their variables
+        # without gradient (no weight, bias-gradient or optimizer work), and the head runs on the library's FC kernels (no vendor
+        # GEMM)
         self._pass = None
         # inside decode_series' shared path: the decode.Windows the first conv layer contracts its windows out of
         self._windows = None
@@ -1847,6 +1848,12 @@ class model_perf(object):
         restore from ``ckp_path``.  ``target_name`` is accepted for symmetry with ``predict`` and not used.  Returns
         ``(maps, counts)``."""
         return s._maps('occlusion_maps', ckp_path, data, labels, batch_size, kw)
+
+    def shapley_maps(s, ckp_path, data, labels, target_name=None, batch_size=128, **kw):
+        """Per-class mean Shapley values (``base_model.shapley_maps``; ``kw``: its keywords) of the model ``predict`` would
+        restore from ``ckp_path``.  ``target_name`` is accepted for symmetry with ``predict`` and not used.  Returns
+        ``(maps, counts)``."""
+        return s._maps('shapley_maps', ckp_path, data, labels, batch_size, kw)
 
     def gradcam_maps(s, ckp_path, data, labels, target_name=None, batch_size=128, **kw):
         """Per-class mean Grad-CAM maps (``base_model.gradcam_maps``; ``kw``: its keywords) of the model ``predict`` would

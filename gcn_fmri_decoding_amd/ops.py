@@ -1719,6 +1719,65 @@ def occlusion_class_sums(drop, cls, acc):
 
 
 # ------------------------------------------------------------------------------------
+# Shapley maps (base_model.shapley): the kernels of csrc/shapley.hip around the inference layers
+# ------------------------------------------------------------------------------------
+
+# The score table [windows, P, G + 1] of a shapley call stays on the device until its windows are reduced; a call whose table
+# would be larger than this is run over as many windows at a time as fit (one window at the least).
+SHAPLEY_TABLE_BYTES = 64 << 20
+
+
+def shapley_rows(data, order, gid, rank, baseline, r0, R, M):
+    """Plane storage ``[R, F, Mp]`` of rows ``r0 .. r0 + R - 1`` of a Shapley run (chebgcn_shapley_rows): with ``rank`` int32
+    device ``[P, G]`` (``rank[p, g]`` the position of group g in permutation p), row r is window ``r // (P (G + 1))`` of
+    ``data`` with its own values on the groups whose rank in permutation ``(r // (G + 1)) % P`` is below ``r % (G + 1)`` and on
+    the positions of no group, and ``baseline`` elsewhere; ``order``, ``gid``: as for ``occlusion_rows``; zero rows past the
+    last window."""
+    _require_cuda(data, order, gid, rank, baseline)
+    S, N, F = data.shape
+    if rank.dtype != torch.int32 or rank.dim() != 2 or not rank.is_contiguous():
+        raise ValueError('shapley_rows: rank must be a contiguous int32 [P, G] tensor')
+    P, G = rank.shape
+    Mp = plane_stride(M)
+    out = torch.empty((int(R), F, Mp), dtype=torch.float32, device=data.device)
+    # the rows written; per workgroup of 16 rows its window's tile (and the baseline's) read once
+    nbytes = 4.0 * (F * (R * Mp + (int(R) + 15) // 16 * N * (1 + (baseline is not None))) + M)
+    _lib.check(_launch('shapley_rows', nbytes, 0.0, lambda: _lib.lib().chebgcn_shapley_rows(
+        _p(data), _p(order), _p(gid), _p(rank), _p(baseline), _p(out), int(r0), int(R), S, P, G, N, int(M), F, _stream())),
+        'shapley_rows')
+    return out
+
+
+def shapley_score(logits, r0, cls, score, table):
+    """The scores of the rows whose logits ``[R, C]`` a pass from row ``r0`` formed, written to ``table`` (float32
+    ``[S, P, G + 1]``, flat index = the row) for the windows' classes ``cls`` (int64 ``[S]``; chebgcn_shapley_score)."""
+    _require_cuda(logits, cls, table)
+    z = logits.detach().contiguous()
+    R, C = z.shape
+    if not (table.dim() == 3 and table.is_contiguous() and table.dtype == torch.float32 and cls.dtype == torch.int64
+            and cls.is_contiguous() and cls.numel() == table.shape[0]):
+        raise ValueError('shapley_score: table float32 [S, P, G + 1] and cls int64 [S]')
+    S, P, G1 = table.shape
+    _lib.check(_launch('shapley_score', 4.0 * R * (C + 1), 0.0, lambda: _lib.lib().chebgcn_shapley_score(
+        _p(z), int(r0), R, S, P, G1 - 1, C, _p(cls), SCORES[score], _p(table), _stream())), 'shapley_score')
+
+
+def shapley_reduce(table, rank, phi):
+    """``phi[w, g]`` (float32 ``[S, G]``) = the mean over the permutations of group g's marginal contribution in the score
+    ``table`` (float32 ``[S, P, G + 1]``), summed in float64 in the order of p (chebgcn_shapley_reduce)."""
+    _require_cuda(table, rank, phi)
+    S, P, G1 = table.shape
+    if not (table.is_contiguous() and table.dtype == torch.float32 and rank.dtype == torch.int32 and rank.is_contiguous()
+            and tuple(rank.shape) == (P, G1 - 1) and phi.dtype == torch.float32 and phi.is_contiguous()
+            and tuple(phi.shape) == (S, G1 - 1)):
+        raise ValueError('shapley_reduce: table float32 [S, P, G + 1], rank int32 [P, G], phi float32 [S, G]')
+    G = G1 - 1
+    _lib.check(_launch('shapley_reduce', 4.0 * (2 * S * P * G + P * G + S * G), 0.0, lambda: _lib.lib().chebgcn_shapley_reduce(
+        _p(table), _p(rank), S, P, G, _p(phi), _stream())), 'shapley_reduce')
+    return phi
+
+
+# ------------------------------------------------------------------------------------
 # Grad-CAM maps (base_model.gradcam): the two kernels of csrc/gradcam.hip behind the pass that stops at a layer
 # ------------------------------------------------------------------------------------
 

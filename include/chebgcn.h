@@ -563,6 +563,35 @@ int chebgcn_occlusion_score(const float* logits, int64_t r0, int R, int S, int G
 int chebgcn_occlusion_class_sums(const float* drop, const int64_t* cls, int S, int G, int ncls, double* acc,
                                  chebgcn_stream stream);
 
+/* ---- Shapley maps: sampled Shapley values of vertex groups (models_gcn.base_model.shapley) --------------------------------
+ * A run has P permutations of the G groups, the same for every window, given as their inverse: rank: int32 [P][G] (device),
+ * rank[p][g] = the position of group g in permutation p.  Rows are (window, permutation, prefix length) triples in that order,
+ * P (G + 1) per window: row r is window w = r / (P (G + 1)), permutation p = (r / (G + 1)) % P, prefix length j = r % (G + 1);
+ * it holds the window's own values on the first j groups of permutation p and the baseline on the others (j = 0: the baseline
+ * window, j = G: the window itself).  P (G + 1) < 2^31.  Between rows and score runs the library's own forward.
+ *
+ * rows: rows r0 .. r0 + R - 1 in plane storage.  x, perm, baseline, out: as chebgcn_occlusion_rows; gid: int32 [M] (or longer)
+ *   group of each internal position, a value outside [0, G) = outside the game (the position always keeps its own value):
+ *     out[r - r0][f][i] = gid[i] outside [0, G) || rank[p_r][gid[i]] < j_r ? x[w_r][perm[i]][f] : baseline[perm[i]][f]
+ *   the pad [M, Mp) and the rows r >= S P (G + 1) are 0.  R <= 65535.  A workgroup writes 16 consecutive rows of 64 positions
+ *   and reads a window's tile once for all of them that belong to that window.
+ * score: logits [R][C] of rows r0 .. r0 + R - 1 -> table[r] = s, the score table float32 [S][P][G + 1] that stays on the device
+ *   for the run; s and cls as chebgcn_occlusion_score (a class outside [0, C) gives NaN).  Rows r >= S P (G + 1) write nothing.
+ *   THE CLASS RULE: cls[w] must be final before the first row of window w is scored.  Under 'predicted' the caller therefore
+ *   runs one plain forward over the windows first (chebgcn_saliency_seed's argmax); the row order is never rearranged.
+ * reduce: once every row of the S windows is scored,
+ *     phi[w][g] = (1/P) sum_p ( table[w][p][rank[p][g] + 1] - table[w][p][rank[p][g]] )        (float32 [S][G])
+ *   the differences and their sum in float64, p ascending, one float64 division, one rounding to float32; one thread per
+ *   (w, g).  A rank entry outside [0, G) gives NaN.  The per-class sums of phi are chebgcn_occlusion_class_sums.
+ * Fixed-order sums throughout; no atomics. */
+/* chebgcn_shapley_supported: 1 where the row kernel serves F channels (its LDS tiles: F <= 125), else 0.  Host only. */
+int chebgcn_shapley_supported(int F);
+int chebgcn_shapley_rows(const float* x, const int32_t* perm, const int32_t* gid, const int32_t* rank, const float* baseline,
+                         float* out, int64_t r0, int R, int S, int P, int G, int N, int M, int F, chebgcn_stream stream);
+int chebgcn_shapley_score(const float* logits, int64_t r0, int R, int S, int P, int G, int C, const int64_t* cls, int score,
+                          float* table, chebgcn_stream stream);
+int chebgcn_shapley_reduce(const float* table, const int32_t* rank, int S, int P, int G, float* phi, chebgcn_stream stream);
+
 /* ---- Grad-CAM maps: class activation maps at a conv layer (models_gcn.base_model.gradcam) --------------------------------
  * A: the layer's activation, G = ds/dA its gradient (the library's input-gradient kernels, stopped at the layer); both plane
  * storage [>= nw][F][Mp(N)] over the N vertices of the layer's level in its internal order, 16-byte aligned.  Only the real
