@@ -130,6 +130,8 @@ SIGNATURES = {
     'chebgcn_gather_windows_indexed': (_i, [_p, _i64, _p, _i64, _i, _i, _p, _p, _i64, _i, _p, _p, _p, _p, _i, _i, _i, _p]),
     'chebgcn_window_stats_indexed_workspace': (C.c_size_t, [_i64, _i, _i]),
     'chebgcn_window_stats_indexed': (_i, [_p, _i64, _p, _i64, _i, _i, _p, _p, _p, _p, _i, _i, _p, C.c_size_t, _p]),
+    'chebgcn_window_drop': (_i, [_p, _p, _i, _i, _i, _i, C.c_uint32, C.c_uint32, _p, _p, _p, _f, _p]),
+    'chebgcn_gather_windows_reflect': (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     'chebgcn_knn_workspace': (C.c_size_t, [_i, _i, _i]),
     'chebgcn_knn': (_i, [_p, _i, _i, _i, _i, _p, _p, _p, C.c_size_t, _p]),
     'chebgcn_series_normalise': (_i, [_p, _i64, _p, _i, _i, _f, _p, _p]),

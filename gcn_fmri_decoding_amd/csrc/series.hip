@@ -15,44 +15,21 @@
 //            d = series[u][m] - series[0][m] (a vertex that is constant over time has d = 0 and variance exactly 0; no
 //            cancellation against a large mean), in ascending u inside a chunk of rows, chunks added in index order: no float
 //            atomics, the result does not depend on the order of rows[] and is bit-identical from run to run.
-#include "common.h"
+#include "gather_piece.h"
 
 namespace chebgcn {
 
-constexpr int GW_T = 256;               // threads of the gather
-constexpr int GW_U = 4;                 // 16-byte pieces per thread
 constexpr int WS_T = 256;               // threads of the statistics kernels
 constexpr int WS_CG = 8;                // channels a statistics workgroup accumulates (registers: 2 * 2 * WS_CG doubles)
 constexpr int WS_ROWS = 512;            // series rows of one chunk (a chunk's partials are 2 * C * Mp doubles)
 
-__device__ __forceinline__ long long clamp_row(long long r, long long last) { return r < 0 ? 0 : (r > last ? last : r); }
-
-// ---- what the gathers do to a piece (16 bytes of a window): float32 adds and divisions of one rounding each, then the epilogue ---
+// ---- what the gathers do to a piece (16 bytes of a window): float32 adds and divisions of one rounding each, then the epilogue
+// (finish_piece, gather_piece.h) ---
 __device__ __forceinline__ float4 add4(float4 a, float4 b) {
     return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
 }
 __device__ __forceinline__ float4 div4(float4 a, float d) {
     return make_float4(__fdiv_rn(a.x, d), __fdiv_rn(a.y, d), __fdiv_rn(a.z, d), __fdiv_rn(a.w, d));
-}
-
-// the tables (a rounded product, then a rounded sum: never one fma), the zero pad (the pad of an output plane is zero whatever
-// the operands hold there), the store
-template <bool Tables>
-__device__ __forceinline__ void finish_piece(float4 r, float4 a, float4 s, int q, int M, float4* __restrict__ dst) {
-    if (Tables) {
-        r.x = __fadd_rn(__fmul_rn(r.x, a.x), s.x);
-        r.y = __fadd_rn(__fmul_rn(r.y, a.y), s.y);
-        r.z = __fadd_rn(__fmul_rn(r.z, a.z), s.z);
-        r.w = __fadd_rn(__fmul_rn(r.w, a.w), s.w);
-    }
-    const int m = 4 * q;
-    if (m + 3 >= M) {
-        if (m >= M) r.x = 0.f;
-        if (m + 1 >= M) r.y = 0.f;
-        if (m + 2 >= M) r.z = 0.f;
-        r.w = 0.f;
-    }
-    *dst = r;
 }
 
 // block (piece of the window's C * Mp/4 float4s, window b)
@@ -453,32 +430,6 @@ static inline size_t ws_count_bytes(int64_t Ttot, int C) {
     return (((size_t)Ttot + C - 1 + WS_CG + 4) * sizeof(int) + 15) & ~(size_t)15;
 }
 static inline int ws_chunks(int64_t Ttot) { return (int)((Ttot + WS_ROWS - 1) / WS_ROWS); }
-
-// the checks the three gather entries share (name: the entry's, as its messages spell it), and their grid
-static int gather_args(const char* name, const void* series, const void* table, const void* out, const float* scale,
-                       const float* shift, int B, int M, int C) {
-    CG_REQUIRE(series && table && out, "%s: NULL argument", name);
-    CG_REQUIRE((scale != nullptr) == (shift != nullptr), "%s: scale and shift come together (both or neither)", name);
-    CG_REQUIRE(B > 0 && B <= 65535 && M > 0 && C > 0 && (int64_t)C * plane_stride(M) / 4 <= 0x7fffffffLL / 2,
-               "%s: bad shape (B = %d, M = %d, C = %d)", name, B, M, C);
-    CG_REQUIRE((((uintptr_t)series | (uintptr_t)out | (uintptr_t)scale | (uintptr_t)shift) & 15) == 0,
-               "%s: series, tables and out must be 16-byte aligned", name);
-    return CHEBGCN_OK;
-}
-static inline dim3 gather_grid(int CMq, int B) { return dim3((CMq + GW_T * GW_U - 1) / (GW_T * GW_U), B); }
-
-// KERNEL<true> with tables, KERNEL<false> without, under its dispatch name; needs scale, grid and stream_ in scope
-#define CG_LAUNCH_GATHER(KERNEL, ...)                                                                                 \
-    do {                                                                                                              \
-        if (scale) {                                                                                                  \
-            note_dispatch(#KERNEL "<tables>");                                                                        \
-            hipLaunchKernelGGL(KERNEL<true>, grid, dim3(GW_T), 0, (hipStream_t)stream_, __VA_ARGS__);                 \
-        } else {                                                                                                      \
-            note_dispatch(#KERNEL "<plain>");                                                                         \
-            hipLaunchKernelGGL(KERNEL<false>, grid, dim3(GW_T), 0, (hipStream_t)stream_, __VA_ARGS__);                \
-        }                                                                                                             \
-        CG_HIP(hipGetLastError());                                                                                    \
-    } while (0)
 
 // the last launch of both statistics entries: the chunks' partials into the four tables
 static int stats_finish(const float* series, const double* part, int G, int64_t S, int M, int Mp, int C, double* mean,

@@ -326,6 +326,10 @@ class base_model(Attribution, Decode, Series):
                         self.fit_log.setdefault('starts', []).append(starts.copy())
                         if train_dev.sources is not None:       # (fit_series(sampling=): this epoch's plan)
                             self.fit_log.setdefault('sources', []).append(tuple(a.copy() for a in train_dev.sources))
+                        if train_dev.aug is not None:           # (fit_series(augment=): this epoch's refill number and shifts)
+                            shifts = train_dev.aug['shifts']
+                            self.fit_log.setdefault('augment', []).append(
+                                (train_dev.aug['refill'], None if shifts is None else shifts.copy()))
                 pool_dev = torch.as_tensor(np.asarray(indices, np.int32)).to(self.device)
                 pool_labels = labels_dev[pool_dev.long()]
                 pool_at = 0
@@ -333,7 +337,8 @@ class base_model(Attribution, Decode, Series):
             idx_dev = pool_dev[pool_at:pool_at + self.batch_size]
             batch_labels = pool_labels[pool_at:pool_at + self.batch_size]
             pool_at += self.batch_size
-            x = self._gather(train_dev, idx_dev, out=self.step_inputs()[0])      # (straight into the captured step's input buffer)
+            # (straight into the captured step's input buffer, outside the capture; of an augmented set the dropout as well)
+            x = self._gather(train_dev, idx_dev, out=self.step_inputs()[0])
             learning_rate, loss_average = self.train_step(x, batch_labels)
             if self.record_fit:
                 self.fit_log['idx'].append(np.asarray(idx))

@@ -375,6 +375,46 @@ def window_stats_indexed(planes, idx, M, C, fold=1):
                          4.0 * S * Cin * Mp, lib.chebgcn_window_stats_indexed, _p(planes), Ttot, _p(idx), S, Cin, int(fold))
 
 
+def gather_windows_reflect(planes, rows, tshift, M, C, sample=None, scale=None, shift=None, out=None):
+    """``gather_windows`` with a time shift per window (chebgcn_gather_windows_reflect): ``tshift`` int32 device table indexed
+    like ``rows`` (None: no shift), channel ``c`` of window ``w`` is plane ``rho(c + tshift[w])`` of the window's ``C`` planes,
+    ``rho`` the symmetric reflection (``series.reflect_channels``); the tables are those of the output channel."""
+    _require_cuda(planes, rows, tshift, sample, scale, shift, out)
+    Ttot, Mp = planes.shape
+    if tshift is not None and (tshift.dtype != torch.int32 or tshift.dim() != 1 or tshift.numel() != rows.numel()
+                               or not tshift.is_contiguous()):
+        raise _lib.ChebgcnError('gather_windows_reflect: tshift must be contiguous int32, one entry per row of the table')
+    B, out = _windows_out(out, rows.numel(), sample, C, planes)
+    _lib.check(_launch('gather_windows_reflect', 8.0 * B * C * Mp, 0.0, lambda: _lib.lib().chebgcn_gather_windows_reflect(
+        _p(planes), Ttot, _p(rows), _p(tshift), _p(sample), _p(scale), _p(shift), _p(out), B, M, C, _stream())),
+        'gather_windows_reflect')
+    return out
+
+
+def window_drop(x, win, M, D, seed, refill, pos=None, scale=None, shift=None, drop_value=1.0):
+    """Vertex dropout in place on a gathered batch (chebgcn_window_drop): ``x`` contiguous storage [B, C, Mp], ``win`` int32
+    device [B] the augmented-set index of every row, ``D`` draws per window out of the ``M`` vertices
+    (``series.drop_vertices(seed, refill, win[b], D, M)``), ``pos`` int32 device [M] caller vertex -> position in ``x`` (None:
+    the identity).  The drawn vertices take ``drop_value`` in every channel, seen through ``scale`` / ``shift`` [C, Mp] where
+    given (a rounded product, then a rounded sum).  Writes ``B * D * C`` floats and nothing else; returns ``x``."""
+    _require_cuda(x, win, pos, scale, shift)
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[2] != plane_stride(M):
+        raise _lib.ChebgcnError('window_drop: x must be contiguous float32 plane storage [B, C, Mp(M = %d)], got %s %s'
+                                % (M, x.dtype, tuple(x.shape)))
+    B, C, Mp = x.shape
+    if win.dtype != torch.int32 or win.dim() != 1 or win.numel() != B or not win.is_contiguous():
+        raise _lib.ChebgcnError('window_drop: win must be contiguous int32 [B = %d]' % B)
+    if pos is not None and (pos.dtype != torch.int32 or pos.dim() != 1 or pos.numel() != M or not pos.is_contiguous()):
+        raise _lib.ChebgcnError('window_drop: pos must be contiguous int32 [M = %d]' % M)
+    for t in (scale, shift):
+        if t is not None and (tuple(t.shape) != (C, Mp) or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.ChebgcnError('window_drop: scale and shift must be contiguous float32 [C, Mp]')
+    _lib.check(_launch('window_drop', 4.0 * B * int(D) * C, 0.0, lambda: _lib.lib().chebgcn_window_drop(
+        _p(x), _p(win), B, M, C, int(D), int(seed), int(refill), _p(pos), _p(scale), _p(shift), float(drop_value), _stream())),
+        'window_drop')
+    return x
+
+
 def knn(planes, N, k, metric):
     """The k nearest other vertices of every vertex (chebgcn_knn): ``planes`` [D, Np] fp32 feature-major planes on the device
     (zero pad), ``metric`` one of ``_lib.KNN_*`` -> ``(dist float32 [N, k] ascending, idx int32 [N, k])`` on the device.  The

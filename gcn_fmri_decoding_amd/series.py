@@ -15,7 +15,12 @@ and the mix gathers form them batch by batch.
 first rows (``stage_windows(starts=)``, ``fit_series``); moving a window a few TRs inside its trial is a new row table, not a
 new array, and only this kind can be displaced.  ``EventWindowSet``: a list of rows per window, ``fold`` of them averaged per
 channel (the windows of an event design, ``events.match_events``: ``stage_windows(index=)`` / ``stage_events`` /
-``fit_events``)."""
+``fit_events``).
+
+``WindowSet.augment`` makes the set stand for ``copies`` perturbed copies of itself (the reference's ``train_dataarg`` /
+``drop_rate``): vertex dropout and a time shift inside the window's symmetric reflection, drawn by a counter-based generator
+(``drop_vertices`` / ``time_shifts``, the NumPy restatement of the one in include/chebgcn.h), applied while a batch is gathered
+(chebgcn_gather_windows_reflect, chebgcn_window_drop) and drawn anew at every ``refill``."""
 import numpy as np
 import torch
 
@@ -69,6 +74,70 @@ def jitter_rows(rows, lo, hi, jitter, rng):
         return rows.copy()
     d = rng.randint(-jitter, jitter + 1, size=rows.shape).astype(np.int64)
     return np.clip(rows + d, lo, hi)
+
+
+# ---- the augmentation generator (include/chebgcn.h), restated in NumPy: uint32 values carried in uint64 and masked ----------------
+AUG_MUL1, AUG_MUL2, AUG_KEY, AUG_WINDOW, AUG_SHIFT_DRAW = 0x7FEB352D, 0x846CA68B, 0x9E3779B9, 0x85EBCA6B, 0xFFFFFFFF
+AUG_COPIES_MAX = 64
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def _aug_fin(x):
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(AUG_MUL1)) & _U32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(AUG_MUL2)) & _U32
+    return x ^ (x >> np.uint64(16))
+
+
+def aug_draw(seed, refill, i, d):
+    """``chebgcn_aug_draw``: 32 uniform bits (in a uint64 array) for augmented windows ``i`` and draw indices ``d`` (arrays that
+    broadcast), a stateless function of ``(seed, refill, i, d)``."""
+    i = np.asarray(i, np.uint64) & _U32
+    d = np.asarray(d, np.uint64) & _U32
+    a = _aug_fin((_aug_fin(np.uint64(int(seed) & 0xFFFFFFFF)) + np.uint64(int(refill) & 0xFFFFFFFF)) & _U32)
+    k0 = _aug_fin((a + i) & _U32)
+    k1 = _aug_fin(((a ^ np.uint64(AUG_KEY)) + ((i * np.uint64(AUG_WINDOW)) & _U32)) & _U32)
+    return _aug_fin(_aug_fin((k0 + d) & _U32) ^ k1)
+
+
+def drop_vertices(seed, refill, i, D, M):
+    """The ``D`` vertices (int64, in ``[0, M)``, with replacement, the caller's vertex order) that augmented window ``i`` drops
+    at refill ``refill``: draw ``d`` mapped as ``(u * M) >> 32``.  ``i`` may be an array: ``[len(i), D]``."""
+    i = np.asarray(i)
+    u = aug_draw(seed, refill, i[..., None], np.arange(int(D), dtype=np.uint64))
+    return ((u * np.uint64(int(M))) >> np.uint64(32)).astype(np.int64)
+
+
+def time_shifts(seed, refill, n, C):
+    """The time shifts ``r`` in ``[0, C)`` of the augmented windows ``0 .. n - 1`` at refill ``refill`` (int32 ``[n]``): draw
+    ``AUG_SHIFT_DRAW`` of every window, mapped as ``(u * C) >> 32``."""
+    u = aug_draw(seed, refill, np.arange(int(n), dtype=np.uint64), np.uint64(AUG_SHIFT_DRAW))
+    return ((u * np.uint64(int(C))) >> np.uint64(32)).astype(np.int32)
+
+
+def reflect_channels(C, r):
+    """``rho(c + r)`` for ``c < C``: the source channel of every channel of a window shifted by ``r`` in ``[0, C)`` inside its
+    symmetric reflection -- ``np.pad(x, C, 'symmetric')[r + C : r + 2 C]`` is ``x[rho(c + r)]``.  ``r`` may be an array
+    ``[n]``: ``[n, C]``."""
+    j = np.asarray(r, np.int64)[..., None] + np.arange(int(C), dtype=np.int64)
+    return np.where(j < C, j, 2 * int(C) - 1 - j)
+
+
+def check_augment_args(what, copies, drop_rate, time_shift, drop_value, seed):
+    """The arguments of ``WindowSet.augment`` / ``fit_series(augment=...)``, refused with a ``ValueError`` or returned as
+    ``(copies, drop_rate, time_shift, drop_value, seed)``."""
+    if not _is_int(copies) or not 0 <= copies <= AUG_COPIES_MAX:
+        raise ValueError('%s: the number of augmented copies must be an int in [0, %d], got %r' % (what, AUG_COPIES_MAX, copies))
+    if isinstance(drop_rate, bool) or not isinstance(drop_rate, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(drop_rate) <= 1.0:
+        raise ValueError('%s: drop_rate must be a number in [0, 1], got %r' % (what, drop_rate))
+    if not isinstance(time_shift, (bool, np.bool_)):
+        raise ValueError('%s: time_shift must be a bool, got %r' % (what, time_shift))
+    if isinstance(drop_value, bool) or not isinstance(drop_value, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(float(drop_value)):
+        raise ValueError('%s: drop_value must be a finite number, got %r' % (what, drop_value))
+    return int(copies), float(drop_rate), bool(time_shift), float(drop_value), check_seed(seed, 'the augmentation seed', what)
 
 
 SAMPLING_MAX = 16              # sources of one synthetic window at most (the mix gather holds them in registers)
@@ -180,13 +249,16 @@ class WindowSet(object):
         self.stats = None               # fit_scaler(): (mean, var) float64 [M, C] in the caller's order
         self.plan = None                # balance(): dict(src, cnt, labels, groups, sampling, resample, rng)
         self.mix_rows_host = self.mix_rows = self.mix_cnt = None   # [S', smax] keys of every source; device: int64 / int32
+        self.aug = None                 # augment(): dict(copies, base_len, D, time_shift, drop_value, seed, refill, shifts)
+        self.aug_shifts = self.aug_pos = None       # device int32: [copies * S'] time shifts; [M] caller vertex -> position
 
     def __len__(self):
         return self.shape[0]
 
     @property
     def nbytes(self):
-        """Device bytes of the set: every device tensor it holds (planes, row or index table, mix tables) and the tables."""
+        """Device bytes of the set: every device tensor it holds (planes, row or index table, mix tables, the tables of an
+        augmentation) and the scaler's tables."""
         held = [t for t in vars(self).values() if isinstance(t, torch.Tensor)] + list(self.tables or ())
         return sum(t.numel() * t.element_size() for t in held)
 
@@ -243,12 +315,115 @@ class WindowSet(object):
             raise ValueError('this WindowSet is staged in the internal vertex order of another model')
         scale, shift = self.tables if self.tables is not None else (None, None)
         sources = None if self.plan is None else self.plan['cnt'].mean()
-        return model.as_internal(self._gather(idx, scale, shift, out, sources))
+        if self.aug is None:
+            return model.as_internal(self._gather(idx, scale, shift, out, sources))
+        # an augmented set: the copy's window (through the reflection where it is shifted), then its dropped vertices -- both on
+        # the current stream, the second in place on what the first wrote
+        aug = self.aug
+        if idx is None:
+            idx = torch.arange(self.shape[0], dtype=torch.int32, device=self.planes.device)
+        if aug['time_shift']:
+            x = self._gather_shifted(idx, scale, shift, out)
+        else:
+            x = self._gather(torch.remainder(idx, aug['base_len']), scale, shift, out, sources)
+        if aug['D']:
+            ops.window_drop(x, idx, self.shape[1], aug['D'], aug['seed'], aug['refill'], self.aug_pos, scale, shift,
+                            aug['drop_value'])
+        return model.as_internal(x)
+
+    # ---------------------------------------------------------------- augmentation
+
+    def augment(self, labels, copies, drop_rate=0.0, time_shift=False, drop_value=1.0, seed=0):
+        """Make the set stand for ``copies`` perturbed copies of itself (the reference's ``train_dataarg`` / ``drop_rate``);
+        returns the labels of the augmented set, ``np.tile(labels, copies)``.  With ``S'`` the set's length now (after
+        ``balance``, if a plan is installed), ``len()`` and ``shape[0]`` become ``copies * S'``; window ``i`` is base window
+        ``i % S'``, copy ``i // S'``, and EVERY copy is perturbed (``copies = 1``: fresh perturbations of the set at every
+        refill).  ``copies = 0`` removes the augmentation (``labels`` may be None then).  ``shape_base`` stays the originals'.
+
+        * vertex dropout: ``D = int(drop_rate * M)`` vertices of every window, drawn with replacement out of the ``M`` real
+          ones in the caller's order, take ``drop_value`` in all channels BEFORE the tables: with tables the stored value is
+          ``fl(fl(drop_value * scale) + shift)``.  The pad stays zero.  Works on every kind of set, balanced or not.
+        * ``time_shift``: one ``r`` in ``[0, channel)`` per window; channel ``c`` takes source channel ``rho(c + r)``
+          (``reflect_channels``): ``np.pad(x, channel, 'symmetric')[r + channel : r + 2 * channel]``.  Not on a balanced set
+          (``ValueError``): the mix kernels average whole source windows.
+        * the draws are ``drop_vertices(seed, refill, i, D, M)`` and ``time_shifts(seed, refill, copies * S', channel)``: a
+          function of the seed, the refill number and the window's index alone -- never of the batch a window lands in.
+          ``refill()`` (once per epoch of ``fit``) advances the refill number: every epoch sees new perturbations.
+
+        Departure from the reference, on purpose: it repeats the labels but draws the SOURCE window of every copy at random,
+        so labels and data come apart there; here the labels follow the base window.  Arguments are refused (``ValueError``)
+        before anything touches the device.  ``materialise()`` returns the windows of the current refill."""
+        copies, drop_rate, time_shift, drop_value, seed = check_augment_args('augment', copies, drop_rate, time_shift,
+                                                                             drop_value, seed)
+        base_len = self.shape[0] if self.aug is None else self.aug['base_len']
+        if copies == 0:
+            self._augment_removed(base_len)
+            return None if labels is None else np.asarray(labels).copy()
+        labels = np.asarray(labels)
+        if labels.ndim != 1 or len(labels) != base_len:
+            raise ValueError('augment: labels must be one label per window (%d), got shape %s' % (base_len, labels.shape))
+        if time_shift and self.plan is not None:
+            raise ValueError('augment: time_shift on a balanced set is not served (the mix kernels average whole source '
+                             'windows); remove the plan (balance(None, 0)) or leave time_shift out')
+        if copies * base_len > 0x7fffffff:
+            raise ValueError('augment: %d copies of %d windows are more than an int32 index names' % (copies, base_len))
+        self._augment_removed(base_len)
+        M = self.shape[1]
+        self.aug = dict(copies=copies, base_len=base_len, D=int(drop_rate * M), time_shift=time_shift, drop_value=drop_value,
+                        seed=seed, refill=0, shifts=None)
+        self.shape = (copies * base_len,) + self.shape[1:]
+        order = self.owner._order
+        if self.aug['D'] and order is not None:
+            pos = np.empty(M, np.int32)
+            pos[np.asarray(order)] = np.arange(M, dtype=np.int32)
+            self.aug_pos = torch.as_tensor(pos).to(self.planes.device)
+        self._aug_draw()
+        return np.tile(labels, copies)
+
+    def _augment_removed(self, base_len):
+        if self.aug is not None:
+            self.aug = self.aug_shifts = self.aug_pos = None
+            self.shape = (base_len,) + self.shape[1:]
+            self._aug_tables()
+
+    def _aug_draw(self):
+        """The time shifts of the current refill, drawn on the host and uploaded once, and the kind's shifted table."""
+        aug = self.aug
+        if not aug['time_shift']:
+            return
+        aug['shifts'] = time_shifts(aug['seed'], aug['refill'], self.shape[0], self.shape[2])
+        if self.aug_shifts is None:
+            self.aug_shifts = torch.as_tensor(aug['shifts']).to(self.planes.device)
+        else:
+            self.aug_shifts.copy_(torch.as_tensor(aug['shifts']))
+        self._aug_tables()
+
+    def _aug_tables(self):
+        """What a kind keeps on the device for its shifted windows (dropped with the augmentation)."""
+
+    def _aug_refill(self):
+        if self.aug is not None:
+            self.aug['refill'] += 1
+            self._aug_draw()
+
+    def _augmented(self, x):
+        """``x`` ``[S', M, C]`` (the caller's order, before the tables) -> the ``copies * S'`` windows of the current refill."""
+        aug = self.aug
+        n, M, C = self.shape
+        x = x[np.arange(n) % aug['base_len']]                                             # (a new array)
+        if aug['time_shift']:
+            x = np.take_along_axis(x, reflect_channels(C, aug['shifts'])[:, None, :], axis=2)
+        if aug['D']:
+            v = drop_vertices(aug['seed'], aug['refill'], np.arange(n), aug['D'], M)           # [n, D]
+            x[np.arange(n)[:, None], v] = np.float32(aug['drop_value'])
+        return x
 
     def materialise(self):
         """The ``[S, M, channel]`` float32 array the set stands for, in the caller's vertex order, as the model sees it: every
         level in float32 like the kernels -- the originals as their kind cuts them, of a balanced set the ``S'`` windows, the
-        sources added in their order and divided once by ``cnt``, then the tables (a rounded product, then a rounded sum)."""
+        sources added in their order and divided once by ``cnt``, then the tables (a rounded product, then a rounded sum).  Of an
+        augmented set the ``copies * S'`` windows of the current refill, bit for bit what ``gather`` forms: the copy's channels
+        taken through the reflection, then ``drop_value`` at its dropped vertices, then the tables."""
         series = self._caller_order(self.planes)                                        # [M, Ttot]
         if self.plan is None:
             x = self._originals(series, self._keys())                                   # [M, S, C]
@@ -262,6 +437,8 @@ class WindowSet(object):
             mixed = cnt > 1
             x[:, mixed] = x[:, mixed] / cnt[mixed].astype(np.float32)[None, :, None]
         x = np.ascontiguousarray(x.transpose(1, 0, 2))
+        if self.aug is not None:
+            x = self._augmented(x)
         if self.scaler is not None:
             x = (x * self.scaler[0][None]).astype(np.float32) + self.scaler[1][None]
         return x.astype(np.float32, copy=False)
@@ -295,9 +472,11 @@ class WindowSet(object):
 
     def refill(self):
         """Called by ``fit`` each time it refills its index deque (once per epoch): redraws the plan when ``resample`` is
-        set, one upload.  Returns the starts (rows) in use."""
+        set, one upload; of an augmented set the refill number advances and the time shifts are drawn again, one upload.
+        Returns the starts (rows) in use."""
         if self._redraw():
             self._upload_mix()
+        self._aug_refill()
         return self.starts
 
     def _plan_removed(self):
@@ -315,6 +494,9 @@ class WindowSet(object):
         global NumPy stream is never touched).  ``resample``: ``refill()`` redraws the plan (once per epoch of ``fit``);
         the labels do not change with it.  Arguments are refused (``ValueError``) before anything touches the device."""
         sampling = check_sampling(sampling, 'balance')
+        if self.aug is not None and (sampling or self.plan is not None):
+            raise ValueError('balance: the set is augmented; remove the augmentation first (augment(None, 0)) -- it goes on top '
+                             'of the plan')
         if sampling == 0:
             if self.plan is not None:
                 self.plan = self.mix_rows_host = self.mix_rows = self.mix_cnt = None
@@ -345,6 +527,7 @@ class StartWindowSet(WindowSet):
         self.rows_host = self.base_rows.copy()
         self.rows = torch.as_tensor(self.rows_host).to(planes.device)
         self.jitter, self.jitter_rng = 0, None
+        self.aug_rows = None            # augment(time_shift=True): int64 device [copies * S]
 
     @property
     def starts(self):
@@ -367,6 +550,15 @@ class StartWindowSet(WindowSet):
             return ops.gather_windows_mix(self.planes, self.mix_rows, self.mix_cnt, M, C, idx, scale, shift, out, sources=sources)
         return ops.gather_windows(self.planes, self.rows, M, C, idx, scale, shift, out)
 
+    def _gather_shifted(self, idx, scale, shift, out):
+        M, C = self.shape[1:]
+        return ops.gather_windows_reflect(self.planes, self.aug_rows, self.aug_shifts, M, C, idx, scale, shift, out)
+
+    def _aug_tables(self):
+        """The rows of every augmented window (the row table once per copy, repeated on the device), indexed like the shifts."""
+        shifted = self.aug is not None and self.aug['time_shift']
+        self.aug_rows = self.rows.repeat(self.aug['copies']) if shifted else None
+
     def _mix_table(self, extra):
         """The originals at their rows in use (every entry), the extra windows at ``extra`` (None: their sources'
         undisplaced rows)."""
@@ -387,6 +579,7 @@ class StartWindowSet(WindowSet):
         self.rows.copy_(torch.as_tensor(self.rows_host))
         if self.plan is not None:
             self._upload_mix()
+        self._aug_tables()
 
     def refill(self):
         """``WindowSet.refill``; with ``jitter > 0`` every window's start is redrawn around its undisplaced one and the table
@@ -401,11 +594,12 @@ class StartWindowSet(WindowSet):
         rows = jitter_rows(self.base_rows, self.lo, self.hi, self.jitter, self.jitter_rng)
         if self.plan is None:
             self.set_rows(rows)
-            return self.starts
-        self.rows_host = rows
-        self._redraw()
-        e = self.plan['src'][self.shape_base[0]:]
-        self._upload_mix(jitter_rows(self.base_rows[e], self.lo[e], self.hi[e], self.jitter, self.plan['rng']))
+        else:
+            self.rows_host = rows
+            self._redraw()
+            e = self.plan['src'][self.shape_base[0]:]
+            self._upload_mix(jitter_rows(self.base_rows[e], self.lo[e], self.hi[e], self.jitter, self.plan['rng']))
+        self._aug_refill()
         return self.starts
 
     def reset_rows(self):
@@ -429,6 +623,7 @@ class EventWindowSet(WindowSet):
         self.fold = int(fold)
         self.index_host = np.ascontiguousarray(np.concatenate(run_index) + self.offsets[:, None], np.int64)
         self.index = torch.as_tensor(self.index_host).to(planes.device)
+        self.aug_index = None           # augment(time_shift=True): int64 device [copies * S, C * fold]
 
     @property
     def jitter(self):
@@ -469,6 +664,26 @@ class EventWindowSet(WindowSet):
 
     def _mix_table(self, extra):
         return self.plan['src']
+
+    def _gather_shifted(self, idx, scale, shift, out):
+        M, C = self.shape[1:]
+        return ops.gather_windows_indexed(self.planes, self.aug_index, M, C, self.fold, None, None, idx, scale, shift, out)
+
+    def _aug_tables(self):
+        """The index table of every augmented window, its columns taken through the reflection on the host --
+        ``idx'[i, f * C + c] = idx[i % S, f * C + rho(c + r_i)]`` -- and uploaded once: ``[copies * S, C * fold]``, read by
+        chebgcn_gather_windows_indexed like any index table."""
+        if self.aug is None or not self.aug['time_shift']:
+            self.aug_index = None
+            return
+        n, C = self.shape[0], self.shape[2]
+        cols = reflect_channels(C, self.aug['shifts'])                                  # [n, C]
+        cols = (np.arange(self.fold)[None, :, None] * C + cols[:, None, :]).reshape(n, self.fold * C)
+        tab = np.take_along_axis(self.index_host[np.arange(n) % self.shape_base[0]], cols, axis=1)
+        if self.aug_index is None or tuple(self.aug_index.shape) != tab.shape:
+            self.aug_index = torch.as_tensor(np.ascontiguousarray(tab)).to(self.planes.device)
+        else:
+            self.aug_index.copy_(torch.as_tensor(np.ascontiguousarray(tab)))
 
 
 class Series(object):
@@ -586,14 +801,18 @@ class Series(object):
         return self._stage_set('stage_events', EventWindowSet, runs, run_index, fold=fold), labels
 
     def fit_events(self, train_series, train_label_runs, val_series, val_label_runs, target_name, block_dura, standardize=False,
-                   sampling=0, seed=0, groups=None, best_checkpoint_dir=None, **match_kw):
+                   sampling=0, seed=0, groups=None, best_checkpoint_dir=None, augment=0, drop_rate=0.0, time_shift=False,
+                   drop_value=1.0, augment_seed=0, **match_kw):
         """``fit`` on event designs: both splits go through ``stage_events`` and ``fit`` runs on the two sets; returns what
         ``fit`` returns.  ``fit_series``' rules: with ``standardize`` the scaler is fitted on the training set's ORIGINAL
         windows (their folded values, chebgcn_window_stats_indexed) before balancing, the validation set takes the training
         tables, and ``model.window_scaler`` goes into the checkpoints; ``sampling = n > 0`` balances the training classes
         (``WindowSet.balance``; ``seed`` starts the balancing stream, ``groups``: one id per training run GIVEN -- runs that
-        yield no window are dropped from it like from the set; None: every run its own)."""
+        yield no window are dropped from it like from the set; None: every run its own); ``augment = n > 0`` trains on ``n``
+        perturbed copies of the (balanced) training set (``fit_series``' ``augment``, ``drop_rate``, ``time_shift``,
+        ``drop_value``, ``augment_seed``)."""
         what = 'fit_events'
+        aug = self._augment_args(what, augment, drop_rate, time_shift, drop_value, augment_seed, sampling)
         tr = self._event_args(train_series, train_label_runs, target_name, block_dura, match_kw, what)
         va = self._event_args(val_series, val_label_runs, target_name, block_dura, match_kw, what)
         train_labels, val_labels = tr[3], va[3]
@@ -605,11 +824,22 @@ class Series(object):
         ws_train = self._stage_set(what, EventWindowSet, tr[0], tr[1], fold=tr[2])
         ws_val = self._stage_set(what, EventWindowSet, va[0], va[1], fold=va[2])
         return self._fit_sets(ws_train, train_labels, ws_val, val_labels, standardize, best_checkpoint_dir,
-                              (sampling, seed, groups))
+                              (sampling, seed, groups), aug)
 
-    def _fit_sets(self, ws_train, train_labels, ws_val, val_labels, standardize, best_checkpoint_dir, plan):
+    @staticmethod
+    def _augment_args(what, copies, drop_rate, time_shift, drop_value, seed, sampling):
+        """``fit_series`` / ``fit_events``' augmentation arguments checked: ``augment``'s arguments from ``copies`` on."""
+        aug = check_augment_args(what, copies, drop_rate, time_shift, drop_value, seed)
+        if aug[0] and aug[2] and _is_int(sampling) and sampling:
+            raise ValueError('%s: time_shift together with sampling is not served (the mix kernels average whole source '
+                             'windows)' % what)
+        return aug
+
+    def _fit_sets(self, ws_train, train_labels, ws_val, val_labels, standardize, best_checkpoint_dir, plan, aug=None):
         """The tail of ``fit_series`` / ``fit_events``: the scaler fitted on the training originals and shared, the classes
-        balanced (``plan``: ``balance``'s arguments from ``sampling`` on), ``fit``; the training set left as it was staged."""
+        balanced (``plan``: ``balance``'s arguments from ``sampling`` on), the balanced set augmented (``aug``: ``augment``'s
+        arguments from ``copies`` on), ``fit``; the training set left as it was staged.  The validation set is never
+        augmented."""
         self.window_scaler = None
         if standardize:
             self.window_scaler = ws_train.fit_scaler()
@@ -617,15 +847,18 @@ class Series(object):
         try:
             if plan[0]:
                 train_labels = ws_train.balance(train_labels, *plan)
+            if aug is not None and aug[0]:
+                train_labels = ws_train.augment(train_labels, *aug)
             return self.fit(ws_train, train_labels, ws_val, val_labels, best_checkpoint_dir)
         finally:
+            ws_train.augment(None, 0)
             if ws_train.jitter:
                 ws_train.reset_rows()
             ws_train.balance(None, 0)
 
     def fit_series(self, train_series, train_starts, train_labels, val_series, val_starts, val_labels, standardize=False,
                    jitter=0, jitter_seed=0, best_checkpoint_dir=None, sampling=0, sampling_seed=0, sampling_groups=None,
-                   resample=False):
+                   resample=False, augment=0, drop_rate=0.0, time_shift=False, drop_value=1.0, augment_seed=0):
         """``fit`` on scans: both splits are staged as ``WindowSet``s (``stage_windows``' rules; labels one per window, runs in
         order, the starts of a run in the caller's order) and ``fit`` runs on them; returns what ``fit`` returns.
 
@@ -647,8 +880,18 @@ class Series(object):
           of the balancing stream.  ``fit`` then runs on ``S'`` windows; with ``record_fit``, ``fit_log['sources']`` holds
           ``(src, cnt)`` of every refill.  ``sampling = 0`` is the training without any of this, on the same kernels as
           before.  Under ``dist.DataParallel`` the ranks' ``S'`` may differ (they depend on each shard's labels); ``fit``'s
-          check of equal training-set sizes then fires -- balance shards that come out equal, or balance before sharding."""
+          check of equal training-set sizes then fires -- balance shards that come out equal, or balance before sharding.
+        * ``augment = n > 0`` (at most 64): ``fit`` trains on ``n`` perturbed copies of the training set
+          (``WindowSet.augment``; the reference's ``train_dataarg``), installed after the scaler is fitted (on the originals)
+          and after balancing.  ``drop_rate``: ``int(drop_rate * M)`` vertices of every window, drawn with replacement, take
+          ``drop_value`` in all channels before the scaler (chebgcn_window_drop).  ``time_shift``: every window is shifted by
+          ``r`` in ``[0, channel)`` inside its symmetric reflection (chebgcn_gather_windows_reflect; not together with
+          ``sampling``).  The draws are a function of ``(augment_seed, refill number, window index)`` alone and are redrawn
+          at every refill: no copy is ever stored.  Labels follow the base window (the reference draws the source of a copy
+          at random and repeats the labels: there they come apart).  With ``record_fit``, ``fit_log['augment']`` holds
+          ``(refill number, shifts or None)`` of every refill.  ``augment = 0`` launches none of the new kernels."""
         what = 'fit_series'
+        aug = self._augment_args(what, augment, drop_rate, time_shift, drop_value, augment_seed, sampling)
         check_jitter(jitter, 'fit_series: ')
         check_seed(jitter_seed, 'jitter_seed', what)
         tr = self._window_args(train_series, train_starts, None, None, what)
@@ -665,7 +908,7 @@ class Series(object):
         ws_val = self._stage_set(what, StartWindowSet, va[0], va[1])
         ws_train.jitter, ws_train.jitter_rng = int(jitter), np.random.RandomState(int(jitter_seed))
         return self._fit_sets(ws_train, train_labels, ws_val, val_labels, standardize, best_checkpoint_dir,
-                              (sampling, sampling_seed, sampling_groups, resample))
+                              (sampling, sampling_seed, sampling_groups, resample), aug)
 
     # ---------------------------------------------------------------- checkpoints
 

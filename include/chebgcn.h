@@ -675,6 +675,48 @@ int chebgcn_window_stats_indexed(const float* series, int64_t Ttot, const int64_
                                  double* mean, double* var, float* scale, float* shift, int M, int C, void* workspace,
                                  size_t workspace_bytes, chebgcn_stream stream);
 
+/* ---- augmented training windows (series.WindowSet.augment): vertex dropout and time shifts, copy by copy, never stored --------
+ * An augmented set stands for copies * S windows; augmented window i is base window i % S, copy i / S.  What perturbs window i
+ * is a stateless function of (seed, refill, i, d) -- never of the batch the window lands in or of its place there:
+ *
+ *   fin(x):  x ^= x >> 16;  x *= CHEBGCN_AUG_MUL1;  x ^= x >> 15;  x *= CHEBGCN_AUG_MUL2;  x ^= x >> 16     (uint32, wrapping)
+ *   a  = fin(fin(seed) + refill)
+ *   k0 = fin(a + i)
+ *   k1 = fin((a ^ CHEBGCN_AUG_KEY) + i * CHEBGCN_AUG_WINDOW)
+ *   chebgcn_aug_draw(seed, refill, i, d) = fin(fin(k0 + d) ^ k1)                                  (32 uniform bits)
+ *   a value u becomes an integer of [0, n) as ((uint64_t)u * n) >> 32, without a modulo.
+ * For fixed (seed, refill), i -> (k0, k1) is one to one: no two windows of a refill share their stream.  Draws d = 0 .. D - 1 of
+ * window i are its dropped vertices (out of [0, M), with replacement); draw d = CHEBGCN_AUG_SHIFT_DRAW is its time shift (out of
+ * [0, C)).  series.drop_vertices / series.time_shifts restate both in NumPy.
+ *
+ * window_drop: in place on a gathered batch x [B][C][Mp(M)].  win: int32 [B] (device), the augmented-set index i of every batch
+ *   row; pos: int32 [M] (device), vertex in the caller's order -> position in the batch's vertex order, NULL: the identity.  For
+ *   every b < B and d < D, with v = the draw (seed, refill, win[b], d) in [0, M) and p = pos[v]:
+ *     x[b][c][p] = drop_value                                   for every c < C, or, with scale / shift ([C][Mp], both or neither),
+ *     x[b][c][p] = drop_value * scale[c][p] + shift[c][p]       as a rounded product followed by a rounded sum (never one fma):
+ *   the value the gathers would have stored had the series held drop_value there.  Nothing else is written -- B * D * C * 4
+ *   bytes per batch, the pad included in "nothing else".  Draws that repeat a vertex store the same value twice: no atomics, the
+ *   result does not depend on the order of the stores.  win[b] enters the generator only; pos[v] is clamped into [0, M - 1]
+ *   before it is an address.  D may exceed M.  D == 0 or B == 0: no launch (chebgcn_last_dispatch(): "").  B * D <= 2^31 * 256.
+ *   chebgcn_last_dispatch(): window_drop_kernel<plain | tables>.
+ * gather_windows_reflect: chebgcn_gather_windows with a time shift per window.  tshift: int32 [.] (device) indexed like rows;
+ *   with w = sample ? sample[b] : b, r = tshift[w] clamped into [0, C - 1] (NULL: 0) and
+ *   rho(j) = j for j < C, 2 C - 1 - j otherwise:
+ *     out[b][c][m] = series[rows[w] + rho(c + r)][m]            (then * scale[c][m] + shift[c][m]: the tables of OUTPUT channel c)
+ *   -- numpy.pad(x, C, 'symmetric')[r + C : r + 2 C] along the channels of window x.  Rows are clamped as gather_windows
+ *   clamps them; pad, alignment and B as there; bit-identical to gather_windows where tshift is NULL or all zero.
+ *   chebgcn_last_dispatch(): gather_windows_reflect_kernel<plain | tables>. */
+#define CHEBGCN_AUG_MUL1 0x7FEB352Du
+#define CHEBGCN_AUG_MUL2 0x846CA68Bu
+#define CHEBGCN_AUG_KEY 0x9E3779B9u
+#define CHEBGCN_AUG_WINDOW 0x85EBCA6Bu
+#define CHEBGCN_AUG_SHIFT_DRAW 0xFFFFFFFFu
+int chebgcn_window_drop(float* x, const int32_t* win, int B, int M, int C, int D, uint32_t seed, uint32_t refill,
+                        const int32_t* pos, const float* scale, const float* shift, float drop_value, chebgcn_stream stream);
+int chebgcn_gather_windows_reflect(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* tshift,
+                                   const int32_t* sample, const float* scale, const float* shift, float* out, int B, int M, int C,
+                                   chebgcn_stream stream);
+
 /* ---- kNN brain graphs on the device (graph.knn_device / graph.connectivity_graph) ------------------------------------------
  * feat: [D][Np(N)] fp32, feature-major planes of N vertices (the staged-series layout with D = time; coordinates are
  * transposed by the caller), zero in the pad.  For every vertex i the k nearest OTHER vertices under `metric`:
