@@ -1281,10 +1281,14 @@ class cgcnn(base_model):
 
     # ------------------------------------------------------------------ network
 
+    def _kinds(self):
+        """(bias_kind, pool_kind) of the standard brelu / pool methods, None for one that was replaced."""
+        bias_kind = {cgcnn.b1relu: BIAS_FILTER, cgcnn.b2relu: BIAS_VERTEX}.get(getattr(self.brelu, '__func__', None))
+        pool_kind = {cgcnn.mpool1: POOL_MAX, cgcnn.apool1: POOL_AVG}.get(getattr(self.pool, '__func__', None))
+        return bias_kind, pool_kind
+
     def _fusable(self):
-        std = lambda m, names: getattr(m, '__func__', None) in [getattr(cgcnn, n) for n in names]
-        return (std(self.filter, ['chebyshev5']) and std(self.brelu, ['b1relu', 'b2relu'])
-                and std(self.pool, ['mpool1', 'apool1']))
+        return getattr(self.filter, '__func__', None) is cgcnn.chebyshev5 and None not in self._kinds()
 
     def _inference(self, x, dropout):
         """Layer loop + head (:658-682) on a logical [N, M, channel] tensor."""
@@ -1312,65 +1316,74 @@ class cgcnn(base_model):
                                    "'length'), which the layer-by-layer path does not know: construct it with "
                                    "CHEBGCN_VERTEX_ORDER=reference to replace filter / brelu / pool methods")
             return self._inference(ops.plane_view(self._to_internal(x), self.L[0].shape[0]), dropout)
+        training = self.training_mode and torch.is_grad_enabled()
+        # training: the layer's gradients go straight into the flat (zeroed) gradient buffer
+        x, mean = self._conv_trunk(x, 0 if training else len(self.p),
+                                   lambda i, W, b: training and W.grad is not None and b.grad is not None,
+                                   fuse_mean=self.fuse_feature_mean, report_done=True)
+        if mean:
+            return self._head(x, dropout)              # already the logical [B, M] view of the [B, Mp] means
+        return self._head(ops.FeatureMean.apply(x, self.graphs[-1].M // self.p[-1]), dropout)
+
+    def _conv_trunk(self, x, lo, direct, pool_top=True, fuse_mean=False, report_done=False, frozen_below=False):
+        """The conv layers on the fused path; returns (the top layer's result, whether that is already the feature mean).
+        ``lo``: the lowest layer that takes a gradient (the number of layers outside a training step); ``direct(i, W, b)``: does
+        layer i write its gradients straight into ``W.grad`` / ``b.grad``; ``pool_top``: the top layer pools; ``fuse_mean``:
+        it may return ``tf.reduce_mean(x, -1)`` in place of its output; ``report_done``: a data-parallel helper hears of every
+        layer whose gradients are enqueued; ``frozen_below``: the layers below ``lo`` run without autograd."""
         win = self._windows                            # (decode_series' shared path: layer 1 reads windows of a series' stack)
         x = self._to_internal(x) if win is None else None
         nl = len(self.p)
         B = x.shape[0] if win is None else win.B
-        per_vertex = getattr(self.brelu, '__func__', None) is cgcnn.b2relu
-        pool_kind = POOL_AVG if getattr(self.pool, '__func__', None) is cgcnn.apool1 else POOL_MAX
+        # (fine-tuning does not ask _fusable: a brelu / pool method replaced there runs as b1relu / mpool1, as it always has)
+        bias_kind, pool_kind = (d if k is None else k for k, d in zip(self._kinds(), (BIAS_FILTER, POOL_MAX)))
         stack, ps = None, self._pass                   # (ps: inside an attribution call, None otherwise)
+        stops = ps is not None and ps.layer is not None
         # training: the weights of every layer that forms its input gradient by the forward recurrence on dy (ops.dx_by_forward),
         # re-indexed in ONE launch here -- they are constant within the step -- instead of one launch per layer inside backward
-        Wts = {}
-        if self.training_mode and torch.is_grad_enabled():
-            fins = [x.shape[1]] + list(self.F[:-1])
-            idxs = [i for i in range(1, nl) if ops.dx_by_forward_shape(self.graphs[i], fins[i], self.K[i], self.F[i], self.contraction)]
-            if idxs:
-                outs = ops.reindex_weights_batch([self._params['conv%d/weights' % (i + 1)] for i in idxs],
-                                                 [(fins[i], self.K[i], self.F[i]) for i in idxs])
-                Wts = dict(zip(idxs, outs))
+        fins = [None] + list(self.F[:-1])              # (no such layer, e.g. outside training: no launch, reindex_weights_batch([]) == [])
+        idxs = [i for i in range(lo + 1, nl) if ops.dx_by_forward_shape(self.graphs[i], fins[i], self.K[i], self.F[i], self.contraction)]
+        Wts = dict(zip(idxs, ops.reindex_weights_batch([self._params['conv%d/weights' % (i + 1)] for i in idxs],
+                                                       [(fins[i], self.K[i], self.F[i]) for i in idxs])))
         # layer i's output feeds layer i + 1 and nothing else: the ReluGrad of layer i can run in the epilogue of layer i + 1's
         # input gradient (ops.GateLink; the layers decide by themselves whether their kernels serve it)
-        links = [ops.GateLink() for _ in range(nl - 1)] if (self.training_mode and torch.is_grad_enabled()) else None
+        links = {i: ops.GateLink() for i in range(lo, nl - 1)}
+        mean = False
         for i in range(nl):
             g = self.graphs[i]
             W = self._params['conv%d/weights' % (i + 1)]
             b = self._params['conv%d/bias' % (i + 1)]
             if ps is not None:
                 W, b = W.detach(), b.detach()
+            top = i + 1 == nl
+            pool, maps = (self.p[i], self._pool_maps[i]) if (pool_top or not top) else (1, None)
             out = next_stack = None
-            if i + 1 < nl and g.M // self.p[i] == self.graphs[i + 1].M:
+            if not top and g.M // self.p[i] == self.graphs[i + 1].M:
                 next_stack = torch.empty((self.K[i + 1], B, self.F[i], self.graphs[i + 1].Mp), dtype=torch.float32,
                                          device=self.device)
                 out = next_stack[0]
             if i == 0 and win is not None:
-                mean = False
-                x = ops.conv_windows(win, W, b, g, self.K[0], self.channel, self.p[0], pool_kind, True,
-                                     BIAS_VERTEX if per_vertex else BIAS_FILTER, out=out, pool_maps=self._pool_maps[0])
+                x = ops.conv_windows(win, W, b, g, self.K[0], self.channel, pool, pool_kind, True, bias_kind, out=out, pool_maps=maps)
                 stack = next_stack
                 continue
-            # training: the layer's gradients go straight into the flat (zeroed) gradient buffer
-            direct = self.training_mode and W.grad is not None and b.grad is not None and torch.is_grad_enabled()
-            done = (lambda layer=i + 1: self._dp.layer_done(layer)) if (direct and self._dp is not None) else None
+            into = direct(i, W, b)
+            done = (lambda layer=i + 1: self._dp.layer_done(layer)) if (report_done and into and self._dp is not None) else None
             # the last layer feeds tf.reduce_mean(x, -1) (:673) only: where the kernel can, it returns that mean and never
             # stores its own output; its gradients read one plane per window
             # (a Grad-CAM pass at the top layer differentiates to its stored output: no fused mean there)
-            mean = bool(i + 1 == nl and self.fuse_feature_mean and (ps is None or ps.layer != i) and
-                        ops.conv_mean_supported(B, g.M, x.shape[1], self.K[i], self.F[i], self.p[i], True, self.contraction))
-            with ps.grad_mode(i) if ps is not None else contextlib.nullcontext():
-                x = ops.cheb_conv(x, W, b, g, self.K[i], self.p[i], pool_kind, True,
-                                  BIAS_VERTEX if per_vertex else BIAS_FILTER, stack=stack, out=out,
-                                  dW=W.grad if direct else None, dbias=b.grad if direct else None,
-                                  precision=self.contraction, done=done, mean=mean, pool_maps=self._pool_maps[i], Wt=Wts.get(i),
-                                  link_in=links[i - 1] if (links and i > 0) else None,
-                                  link_out=links[i] if (links and i + 1 < nl) else None)
+            mean = bool(top and fuse_mean and (ps is None or ps.layer != i) and
+                        ops.conv_mean_supported(B, g.M, x.shape[1], self.K[i], self.F[i], pool, True, self.contraction))
+            # (a Grad-CAM pass: autograd from the layer above the one it stops at, on detached variables)
+            grad_mode = ps.grad_mode(i) if stops else torch.no_grad() if (frozen_below and i < lo) else contextlib.nullcontext()
+            with grad_mode:
+                x = ops.cheb_conv(x, W, b, g, self.K[i], pool, pool_kind, True, bias_kind, stack=stack, out=out,
+                                  dW=W.grad if into else None, dbias=b.grad if into else None, precision=self.contraction,
+                                  done=done, mean=mean, pool_maps=maps, Wt=Wts.get(i), link_in=links.get(i - 1),
+                                  link_out=links.get(i))
             if ps is not None:
                 x = ps.tap(i, x)
             stack = next_stack
-        M_last = self.graphs[-1].M // self.p[-1]
-        if mean:
-            return self._head(x, dropout)              # already the logical [B, M] view of the [B, Mp] means
-        return self._head(ops.FeatureMean.apply(x, M_last), dropout)
+        return x, mean
 
     def _head(self, x, dropout):
         """reduce_mean output -> FC stack with dropout -> logits (:674-682)."""
@@ -1699,56 +1712,8 @@ class finetuning_cgcnn(cgcnn):
     def _inference_storage(self, x, dropout):
         """The trunk on the fused path -- the layers below the lowest trained one without autograd, the top layer without its
         pooling -- then the head."""
-        win = self._windows                            # (decode_series' shared path: see cgcnn._inference_storage)
-        x = self._to_internal(x) if win is None else None
-        nl = len(self.p)
-        B = x.shape[0] if win is None else win.B
-        per_vertex = getattr(self.brelu, '__func__', None) is cgcnn.b2relu
-        pool_kind = POOL_AVG if getattr(self.pool, '__func__', None) is cgcnn.apool1 else POOL_MAX
-        training = self.training_mode and torch.is_grad_enabled()
-        lo = self._lowest if training else nl
-        Wts = {}
-        if training:
-            fins = [x.shape[1]] + list(self.F[:-1])
-            idxs = [i for i in range(lo + 1, nl)
-                    if ops.dx_by_forward_shape(self.graphs[i], fins[i], self.K[i], self.F[i], self.contraction)]
-            if idxs:
-                outs = ops.reindex_weights_batch([self._params['conv%d/weights' % (i + 1)] for i in idxs],
-                                                 [(fins[i], self.K[i], self.F[i]) for i in idxs])
-                Wts = dict(zip(idxs, outs))
-        links = {i: ops.GateLink() for i in range(lo, nl - 1)}
-        stack, ps = None, self._pass
-        stops = ps is not None and ps.layer is not None
-        for i in range(nl):
-            g = self.graphs[i]
-            W = self._params['conv%d/weights' % (i + 1)]
-            b = self._params['conv%d/bias' % (i + 1)]
-            if ps is not None:
-                W, b = W.detach(), b.detach()
-            top = i + 1 == nl
-            out = next_stack = None
-            if not top and g.M // self.p[i] == self.graphs[i + 1].M:
-                next_stack = torch.empty((self.K[i + 1], B, self.F[i], self.graphs[i + 1].Mp), dtype=torch.float32,
-                                         device=self.device)
-                out = next_stack[0]
-            if i == 0 and win is not None:
-                x = ops.conv_windows(win, W, b, g, self.K[0], self.channel, 1 if top else self.p[0], pool_kind, True,
-                                     BIAS_VERTEX if per_vertex else BIAS_FILTER, out=out,
-                                     pool_maps=None if top else self._pool_maps[0])
-                stack = next_stack
-                continue
-            trained = i >= lo and W.requires_grad
-            # (a Grad-CAM pass: autograd from the layer above the one it stops at, on detached variables)
-            grad_mode = ps.grad_mode(i) if stops else contextlib.nullcontext() if i >= lo else torch.no_grad()
-            with grad_mode:
-                x = ops.cheb_conv(x, W, b, g, self.K[i], 1 if top else self.p[i], pool_kind, True,
-                                  BIAS_VERTEX if per_vertex else BIAS_FILTER, stack=stack, out=out,
-                                  dW=W.grad if trained else None, dbias=b.grad if trained else None,
-                                  precision=self.contraction, pool_maps=None if top else self._pool_maps[i], Wt=Wts.get(i),
-                                  link_in=links.get(i - 1), link_out=links.get(i))
-            if ps is not None:
-                x = ps.tap(i, x)
-            stack = next_stack
+        lo = self._lowest if (self.training_mode and torch.is_grad_enabled()) else len(self.p)
+        x, _ = self._conv_trunk(x, lo, lambda i, W, b: i >= lo and W.requires_grad, pool_top=False, frozen_below=True)
         return self._head(x, dropout)
 
     def _head(self, x, dropout):

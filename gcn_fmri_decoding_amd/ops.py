@@ -9,6 +9,7 @@ contiguous *storage* tensor ``[N, F, Mp]`` (vertex axis fastest, ``Mp = plane_st
 ``plane_view(storage, M)`` exposes it with the reference's logical shape ``[N, M, F]``
 without copying; ``plane_storage(x)`` goes back (zero-copy when ``x`` is such a view).
 """
+import collections
 import ctypes as C
 import os
 import weakref
@@ -661,17 +662,292 @@ def contract_fwd_into(stack, W, bias, bias_kind, out, argmax, B, M, Fin, K, Fout
                what + '_bf16')
 
 
-def _grad_mode(bufs):
-    """Grad mode of the caller of ``cheb_conv`` (``Buffers.grad_mode``); a bare ``ChebConv.apply`` without buffers: on."""
-    return True if bufs is None else bool(bufs.grad_mode)
+def _detached(t):
+    """``t`` as a kernel operand: detached and contiguous (None stays None)."""
+    return None if t is None else t.detach().contiguous()
+
+
+def _out_buffer(out, B, F, M, device):
+    """The caller's ``out``, checked, or new planes ``[B, F, stride(M)]``."""
+    if out is None:
+        return plane_empty(B, F, M, device)
+    if tuple(out.shape) != (B, F, plane_stride(M)) or not out.is_contiguous():
+        raise ValueError('out buffer has the wrong shape')
+    return out
+
+
+def _contract_cost(B, M, Fin, K, Fout, planes=None):
+    """(algorithmic bytes, flops) of a contraction or one of its gradients, for ``_launch``: the compulsory
+    traffic is the stack, 4*M*Fin*K per window, and ``planes`` planes of M vertices (the layer's Fout; 1 under the fused
+    feature mean)."""
+    return 4.0 * B * M * (Fin * K + (Fout if planes is None else planes)), 2.0 * B * M * Fin * K * Fout
+
+
+def _pool_gather(y, maps, out, sel, B, M, Fout, pool, pool_kind, relu):
+    """Pooling between two vertex orders: gathers the clusters of the unpooled ``y`` (source order) through LDS into ``out``
+    (csrc/pointwise.hip pool_gather_fwd_kernel); ``sel``: the selection bytes a backward pass reads, or None."""
+    Mo = M // pool
+    _lib.check(_launch('pool_gather_fwd', B * Fout * (4.0 * (M + Mo) + Mo), 0.0, lambda: _lib.lib().chebgcn_pool_gather_fwd(
+        _p(y), _p(maps[0]), _p(out), _p(sel), B, M, Fout, pool, pool_kind, int(relu), _stream())), 'pool_gather_fwd')
+
+
+def dx_by_forward_shape(graph, Fin, K, Fout, precision):
+    """Does a layer of this shape form its input gradient by the forward recurrence on dy (``dx_by_forward``)?  THE rule:
+    ``ChebConv.backward`` takes that form, and ``ChebConv.forward`` offers its mask to the layer above (``GateLink``), where
+    this holds and their own conditions do; the models pre-index the weights of such layers, which read
+    W'[fo*K + k][fin] = W[fin*K + k][fo].
+    On graphs in length order only: there the forward recurrence kernel is the faster of the two (0.49 against 0.43 of the
+    HBM roofline in the step).  In the caller's order the Clenshaw kernels are as fast or faster -- measured: the reference's
+    own shape at N = 1000 / 2000 (batch 128, K = 10) 1.93 / 3.32 ms this way against 1.89 / 3.16 ms; the level-0 layers of
+    the pooling network run their forward recurrence on two planes, the adjoint on four (common.h pick_ell)."""
+    return bool(dx_by_forward and K > 1 and Fout <= Fin and resolve_precision(precision, Fin, K, Fout) != 'bf16' and graph.ordered)
+
+
+# What one backward pass of ChebConv runs, decided before anything is launched (_bwd_choose):
+#   dy     how dy and the bias gradient are obtained (_bwd_dy): 'mean_gate', 'fold', 'dy16', 'link' or 'plain'
+#   grads  which contraction gradients read it (_BWD_W, _BWD_X): 'dy16', 'bf16', 'relu_mean', 'relu_bias', 'relu' or 'plain'
+#   by_fwd the input gradient by the forward recurrence on dy;  merge_bias: dbias rides in the weight gradient's launch;
+#   defer_bias: the bias reduction is enqueued behind the layer's other gradients;  side: the weight gradient on a second stream
+_BwdChoice = collections.namedtuple('_BwdChoice', 'dy grads by_fwd merge_bias defer_bias side')
+
+# One arm of a contraction gradient, by ``grads``: its entry point and what that takes besides the operands every arm has.
+# mask: reads the ReLU mask;  dbias: writes the bias gradient too;  passes: takes the number of bf16 passes;  what: the name
+# _lib.check reports (None: the launch's name);  planes: planes of dy per window (None: Fout).  A new arm is one row here.
+_Arm = collections.namedtuple('_Arm', 'entry mask dbias passes what planes', defaults=(False, False, False, None, None))
+_BWD_W = {                                     # the weight gradient
+    'dy16': _Arm('chebgcn_contract_bwd_w_bf16_dy16'),
+    'bf16': _Arm('chebgcn_contract_bwd_w_bf16', passes=True),
+    'relu_mean': _Arm('chebgcn_contract_bwd_w_relu_mean', mask=True),
+    'relu_bias': _Arm('chebgcn_contract_bwd_w_relu_bias', mask=True, dbias=True),
+    'relu': _Arm('chebgcn_contract_bwd_w_relu', mask=True),
+    'plain': _Arm('chebgcn_contract_bwd_w'),
+}
+_BWD_X = {                                     # the input gradient in Clenshaw form
+    'dy16': _Arm('chebgcn_contract_bwd_x_bf16_dy16'),
+    'bf16': _Arm('chebgcn_contract_bwd_x_bf16', passes=True),
+    'relu_mean': _Arm('chebgcn_contract_bwd_x_relu_mean', mask=True, what='contract_bwd_x_relu_mean', planes=1),
+    'relu': _Arm('chebgcn_contract_bwd_x_relu', mask=True, what='contract_bwd_x_relu'),
+    'plain': _Arm('chebgcn_contract_bwd_x', what='contract_bwd_x'),
+}
+_BWD_X['relu_bias'] = _BWD_X['relu']           # (the merged bias gradient is the weight gradient's business)
+
+
+def _bwd_choose(ctx, gout, argmax, dbias):
+    """The ``_BwdChoice`` of one backward pass: reads the module switches, launches nothing."""
+    lib = _lib.lib()
+    B, M, Fin, K, Fout, pool, pool_kind, relu, bias_kind = ctx.cfg
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    # gradient wrt the input by the forward recurrence on dy (dx_by_forward_shape): dy is then materialised (slab 0 of the stack
+    # the recurrence fills), so the ReluGrad is not folded into the contraction gradients of this layer.  Under the fused
+    # feature mean only where one pass can gate the mean's gradient AND reduce the bias gradient (relu_grad_mean)
+    by_fwd = bool(need_x and not ctx.fused and dx_by_forward_shape(ctx.graph, Fin, K, Fout, ctx.precision)
+                  and (not ctx.mean or (ctx.fold and dbias is not None)))
+    fold = ctx.fold and not by_fwd
+    dy16 = bool(bf16_dy16 and not fold and ctx.precision == 'bf16' and pool == 1 and relu and argmax is not None
+                and lib.chebgcn_bf16_dy16_supported(B, M, Fin, K, Fout))
+    link, merge_bias = ctx.link_out, False
+    if by_fwd and ctx.mean:
+        dy = 'mean_gate'             # leaves an ordinary materialised dy: the contraction gradients below are not the mean's
+    elif fold:
+        dy = 'fold'
+        # small launches (atlas-sized layers): the per-vertex bias gradient rides in the launch that adds the weight gradient's
+        # partials (chebgcn_contract_bwd_w_relu_bias) -- one ~5 us launch less per layer
+        merge_bias = bool(merge_bias_small and dbias is not None and bias_kind == BIAS_VERTEX and not ctx.mean
+                          and need_w and not PRECISIONS[ctx.precision]
+                          and lib.chebgcn_contract_bwd_w_relu_bias_merged(B, M, Fin, K, Fout))
+    elif dy16:
+        dy = 'dy16'
+    elif (by_fwd and link is not None and link.gstack is not None and link.gstack.data_ptr() == gout.data_ptr()
+          and tuple(gout.shape) == (B, Fout, ctx.graph.Mp)):
+        dy = 'link'                  # the slab the layer above stored its gated input gradient in, recognised by address
+    else:
+        dy = 'plain'
+    grads = ('dy16' if dy16 else 'bf16' if PRECISIONS[ctx.precision] else 'plain' if not fold
+             else 'relu_mean' if ctx.mean else 'relu_bias' if merge_bias else 'relu')
+    # the weight gradient on a second stream (see overlap_bwd_w); never on instrumented steps
+    want_side = (Fout > 32) if overlap_bwd_w == 'auto' else bool(overlap_bwd_w)
+    side = bool(need_w and want_side and need_x and (timers is None or not timers.active))
+    return _BwdChoice(dy, grads, by_fwd, merge_bias, dy == 'fold' and dbias is not None and not merge_bias, side)
+
+
+def _bwd_dy(ctx, ch, gout, out, argmax, dbias):
+    """dy and the bias gradient.  Returns (dy, mask, gstack, bias job): ``mask`` where the contraction gradients gate dy
+    themselves, ``gstack`` the [K, B, Fout, Mp] stack whose slab 0 dy is (``ch.by_fwd``), the job a bias reduction still to
+    be enqueued."""
+    lib = _lib.lib()
+    B, M, Fin, K, Fout, pool, pool_kind, relu, bias_kind = ctx.cfg
+    g, dev = ctx.graph, gout.device
+    if ch.dy == 'mean_gate':
+        # the last layer under the fused feature mean: every filter's gradient is the plane gout / Fout; one pass gates it
+        # with the ReLU mask into slab 0 of the stack the recurrence fills and reduces the bias gradient
+        gstack = torch.empty((K, B, Fout, g.Mp), dtype=torch.float32, device=dev)
+        dy = gstack[0]
+        bws, nbws = _brelu_bwd_ws(B, M, Fout, 1, bias_kind, dev)
+        _lib.check(_launch('relu_grad_mean', B * M * (4.0 + Fout * 4.25), 0.0, lambda: lib.chebgcn_relu_grad_mean(
+            _p(gout), _p(argmax), _p(dy), _p(dbias), bias_kind, B, M, Fout, _p(bws), nbws, _stream())), 'relu_grad_mean')
+        return dy, None, gstack, None
+    if ch.dy == 'fold':
+        # ReluGrad folded into the two contraction gradients (chebgcn_contract_bwd_*_relu read gout and the
+        # mask); what is left of this pass is the bias reduction, which writes nothing but dbias
+        if not ch.defer_bias:
+            return gout, argmax, None, None
+
+        # feeds nothing in backward: enqueued BEHIND contract_bwd_x / recurrence_bwd (the chain the next layer waits
+        # for) -- 3.88 against 3.93 ms per step at the bench shape; on the second stream it costs 4 %
+        def bias_job():
+            bws, nbws = _brelu_bwd_ws(B, M, Fout, 1, bias_kind, dev)
+            if ctx.mean:
+                _lib.check(_launch('bias_grad', B * M * (4.0 + Fout * 0.25), 0.0, lambda: lib.chebgcn_bias_grad_relu_mean(
+                    _p(gout), _p(argmax), _p(dbias), bias_kind, B, M, Fout, _p(bws), nbws, _stream())), 'bias_grad_relu_mean')
+                return
+            _lib.check(_launch('bias_grad', B * Fout * M * (4.0 + 0.25), 0.0, lambda: lib.chebgcn_brelu_pool_bwd(
+                _p(gout), None, _p(argmax), None, _p(dbias), bias_kind, B, M, Fout, 1, pool_kind, 1, _p(bws), nbws,
+                _stream())), 'brelu_pool_bwd')
+        return gout, argmax, None, bias_job
+    bk = bias_kind if dbias is not None else BIAS_NONE
+    if ch.dy == 'dy16':
+        # one-pass bf16 gradients of a wide layer: the ReluGrad pass writes dy as bf16 -- what the matrix cores would round it
+        # to anyway (bit-identical results), half the bytes of the largest operand of both gradients
+        dy = torch.empty((B, Fout, g.Mp), dtype=torch.bfloat16, device=dev)
+        bws, nbws = _brelu_bwd_ws(B, M, Fout, 1, bk, dev)
+        _lib.check(_launch('relu_grad_bf16', B * Fout * M * (6.0 + 0.25), 0.0, lambda: lib.chebgcn_relu_grad_bf16(
+            _p(gout), _p(argmax), _p(dy), _p(dbias), bk, B, M, Fout, _p(bws), nbws, _stream())), 'relu_grad_bf16')
+        return dy, None, None, None
+    if ch.dy == 'link':
+        # the layer above stored its input gradient gated by this layer's mask, straight into slab 0 of this stack
+        # (GateLink): what is left of the ReluGrad pass is the bias reduction, a plain sum of gated values over the windows
+        gstack, ctx.link_out.gstack = ctx.link_out.gstack, None
+        dy = gstack[0]
+        if dbias is not None:
+            # at once, not behind the layer's other gradients like the bias reduction of the 'fold' arm: dy was written
+            # by the kernel in front of this one (2.95 against 2.97-3.01 ms per step at the bench shape, same box)
+            bws, nbws = _brelu_bwd_ws(B, M, Fout, 1, bias_kind, dev)
+            _lib.check(_launch('bias_grad', B * Fout * M * 4.0, 0.0, lambda: lib.chebgcn_brelu_pool_bwd(
+                _p(dy), None, None, None, _p(dbias), bias_kind, B, M, Fout, 1, pool_kind, 0, _p(bws), nbws,
+                _stream())), 'brelu_pool_bwd')
+        return dy, None, gstack, None
+    # 'plain': one pass over gout materialises dy (un-pooling, ReluGrad) and reduces the bias gradient
+    if ctx.link_out is not None:
+        ctx.link_out.gstack = None
+    gstack = None
+    if ch.by_fwd:
+        gstack = torch.empty((K, B, Fout, g.Mp), dtype=torch.float32, device=dev)
+        dy = gstack[0]                      # T_0 of the recurrence on dy: written in place
+    else:
+        dy = torch.empty((B, Fout, g.Mp), dtype=torch.float32, device=dev)
+    Mo = M // pool
+    if ctx.pool_maps is not None:
+        # pooled between two vertex orders: the forward's selection bytes carry the ReLU of the maximum as well
+        nbws = lib.chebgcn_pool_scatter_bwd_workspace(B, M, Fout, pool, bk)
+        bws = torch.empty(nbws, dtype=torch.uint8, device=dev) if nbws else None
+        _lib.check(_launch('pool_scatter_bwd', B * Fout * (4.0 * M + 5.0 * Mo), 0.0, lambda: lib.chebgcn_pool_scatter_bwd(
+            _p(gout), _p(argmax), _p(ctx.pool_maps[1]), _p(dy), _p(dbias), bk, B, M, Fout, pool, pool_kind, relu,
+            _p(bws), nbws, _stream())), 'pool_scatter_bwd')
+    else:
+        # with the ReLU mask of a pool == 1 layer `out` is not read (a byte per four vertices instead)
+        nbytes = B * Fout * M * (8.0 + 0.25) if out is None else 4.0 * B * Fout * (2 * Mo + M)
+        bws, nbws = _brelu_bwd_ws(B, M, Fout, pool, bk, dev)
+        _lib.check(_launch('brelu_pool_bwd', nbytes, 0.0, lambda: lib.chebgcn_brelu_pool_bwd(
+            _p(gout), _p(out), _p(argmax), _p(dy), _p(dbias), bk, B, M, Fout,
+            pool, pool_kind, relu, _p(bws), nbws, _stream())), 'brelu_pool_bwd')
+    return dy, None, gstack, None
+
+
+def _bwd_w(ctx, ch, stack, dy, mask, dbias, dW_buf, bias_job):
+    """The weight gradient, on the second stream where ``ch.side``.  Returns (dW, that stream or None -- the caller joins it --,
+    the bias job if it is still to be enqueued)."""
+    lib = _lib.lib()
+    B, M, Fin, K, Fout = ctx.cfg[:5]
+    dev = dy.device
+    passes = PRECISIONS[ctx.precision]
+    ws = _workspace((lib.chebgcn_contract_bwd_w_bf16_workspace if passes else lib.chebgcn_contract_bwd_w_workspace)(
+        B, M, Fin, K, Fout), dev)
+    if dW_buf is not None:
+        _check_grad_buffer(dW_buf, (Fin * K, Fout), 'dW')
+        dW = dW_buf                       # written, not accumulated: one use per step
+    else:
+        dW = torch.empty((Fin * K, Fout), dtype=torch.float32, device=dev)
+    arm = _BWD_W[ch.grads]
+    args = ([_p(stack), _p(dy)] + ([_p(mask)] if arm.mask else []) + [_p(dW)] + ([_p(dbias)] if arm.dbias else [])
+            + [_p(ws), ws.numel(), B, M, Fin, K, Fout] + ([passes] if arm.passes else []))
+    what = 'contract_bwd_w' + ('_' + ctx.precision if passes else '')
+
+    def launch():
+        _lib.check(_launch(what, *_contract_cost(B, M, Fin, K, Fout), lambda: getattr(lib, arm.entry)(*args, _stream())), what)
+
+    if not ch.side:
+        launch()
+        return dW, None, bias_job
+    # dW does not feed dx: it runs beside contract_bwd_x / recurrence_bwd on a second stream
+    side = _side_stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        launch()
+        if bias_job is not None and ctx.fused and bias_side_small:
+            # atlas-sized layers: the main stream is the critical path of a chain of short launches and the second
+            # stream has slack -- the bias reduction goes there too (on the benchmark graph that costs 4 %: it stays
+            # behind contract_bwd_x / recurrence_bwd on the main stream)
+            bias_job()
+            bias_job = None
+    return dW, side, bias_job
+
+
+def _bwd_x(ctx, ch, Wc, dy, mask, gstack):
+    """The input gradient: fused on chip, by the forward recurrence on dy (``ch.by_fwd``; ``gstack``: the stack whose slab 0 dy
+    is), or in Clenshaw form."""
+    lib = _lib.lib()
+    B, M, Fin, K, Fout = ctx.cfg[:5]
+    g, dev = ctx.graph, dy.device
+    if ctx.fused:
+        # G_j = dy W_j^T on the matrix cores feeding the adjoint recurrence on chip: no gradient stack in memory
+        dx = torch.empty((B, Fin, g.Mp), dtype=torch.float32, device=dev)
+        _lib.check(_launch('fused_layer_bwd_x', 4.0 * B * M * (Fin + Fout), 2.0 * B * M * Fin * K * Fout,
+                           lambda: lib.chebgcn_fused_layer_bwd_x(g.handle, _p(dy), _p(mask), _p(Wc), _p(dx), B, Fin, K, Fout,
+                                                                 _stream())), 'fused_layer_bwd_x')
+        return dx
+    if ch.by_fwd:
+        _lib.check(_launch('recurrence_fwd_t', 4.0 * B * M * Fout * K, 0.0, lambda: lib.chebgcn_recurrence_fwd_t(
+            g.handle, _p(dy), _p(gstack), B, Fout, K, _stream())), 'recurrence_fwd_t')
+        Wt = ctx.Wt                                                                        # W'[fo*K + k][fin] = W[fin*K + k][fo]
+        if Wt is None or tuple(Wt.shape) != (Fout * K, Fin):
+            Wt = torch.empty((Fout * K, Fin), dtype=torch.float32, device=dev)
+            _lib.check(lib.chebgcn_reindex_weights(_p(Wc), _p(Wt), Fin, K, Fout, _stream()), 'reindex_weights')
+        li, gate = ctx.link_in, None
+        if (li is not None and li.mask is not None and ctx.precision == 'f32' and li.shape[1:] == (B, Fin, g.Mp)
+                and lib.chebgcn_contract_fwd_gated_supported(B, M, Fout, K, Fin)):
+            # the layer below wants its dy as slab 0 of a gradient stack: this contraction stores it there, gated by that
+            # layer's ReLU mask
+            li.gstack = torch.empty(li.shape, dtype=torch.float32, device=dev)
+            dx, gate = li.gstack[0], li.mask
+        else:
+            dx = torch.empty((B, Fin, g.Mp), dtype=torch.float32, device=dev)
+        contract_fwd_into(gstack, Wt, None, BIAS_NONE, dx, None, B, M, Fout, K, Fin, 1, POOL_MAX, False, ctx.precision,
+                          what='contract_bwd_x', gate=gate)
+        return dx
+    gstack = torch.empty((K, B, Fin, g.Mp), dtype=torch.float32, device=dev)
+    arm = _BWD_X[ch.grads]
+    passes = PRECISIONS[ctx.precision]
+    name = 'contract_bwd_x' + ('_' + ctx.precision if passes else '')
+    args = [_p(dy)] + ([_p(mask)] if arm.mask else []) + [_p(Wc), _p(gstack), B, M, Fin, K, Fout] + ([passes] if arm.passes else [])
+    if passes:
+        nws = lib.chebgcn_contract_bwd_x_bf16_workspace(Fin, K, Fout)
+        args += [_p(_workspace(nws, dev, 'bwd_x_bf16')), nws]                  # its own: bwd_w may be running beside it
+    _lib.check(_launch(name, *_contract_cost(B, M, Fin, K, Fout, arm.planes), lambda: getattr(lib, arm.entry)(*args, _stream())),
+               arm.what or name)
+    dx = torch.empty((B, Fin, g.Mp), dtype=torch.float32, device=dev)
+    _lib.check(_launch('recurrence_bwd', 4.0 * B * M * Fin * (K + 1), 0.0, lambda: lib.chebgcn_recurrence_bwd(
+        g.handle, _p(gstack), _p(dx), B, Fin, K, _stream())), 'recurrence_bwd')
+    return dx
 
 
 class ChebConv(torch.autograd.Function):
     """y = pool(act(sum_k T_k(L~) x W_k + bias)) on plane storage tensors.
 
-    forward : recurrence_fwd (models_gcn.py:598-610) + contract_fwd (:611-648)
-    backward: brelu_pool_bwd, contract_bwd_w, contract_bwd_x, recurrence_bwd; for pool == 1 layers with
-              ReLU the ReluGrad runs inside contract_bwd_w_relu / contract_bwd_x_relu on the bit mask the
+    forward : recurrence_fwd (models_gcn.py:598-610) + contract_fwd (:611-648); four exits -- the fused atlas layer, the fused
+              feature mean, pooling between two vertex orders, the plain one -- which all end in ``_keep``
+    backward: ``_bwd_choose`` decides, then ``_bwd_dy`` (brelu_pool_bwd and its kin), ``_bwd_w`` (contract_bwd_w*) and
+              ``_bwd_x`` (contract_bwd_x* + recurrence_bwd, or recurrence_fwd_t + contract_fwd) only launch; for pool == 1
+              layers with ReLU the ReluGrad runs inside contract_bwd_w_relu / contract_bwd_x_relu on the bit mask the
               forward left, and brelu_pool_bwd only reduces the bias gradient
     ``bufs`` is a ``Buffers`` holder (kept out of autograd's sight): ``bufs.stack`` is an
     optional preallocated [K, B, Fin, Mp] buffer -- when ``x`` already is its slab 0 no copy
@@ -680,9 +956,31 @@ class ChebConv(torch.autograd.Function):
     """
 
     @staticmethod
+    def _keep(ctx, bufs, graph, cfg, bias, saved, fold=False, mean=False, fused=False, precision='f32', pool_maps=None, Wt=None,
+              link_in=None, link_out=None):
+        """Everything ``backward`` reads, in one place: what differs between the forward's exits is passed in, the rest comes
+        from ``bufs``.  ``saved``: (stack, W, out, mask / argmax / selection bytes)."""
+        ctx.save_for_backward(*saved)
+        ctx.fold, ctx.mean, ctx.fused = fold, mean, fused
+        ctx.graph, ctx.cfg = graph, cfg
+        ctx.bias_shape = None if bias is None else tuple(bias.shape)
+        ctx.grad_bufs = (bufs.dW, bufs.dbias)
+        ctx.done = bufs.done
+        ctx.precision = precision
+        ctx.pool_maps = pool_maps
+        ctx.Wt = Wt
+        ctx.link_in, ctx.link_out = link_in, link_out
+
+    @staticmethod
     def forward(ctx, x, W, bias, graph, K, pool, pool_kind, relu, bias_kind, bufs):
         _require_cuda(x, W, bias)
-        stack, out = (bufs.stack, bufs.out) if bufs is not None else (None, None)
+        if bufs is None:
+            # a bare ChebConv.apply without buffers: the caller's grad mode counts as on (grad mode is always off in here, and
+            # that is what a Buffers() made here would record)
+            bufs = Buffers()
+            bufs.grad_mode = True
+        stack = bufs.stack
+        given = None if bufs.out is None else bufs.out.detach()                # fresh alias: an output, not an input, for autograd
         lib = _lib.lib()
         x = x if x.is_contiguous() else x.contiguous()
         B, Fin, Mp = x.shape
@@ -693,72 +991,63 @@ class ChebConv(torch.autograd.Function):
         if FinK != Fin * K:
             raise ValueError('weight rows %d != Fin*K = %d' % (FinK, Fin * K))
         Wc = W.detach().contiguous()
+        b = _detached(bias)
         Mo = M // pool
-        mean = bool(bufs is not None and bufs.mean)
-        precision = getattr(bufs, 'precision', 'f32') if bufs is not None else 'f32'
+        mean, precision = bool(bufs.mean), bufs.precision
+        need_w = ctx.needs_input_grad[1]
+        wants_grad = bufs.grad_mode and any(ctx.needs_input_grad[:3])         # inference: no mask is written
         # atlas-sized graphs (<= 384 vertices, Fin, Fout <= 32, no pooling): the whole layer in one on-chip launch
         # (csrc/fused_small.hip); the stack is written only when a weight gradient will read it
         if (fused_small and pool == 1 and precision == 'f32' and not mean
                 and lib.chebgcn_fused_layer_supported(graph.handle, B, Fin, K, Fout)):
-            return ChebConv._forward_fused(ctx, x, Wc, bias, graph, K, relu, bias_kind, bufs, stack, out)
+            if not (bufs.grad_mode and need_w):
+                stack = None                      # nothing will read it (inference, frozen weights): it is never written
+            elif stack is None:
+                stack = torch.empty((K, B, Fin, Mp), dtype=torch.float32, device=x.device)
+            out = _out_buffer(given, B, Fout, M, x.device)
+            mask = torch.empty((B, Fout, Mp // 4), dtype=torch.uint8, device=x.device) if (relu and wants_grad) else None
+            nws = lib.chebgcn_fused_layer_workspace(graph.handle, B, Fin, K, Fout)
+            ws = _workspace(nws, x.device, 'fused_fwd') if nws else None
+            nbytes = 4.0 * B * M * (Fin + Fout + (Fin * (K - 1) if stack is not None else 0))
+            _lib.check(_launch('fused_layer_fwd', nbytes, 2.0 * B * M * Fin * K * Fout, lambda: lib.chebgcn_fused_layer_fwd(
+                graph.handle, _p(x), _p(Wc), _p(b), bias_kind, _p(stack), _p(out), _p(mask), _p(ws), nws, B, Fin, K, Fout,
+                int(relu), _stream())), 'fused_layer_fwd')
+            # (its backward never takes the forward form: no re-indexed weights, no links)
+            ChebConv._keep(ctx, bufs, graph, (B, M, Fin, K, Fout, 1, POOL_MAX, int(relu), bias_kind), bias,
+                           (stack, Wc, None if relu else out, mask), fold=bool(relu), fused=True)
+            return out
         if stack is None:
             stack = torch.empty((K, B, Fin, Mp), dtype=torch.float32, device=x.device)
-        # algorithmic bytes: recurrence 4*M*Fin*K per window; the contraction's
-        # compulsory traffic 4*(M*Fin*K + M*Fout/pool) per window, flops 2*M*Fin*K*Fout
+        # algorithmic bytes: recurrence 4*M*Fin*K per window; the contraction: _contract_cost
         _lib.check(_launch('recurrence_fwd', 4.0 * M * Fin * K * B, 0.0, lambda: lib.chebgcn_recurrence_fwd(
             graph.handle, _p(x), _p(stack), B, Fin, K, _stream())), 'recurrence_fwd')
+        cfg = (B, M, Fin, K, Fout, pool, pool_kind, int(relu), bias_kind)
+        # the stack feeds the weight gradient alone: without one (saliency passes) it is not kept alive until the backward
+        kept = stack if need_w else None
         if mean:
-            if not conv_mean_supported(B, M, Fin, K, Fout, pool, relu, getattr(bufs, 'precision', 'f32')):
+            if not conv_mean_supported(B, M, Fin, K, Fout, pool, relu, precision):
                 raise ValueError('cheb_conv(mean=True): layer not served (ops.conv_mean_supported)')
-            wants_grad = _grad_mode(bufs) and any(ctx.needs_input_grad[:3])
             mask = torch.empty((B, Fout, Mp // 4), dtype=torch.uint8, device=x.device) if wants_grad else None
             y = torch.empty((B, Mp), dtype=torch.float32, device=x.device)
-            b = bias.detach().contiguous() if bias is not None else None
-            _lib.check(_launch('contract_fwd', 4.0 * B * M * (Fin * K + 1), 2.0 * B * M * Fin * K * Fout,
+            _lib.check(_launch('contract_fwd', *_contract_cost(B, M, Fin, K, Fout, 1),
                                lambda: lib.chebgcn_contract_fwd_mean(_p(stack), _p(Wc), _p(b), bias_kind, _p(y), _p(mask), B, M,
                                                                      Fin, K, Fout, _stream())), 'contract_fwd_mean')
-            ctx.save_for_backward(stack if ctx.needs_input_grad[1] else None, Wc, None, mask)
-            ctx.fold, ctx.mean, ctx.fused = True, True, False
-            ctx.graph, ctx.cfg = graph, (B, M, Fin, K, Fout, pool, pool_kind, int(relu), bias_kind)
-            ctx.bias_shape = None if bias is None else tuple(bias.shape)
-            ctx.grad_bufs = (bufs.dW, bufs.dbias)
-            ctx.done = bufs.done
-            ctx.precision = 'f32'
-            ctx.pool_maps = None
-            ctx.Wt = bufs.Wt
-            ctx.link_in, ctx.link_out = bufs.link_in, None
+            ChebConv._keep(ctx, bufs, graph, cfg, bias, (kept, Wc, None, mask), fold=True, mean=True, Wt=bufs.Wt,
+                           link_in=bufs.link_in)
             return y[:, :M]                   # the logical [B, M] mean (row stride Mp): its gradient arrives dense
-        if out is None:
-            out = plane_empty(B, Fout, Mo, x.device)
-        else:
-            out = out.detach()                # fresh alias: an output, not an input, for autograd
-            if tuple(out.shape) != (B, Fout, plane_stride(Mo)) or not out.is_contiguous():
-                raise ValueError('out buffer has the wrong shape')
-        argmax = None
-        maps = bufs.pool_maps if (bufs is not None and pool > 1) else None
-        wants_grad = _grad_mode(bufs) and any(ctx.needs_input_grad[:3])       # inference: no mask is written
+        out = _out_buffer(given, B, Fout, Mo, x.device)
+        maps = bufs.pool_maps if pool > 1 else None
         if maps is not None:
             # pooling between two vertex orders: the contraction (bias, ReLU) leaves the unpooled result in the source order,
-            # one more pass gathers the clusters through LDS (csrc/pointwise.hip pool_gather_fwd_kernel)
-            b = bias.detach() if bias is not None else None
-            if b is not None and not b.is_contiguous():
-                b = b.contiguous()
+            # one more pass gathers the clusters (_pool_gather)
             y_full = plane_empty(B, Fout, M, x.device)
             contract_fwd_into(stack, Wc, b, bias_kind, y_full, None, B, M, Fin, K, Fout, 1, pool_kind, relu, precision)
             sel = torch.empty(out.shape, dtype=torch.uint8, device=x.device) if wants_grad else None
-            _lib.check(_launch('pool_gather_fwd', B * Fout * (4.0 * (M + Mo) + Mo), 0.0, lambda: lib.chebgcn_pool_gather_fwd(
-                _p(y_full), _p(maps[0]), _p(out), _p(sel), B, M, Fout, pool, pool_kind, int(relu), _stream())), 'pool_gather_fwd')
-            ctx.save_for_backward(stack if ctx.needs_input_grad[1] else None, Wc, None, sel)
-            ctx.fold, ctx.mean, ctx.fused = False, False, False
-            ctx.graph, ctx.cfg = graph, (B, M, Fin, K, Fout, pool, pool_kind, int(relu), bias_kind)
-            ctx.bias_shape = None if bias is None else tuple(bias.shape)
-            ctx.grad_bufs = (bufs.dW, bufs.dbias)
-            ctx.done = bufs.done
-            ctx.precision = precision
-            ctx.pool_maps = maps
-            ctx.Wt = bufs.Wt
-            ctx.link_in, ctx.link_out = bufs.link_in, None
+            _pool_gather(y_full, maps, out, sel, B, M, Fout, pool, pool_kind, relu)
+            ChebConv._keep(ctx, bufs, graph, cfg, bias, (kept, Wc, None, sel), precision=precision, pool_maps=maps, Wt=bufs.Wt,
+                           link_in=bufs.link_in)
             return out
+        argmax = None
         if pool > 1 and (pool_kind == POOL_MAX or relu):
             argmax = torch.empty(out.shape, dtype=torch.uint8, device=x.device)
         # pool == 1 with ReLU: contract_fwd leaves a bit per vertex (the ReLU mask) and the gradients of the
@@ -767,78 +1056,25 @@ class ChebConv(torch.autograd.Function):
         if pool == 1 and relu and wants_grad:
             # the mask also serves the separate ReluGrad pass (bf16 gradients): a byte per four vertices instead of `out`
             argmax = torch.empty((B, Fout, Mp // 4), dtype=torch.uint8, device=x.device)
-        b = bias.detach() if bias is not None else None
-        if b is not None and not b.is_contiguous():
-            b = b.contiguous()
         contract_fwd_into(stack, Wc, b, bias_kind, out, argmax, B, M, Fin, K, Fout, pool, pool_kind, relu, precision)
-        # the stack feeds the weight gradient alone: without one (saliency passes) it is not kept alive until the backward
-        ctx.save_for_backward(stack if ctx.needs_input_grad[1] else None, Wc, None if (pool == 1 and relu) else out, argmax)
-        ctx.fold, ctx.mean, ctx.fused = fold, False, False
-        ctx.graph, ctx.cfg = graph, (B, M, Fin, K, Fout, pool, pool_kind, int(relu), bias_kind)
-        ctx.bias_shape = None if bias is None else tuple(bias.shape)
-        ctx.grad_bufs = (bufs.dW, bufs.dbias) if bufs is not None else (None, None)
-        ctx.done = bufs.done if bufs is not None else None
-        ctx.precision = precision
-        ctx.pool_maps = None
-        ctx.Wt = bufs.Wt if bufs is not None else None
-        ctx.link_in = bufs.link_in if bufs is not None else None
-        ctx.link_out = lo = bufs.link_out if bufs is not None else None
-        if lo is not None:
-            # this layer's backward takes its gated dy as slab 0 of the stack its recurrence_fwd_t fills (the by_fwd arm below)
-            lo.gstack = None
-            ok = bool(gate_links and pool == 1 and relu and wants_grad and argmax is not None and precision != 'bf16'
-                      and dx_by_forward and ctx.needs_input_grad[0] and K > 1 and Fout <= Fin and graph.ordered)
-            lo.mask, lo.shape = (argmax, (K, B, Fout, Mp)) if ok else (None, None)
-        return out
-
-    @staticmethod
-    def _forward_fused(ctx, x, Wc, bias, graph, K, relu, bias_kind, bufs, stack, out):
-        lib = _lib.lib()
-        B, Fin, Mp = x.shape
-        M, Fout = graph.M, Wc.shape[1]
-        need_w = bool(_grad_mode(bufs) and ctx.needs_input_grad[1])
-        wants_grad = _grad_mode(bufs) and any(ctx.needs_input_grad[:3])
-        if not need_w:
-            stack = None                          # nothing will read it (inference, frozen weights): it is never written
-        elif stack is None:
-            stack = torch.empty((K, B, Fin, Mp), dtype=torch.float32, device=x.device)
-        if out is None:
-            out = plane_empty(B, Fout, M, x.device)
-        else:
-            out = out.detach()
-            if tuple(out.shape) != (B, Fout, Mp) or not out.is_contiguous():
-                raise ValueError('out buffer has the wrong shape')
-        mask = torch.empty((B, Fout, Mp // 4), dtype=torch.uint8, device=x.device) if (relu and wants_grad) else None
-        b = bias.detach() if bias is not None else None
-        if b is not None and not b.is_contiguous():
-            b = b.contiguous()
-        nws = lib.chebgcn_fused_layer_workspace(graph.handle, B, Fin, K, Fout)
-        ws = _workspace(nws, x.device, 'fused_fwd') if nws else None
-        nbytes = 4.0 * B * M * (Fin + Fout + (Fin * (K - 1) if stack is not None else 0))
-        _lib.check(_launch('fused_layer_fwd', nbytes, 2.0 * B * M * Fin * K * Fout, lambda: lib.chebgcn_fused_layer_fwd(
-            graph.handle, _p(x), _p(Wc), _p(b), bias_kind, _p(stack), _p(out), _p(mask), _p(ws), nws, B, Fin, K, Fout, int(relu),
-            _stream())), 'fused_layer_fwd')
-        ctx.save_for_backward(stack, Wc, None if relu else out, mask)
-        ctx.fold, ctx.mean, ctx.fused = bool(relu), False, True
-        ctx.graph, ctx.cfg = graph, (B, M, Fin, K, Fout, 1, POOL_MAX, int(relu), bias_kind)
-        ctx.bias_shape = None if bias is None else tuple(bias.shape)
-        ctx.grad_bufs = (bufs.dW, bufs.dbias) if bufs is not None else (None, None)
-        ctx.done = bufs.done if bufs is not None else None
-        ctx.precision = 'f32'
-        ctx.pool_maps = None
-        ctx.Wt = None
-        ctx.link_in = ctx.link_out = None
+        link = bufs.link_out
+        if link is not None:
+            # where this layer's backward will take its gated dy as slab 0 of the stack its recurrence_fwd_t fills (by_fwd in
+            # _bwd_choose; of the four exits this one alone makes the offer), the layer above gets the mask to gate with
+            link.gstack = None
+            ok = bool(gate_links and pool == 1 and relu and wants_grad and argmax is not None and ctx.needs_input_grad[0]
+                      and dx_by_forward_shape(graph, Fin, K, Fout, precision))
+            link.mask, link.shape = (argmax, (K, B, Fout, Mp)) if ok else (None, None)
+        ChebConv._keep(ctx, bufs, graph, cfg, bias, (kept, Wc, None if (pool == 1 and relu) else out, argmax), fold=fold,
+                       precision=precision, Wt=bufs.Wt, link_in=bufs.link_in, link_out=link)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        lib = _lib.lib()
         stack, Wc, out, argmax = ctx.saved_tensors
         dW_buf, dbias_buf = ctx.grad_bufs
         B, M, Fin, K, Fout, pool, pool_kind, relu, bias_kind = ctx.cfg
-        g = ctx.graph
-        mean = ctx.mean
-        if mean:
+        if ctx.mean:
             # every filter's dy is gout / Fout, one plane [B][Mp] per window, zero in the padding: scaled into a buffer whose
             # padding was zeroed once (one kernel per step instead of autograd's zero-fill + copy of a sliced output)
             gm = _mean_grad_buffer(B, ctx.graph.Mp, gout.device)
@@ -848,209 +1084,19 @@ class ChebConv(torch.autograd.Function):
             gout = gout.contiguous()
         dev = gout.device
         dbias = None
-        bias_job = None
         if bias_kind != BIAS_NONE and ctx.needs_input_grad[2]:
             if dbias_buf is not None:
                 _check_grad_buffer(dbias_buf, ctx.bias_shape, 'dbias')
                 dbias = dbias_buf                 # overwritten, like dW: one use per step
             else:
                 dbias = torch.zeros(ctx.bias_shape, dtype=torch.float32, device=dev)
-        # gradient wrt the input by the forward recurrence on dy (see dx_by_forward): dy is then materialised (slab 0 of the stack
-        # the recurrence fills), so the ReluGrad is not folded into the contraction gradients of this layer
-        # On graphs in length order only: there the forward recurrence kernel is the faster of the two (0.49 against 0.43 of the
-        # HBM roofline in the step).  In the caller's order the Clenshaw kernels are as fast or faster -- measured: the reference's
-        # own shape at N = 1000 / 2000 (batch 128, K = 10) 1.93 / 3.32 ms this way against 1.89 / 3.16 ms; the level-0 layers of
-        # the pooling network run their forward recurrence on two planes, the adjoint on four (common.h pick_ell)
-        by_fwd = bool(dx_by_forward and ctx.needs_input_grad[0] and not ctx.fused and K > 1 and Fout <= Fin
-                      and ctx.precision != 'bf16' and g.ordered
-                      and (not mean or (ctx.fold and dbias is not None)))
-        fold = ctx.fold and not by_fwd
-        Mo = M // pool
-        dy16 = bool(bf16_dy16 and not fold and ctx.precision == 'bf16' and pool == 1 and relu and argmax is not None
-                    and lib.chebgcn_bf16_dy16_supported(B, M, Fin, K, Fout))
-        gstack = None
-        merge_bias = False
-        if by_fwd and mean:
-            # the last layer under the fused feature mean: every filter's gradient is the plane gout / Fout; one pass gates it
-            # with the ReLU mask into slab 0 of the stack the recurrence fills and reduces the bias gradient
-            gstack = torch.empty((K, B, Fout, g.Mp), dtype=torch.float32, device=dev)
-            dy, mask = gstack[0], None
-            bws, nbws = _brelu_bwd_ws(B, M, Fout, 1, bias_kind, dev)
-            _lib.check(_launch('relu_grad_mean', B * M * (4.0 + Fout * 4.25), 0.0, lambda: lib.chebgcn_relu_grad_mean(
-                _p(gout), _p(argmax), _p(dy), _p(dbias), bias_kind, B, M, Fout, _p(bws), nbws, _stream())), 'relu_grad_mean')
-            mean = False                                  # from here on an ordinary layer with a materialised dy
-        elif fold:
-            # ReluGrad folded into the two contraction gradients (chebgcn_contract_bwd_*_relu read gout and the
-            # mask); what is left of this pass is the bias reduction, which writes nothing but dbias
-            dy, mask = gout, argmax
-            # small launches (atlas-sized layers): the per-vertex bias gradient rides in the launch that adds the weight gradient's
-            # partials (chebgcn_contract_bwd_w_relu_bias) -- one ~5 us launch less per layer
-            merge_bias = bool(merge_bias_small and dbias is not None and bias_kind == BIAS_VERTEX and not mean
-                              and ctx.needs_input_grad[1] and not PRECISIONS[ctx.precision]
-                              and lib.chebgcn_contract_bwd_w_relu_bias_merged(B, M, Fin, K, Fout))
-            if dbias is not None and not merge_bias:
-                # feeds nothing in backward: enqueued BEHIND contract_bwd_x / recurrence_bwd (the chain the next layer waits
-                # for) -- 3.88 against 3.93 ms per step at the bench shape; on the second stream it costs 4 %
-                def bias_job():
-                    bws, nbws = _brelu_bwd_ws(B, M, Fout, 1, bias_kind, dev)
-                    if mean:
-                        _lib.check(_launch('bias_grad', B * M * (4.0 + Fout * 0.25), 0.0, lambda: lib.chebgcn_bias_grad_relu_mean(
-                            _p(gout), _p(mask), _p(dbias), bias_kind, B, M, Fout, _p(bws), nbws, _stream())), 'bias_grad_relu_mean')
-                        return
-                    _lib.check(_launch('bias_grad', B * Fout * M * (4.0 + 0.25), 0.0, lambda: lib.chebgcn_brelu_pool_bwd(
-                        _p(gout), None, _p(mask), None, _p(dbias), bias_kind, B, M, Fout, 1, pool_kind, 1, _p(bws), nbws,
-                        _stream())), 'brelu_pool_bwd')
-        elif dy16:
-            # one-pass bf16 gradients of a wide layer: the ReluGrad pass writes dy as bf16 -- what the matrix cores would round it
-            # to anyway (bit-identical results), half the bytes of the largest operand of both gradients
-            dy, mask = torch.empty((B, Fout, g.Mp), dtype=torch.bfloat16, device=dev), None
-            bk = bias_kind if dbias is not None else BIAS_NONE
-            bws, nbws = _brelu_bwd_ws(B, M, Fout, 1, bk, dev)
-            _lib.check(_launch('relu_grad_bf16', B * Fout * M * (6.0 + 0.25), 0.0, lambda: lib.chebgcn_relu_grad_bf16(
-                _p(gout), _p(argmax), _p(dy), _p(dbias), bk, B, M, Fout, _p(bws), nbws, _stream())), 'relu_grad_bf16')
-        elif (by_fwd and ctx.link_out is not None and ctx.link_out.gstack is not None
-              and ctx.link_out.gstack.data_ptr() == gout.data_ptr() and tuple(gout.shape) == (B, Fout, g.Mp)):
-            # the layer above stored its input gradient gated by this layer's mask, straight into slab 0 of this stack
-            # (GateLink): what is left of the ReluGrad pass is the bias reduction, a plain sum of gated values over the windows
-            gstack, ctx.link_out.gstack = ctx.link_out.gstack, None
-            dy, mask = gstack[0], None
-            if dbias is not None:
-                # at once, not behind the layer's other gradients like the bias reduction of the `fold` arm below: dy was written
-                # by the kernel in front of this one (2.95 against 2.97-3.01 ms per step at the bench shape, same box)
-                bws, nbws = _brelu_bwd_ws(B, M, Fout, 1, bias_kind, dev)
-                _lib.check(_launch('bias_grad', B * Fout * M * 4.0, 0.0, lambda: lib.chebgcn_brelu_pool_bwd(
-                    _p(dy), None, None, None, _p(dbias), bias_kind, B, M, Fout, 1, pool_kind, 0, _p(bws), nbws,
-                    _stream())), 'brelu_pool_bwd')
-        else:
-            if ctx.link_out is not None:
-                ctx.link_out.gstack = None
-            if by_fwd:
-                gstack = torch.empty((K, B, Fout, g.Mp), dtype=torch.float32, device=dev)
-                dy, mask = gstack[0], None          # T_0 of the recurrence on dy: written in place
-            else:
-                dy, mask = torch.empty((B, Fout, g.Mp), dtype=torch.float32, device=dev), None
-            bk = bias_kind if dbias is not None else BIAS_NONE
-            if ctx.pool_maps is not None:
-                # pooled between two vertex orders: the forward's selection bytes carry the ReLU of the maximum as well
-                nbws = lib.chebgcn_pool_scatter_bwd_workspace(B, M, Fout, pool, bk)
-                bws = torch.empty(nbws, dtype=torch.uint8, device=dev) if nbws else None
-                _lib.check(_launch('pool_scatter_bwd', B * Fout * (4.0 * M + 5.0 * Mo), 0.0, lambda: lib.chebgcn_pool_scatter_bwd(
-                    _p(gout), _p(argmax), _p(ctx.pool_maps[1]), _p(dy), _p(dbias), bk, B, M, Fout, pool, pool_kind, relu,
-                    _p(bws), nbws, _stream())), 'pool_scatter_bwd')
-            else:
-                # with the ReLU mask of a pool == 1 layer `out` is not read (a byte per four vertices instead)
-                nbytes = B * Fout * M * (8.0 + 0.25) if out is None else 4.0 * B * Fout * (2 * Mo + M)
-                bws, nbws = _brelu_bwd_ws(B, M, Fout, pool, bk, dev)
-                _lib.check(_launch('brelu_pool_bwd', nbytes, 0.0, lambda: lib.chebgcn_brelu_pool_bwd(
-                    _p(gout), _p(out), _p(argmax), _p(dy), _p(dbias), bk, B, M, Fout,
-                    pool, pool_kind, relu, _p(bws), nbws, _stream())), 'brelu_pool_bwd')
-        dW = None
+        ch = _bwd_choose(ctx, gout, argmax, dbias)
+        dy, mask, gstack, bias_job = _bwd_dy(ctx, ch, gout, out, argmax, dbias)
+        dW = side = dx = None
         if ctx.needs_input_grad[1]:
-            passes = PRECISIONS[ctx.precision]
-            if passes:
-                nbytes = lib.chebgcn_contract_bwd_w_bf16_workspace(B, M, Fin, K, Fout)
-            else:
-                nbytes = lib.chebgcn_contract_bwd_w_workspace(B, M, Fin, K, Fout)
-            ws = _workspace(nbytes, dev)
-            if dW_buf is not None:
-                _check_grad_buffer(dW_buf, (Fin * K, Fout), 'dW')
-                dW = dW_buf                       # written, not accumulated: one use per step
-            else:
-                dW = torch.empty((Fin * K, Fout), dtype=torch.float32, device=dev)
-
-            def launch_bwd_w():
-                if dy16:
-                    call = lambda: lib.chebgcn_contract_bwd_w_bf16_dy16(_p(stack), _p(dy), _p(dW), _p(ws), ws.numel(), B, M, Fin,
-                                                                        K, Fout, _stream())
-                elif passes:
-                    call = lambda: lib.chebgcn_contract_bwd_w_bf16(_p(stack), _p(dy), _p(dW), _p(ws), ws.numel(), B, M, Fin,
-                                                                   K, Fout, passes, _stream())
-                elif fold and mean:
-                    call = lambda: lib.chebgcn_contract_bwd_w_relu_mean(_p(stack), _p(dy), _p(mask), _p(dW), _p(ws), ws.numel(),
-                                                                        B, M, Fin, K, Fout, _stream())
-                elif fold and merge_bias:
-                    call = lambda: lib.chebgcn_contract_bwd_w_relu_bias(_p(stack), _p(dy), _p(mask), _p(dW), _p(dbias), _p(ws),
-                                                                        ws.numel(), B, M, Fin, K, Fout, _stream())
-                elif fold:
-                    call = lambda: lib.chebgcn_contract_bwd_w_relu(_p(stack), _p(dy), _p(mask), _p(dW), _p(ws), ws.numel(), B,
-                                                                   M, Fin, K, Fout, _stream())
-                else:
-                    call = lambda: lib.chebgcn_contract_bwd_w(_p(stack), _p(dy), _p(dW), _p(ws), ws.numel(), B, M, Fin, K,
-                                                              Fout, _stream())
-                what = 'contract_bwd_w' + ('_' + ctx.precision if passes else '')
-                _lib.check(_launch(what, 4.0 * B * M * (Fin * K + Fout), 2.0 * B * M * Fin * K * Fout, call), what)
-
-            want_side = (Fout > 32) if overlap_bwd_w == 'auto' else bool(overlap_bwd_w)
-            side = _side_stream(dev) if (want_side and ctx.needs_input_grad[0] and (timers is None or not timers.active)) else None
-            if side is not None:
-                # dW does not feed dx: it runs beside contract_bwd_x / recurrence_bwd on a second stream
-                side.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(side):
-                    launch_bwd_w()
-                    if bias_job is not None and ctx.fused and bias_side_small:
-                        # atlas-sized layers: the main stream is the critical path of a chain of short launches and the second
-                        # stream has slack -- the bias reduction goes there too (on the benchmark graph that costs 4 %: it stays
-                        # behind contract_bwd_x / recurrence_bwd on the main stream)
-                        bias_job()
-                        bias_job = None
-            else:
-                launch_bwd_w()
-        else:
-            side = None
-        dx = None
-        if ctx.needs_input_grad[0] and ctx.fused:
-            # G_j = dy W_j^T on the matrix cores feeding the adjoint recurrence on chip: no gradient stack in memory
-            dx = torch.empty((B, Fin, g.Mp), dtype=torch.float32, device=dev)
-            _lib.check(_launch('fused_layer_bwd_x', 4.0 * B * M * (Fin + Fout), 2.0 * B * M * Fin * K * Fout,
-                               lambda: lib.chebgcn_fused_layer_bwd_x(g.handle, _p(dy), _p(mask), _p(Wc), _p(dx), B, Fin, K, Fout,
-                                                                     _stream())), 'fused_layer_bwd_x')
-        elif by_fwd:
-            _lib.check(_launch('recurrence_fwd_t', 4.0 * B * M * Fout * K, 0.0, lambda: lib.chebgcn_recurrence_fwd_t(
-                g.handle, _p(dy), _p(gstack), B, Fout, K, _stream())), 'recurrence_fwd_t')
-            Wt = ctx.Wt                                                                        # W'[fo*K + k][fin] = W[fin*K + k][fo]
-            if Wt is None or tuple(Wt.shape) != (Fout * K, Fin):
-                Wt = torch.empty((Fout * K, Fin), dtype=torch.float32, device=dev)
-                _lib.check(lib.chebgcn_reindex_weights(_p(Wc), _p(Wt), Fin, K, Fout, _stream()), 'reindex_weights')
-            li, gate = ctx.link_in, None
-            if (li is not None and li.mask is not None and ctx.precision == 'f32' and li.shape[1:] == (B, Fin, g.Mp)
-                    and lib.chebgcn_contract_fwd_gated_supported(B, M, Fout, K, Fin)):
-                # the layer below wants its dy as slab 0 of a gradient stack: this contraction stores it there, gated by that
-                # layer's ReLU mask
-                li.gstack = torch.empty(li.shape, dtype=torch.float32, device=dev)
-                dx, gate = li.gstack[0], li.mask
-            else:
-                dx = torch.empty((B, Fin, g.Mp), dtype=torch.float32, device=dev)
-            contract_fwd_into(gstack, Wt, None, BIAS_NONE, dx, None, B, M, Fout, K, Fin, 1, POOL_MAX, False, ctx.precision,
-                              what='contract_bwd_x', gate=gate)
-        elif ctx.needs_input_grad[0]:
-            gstack = torch.empty((K, B, Fin, g.Mp), dtype=torch.float32, device=dev)
-            passes = PRECISIONS[ctx.precision]
-            if passes:
-                nws = lib.chebgcn_contract_bwd_x_bf16_workspace(Fin, K, Fout)
-                wsx = _workspace(nws, dev, 'bwd_x_bf16')                  # its own: bwd_w may be running beside it
-                what = 'contract_bwd_x_' + ctx.precision
-                if dy16:
-                    call = lambda: lib.chebgcn_contract_bwd_x_bf16_dy16(_p(dy), _p(Wc), _p(gstack), B, M, Fin, K, Fout, _p(wsx), nws,
-                                                                        _stream())
-                else:
-                    call = lambda: lib.chebgcn_contract_bwd_x_bf16(_p(dy), _p(Wc), _p(gstack), B, M, Fin, K, Fout, passes,
-                                                                   _p(wsx), nws, _stream())
-                _lib.check(_launch(what, 4.0 * B * M * (Fin * K + Fout), 2.0 * B * M * Fin * K * Fout, call), what)
-            elif fold and mean:
-                _lib.check(_launch('contract_bwd_x', 4.0 * B * M * (Fin * K + 1), 2.0 * B * M * Fin * K * Fout,
-                                   lambda: lib.chebgcn_contract_bwd_x_relu_mean(_p(dy), _p(mask), _p(Wc), _p(gstack), B, M, Fin,
-                                                                                K, Fout, _stream())), 'contract_bwd_x_relu_mean')
-            elif fold:
-                _lib.check(_launch('contract_bwd_x', 4.0 * B * M * (Fin * K + Fout), 2.0 * B * M * Fin * K * Fout,
-                                   lambda: lib.chebgcn_contract_bwd_x_relu(_p(dy), _p(mask), _p(Wc), _p(gstack), B, M, Fin, K,
-                                                                           Fout, _stream())), 'contract_bwd_x_relu')
-            else:
-                _lib.check(_launch('contract_bwd_x', 4.0 * B * M * (Fin * K + Fout), 2.0 * B * M * Fin * K * Fout,
-                                   lambda: lib.chebgcn_contract_bwd_x(_p(dy), _p(Wc), _p(gstack), B, M, Fin, K, Fout,
-                                                                      _stream())), 'contract_bwd_x')
-            dx = torch.empty((B, Fin, g.Mp), dtype=torch.float32, device=dev)
-            _lib.check(_launch('recurrence_bwd', 4.0 * B * M * Fin * (K + 1), 0.0, lambda: lib.chebgcn_recurrence_bwd(
-                g.handle, _p(gstack), _p(dx), B, Fin, K, _stream())), 'recurrence_bwd')
+            dW, side, bias_job = _bwd_w(ctx, ch, stack, dy, mask, dbias, dW_buf, bias_job)
+        if ctx.needs_input_grad[0]:
+            dx = _bwd_x(ctx, ch, Wc, dy, mask, gstack)
         if bias_job is not None:
             bias_job()
         if side is not None:
@@ -1142,12 +1188,6 @@ def pool_maps(pool, src_order, dst_order, M, device):
     return (torch.as_tensor(pmap.astype(np.int32)).to(dev), torch.as_tensor(smap.astype(np.int32)).to(dev))
 
 
-def dx_by_forward_shape(graph, Fin, K, Fout, precision):
-    """Does a layer of this shape form its input gradient by the forward recurrence on dy (``dx_by_forward``; the shape part of
-    the rule in ``ChebConv.backward``)?  Such layers read the re-indexed weights W'[fo*K + k][fin] = W[fin*K + k][fo]."""
-    return bool(dx_by_forward and K > 1 and Fout <= Fin and resolve_precision(precision, Fin, K, Fout) != 'bf16' and graph.ordered)
-
-
 def reindex_weights_batch(Ws, shapes):
     """``[W'_l]`` for the layers ``Ws`` ([Fin*K, Fout] each, ``shapes`` = [(Fin, K, Fout)]) in ONE launch
     (chebgcn_reindex_weights_batch): W'[fo*K + k][fin] = W[fin*K + k][fo]."""
@@ -1194,23 +1234,17 @@ def conv_windows(win, W, bias, graph, K, C, pool=1, pool_kind=POOL_MAX, relu=Tru
         raise ValueError('conv_windows: stack [K, T, Mp] float32 and int32 starts expected')
     if W.shape[0] != C * K:
         raise ValueError('weight rows %d != C*K = %d' % (W.shape[0], C * K))
-    W = W.detach().contiguous()
-    b = bias.detach().contiguous() if bias is not None else None
+    W, b = _detached(W), _detached(bias)
     maps = pool_maps if pool > 1 else None
     cp = 1 if maps is not None else pool
-    Mo = M // pool
-    if out is None:
-        out = plane_empty(B, Fout, Mo, W.device)
-    elif tuple(out.shape) != (B, Fout, plane_stride(Mo)) or not out.is_contiguous():
-        raise ValueError('out buffer has the wrong shape')
+    out = _out_buffer(out, B, Fout, M // pool, W.device)
     y = plane_empty(B, Fout, M, W.device) if maps is not None else out
     _lib.check(_launch('contract_fwd_windows', 4.0 * B * M * (C * K + Fout / cp), 2.0 * B * M * C * K * Fout,
                        lambda: lib.chebgcn_contract_fwd_windows(_p(win.stack), win.T, _p(win.starts), _p(W), _p(b), bias_kind, _p(y),
                                                                 None, B, M, C, K, Fout, cp, pool_kind, int(relu), _stream())),
                'contract_fwd_windows')
     if maps is not None:
-        _lib.check(_launch('pool_gather_fwd', B * Fout * (4.0 * (M + Mo) + Mo), 0.0, lambda: lib.chebgcn_pool_gather_fwd(
-            _p(y), _p(maps[0]), _p(out), None, B, M, Fout, pool, pool_kind, int(relu), _stream())), 'pool_gather_fwd')
+        _pool_gather(y, maps, out, None, B, M, Fout, pool, pool_kind, relu)
     return out
 
 
