@@ -13,6 +13,7 @@ BIAS_NONE, BIAS_FILTER, BIAS_VERTEX = 0, 1, 2
 POOL_MAX, POOL_AVG = 0, 1
 KNN_EUCLIDEAN, KNN_COSINE, KNN_CORRELATION, KNN_DOT = 0, 1, 2, 3
 KNN_KMAX = 32
+MC_SITES = 16
 PARCEL_MEAN, PARCEL_SUM = 0, 1
 
 
@@ -132,6 +133,12 @@ SIGNATURES = {
     'chebgcn_window_stats_indexed': (_i, [_p, _i64, _p, _i64, _i, _i, _p, _p, _p, _p, _i, _i, _p, C.c_size_t, _p]),
     'chebgcn_window_drop': (_i, [_p, _p, _i, _i, _i, _i, C.c_uint32, C.c_uint32, _p, _p, _p, _f, _p]),
     'chebgcn_gather_windows_reflect': (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    'chebgcn_fc_fwd_dropout_supported': (_i, [_i, _i, _i, _i]),
+    'chebgcn_fc_fwd_dropout_workspace': (C.c_size_t, [_i, _i, _i, _i]),
+    'chebgcn_fc_fwd_dropout': (_i, [_p, _i64, _i64, _p, _p, _p, _p, C.c_size_t, _p, _i, _i, _i, _i, _i, C.c_uint32, _i, _i, C.c_uint32,
+                               _f, _p]),
+    'chebgcn_mc_reduce_supported': (_i, [_i, _i]),
+    'chebgcn_mc_reduce': (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     'chebgcn_knn_workspace': (C.c_size_t, [_i, _i, _i]),
     'chebgcn_knn': (_i, [_p, _i, _i, _i, _i, _p, _p, _p, C.c_size_t, _p]),
     'chebgcn_series_normalise': (_i, [_p, _i64, _p, _i, _i, _f, _p, _p]),

@@ -8,21 +8,12 @@
 //   reflect:  gather_windows with the channel map rho(c + tshift[w]): the window shifted in time by r inside its symmetric
 //             reflection, np.pad(x, C, 'symmetric')[r + C : r + 2 C].  Channel c of the output is plane rho(c + r) of the same
 //             C contiguous planes, so the loads stay 16 bytes per lane and coalesced; r = 0 is gather_windows' loads exactly.
+#include "aug_draw.h"
 #include "gather_piece.h"
 
 namespace chebgcn {
 
 constexpr int WD_T = 256;               // threads of the scatter: one draw each
-
-// ---- the generator (include/chebgcn.h; series.drop_vertices is its NumPy restatement) -----------------------------------------
-__device__ __forceinline__ uint32_t aug_fin(uint32_t x) {
-    x ^= x >> 16;
-    x *= CHEBGCN_AUG_MUL1;
-    x ^= x >> 15;
-    x *= CHEBGCN_AUG_MUL2;
-    x ^= x >> 16;
-    return x;
-}
 
 // thread (draw t of the B * D of the batch): window b = t / D, draw d = t % D.  Two draws of one window may name the same
 // vertex, and two threads then store to the same addresses: they store the SAME value (it depends on the channel and the
@@ -37,10 +28,7 @@ window_drop_kernel(float* __restrict__ x, const int32_t* __restrict__ win, long 
     const long long b = t / D;
     const uint32_t d = (uint32_t)(t - b * D);
     const uint32_t i = (uint32_t)win[b];                    // (enters the hash only: never an address)
-    const uint32_t a = aug_fin(aug_fin(seed) + refill);
-    const uint32_t k0 = aug_fin(a + i);
-    const uint32_t k1 = aug_fin((a ^ CHEBGCN_AUG_KEY) + i * CHEBGCN_AUG_WINDOW);
-    const uint32_t u = aug_fin(aug_fin(k0 + d) ^ k1);
+    const uint32_t u = aug_draw(aug_keys(seed, refill, i), d);          // (aug_draw.h; series.drop_vertices restates it in NumPy)
     int p = (int)__umulhi(u, (uint32_t)M);                  // (u * M) >> 32: in [0, M) by construction
     if (pos) {
         p = pos[p];

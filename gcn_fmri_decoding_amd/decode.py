@@ -161,7 +161,7 @@ class Decode(object):
     # ---------------------------------------------------------------- the method
 
     def decode_series(self, series, starts=None, stride=1, scale=None, shift=None, share='auto', batch_size=None,
-                      output='logits', max_stack_bytes=None):
+                      output='logits', max_stack_bytes=None, mc=None):
         """The model's output for every window of a scan.  ``series``: ``[T, M]`` (NumPy, any numeric dtype, or a torch
         tensor), time points x vertices in the vertex layout ``predict`` takes (``M = L[0].shape[0]``, after
         ``coarsening.perm_data``), or a list of such runs (a list returns a list; windows never cross runs).  Window ``w``
@@ -187,6 +187,13 @@ class Decode(object):
           layer of at most 32 filters, no ``scale`` / ``shift``), the windows overlap, and the graph is larger than the
           atlas sizes whose first layer already runs on chip in one launch.  ``last_decode_path`` names the path taken.
 
+        * ``mc``: ``dict(samples=32, seed=0, keep=None)`` decodes with Monte-Carlo dropout (``predict_mc``, whose keywords
+          these are): every run returns an ``uncertainty.MCResult`` -- mean probabilities, labels, entropy, expected entropy,
+          mutual information, votes and agreement per window -- instead of logits, and ``output`` is not used.  The windows
+          are numbered in the order of the starts, on across the runs of a list; the masks depend on that number alone, so
+          the result equals ``predict_mc`` on the same windows cut out by hand, on either path.  ``None`` (default): no
+          sampling, everything as described above.
+
         The two paths agree to fp32 round-off, and bit for bit wherever the first layer of the materialised path runs the
         recurrence + contraction kernels (graphs beyond the on-chip layer's 384 vertices).  Results do not depend on
         ``batch_size`` or on the chunking as long as those keep every launch on the same kernels (include/chebgcn.h: the
@@ -195,6 +202,7 @@ class Decode(object):
                                                                      output)
         if max_stack_bytes is not None and (isinstance(max_stack_bytes, bool) or int(max_stack_bytes) < 1):
             raise ValueError('decode_series: max_stack_bytes must be a positive int, got %r' % (max_stack_bytes,))
+        mc_args = None if mc is None else self._mc_dict(mc, bs)
         if self.device.type != 'cuda':
             raise RuntimeError('decode_series: the model has no device to run on (%s)' % self.device)
         scaled = scale is not None or shift is not None
@@ -210,24 +218,33 @@ class Decode(object):
         budget = STACK_BYTES if max_stack_bytes is None else int(max_stack_bytes)
         was_training = self.training_mode
         self.training_mode = False
-        results = []
+        results, first = [], 0
         try:
             with torch.no_grad():
                 tabs = self._scale_tables(scale, shift) if scaled else None
                 for run, st in zip(runs, run_starts):
                     planes = self._stage_series(run)
-                    res = torch.empty((len(st), int(self.M[-1])), dtype=torch.float32, device=self.device)
+                    if mc_args is not None:
+                        from .uncertainty import MCHead          # (here: uncertainty imports series, which imports this module)
+                        self._mc = MCHead(self, len(st), mc_args[0], mc_args[1], mc_args[2], first_window=first)
+                        first += len(st)
+                    # (Monte-Carlo decoding: the head writes into the MCHead's buffers; there are no logits to collect)
+                    res = None if mc_args is not None else torch.empty((len(st), int(self.M[-1])), dtype=torch.float32,
+                                                                       device=self.device)
                     if shared:
                         self._decode_shared(planes, st, bs, res, budget)
                     else:
                         self._decode_materialised(planes, st, bs, res, tabs)
+                    if mc_args is not None:
+                        results.append(self._mc.result())
+                        continue
                     if output == 'probabilities':
                         res = self.probabilities(res)
                     elif output == 'labels':
                         res = self.prediction(res).to(torch.int64)
                     results.append(res.cpu().numpy())
         finally:
-            self.training_mode, self._windows = was_training, None
+            self.training_mode, self._windows, self._mc = was_training, None, None
         self.last_decode_path = 'shared' if shared else 'materialised'
         return results if many else results[0]
 
@@ -268,7 +285,11 @@ class Decode(object):
             x = planes[st[b0:b0 + bs, None] + offs[None, :]]           # [B, C, Mp]: the windows, a strided copy
             if tabs is not None:
                 x = x * tabs[0] + tabs[1]
-            res[b0:b0 + bs] = self._inference_storage(self.as_internal(x), 1)
+            if self._mc is not None:
+                self._mc.at(np.arange(b0, min(b0 + bs, len(starts))))
+            out = self._inference_storage(self.as_internal(x), 1)
+            if res is not None:
+                res[b0:b0 + bs] = out
 
     def _decode_shared(self, planes, starts, bs, res, budget):
         lib = _lib.lib()
@@ -285,8 +306,11 @@ class Decode(object):
             where = torch.as_tensor(idx.astype(np.int64)).to(self.device)
             for b0 in range(0, len(idx), bs):
                 self._windows = Windows(stack, Tc, rel[b0:b0 + bs])
+                if self._mc is not None:
+                    self._mc.at(idx[b0:b0 + bs])
                 try:
                     logits = self._inference_storage(None, 1)
                 finally:
                     self._windows = None
-                res.index_copy_(0, where[b0:b0 + bs], logits)
+                if res is not None:
+                    res.index_copy_(0, where[b0:b0 + bs], logits)

@@ -33,6 +33,7 @@ from ._lib import BIAS_FILTER, BIAS_NONE, BIAS_VERTEX, POOL_AVG, POOL_MAX, plane
 from .attribution import Attribution
 from .decode import Decode
 from .series import Series, WindowSet
+from .uncertainty import Uncertainty
 
 
 class _Spec:
@@ -90,10 +91,10 @@ class InternalPlanes(object):
         return self
 
 
-class base_model(Attribution, Decode, Series):
+class base_model(Attribution, Decode, Series, Uncertainty):
     """Counterpart of ``base_model`` (:18-355): run-time interface + variable helpers.  The attribution maps (``saliency``,
     ``occlusion``, ``shapley``, ``gradcam`` and their ``*_maps``) come from ``attribution.Attribution``, ``decode_series`` from
-    ``decode.Decode``, ``stage_windows`` / ``fit_series`` from ``series.Series``."""
+    ``decode.Decode``, ``stage_windows`` / ``fit_series`` from ``series.Series``, ``predict_mc`` from ``uncertainty.Uncertainty``."""
 
     def __init__(self, config=None):
         self.regularizers = []          # names of L2-regularised variables (:345, :353)
@@ -135,6 +136,8 @@ class base_model(Attribution, Decode, Series):
         self._pass = None
         # inside decode_series' shared path: the decode.Windows the first conv layer contracts its windows out of
         self._windows = None
+        # inside predict_mc / decode_series(mc=...): the uncertainty.MCHead the head samples with and writes its measures to
+        self._mc = None
 
     # ---------------------------------------------------------------- run-time API
 
@@ -1387,6 +1390,8 @@ class cgcnn(base_model):
 
     def _head(self, x, dropout):
         """reduce_mean output -> FC stack with dropout -> logits (:674-682)."""
+        if self._mc is not None:
+            return self._mc.head(self, x)              # Monte-Carlo dropout: fc1 once, the layers behind it once per sample
         self._fc_on_vertices = True                    # (build pass: the next weight variable has one row per vertex)
         for i, Mi in enumerate(self.M[:-1]):
             with self.variable_scope('fc{}'.format(i + 1)):
@@ -1631,6 +1636,10 @@ class finetuning_cgcnn(cgcnn):
 
     saliency_maps = saliency
 
+    def _mc_refusal(self):
+        raise NotImplementedError('finetuning_cgcnn: its head never drops out, so Monte-Carlo dropout has nothing to sample; '
+                                  'predict_mc runs on cgcnn')
+
     def _cam_level(self, i):
         if i + 1 < len(self.p):
             return super()._cam_level(i)
@@ -1836,6 +1845,12 @@ class model_perf(object):
         logits (probabilities, labels) of every window of a scan, or of a list of runs."""
         model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
         return model.decode_series(series, **kw)
+
+    def predict_mc(s, ckp_path, data, batch_size=128, **kw):
+        """``base_model.predict_mc`` (``kw``: its keywords) of the model ``predict`` would restore from ``ckp_path``: the
+        Monte-Carlo dropout probabilities, labels and uncertainty measures of every window of ``data``."""
+        model = s._restore(ckp_path, batch_size, kw.pop('model', None), kw.pop('config', None))
+        return model.predict_mc(data, **kw)
 
     def predict(s, ckp_path, test_data, test_labels, target_name=None, batch_size=128, trial_dura=17,
                 flag_starttr=False, sub_name=None, model=None, config=None):

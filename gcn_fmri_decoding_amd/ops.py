@@ -1887,3 +1887,91 @@ def gradcam_map(A, G, method, order, nw, N, P, relu, out):
         _p(A), _p(G) if alpha is None else None, _p(alpha), _p(order), nw, F, N, P, int(bool(relu)), _p(out), N * P,
         _stream())), 'gradcam_map')
     return out
+
+
+# ------------------------------------------------------------------------------------ Monte-Carlo dropout (uncertainty.py)
+
+MC_SAMPLES_MAX = 1024        # chebgcn_mc_reduce_supported
+MC_CLASSES_MAX = 64
+
+
+def fc_forward_native(x, W, b, relu, who):
+    """``act(x @ W + b)`` on chebgcn_fc_fwd at every size it serves; a size it does not serve raises (``who`` names the caller):
+    never the vendor GEMM.  ``x`` [B, I] may be any view (ops._fc_rows copies rows the kernel cannot take)."""
+    _require_cuda(x, W, b)
+    B, I = x.shape
+    O = W.shape[1]
+    L = _lib.lib()
+    if not L.chebgcn_fc_fwd_supported(B, I, O):
+        raise ValueError('%s: the FC layer %d x %d x %d is outside the range of chebgcn_fc_fwd' % (who, B, I, O))
+    rows = _fc_rows(x.detach())
+    Wc, bc = W.detach().contiguous(), b.detach().contiguous()
+    y = torch.empty((B, O), dtype=torch.float32, device=x.device)
+    nws = L.chebgcn_fc_fwd_workspace(B, I, O)
+    ws = _workspace(nws, x.device, 'fc_fwd') if nws else None
+    _lib.check(_launch('fc_fwd', 4.0 * (B * I + I * O + B * O), 2.0 * B * I * O, lambda: L.chebgcn_fc_fwd(
+        _p(rows), rows.stride(0), _p(Wc), _p(bc), _p(y), _p(ws), nws, B, I, O, 1 if relu else 0, _stream())), 'fc_fwd')
+    return y
+
+
+def _fc_sample_rows(x):
+    """``x`` [S, B, I] as sample matrices the dropout FC kernel takes (unit stride along I, row and sample strides multiples of 4
+    floats, 16-byte aligned): itself where it is such a tensor, else a copy with rows padded by zeros."""
+    S, B, I = x.shape
+    if (x.stride(2) == 1 and x.stride(1) % 4 == 0 and x.stride(1) >= I and x.stride(0) % 4 == 0
+            and x.stride(0) >= (B - 1) * x.stride(1) + I and x.data_ptr() % 16 == 0):
+        return x
+    buf = torch.zeros((S, B, (I + 3) & ~3), dtype=torch.float32, device=x.device)
+    buf[:, :, :I].copy_(x)
+    return buf[:, :, :I]
+
+
+def fc_forward_dropout(x, W, b, relu, win, S, s0, layer, seed, threshold, inv_keep):
+    """``S`` Monte-Carlo dropout samples of one FC layer (chebgcn_fc_fwd_dropout): ``y[s] = act((mask_s * x_s / keep) @ W + b)``,
+    float32 ``[S, B, O]``.  ``x``: ``[B, I]``, one input shared by every sample, or ``[S, B, I]``; ``win``: int32 device ``[B]``, the
+    window number of every row; ``s0``: the number of the first sample; ``layer``: the dropout site; ``threshold`` / ``inv_keep``:
+    ``uncertainty.dropout_threshold``.  A size the kernel does not serve raises: there is no other path."""
+    _require_cuda(x, W, b, win)
+    shared = x.dim() == 2
+    rows = _fc_rows(x.detach()) if shared else _fc_sample_rows(x.detach())
+    B, I = rows.shape[-2:]
+    O = W.shape[1]
+    S = int(S)
+    if not shared and rows.shape[0] != S:
+        raise ValueError('fc_forward_dropout: x holds %d samples, S = %d' % (rows.shape[0], S))
+    if win.dtype != torch.int32 or not win.is_contiguous() or win.numel() != B:
+        raise ValueError('fc_forward_dropout: win must be a contiguous int32 vector with a window number per row')
+    L = _lib.lib()
+    if not L.chebgcn_fc_fwd_dropout_supported(S, B, I, O):
+        raise ValueError('fc_forward_dropout: %d samples of the FC layer %d x %d x %d are outside the range of '
+                         'chebgcn_fc_fwd_dropout' % (S, B, I, O))
+    Wc, bc = W.detach().contiguous(), b.detach().contiguous()
+    y = torch.empty((S, B, O), dtype=torch.float32, device=rows.device)
+    nws = L.chebgcn_fc_fwd_dropout_workspace(S, B, I, O)
+    ws = _workspace(nws, rows.device, 'fc_fwd_dropout') if nws else None
+    ldx, sx = (rows.stride(0), 0) if shared else (rows.stride(1), rows.stride(0))
+    _lib.check(_launch('fc_fwd_dropout', 4.0 * ((1 if shared else S) * B * I + I * O + S * B * O), 2.0 * S * B * I * O,
+                       lambda: L.chebgcn_fc_fwd_dropout(_p(rows), ldx, sx, _p(Wc), _p(bc), _p(y), _p(ws), nws, _p(win), S, B, I, O,
+                                                        1 if relu else 0, int(seed), int(s0), int(layer), int(threshold),
+                                                        float(inv_keep), _stream())), 'fc_fwd_dropout')
+    return y
+
+
+def mc_reduce(logits):
+    """The uncertainty measures of sampled logits float32 ``[S, B, C]`` (chebgcn_mc_reduce), as device tensors: ``probabilities``
+    ``[B, C]``, ``entropy``, ``expected_entropy``, ``mutual_information``, ``agreement`` float32 ``[B]``, ``labels`` int32 ``[B]``,
+    ``votes`` int32 ``[B, C]``."""
+    _require_cuda(logits)
+    z = logits.detach().contiguous()
+    S, B, C = z.shape
+    if z.dtype != torch.float32 or not _lib.lib().chebgcn_mc_reduce_supported(S, C):
+        raise ValueError('mc_reduce: float32 logits of 1 <= S <= %d samples and 1 <= C <= %d classes, got %s [%d, %d, %d]'
+                         % (MC_SAMPLES_MAX, MC_CLASSES_MAX, z.dtype, S, B, C))
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=z.device)
+    i = lambda *shape: torch.empty(shape, dtype=torch.int32, device=z.device)
+    out = dict(probabilities=f(B, C), entropy=f(B), expected_entropy=f(B), mutual_information=f(B), labels=i(B), votes=i(B, C),
+               agreement=f(B))
+    _lib.check(_launch('mc_reduce', 4.0 * (S * B * C + 2 * B * C + 5 * B), 0.0, lambda: _lib.lib().chebgcn_mc_reduce(
+        _p(z), S, B, C, _p(out['probabilities']), _p(out['entropy']), _p(out['expected_entropy']), _p(out['mutual_information']),
+        _p(out['labels']), _p(out['votes']), _p(out['agreement']), _stream())), 'mc_reduce')
+    return out

@@ -717,6 +717,50 @@ int chebgcn_gather_windows_reflect(const float* series, int64_t Ttot, const int6
                                    const int32_t* sample, const float* scale, const float* shift, float* out, int B, int M, int C,
                                    chebgcn_stream stream);
 
+/* ---- Monte-Carlo dropout: S stochastic passes of the head from one pass of the trunk (models_gcn.base_model.predict_mc) ----------
+ * Dropout exists only behind the hidden FC layers of the head (tf.nn.dropout, models_gcn.py:674-682): dropout site j (0-based)
+ * follows fc{j+1}.  The mask is a pure function of (seed, sample, site, window, feature) on the generator above:
+ *     u    = chebgcn_aug_draw(seed, refill = sample * CHEBGCN_MC_SITES + site, i = window, d = feature)
+ *     kept = u < T,   T = min((uint64_t)(keep * 2^32), 2^32 - 1)   (computed by the CALLER from the float64 keep, passed as uint32)
+ *     value = kept ? x * inv_keep : +0,   inv_keep = (float)(1 / keep), ONE rounded float32 product (never part of an fma)
+ * `window` is the index of the window in the caller's data, never its place in a batch: results do not depend on the batching.
+ * uncertainty.dropout_keep restates the mask in NumPy.  No mask is ever stored.
+ *
+ * fc_fwd_dropout: chebgcn_fc_fwd for S samples of one layer,
+ *     y[s][b][o] = act( sum_{i<I} value(s0 + s, layer, win[b], i; x_s[b][i]) * W[i][o] + bias[o] ),   s < S, y float32 [S][B][O]
+ *   x_s = x + s * sample_stride, B rows of row stride ldx >= I each (elements; 16-byte aligned, ldx and sample_stride multiples
+ *   of 4, whole rows readable: chebgcn_fc_fwd's rules; values past I in a row never reach the product).  sample_stride == 0: one
+ *   [B][ldx] matrix shared by every sample (the first site: fc1's output is computed once); else >= (B - 1) * ldx + I.  win: int32
+ *   [B] (device), the window number of every row; it enters the generator as a uint32 and is never an address.  s0 >= 0: the
+ *   number of the launch's first sample (callers send S samples in chunks); 0 <= layer < CHEBGCN_MC_SITES.  The tiling, the
+ *   order of every sum and the split of the reduction across workgroups are chebgcn_fc_fwd's (the splits count the tiles of all S
+ *   samples): deterministic, no atomics.  Served: chebgcn_fc_fwd_dropout_supported -- I <= 2^20, S * B * O <= 2^20 per launch,
+ *   S <= 32768; CHEBGCN_EUNSUPPORTED beyond, or for an unaligned x / ldx / sample_stride.  workspace: at least
+ *   chebgcn_fc_fwd_dropout_workspace() bytes of device scratch (0: none needed).  chebgcn_last_dispatch():
+ *   fc_fwd_dropout_kernel<shared | per_sample>, or fc_fwd_dropout_kernel<shared | per_sample, split> + fc_fwd_reduce_kernel.
+ * mc_reduce: logits float32 [S][B][C] -> per window b, with p_s = softmax(logits[s][b]) (maximum subtracted) and
+ *   H(p) = -sum_c p_c log p_c in nats, 0 log 0 = 0:
+ *     mean_p[b][c]           = (sum_s p_s[c]) / S        (float32 [B][C]; the sum in sample order, one division)
+ *     entropy[b]             = H(mean_p)
+ *     expected_entropy[b]    = (sum_s H(p_s)) / S
+ *     mutual_information[b]  = max(0, entropy - expected_entropy)   (>= 0 in exact arithmetic; the two sums are rounded apart)
+ *     label[b]               = the first maximum of mean_p[b]        (int32)
+ *     votes[b][c]            = #{s : c is the first maximum of logits[s][b]}, a NaN counting as the largest value
+ *                              (chebgcn_saliency_seed's rule; int32 [B][C])
+ *     agreement[b]           = votes[b][label[b]] / S
+ *   Never NaN for finite logits (saturated softmaxes included).  One wave per window; fixed-order sums (float64 over the samples),
+ *   no atomics: reruns are bit-identical.  Served: chebgcn_mc_reduce_supported -- 1 <= C <= 64, 1 <= S <= 1024;
+ *   CHEBGCN_EUNSUPPORTED beyond, before any launch.  chebgcn_last_dispatch(): mc_reduce_kernel. */
+#define CHEBGCN_MC_SITES 16
+int chebgcn_fc_fwd_dropout_supported(int S, int B, int I, int O);
+size_t chebgcn_fc_fwd_dropout_workspace(int S, int B, int I, int O);
+int chebgcn_fc_fwd_dropout(const float* x, int64_t ldx, int64_t sample_stride, const float* W, const float* bias, float* y,
+                           void* workspace, size_t workspace_bytes, const int32_t* win, int S, int B, int I, int O, int relu,
+                           uint32_t seed, int s0, int layer, uint32_t threshold, float inv_keep, chebgcn_stream stream);
+int chebgcn_mc_reduce_supported(int S, int C);
+int chebgcn_mc_reduce(const float* logits, int S, int B, int C, float* mean_p, float* entropy, float* expected_entropy,
+                      float* mutual_information, int32_t* label, int32_t* votes, float* agreement, chebgcn_stream stream);
+
 /* ---- kNN brain graphs on the device (graph.knn_device / graph.connectivity_graph) ------------------------------------------
  * feat: [D][Np(N)] fp32, feature-major planes of N vertices (the staged-series layout with D = time; coordinates are
  * transposed by the caller), zero in the pad.  For every vertex i the k nearest OTHER vertices under `metric`:
