@@ -15,6 +15,8 @@ KNN_EUCLIDEAN, KNN_COSINE, KNN_CORRELATION, KNN_DOT = 0, 1, 2, 3
 KNN_KMAX = 32
 MC_SITES = 16
 PARCEL_MEAN, PARCEL_SUM = 0, 1
+FILTER_AUTO, FILTER_ROLLING, FILTER_STACK = 0, 1, 2
+FILTER_JMAX, FILTER_KMAX = 8, 256
 
 
 class ChebgcnError(RuntimeError):
@@ -145,6 +147,8 @@ SIGNATURES = {
     'chebgcn_parcellate_query': (_i, [_i]),
     'chebgcn_parcellate': (_i, [_p, _i64, _p, _p, _i64, _p, _p, _i64, _i64, _i, _i, _i, _p]),
     'chebgcn_parcel_expand': (_i, [_p, _p, _p, _i64, _i, _i, _f, _p]),
+    'chebgcn_cheb_filter_workspace': (C.c_size_t, [_p, _i, _i, _i, _i]),
+    'chebgcn_cheb_filter': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

@@ -527,6 +527,41 @@ def parcel_expand(maps, region_of, fill=0.0, out=None):
     return out
 
 
+def cheb_filter_workspace(graph, nplanes, K, J, arm=_lib.FILTER_AUTO):
+    """Bytes of scratch ``cheb_filter`` takes for this launch (chebgcn_cheb_filter_workspace): two slabs of ``nplanes`` planes
+    in the rolling arm, K in the stack arm; ``arm = 0`` answers for the arm the library would choose."""
+    return int(_lib.lib().chebgcn_cheb_filter_workspace(graph.handle, int(nplanes), int(K), int(J), int(arm)))
+
+
+def cheb_filter(graph, x, coeff, arm=_lib.FILTER_AUTO, out=None):
+    """``y[j] = sum_k coeff[j, k] T_k(L~) x`` (chebgcn_cheb_filter): ``x`` contiguous float32 plane storage ``[..., Mp]`` in the
+    graph's vertex order (every leading axis counts planes), ``coeff`` float32 ``[J, K]`` on the device, 1 <= J <= 8,
+    1 <= K <= 256 -> ``out`` float32 ``[J, ..., Mp]``.  ``arm``: 0 automatic, 1 rolling (two work slabs, any graph), 2 stack (K
+    slabs, the on-chip / ordered recurrence kernels).  x is not written; the pad of ``out`` is scratch."""
+    _require_cuda(x, coeff, out)
+    Mp = graph.Mp
+    if x.dtype != torch.float32 or x.dim() < 1 or x.shape[-1] != Mp or not x.is_contiguous() or x.numel() == 0:
+        raise _lib.ChebgcnError('cheb_filter: x must be contiguous float32 planes [..., %d]' % Mp)
+    if coeff.dtype != torch.float32 or coeff.dim() != 2 or not coeff.is_contiguous():
+        raise _lib.ChebgcnError('cheb_filter: coeff must be a contiguous float32 [J, K] device tensor')
+    J, K = int(coeff.shape[0]), int(coeff.shape[1])
+    nplanes = x.numel() // Mp
+    shape = (J,) + tuple(x.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.ChebgcnError('cheb_filter: out must be contiguous float32 %r' % (shape,))
+    lib = _lib.lib()
+    nws = int(lib.chebgcn_cheb_filter_workspace(graph.handle, nplanes, K, J, int(arm)))
+    ws = _workspace(nws, x.device, 'cheb_filter') if nws else None
+    slab = 4.0 * nplanes * Mp
+    steps = max(K - 1, 1)
+    _lib.check(_launch('cheb_filter', slab * (steps * (3 + 2 * J) + 1), 2.0 * nplanes * (graph.nnz * (K - 1) + graph.M * K * J),
+                       lambda: lib.chebgcn_cheb_filter(graph.handle, _p(x), _p(coeff), _p(out), _p(ws), nplanes, K, J, int(arm),
+                                                       _stream())), 'cheb_filter')
+    return out
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------
@@ -1502,17 +1537,23 @@ def nadam_step_sq_all(p, g, m, v, n_reg, lr_t, sq_partials, beta1=0.9, beta2=0.9
     return nparts
 
 
-def planes_to_rows(planes, M, order=None, ld=None):
+def planes_to_rows(planes, M, order=None, ld=None, out=None):
     """``tf.reshape(conv, [N, M*F])`` (models_gcn.py:805-806) of plane storage ``[B, F, Mp]``: ``[B, ld]`` rows (``ld``
     defaults to M*F rounded up to 4; the columns past M*F are left unwritten), element ``m*F + f`` = vertex m (the caller's
     order), filter f.  ``order``: int32 device tensor, internal position -> reference vertex, or None (planes in the caller's
-    order)."""
-    _require_cuda(planes)
+    order).  ``out``: float32 ``[B, >= M*F]`` with contiguous rows (any row stride) to write into instead of a new tensor."""
+    _require_cuda(planes, out)
     B, F, Mp = planes.shape
     if Mp != plane_stride(M) or not planes.is_contiguous():
         raise ValueError('planes_to_rows: planes of %d vertices expected' % M)
-    ld = ld or ((M * F + 3) & ~3)
-    rows = torch.empty((B, ld), dtype=torch.float32, device=planes.device)
+    if out is not None:
+        if out.dim() != 2 or out.shape[0] != B or out.shape[1] < M * F or out.dtype != torch.float32:
+            raise ValueError('planes_to_rows: out must be float32 [%d, >= %d]' % (B, M * F))
+        ld = _rows_of(out, int(out.shape[1]), 'planes_to_rows: out')
+        rows = out
+    else:
+        ld = ld or ((M * F + 3) & ~3)
+        rows = torch.empty((B, ld), dtype=torch.float32, device=planes.device)
     _lib.check(_launch('planes_to_rows', 8.0 * B * M * F, 0.0, lambda: _lib.lib().chebgcn_planes_to_rows(
         _p(planes), _p(rows), _p(order), B, M, F, ld, _stream())), 'planes_to_rows')
     return rows

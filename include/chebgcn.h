@@ -837,6 +837,31 @@ int chebgcn_parcellate(const float* x, int64_t ldx, const int32_t* ptr, const in
 int chebgcn_parcel_expand(const float* maps, const int32_t* region_of, float* out, int64_t B, int R, int V, float fill,
                           chebgcn_stream stream);
 
+/* ---- graph filters: y = h(L) x with fixed Chebyshev coefficients (filters.GraphFilter) ------------------------------------------
+ * For every filter j < J and plane p < nplanes
+ *     y[j][p] = sum_{k<K} coeff[j][k] * T_k(L~) x[p],    T_0 = x, T_1 = L~ x, T_k = 2 L~ T_{k-1} - T_{k-2},
+ * summed in ascending k: coeff[j][0] * x as a rounded product, then one fmaf per order.  x: [nplanes][Mp]; coeff: float32 [J][K]
+ * in DEVICE memory (a call uploads nothing); y: [J][nplanes][Mp].  x is never written; y may not overlap x; the pad [M, Mp) of
+ * every plane of y and of the workspace is scratch (it may be written, it never reaches [0, M)).  The call does not synchronise
+ * and does not allocate.  1 <= J <= 8, 1 <= K <= 256, 1 <= nplanes < 2^30; x, y and workspace 16-byte aligned.
+ * arm: 0 automatic, 1 rolling, 2 stack.
+ *   rolling  one launch of cheb_filter_step_kernel<P> per order (K == 1: one scale pass of the same kernel, no gather).  A thread
+ *            owns one row of L~ for P consecutive planes (P = 4 from nplanes >= 4, the last group guarded; else 1), sums the row
+ *            as one fmaf chain in the order of the CSR the handle was created from, stores T_k over T_{k-2} and adds it into the
+ *            J accumulators.  Workspace: TWO slabs, 2 * nplanes * Mp * 4 bytes, whatever K and J.  Any graph; any nplanes in
+ *            range (plane groups beyond the grid are looped over).  A plane's result is a function of that plane alone:
+ *            bit-identical alone or among others, and from run to run.
+ *   stack    the dispatch of chebgcn_recurrence_fwd into a workspace of K slabs, then one streaming launch of
+ *            cheb_filter_mix_kernel (16-byte accesses, every stack element read once for all J filters).  Needs a handle with an
+ *            on-chip or ordered image (chebgcn_graph_query 3 or 12), CHEBGCN_EUNSUPPORTED otherwise; K == 1 mixes x directly.
+ *   automatic: stack when the handle has such an image and K > 1, rolling otherwise.
+ * The arms differ in the order inside a row sum of L~ and agree to fp32 round-off, not bit for bit.
+ * chebgcn_cheb_filter_workspace: bytes of the arm the call would take (0 for a NULL handle or arguments out of range).
+ * chebgcn_last_dispatch(): cheb_filter_step_kernel<4 | 1>, or <the recurrence kernel> + cheb_filter_mix_kernel. */
+size_t chebgcn_cheb_filter_workspace(const chebgcn_graph* g, int nplanes, int K, int J, int arm);
+int chebgcn_cheb_filter(const chebgcn_graph* g, const float* x, const float* coeff, float* y, void* workspace, int nplanes, int K,
+                        int J, int arm, chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose
