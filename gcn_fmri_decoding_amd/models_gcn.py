@@ -31,6 +31,7 @@ from . import graph as graph_mod
 from . import ops
 from ._lib import BIAS_FILTER, BIAS_NONE, BIAS_VERTEX, POOL_AVG, POOL_MAX, plane_stride
 from .attribution import Attribution
+from .crossval import CrossValidate, CVResult  # noqa: F401
 from .decode import Decode
 from .series import Series, WindowSet
 from .uncertainty import Uncertainty
@@ -91,10 +92,11 @@ class InternalPlanes(object):
         return self
 
 
-class base_model(Attribution, Decode, Series, Uncertainty):
+class base_model(Attribution, Decode, Series, Uncertainty, CrossValidate):
     """Counterpart of ``base_model`` (:18-355): run-time interface + variable helpers.  The attribution maps (``saliency``,
     ``occlusion``, ``shapley``, ``gradcam`` and their ``*_maps``) come from ``attribution.Attribution``, ``decode_series`` from
-    ``decode.Decode``, ``stage_windows`` / ``fit_series`` from ``series.Series``, ``predict_mc`` from ``uncertainty.Uncertainty``."""
+    ``decode.Decode``, ``stage_windows`` / ``fit_series`` from ``series.Series``, ``predict_mc`` from ``uncertainty.Uncertainty``,
+    ``cross_validate_series`` / ``cross_validate_events`` from ``crossval.CrossValidate``."""
 
     def __init__(self, config=None):
         self.regularizers = []          # names of L2-regularised variables (:345, :353)

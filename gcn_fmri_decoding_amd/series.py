@@ -20,7 +20,10 @@ channel (the windows of an event design, ``events.match_events``: ``stage_window
 ``WindowSet.augment`` makes the set stand for ``copies`` perturbed copies of itself (the reference's ``train_dataarg`` /
 ``drop_rate``): vertex dropout and a time shift inside the window's symmetric reflection, drawn by a counter-based generator
 (``drop_vertices`` / ``time_shifts``, the NumPy restatement of the one in include/chebgcn.h), applied while a batch is gathered
-(chebgcn_gather_windows_reflect, chebgcn_window_drop) and drawn anew at every ``refill``."""
+(chebgcn_gather_windows_reflect, chebgcn_window_drop) and drawn anew at every ``refill``.
+
+``WindowSet.select`` makes a VIEW: a set of the same kind over some of the runs that shares the planes and has tables of its own
+(``select_runs``) -- what a fold of ``crossval.CrossValidate`` is."""
 import numpy as np
 import torch
 
@@ -49,19 +52,45 @@ def check_seed(seed, name, what):
     return int(seed)
 
 
-def row_table(run_lengths, run_starts, C):
+def run_offsets(run_lengths):
+    """The first row of every run in the concatenation of the runs, int64."""
+    return np.concatenate([[0], np.cumsum([int(t) for t in run_lengths])[:-1]]).astype(np.int64)
+
+
+def row_table(run_lengths, run_starts, C, offsets=None):
     """The windows of a list of runs as rows of their concatenation: ``(rows, lo, hi)`` int64 ``[S]`` -- the global row of each
     window's first time point (run offset + start; runs in order, the starts of a run in the caller's order) and the first /
-    last row a window of that run may start at (what ``jitter_rows`` clips to)."""
+    last row a window of that run may start at (what ``jitter_rows`` clips to).  ``offsets``: the first row of every run where
+    the runs are not the whole concatenation in order (the runs of a view, ``select_runs``)."""
     rows, lo, hi = [], [], []
-    off = 0
-    for T, st in zip(run_lengths, run_starts):
-        st = np.asarray(st, np.int64)
+    offsets = run_offsets(run_lengths) if offsets is None else offsets
+    for T, st, off in zip(run_lengths, run_starts, offsets):
+        st, off = np.asarray(st, np.int64), int(off)
         rows.append(off + st)
         lo.append(np.full(len(st), off, np.int64))
         hi.append(np.full(len(st), off + int(T) - int(C), np.int64))
-        off += int(T)
     return np.concatenate(rows), np.concatenate(lo), np.concatenate(hi)
+
+
+def select_runs(run_lengths, offsets, run_windows, runs, what='select'):
+    """The table arithmetic of a view over the runs ``runs`` (positions into the set's runs, any order, no repeats) of a set
+    whose runs have ``run_lengths`` time points, begin at the rows ``offsets`` of the planes and hold ``run_windows`` windows:
+    ``(windows, lengths, offsets, counts)`` -- the int64 indices of the set's original windows that belong to those runs, run
+    by run in the order of ``runs`` and inside a run in the set's order, and the lengths, first rows and window counts of the
+    selected runs.  Host only."""
+    a = np.asarray(runs)
+    if a.ndim != 1 or a.size == 0 or a.dtype.kind not in 'iu':
+        raise ValueError('%s: runs must be a non-empty 1-D int array of run positions, got %s %s' % (what, a.dtype, a.shape))
+    a = a.astype(np.int64)
+    n = len(run_lengths)
+    if a.min() < 0 or a.max() >= n:
+        raise ValueError('%s: every run position must lie in [0, %d); got %d ... %d' % (what, n, a.min(), a.max()))
+    if len(np.unique(a)) != len(a):
+        raise ValueError('%s: a run is named twice in %s' % (what, a.tolist()))
+    counts = np.asarray(run_windows, np.int64)
+    first = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)      # the first window of every run
+    windows = np.concatenate([first[r] + np.arange(counts[r], dtype=np.int64) for r in a])
+    return windows, np.asarray(run_lengths, np.int64)[a], np.asarray(offsets, np.int64)[a], counts[a]
 
 
 def jitter_rows(rows, lo, hi, jitter, rng):
@@ -237,12 +266,14 @@ class WindowSet(object):
     become windows on the host (``_originals``) and on the device (``_gather``, ``_stats``), and what the mix table of a plan
     holds (``_mix_table``: ``[S', smax]`` keys)."""
 
-    def __init__(self, owner, planes, run_lengths, run_windows, M, C):
+    def __init__(self, owner, planes, run_lengths, run_windows, M, C, offsets=None):
         self.owner, self.planes = owner, planes
         self.run_lengths = [int(t) for t in run_lengths]
         self.run_windows = [int(n) for n in run_windows]                # windows of every run
-        offs = np.concatenate([[0], np.cumsum(self.run_lengths)[:-1]]).astype(np.int64)
-        self.offsets = np.repeat(offs, self.run_windows)                # run offset of every window: start = row - offset
+        # the first row of every run in ``planes``: the runs one behind the other, or -- of a view (``select``) -- wherever the
+        # parent staged them
+        self.run_offsets = run_offsets(self.run_lengths) if offsets is None else np.asarray(offsets, np.int64).copy()
+        self.offsets = np.repeat(self.run_offsets, self.run_windows)    # run offset of every window: start = row - offset
         self.shape = self.shape_base = (int(sum(self.run_windows)), int(M), int(C))   # shape_base: the originals', whatever plan
         self.tables = None              # (scale, shift) device [C, Mp], internal order
         self.scaler = None              # the same as NumPy [M, C] in the caller's order
@@ -304,6 +335,47 @@ class WindowSet(object):
         self.scaler = (self._caller_order(scale), self._caller_order(shift))
         self.stats = (self._caller_order(mean), self._caller_order(var))
         return self.scaler
+
+    def _stat_planes(self):
+        """``(planes, delta)`` the statistics kernels run over: the set's runs one behind the other and nothing else, and per
+        run what to add to a row of ``self.planes`` to name the same row there.  The kernels sum in float64 relative to the
+        FIRST row of the buffer they are given and in the order of its rows, so the statistics of a view are those of a set
+        staged from its runs alone, bit for bit, only when the kernels see exactly those runs in the view's order: the set's
+        own planes (a set that is no view), a slice of them (a view of consecutive runs), else a compact copy of the view's
+        runs that lives for the call."""
+        delta = run_offsets(self.run_lengths) - self.run_offsets
+        total = int(sum(self.run_lengths))
+        if (delta == delta[0]).all():
+            first = int(self.run_offsets[0])
+            whole = first == 0 and total == int(self.planes.shape[0])
+            return (self.planes if whole else self.planes[first:first + total]), delta
+        return torch.cat([self.planes[o:o + t] for o, t in zip(self.run_offsets.tolist(), self.run_lengths)]), delta
+
+    # ---------------------------------------------------------------- views
+
+    def windows_of(self, runs):
+        """The int64 indices of the set's ORIGINAL windows that belong to the runs ``runs`` (positions into the set's runs, any
+        order, no repeats): run by run in that order, inside a run in the set's order -- what slices the labels of a view."""
+        return select_runs(self.run_lengths, self.run_offsets, self.run_windows, runs, 'windows_of')[0]
+
+    def select(self, runs):
+        """A view: a set of the same kind over the original windows of the runs ``runs`` (``windows_of(runs)``, in that order)
+        that SHARES this set's ``planes`` -- the same tensor, nothing is copied and no kernel runs -- and has row / index
+        tables of its own.  ``view.materialise()`` is ``self.materialise()[self.windows_of(runs)]``; its starts, jitter bounds
+        and run lengths are those of the selected runs; it takes over this set's scaler tables (``share_tables``), and
+        ``fit_scaler``, ``balance`` (``groups``: one id per SELECTED run), ``augment``, ``jitter`` / ``refill`` and
+        ``set_rows`` work on it as on a set staged from those runs alone and change neither this set nor another view.  A view
+        of a view is a view of the first set.  A set that carries a plan, an augmentation or displaced rows refuses
+        (``ValueError``): select first, then perturb."""
+        if self.plan is not None or self.aug is not None or self._displaced():
+            raise ValueError('select: the set carries %s; select first, then perturb (balance(None, 0), augment(None, 0), '
+                             'reset_rows())' % ('a plan' if self.plan is not None else 'an augmentation' if self.aug is not None
+                                                else 'displaced rows'))
+        windows, lengths, offsets, counts = select_runs(self.run_lengths, self.run_offsets, self.run_windows, runs)
+        return self._view(windows, lengths, offsets, counts).share_tables(self)
+
+    def _displaced(self):
+        return False
 
     # ---------------------------------------------------------------- windows
 
@@ -520,10 +592,10 @@ class StartWindowSet(WindowSet):
     table of first rows, and the only kind that can be displaced (``jitter``: every window moved a few TRs inside its run, a
     new row table, not a new array).  The mix table of a plan holds the first rows of every source."""
 
-    def __init__(self, owner, planes, run_lengths, run_starts, M, C):
+    def __init__(self, owner, planes, run_lengths, run_starts, M, C, offsets=None):
         run_starts = [np.asarray(s, np.int64) for s in run_starts]
-        WindowSet.__init__(self, owner, planes, run_lengths, [len(s) for s in run_starts], M, C)
-        self.base_rows, self.lo, self.hi = row_table(self.run_lengths, run_starts, C)
+        WindowSet.__init__(self, owner, planes, run_lengths, [len(s) for s in run_starts], M, C, offsets)
+        self.base_rows, self.lo, self.hi = row_table(self.run_lengths, run_starts, C, self.run_offsets)
         self.rows_host = self.base_rows.copy()
         self.rows = torch.as_tensor(self.rows_host).to(planes.device)
         self.jitter, self.jitter_rng = 0, None
@@ -541,8 +613,16 @@ class StartWindowSet(WindowSet):
         return series[:, rows[:, None] + np.arange(self.shape[2])[None, :]]
 
     def _stats(self):
-        rows = torch.as_tensor(self.base_rows).to(self.planes.device)
-        return ops.window_stats(self.planes, rows, *self.shape[1:])
+        planes, delta = self._stat_planes()
+        rows = torch.as_tensor(self.base_rows + np.repeat(delta, self.run_windows)).to(self.planes.device)
+        return ops.window_stats(planes, rows, *self.shape[1:])
+
+    def _view(self, windows, lengths, offsets, counts):
+        starts = np.split((self.base_rows - self.offsets)[windows], np.cumsum(counts)[:-1])
+        return StartWindowSet(self.owner, self.planes, lengths, starts, self.shape[1], self.shape[2], offsets)
+
+    def _displaced(self):
+        return bool(self.jitter) or not np.array_equal(self.rows_host, self.base_rows)
 
     def _gather(self, idx, scale, shift, out, sources):
         M, C = self.shape[1:]
@@ -617,9 +697,9 @@ class EventWindowSet(WindowSet):
     a ``ValueError`` -- a displaced window leaves its trial.  The mix table of a plan holds the plan's sources themselves:
     they are places in ``index``."""
 
-    def __init__(self, owner, planes, run_lengths, run_index, M, C, fold):
+    def __init__(self, owner, planes, run_lengths, run_index, M, C, fold, offsets=None):
         run_index = [np.asarray(i, np.int64) for i in run_index]
-        WindowSet.__init__(self, owner, planes, run_lengths, [len(i) for i in run_index], M, C)
+        WindowSet.__init__(self, owner, planes, run_lengths, [len(i) for i in run_index], M, C, offsets)
         self.fold = int(fold)
         self.index_host = np.ascontiguousarray(np.concatenate(run_index) + self.offsets[:, None], np.int64)
         self.index = torch.as_tensor(self.index_host).to(planes.device)
@@ -655,7 +735,15 @@ class EventWindowSet(WindowSet):
         return piece / np.float32(self.fold) if self.fold > 1 else piece
 
     def _stats(self):
-        return ops.window_stats_indexed(self.planes, self.index, *self.shape[1:], self.fold)
+        planes, delta = self._stat_planes()
+        if planes is self.planes:
+            return ops.window_stats_indexed(planes, self.index, *self.shape[1:], self.fold)
+        index = torch.as_tensor(self.index_host + np.repeat(delta, self.run_windows)[:, None]).to(self.planes.device)
+        return ops.window_stats_indexed(planes, index, *self.shape[1:], self.fold)
+
+    def _view(self, windows, lengths, offsets, counts):
+        index = np.split(self.starts[windows], np.cumsum(counts)[:-1])
+        return EventWindowSet(self.owner, self.planes, lengths, index, self.shape[1], self.shape[2], self.fold, offsets)
 
     def _gather(self, idx, scale, shift, out, sources):
         M, C = self.shape[1:]
@@ -835,13 +923,18 @@ class Series(object):
                              'windows)' % what)
         return aug
 
-    def _fit_sets(self, ws_train, train_labels, ws_val, val_labels, standardize, best_checkpoint_dir, plan, aug=None):
+    def _fit_sets(self, ws_train, train_labels, ws_val, val_labels, standardize, best_checkpoint_dir, plan, aug=None,
+                  fitted=None):
         """The tail of ``fit_series`` / ``fit_events``: the scaler fitted on the training originals and shared, the classes
         balanced (``plan``: ``balance``'s arguments from ``sampling`` on), the balanced set augmented (``aug``: ``augment``'s
         arguments from ``copies`` on), ``fit``; the training set left as it was staged.  The validation set is never
-        augmented."""
+        augmented.  ``fitted``: a set whose scaler both sets take over instead (cross-validation's pool scaler)."""
         self.window_scaler = None
-        if standardize:
+        if fitted is not None:
+            ws_train.share_tables(fitted)
+            ws_val.share_tables(fitted)
+            self.window_scaler = fitted.scaler
+        elif standardize:
             self.window_scaler = ws_train.fit_scaler()
             ws_val.share_tables(ws_train)
         try:
