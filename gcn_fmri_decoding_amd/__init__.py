@@ -6,11 +6,13 @@ and ``lib_new.coarsening`` (pooling index maps), on PyTorch-ROCm tensors, with t
 arithmetic in hand-written gfx950 kernels behind the C ABI of ``include/chebgcn.h``.
 """
 from . import _lib  # noqa: F401
-from . import graph, coarsening, parcellation, filters, splits  # noqa: F401
+from . import graph, coarsening, parcellation, filters, splits, stats  # noqa: F401
 from .parcellation import Parcellation  # noqa: F401
 from .filters import GraphFilter  # noqa: F401
+from .stats import MapTestResult, map_test, map_test_host, sign_flips  # noqa: F401
 
-__all__ = ['graph', 'coarsening', 'parcellation', 'Parcellation', 'filters', 'GraphFilter', 'splits', 'models_gcn', 'ops']
+__all__ = ['graph', 'coarsening', 'parcellation', 'Parcellation', 'filters', 'GraphFilter', 'splits', 'stats', 'map_test',
+           'map_test_host', 'sign_flips', 'MapTestResult', 'models_gcn', 'ops']
 
 
 def __getattr__(name):

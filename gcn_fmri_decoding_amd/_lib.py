@@ -17,6 +17,9 @@ MC_SITES = 16
 PARCEL_MEAN, PARCEL_SUM = 0, 1
 FILTER_AUTO, FILTER_ROLLING, FILTER_STACK = 0, 1, 2
 FILTER_JMAX, FILTER_KMAX = 8, 256
+CLUSTER_MAX, CLUSTER_EXTENT, CLUSTER_TFCE = 0, 1, 2
+CLUSTER_AUTO, CLUSTER_ONCHIP, CLUSTER_STREAMED = 0, 1, 2
+CLUSTER_EHEIGHTS, CLUSTER_ELOOP = 1, 2
 
 
 class ChebgcnError(RuntimeError):
@@ -149,6 +152,11 @@ SIGNATURES = {
     'chebgcn_parcel_expand': (_i, [_p, _p, _p, _i64, _i, _i, _f, _p]),
     'chebgcn_cheb_filter_workspace': (C.c_size_t, [_p, _i, _i, _i, _i]),
     'chebgcn_cheb_filter': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    'chebgcn_cluster_query': (_i, [_i]),
+    'chebgcn_cluster_enhance_workspace': (C.c_size_t, [_i, _i, _i, _i]),
+    'chebgcn_signflip_t': (_i, [_p, _p, _p, _p, _i, _i, C.c_uint32, _i, C.c_uint32, _p]),
+    'chebgcn_cluster_enhance': (_i, [_p, _p, _i64, _p, _i, _p, _p, _i, _p, C.c_double, _p, _p, _p, _p, _p, C.c_size_t, _i, _i, _i,
+                                     _i, _p]),
 }
 
 _lib = None

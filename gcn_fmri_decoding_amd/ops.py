@@ -562,6 +562,94 @@ def cheb_filter(graph, x, coeff, arm=_lib.FILTER_AUTO, out=None):
     return out
 
 
+def cluster_geometry():
+    """The limits of the permutation-inference kernels (chebgcn_cluster_query): ``onchip_M`` the largest M of the on-chip arm of
+    ``cluster_enhance`` (LDS of a workgroup / ``state_bytes`` per vertex), ``max_S`` subjects, ``max_M`` vertices, ``max_heights``,
+    ``max_perms`` permutations of one call, ``state_bytes`` of state per (permutation, vertex)."""
+    q = _lib.lib().chebgcn_cluster_query
+    return {'onchip_M': q(0), 'max_S': q(1), 'max_M': q(2), 'max_heights': q(3), 'max_perms': q(4), 'state_bytes': q(5)}
+
+
+def _vec(t, dtype, n, what):
+    if t.dtype != dtype or t.dim() != 1 or t.numel() < n or not t.is_contiguous():
+        raise _lib.ChebgcnError('%s must be a contiguous %s vector of at least %d entries' % (what, str(dtype).split('.')[-1], n))
+
+
+def signflip_t(x, q, p0, Pb, seed, bits=None, out=None):
+    """The sign-flip t maps of permutations ``p0 .. p0 + Pb - 1`` (chebgcn_signflip_t): ``x`` float32 [S, M] and ``q`` float64 [M]
+    on the device -> float32 [Pb, M].  ``bits``: int32 [Pb, ceil(S / 32)] packed signs (bit set: negated), or None: the
+    signs are drawn from ``(seed, permutation)`` and permutation 0 is the identity.  The arithmetic: include/chebgcn.h."""
+    _require_cuda(x, q, bits, out)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.ChebgcnError('signflip_t: x must be contiguous float32 [S, M]')
+    S, M = int(x.shape[0]), int(x.shape[1])
+    _vec(q, torch.float64, M, 'signflip_t: q')
+    Pb = int(Pb)
+    if bits is not None and (bits.dtype != torch.int32 or tuple(bits.shape) != (Pb, (S + 31) // 32) or not bits.is_contiguous()):
+        raise _lib.ChebgcnError('signflip_t: bits must be contiguous int32 words [%d, %d]' % (Pb, (S + 31) // 32))
+    if out is None:
+        out = torch.empty((Pb, M), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (Pb, M) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.ChebgcnError('signflip_t: out must be contiguous float32 [%d, %d]' % (Pb, M))
+    _lib.check(_launch('signflip_t', 4.0 * Pb * M + 4.0 * S * M, 2.0 * Pb * M * S, lambda: _lib.lib().chebgcn_signflip_t(
+        _p(x), _p(q), _p(bits), _p(out), S, M, int(p0) & 0xFFFFFFFF, Pb, int(seed) & 0xFFFFFFFF, _stream())), 'signflip_t')
+    return out
+
+
+def cluster_enhance_workspace(Pb, M, mode, arm=_lib.CLUSTER_AUTO):
+    """Bytes of scratch ``cluster_enhance`` takes (chebgcn_cluster_enhance_workspace): 0 on chip, ``state_bytes`` per
+    (permutation, vertex) streamed."""
+    return int(_lib.lib().chebgcn_cluster_enhance_workspace(int(Pb), int(M), int(mode), int(arm)))
+
+
+def cluster_check(status):
+    """Read the status word of ``cluster_enhance`` calls (synchronises) and raise what it reports."""
+    code = int(status.item())
+    if code:
+        raise _lib.ChebgcnError('cluster_enhance: %s' % {
+            _lib.CLUSTER_EHEIGHTS: 'a permutation has more heights than the tables hold',
+            _lib.CLUSTER_ELOOP: 'a union-find loop ran past its bound'}.get(code, 'status %d' % code))
+
+
+def cluster_enhance(t, mode, ptr=None, idx=None, hf=None, hw=None, ep=None, step=1.0, NH=1, negate=False, want_out=True,
+                    want_labels=False, want_max=True, arm=_lib.CLUSTER_AUTO, status=None):
+    """Cluster enhancement of a batch of t maps (chebgcn_cluster_enhance): ``t`` float32 [Pb, M] on the device, the graph as
+    int32 CSR ``ptr`` [M + 1] / ``idx`` on the device, the tables ``hf`` float32 / ``hw`` float64 (at least NH + 1 entries) and
+    ``ep`` float64 [M + 1].  Returns ``(out float64 [Pb, M] | None, labels int32 [Pb, M] | None, pmax float64 [Pb] | None)``.
+    ``status``: an int32 [1] device tensor the caller zeroed and reads later with ``cluster_check`` (one synchronisation for many
+    calls); None: the call checks its own and synchronises."""
+    _require_cuda(t, ptr, idx, hf, hw, ep, status)
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0:
+        raise _lib.ChebgcnError('cluster_enhance: t must be contiguous float32 [Pb, M]')
+    Pb, M = int(t.shape[0]), int(t.shape[1])
+    mode, NH = int(mode), int(NH)
+    own = None
+    if mode != _lib.CLUSTER_MAX:
+        if NH < 1:
+            raise _lib.ChebgcnError('cluster_enhance: NH = %d heights' % NH)
+        _vec(ptr, torch.int32, M + 1, 'cluster_enhance: ptr')
+        _vec(idx, torch.int32, 0, 'cluster_enhance: idx')
+        _vec(hf, torch.float32, NH + 1, 'cluster_enhance: hf')
+        _vec(hw, torch.float64, NH + 1, 'cluster_enhance: hw')
+        _vec(ep, torch.float64, M + 1, 'cluster_enhance: ep')
+        if status is None:
+            status = own = torch.zeros(1, dtype=torch.int32, device=t.device)
+        _vec(status, torch.int32, 1, 'cluster_enhance: status')
+    lib = _lib.lib()
+    nws = int(lib.chebgcn_cluster_enhance_workspace(Pb, M, mode, int(arm)))
+    ws = _workspace(nws, t.device, 'cluster_enhance') if nws else None
+    out = torch.empty((Pb, M), dtype=torch.float64, device=t.device) if want_out else None
+    labels = torch.empty((Pb, M), dtype=torch.int32, device=t.device) if want_labels else None
+    pmax = torch.empty((Pb,), dtype=torch.float64, device=t.device) if want_max else None
+    nnz = int(idx.numel()) if idx is not None else 0
+    _lib.check(_launch('cluster_enhance', 4.0 * Pb * M, 0.0, lambda: lib.chebgcn_cluster_enhance(
+        _p(ptr), _p(idx), nnz, _p(t), int(bool(negate)), _p(hf), _p(hw), NH, _p(ep), float(step), _p(out), _p(labels), _p(pmax),
+        _p(status), _p(ws), nws, Pb, M, mode, int(arm), _stream())), 'cluster_enhance')
+    if own is not None:
+        cluster_check(own)
+    return out, labels, pmax
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------

@@ -1,0 +1,402 @@
+"""Permutation inference on maps: where does an effect hold across subjects, corrected for the number of vertices?
+
+``map_test`` takes one map per subject (or fold, or run) -- attribution maps ``[S, classes, M]``, smoothed or not -- and tests the
+group mean at every vertex with a sign-flip permutation test: under the null hypothesis a subject's map is as likely as its
+negative, so every vector of S signs gives a map that is as likely as the observed one.  Family-wise error is controlled by the
+maximum statistic: ``p[v]`` is the share of permutations whose LARGEST value anywhere reaches the observed value at ``v``.  The
+statistic is the vertex-wise t (``'max'``), the extent of the vertex's cluster above a forming threshold (``'extent'``), or
+threshold-free cluster enhancement (``'tfce'``, Smith & Nichols 2009) on the neighbourhood of the brain graph.
+
+On the device (``chebgcn_signflip_t``, ``chebgcn_cluster_enhance``) the permutations run in batches; ``map_test_host`` restates
+the same arithmetic with NumPy and SciPy, operation for operation: the two agree to the bit.  The stated arithmetic (see
+include/chebgcn.h), per vertex and permutation in float64, every operation rounded on its own::
+
+    s = sum_j sign_j x_j  (ascending j, from 0)      q = sum_j x_j x_j      m = s / S      d = q - s m
+    t = float32(m / sqrt(d / (S (S - 1))))  where d > 0, else 0
+
+A vertex is active at height h when ``t > float32(h)``.  TFCE: ``step`` defaults to the observed maximum / 100 and is the same
+for every permutation; a map with maximum ``t_max`` has the heights ``h_i = i step``, ``i = 1 .. floor(t_max / step)``, and
+``tfce[v] = sum_i extent_i(v)^E h_i^H step`` over the heights at which v is active, accumulated in float64 in DESCENDING i (the
+kernels walk the heights downwards, where components only merge), each term ``ep[extent] * hw[i]`` a rounded product of the two
+host-built tables ``ep[e] = e^E`` and ``hw[i] = h_i^H step``.  A cluster's id is its smallest vertex.
+
+The host-only parts need NumPy and SciPy only.
+"""
+import collections
+
+import numpy as np
+import scipy.sparse as sp
+from scipy.sparse import csgraph
+
+CHUNK_BYTES = 256 << 20         # the t maps and the labelling state of one batch of permutations on the device, at most
+ARM = 0                         # chebgcn_cluster_enhance's arm: 0 automatic; 2 forces the streamed arm (measurements, tests)
+HOST_CHUNK = 1 << 22            # (permutation, vertex) pairs of one slice of the host restatement
+SMAX = 4096                     # subjects (chebgcn_signflip_t)
+MMAX = 1 << 24                  # vertices
+NHMAX = 1 << 16                 # heights of one map
+PBMAX = 65535                   # permutations of one launch
+STATS = ('max', 'extent', 'tfce')
+_MODE = {'max': 0, 'extent': 1, 'tfce': 2}
+
+_MUL1, _MUL2, _KEY, _WINDOW = 0x7FEB352D, 0x846CA68B, 0x9E3779B9, 0x85EBCA6B      # chebgcn_aug_draw (include/chebgcn.h)
+_U32 = np.uint64(0xFFFFFFFF)
+
+MapTestResult = collections.namedtuple('MapTestResult', 't stat p null labels step n_perm exact seed')
+MapTestResult.__doc__ = """What ``map_test`` returns.  ``t`` float32 [C, M] the observed t map (of the negated maps for
+``tail=-1``); ``stat`` float64 [C, M] the observed statistic; ``p`` float64 [C, M] family-wise corrected p-values (>= 1 / n_perm);
+``null`` float64 [C, P] every permutation's maximum; ``labels`` int32 [C, M] for ``'extent'`` (the cluster's smallest vertex, -1
+below the threshold), else None; ``step`` the TFCE step per class (float64 [C], None for the other statistics); ``n_perm`` the
+permutations actually run; ``exact`` whether they enumerate all sign vectors; ``seed``.  For ``[S, M]`` input the class axis is
+dropped (``step`` a float)."""
+
+
+def _is_tensor(a):
+    return type(a).__module__.split('.')[0] == 'torch'
+
+
+def _fin(x):
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(_MUL1)) & _U32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(_MUL2)) & _U32
+    return x ^ (x >> np.uint64(16))
+
+
+def _draw(seed, i, d):
+    """``chebgcn_aug_draw(seed, refill=0, i, d)`` (``series.aug_draw`` is the same function)."""
+    i = np.asarray(i, np.uint64) & _U32
+    d = np.asarray(d, np.uint64) & _U32
+    a = _fin(_fin(np.uint64(int(seed) & 0xFFFFFFFF)))
+    k0 = _fin((a + i) & _U32)
+    k1 = _fin(((a ^ np.uint64(_KEY)) + ((i * np.uint64(_WINDOW)) & _U32)) & _U32)
+    return _fin(_fin((k0 + d) & _U32) ^ k1)
+
+
+def sign_flips(S, n_perm, seed):
+    """The sign vectors ``map_test`` runs: ``(signs int8 [P, S] of +1 / -1, exact)``.  Row 0 is all +1 (the observed maps, which
+    count as a permutation).  When ``2**S <= n_perm`` every sign vector is enumerated once: ``P = 2**S``, subject j of row q is
+    negated where bit j of q is set, ``exact`` is True.  Otherwise ``P = n_perm`` and subject j of row q >= 1 is negated where the
+    top bit of ``chebgcn_aug_draw(seed, refill=0, i=q, d=j)`` is set."""
+    S, n_perm = int(S), int(n_perm)
+    if S < 1 or n_perm < 1:
+        raise ValueError('sign_flips: S = %d, n_perm = %d' % (S, n_perm))
+    if S < 62 and (1 << S) <= n_perm:
+        neg = (np.arange(1 << S, dtype=np.int64)[:, None] >> np.arange(S, dtype=np.int64)[None, :]) & 1
+        return (1 - 2 * neg).astype(np.int8), True
+    neg = (_draw(seed, np.arange(n_perm, dtype=np.uint64)[:, None], np.arange(S, dtype=np.uint64)[None, :]) >> np.uint64(31)).astype(np.int64)
+    neg[0] = 0
+    return (1 - 2 * neg).astype(np.int8), False
+
+
+def edges(A, M=None):
+    """The neighbour lists ``map_test`` uses, from a SciPy sparse adjacency or Laplacian: the off-diagonal non-zeros, symmetrised
+    by union, as CSR ``(ptr int32 [M + 1], idx int32 [nnz])`` with ascending neighbours."""
+    if not sp.issparse(A):
+        raise ValueError('map_test: A must be a SciPy sparse matrix, not %s' % type(A).__name__)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or A.shape[0] < 1:
+        raise ValueError('map_test: A must be square, got shape %r' % (tuple(A.shape),))
+    if M is not None and A.shape[0] != M:
+        raise ValueError('map_test: A is %d x %d but the maps have M = %d vertices' % (A.shape[0], A.shape[1], M))
+    n = int(A.shape[0])
+    if n > MMAX:
+        raise ValueError('map_test: M = %d vertices, served: up to %d' % (n, MMAX))
+    C = sp.coo_matrix(A)
+    keep = (C.row != C.col) & (C.data != 0)
+    r, c = C.row[keep].astype(np.int64), C.col[keep].astype(np.int64)
+    G = sp.csr_matrix((np.ones(2 * r.size, np.int8), (np.concatenate([r, c]), np.concatenate([c, r]))), shape=(n, n))
+    G.sum_duplicates()
+    G.sort_indices()
+    if G.nnz >= 2 ** 31:
+        raise ValueError('map_test: %d edges' % G.nnz)
+    return G.indptr.astype(np.int32), G.indices.astype(np.int32)
+
+
+# ---- arguments ----------------------------------------------------------------------------------------------------------------------
+
+_Plan = collections.namedtuple('_Plan', 'x single S C M ptr idx stat tail n_perm threshold step E H seed')
+
+
+def _plan(maps, A, stat, n_perm, tail, threshold, step, E, H, seed):
+    """Everything checked before any work (and before the device is touched); x: float32 host array [C, S, M], tail applied."""
+    if _is_tensor(maps):
+        if str(maps.dtype) != 'torch.float32':
+            raise ValueError('map_test: maps must be float32, not %s' % maps.dtype)
+        x = maps.detach().cpu().numpy()
+    else:
+        x = np.asarray(maps)
+        if not (np.issubdtype(x.dtype, np.floating) or np.issubdtype(x.dtype, np.integer)):
+            raise ValueError('map_test: maps of dtype %s' % x.dtype)
+        x = x.astype(np.float32)
+    if x.ndim not in (2, 3):
+        raise ValueError('map_test: maps must be [S, M] or [S, C, M], got shape %r' % (tuple(x.shape),))
+    single = x.ndim == 2
+    if single:
+        x = x[:, None, :]
+    S, C, M = (int(v) for v in x.shape)
+    if S < 2:
+        raise ValueError('map_test: S = %d maps; a one-sample test needs at least 2' % S)
+    if S > SMAX:
+        raise ValueError('map_test: S = %d maps, served: up to %d' % (S, SMAX))
+    if C < 1 or M < 1:
+        raise ValueError('map_test: maps of shape %r' % (tuple(x.shape),))
+    if not np.isfinite(x).all():
+        raise ValueError('map_test: maps hold non-finite values')
+    ptr, idx = edges(A, M)
+    if stat not in STATS:
+        raise ValueError('map_test: stat must be one of %r, not %r' % (STATS, stat))
+    if tail not in (1, -1, 0):
+        raise ValueError('map_test: tail must be 1, -1 or 0, not %r' % (tail,))
+    if int(n_perm) != n_perm or n_perm < 1 or n_perm > 2 ** 31 - 1:
+        raise ValueError('map_test: n_perm = %r' % (n_perm,))
+    if stat == 'extent':
+        if threshold is None or not np.isfinite(threshold):
+            raise ValueError("map_test: stat='extent' needs a finite forming threshold, got %r" % (threshold,))
+        threshold = float(threshold)
+    if step is not None and not (np.isfinite(step) and step > 0):
+        raise ValueError('map_test: step = %r must be positive and finite' % (step,))
+    if not (np.isfinite(E) and np.isfinite(H)):
+        raise ValueError('map_test: E = %r, H = %r must be finite' % (E, H))
+    x = np.ascontiguousarray(x.transpose(1, 0, 2))
+    if tail == -1:
+        x = -x
+    return _Plan(x, single, S, C, M, ptr, idx, stat, int(tail), int(n_perm), threshold, None if step is None else float(step),
+                 float(E), float(H), int(seed))
+
+
+def _tables(pl, step, NH):
+    """``(hf float32 [NH + 1], hw float64 [NH + 1], ep float64 [M + 1])``: the heights, ``h^H step`` and ``e^E`` -- for 'extent'
+    the threshold, 1 and e, so that the same sum gives the extent."""
+    e = np.arange(pl.M + 1, dtype=np.float64)
+    if pl.stat == 'extent':
+        return np.array([0.0, pl.threshold], np.float32), np.array([0.0, 1.0]), e
+    h = np.arange(NH + 1, dtype=np.float64) * step
+    with np.errstate(divide='ignore', over='ignore'):
+        hw = np.power(h, pl.H) * step
+        ep = np.power(e, pl.E)
+    hw[0] = 0.0
+    if not (np.isfinite(hw[1:]).all() and np.isfinite(ep[1:]).all()):
+        raise ValueError('map_test: E = %r, H = %r overflow float64 at this step and size' % (pl.E, pl.H))
+    ep[0] = 0.0
+    return h.astype(np.float32), hw, ep
+
+
+def _default_step(pl, t_obs):
+    """The TFCE step of one class: the observed maximum over the tested tail / 100 (1 where nothing is positive: no heights)."""
+    if pl.step is not None:
+        return pl.step
+    top = float(np.abs(t_obs).max()) if pl.tail == 0 else float(t_obs.max())
+    return top / 100.0 if top > 0 else 1.0
+
+
+def _heights_needed(pl, step, top):
+    """Heights of a map whose largest value is ``top`` (what the kernels compute per permutation)."""
+    if pl.stat != 'tfce' or not top > 0:
+        return 1
+    n = np.floor(np.float64(top) / np.float64(step))
+    if n > NHMAX:
+        raise ValueError('map_test: step = %g gives %d heights, served: up to %d' % (step, int(n), NHMAX))
+    return max(int(n), 1)
+
+
+def _result(pl, t, stat, null, labels, steps, P, exact):
+    p = np.empty_like(stat)
+    for c in range(pl.C):
+        srt = np.sort(null[c])
+        p[c] = (P - np.searchsorted(srt, stat[c], side='left')) / float(P)
+    if pl.stat != 'extent':
+        labels = None
+    steps = np.asarray(steps, np.float64) if pl.stat == 'tfce' else None
+    if pl.single:
+        return MapTestResult(t[0], stat[0], p[0], null[0], None if labels is None else labels[0],
+                             None if steps is None else float(steps[0]), P, exact, pl.seed)
+    return MapTestResult(t, stat, p, null, labels, steps, P, exact, pl.seed)
+
+
+def _combine(t, pos, neg, lpos, lneg):
+    """Two-sided: every vertex carries the value (and the cluster) of its own sign's part."""
+    stat = np.where(t > 0, pos, np.where(t < 0, neg, 0.0))
+    lab = None if lpos is None else np.where(t > 0, lpos, np.where(t < 0, lneg, -1)).astype(np.int32)
+    return stat, lab
+
+
+# ---- the host restatement -----------------------------------------------------------------------------------------------------------
+
+def t_host(x, signs):
+    """The stated t arithmetic: ``x`` float32 [S, M], ``signs`` [P, S] of +-1 -> float32 [P, M]."""
+    S, M = x.shape
+    xd = x.astype(np.float64)
+    q = np.zeros(M)
+    for j in range(S):
+        q = q + xd[j] * xd[j]
+    s = np.zeros((signs.shape[0], M))
+    for j in range(S):
+        s = s + signs[:, j, None].astype(np.float64) * xd[j][None, :]
+    m = s / np.float64(S)
+    d = q[None, :] - s * m
+    with np.errstate(divide='ignore', invalid='ignore'):
+        t = m / np.sqrt(d / np.float64(S * (S - 1)))
+    return np.where(d > 0, t, 0.0).astype(np.float32)
+
+
+def enhance_host(u, ptr, idx, mode, hf, hw, ep, step):
+    """One map ``u`` float32 [M] -> ``(stat float64 [M], labels int32 [M])`` as ``chebgcn_cluster_enhance`` states it: SciPy's
+    connected components of every supra-threshold subgraph, heights descending."""
+    M = u.size
+    if mode == 'max':
+        return u.astype(np.float64), np.full(M, -1, np.int32)
+    top = float(u.max())
+    if mode == 'extent':
+        n = 1
+    else:
+        n = int(np.floor(np.float64(top) / np.float64(step))) if top > 0 else 0
+        if n > hf.size - 1:
+            raise ValueError('map_test: %d heights, the tables hold %d' % (n, hf.size - 1))
+    G = sp.csr_matrix((np.ones(idx.size, np.int8), idx, ptr), shape=(M, M))
+    acc = np.zeros(M)
+    labels = np.full(M, -1, np.int32)
+    for i in range(n, 0, -1):
+        act = np.nonzero(u > hf[i])[0]
+        if act.size == 0:
+            continue
+        _, lab = csgraph.connected_components(G[act][:, act], directed=False)
+        size = np.bincount(lab)
+        acc[act] = acc[act] + ep[size[lab]] * hw[i]
+        if i == 1:
+            first = np.full(size.size, M, np.int64)
+            np.minimum.at(first, lab, act)
+            labels[act] = first[lab]
+    return acc, labels
+
+
+def map_test_host(maps, A, stat='tfce', n_perm=5000, tail=0, threshold=None, step=None, E=0.5, H=2.0, seed=0, device=None):
+    """``map_test`` restated with NumPy and SciPy, operation for operation (no device; ``device`` is ignored): the same
+    ``MapTestResult``, bit for bit.  One ``connected_components`` call per height and permutation: minutes at atlas size."""
+    pl = _plan(maps, A, stat, n_perm, tail, threshold, step, E, H, seed)
+    signs, exact = sign_flips(pl.S, pl.n_perm, pl.seed)
+    P = signs.shape[0]
+    sides = (1, -1) if pl.tail == 0 else (1,)
+    t_all = np.empty((pl.C, pl.M), np.float32)
+    stat_all = np.empty((pl.C, pl.M))
+    null = np.empty((pl.C, P))
+    labels = np.full((pl.C, pl.M), -1, np.int32)
+    steps = []
+    rows = max(1, HOST_CHUNK // pl.M)
+    for c in range(pl.C):
+        t_obs = t_host(pl.x[c], signs[:1])[0]
+        st = _default_step(pl, t_obs)
+        steps.append(st)
+        tabs = None
+        for p0 in range(0, P, rows):
+            tb = t_host(pl.x[c], signs[p0:p0 + rows])
+            NH = _heights_needed(pl, st, float(np.abs(tb).max()) if pl.tail == 0 else float(tb.max()))
+            if tabs is None or tabs[0].size < NH + 1:
+                tabs = _tables(pl, st, NH)
+            for k in range(tb.shape[0]):
+                parts = [enhance_host(tb[k] if sd > 0 else -tb[k], pl.ptr, pl.idx, pl.stat, tabs[0], tabs[1], tabs[2], st)
+                         for sd in sides]
+                null[c, p0 + k] = max(float(a.max()) for a, _ in parts)
+                if p0 + k == 0:
+                    t_all[c] = tb[k]
+                    if pl.tail == 0:
+                        stat_all[c], lab = _combine(tb[k], parts[0][0], parts[1][0], parts[0][1], parts[1][1])
+                    else:
+                        stat_all[c], lab = parts[0]
+                    labels[c] = lab
+    return _result(pl, t_all, stat_all, null, labels, steps, P, exact)
+
+
+# ---- the device ---------------------------------------------------------------------------------------------------------------------
+
+def map_test(maps, A, stat='tfce', n_perm=5000, tail=0, threshold=None, step=None, E=0.5, H=2.0, seed=0, device=None):
+    """Sign-flip permutation test of the group mean of ``maps`` at every vertex, family-wise corrected by the maximum statistic.
+
+    ``maps``: float32 ``[S, M]`` or ``[S, C, M]`` (NumPy or a device tensor): one map per subject, fold or run, C classes; the
+    classes are tested one after the other with the SAME sign flips; ``S >= 2``, finite values.  ``A``: SciPy sparse ``[M, M]``
+    adjacency or Laplacian -- its off-diagonal non-zeros are the edges, symmetrised by union, so the ``L`` a model was built with
+    is accepted as it is.  ``stat``: ``'max'`` (the vertex-wise t, no neighbourhood), ``'extent'`` (the size of the vertex's
+    cluster above the forming ``threshold``, required) or ``'tfce'`` (``E``, ``H``; ``step`` defaults to the observed maximum /
+    100).  ``tail``: 1 positive effects, -1 the maps are negated first, 0 two-sided (positive and negative parts are enhanced
+    separately, each vertex carries the value of its own sign's part, the null takes the larger of the two maxima).
+
+    Permutation 0 is the identity and is counted: ``p[v] = #{perm : null[perm] >= stat[v]} / P >= 1 / P``.  When
+    ``2**S <= n_perm`` all sign vectors are enumerated (``exact``, ``P = 2**S``), else ``sign_flips`` draws them from ``seed``.
+    The result is a pure function of the arguments: the same at any permutation batch size, from call to call, and bit for bit
+    what ``map_test_host`` computes.  Bad arguments raise ``ValueError`` before the device is touched.  Returns a
+    ``MapTestResult``."""
+    pl = _plan(maps, A, stat, n_perm, tail, threshold, step, E, H, seed)
+    import torch
+    from . import _lib, ops
+    if device is None:
+        dev = maps.device if (_is_tensor(maps) and maps.is_cuda) else torch.device('cuda', torch.cuda.current_device())
+    else:
+        dev = torch.device(device)
+    exact = pl.S < 62 and (1 << pl.S) <= pl.n_perm
+    P = (1 << pl.S) if exact else pl.n_perm
+    mode = _MODE[pl.stat]
+    sides = (False, True) if pl.tail == 0 else (False,)
+    clustered = mode != _lib.CLUSTER_MAX
+    t_all = np.empty((pl.C, pl.M), np.float32)
+    stat_all = np.empty((pl.C, pl.M))
+    null = np.empty((pl.C, P))
+    labels = np.full((pl.C, pl.M), -1, np.int32)
+    steps = []
+    with torch.cuda.device(dev):
+        ptr = idx = status = bits = None
+        if clustered:
+            ptr = torch.as_tensor(pl.ptr).to(dev)
+            idx = torch.as_tensor(pl.idx).to(dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+        if exact:                       # the enumeration as a table: bit j of word 0 of row q is bit j of q (S <= 31 here)
+            bits = torch.arange(P, dtype=torch.int32, device=dev).reshape(P, 1).contiguous()
+        per_perm = 4 * pl.M + ops.cluster_enhance_workspace(1, pl.M, mode, ARM) + 8
+        Pb = int(max(1, min(PBMAX, P, CHUNK_BYTES // per_perm)))
+        for c in range(pl.C):
+            x = torch.as_tensor(pl.x[c]).to(dev)
+            xd = pl.x[c].astype(np.float64)
+            q = np.zeros(pl.M)
+            for j in range(pl.S):
+                q = q + xd[j] * xd[j]
+            q = torch.as_tensor(q).to(dev)
+            t0 = ops.signflip_t(x, q, 0, 1, pl.seed, bits=None if bits is None else bits[:1])
+            t_obs = t0[0].cpu().numpy()
+            st = _default_step(pl, t_obs)
+            steps.append(st)
+            tabs = None                 # (hf, hw, ep) on the device, grown when a batch needs more heights
+
+            def tables(NH):
+                nonlocal tabs
+                if tabs is None or tabs[0].numel() < NH + 1:
+                    tabs = tuple(torch.as_tensor(a).to(dev) for a in _tables(pl, st, NH))
+                return tabs
+
+            def enhance(tb, neg, obs):
+                if not clustered:
+                    return ops.cluster_enhance(tb, mode, negate=neg, want_out=obs)
+                top = float(tb.abs().max()) if pl.tail == 0 else float(tb.max())
+                NH = _heights_needed(pl, st, top)
+                hf, hw, ep = tables(NH)
+                return ops.cluster_enhance(tb, mode, ptr, idx, hf, hw, ep, step=st, NH=NH, negate=neg, want_out=obs,
+                                           want_labels=obs and pl.stat == 'extent', arm=ARM, status=status)
+
+            parts = [enhance(t0, neg, True) for neg in sides]
+            if clustered:
+                ops.cluster_check(status)
+            outs = [o[0].cpu().numpy() for o, _, _ in parts]
+            labs = [None if l is None else l[0].cpu().numpy() for _, l, _ in parts]
+            t_all[c] = t_obs
+            if pl.tail == 0:
+                stat_all[c], lab = _combine(t_obs, outs[0], outs[1], labs[0], labs[1])
+            else:
+                stat_all[c], lab = outs[0], labs[0]
+            if lab is not None:
+                labels[c] = lab
+            nul = torch.empty(P, dtype=torch.float64, device=dev)
+            for p0 in range(0, P, Pb):
+                n = min(Pb, P - p0)
+                tb = ops.signflip_t(x, q, p0, n, pl.seed, bits=None if bits is None else bits[p0:p0 + n])
+                mx = [enhance(tb, neg, False)[2] for neg in sides]
+                nul[p0:p0 + n] = mx[0] if len(mx) == 1 else torch.maximum(mx[0], mx[1])
+            if clustered:
+                ops.cluster_check(status)
+            null[c] = nul.cpu().numpy()
+    return _result(pl, t_all, stat_all, null, labels, steps, P, exact)

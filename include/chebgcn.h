@@ -862,6 +862,65 @@ size_t chebgcn_cheb_filter_workspace(const chebgcn_graph* g, int nplanes, int K,
 int chebgcn_cheb_filter(const chebgcn_graph* g, const float* x, const float* coeff, float* y, void* workspace, int nplanes, int K,
                         int J, int arm, chebgcn_stream stream);
 
+/* ---- permutation inference on maps: sign-flip t maps and cluster enhancement on the graph (stats.map_test) ----------------------
+ * signflip_t: x float32 [S][M] (one map per subject, contiguous), q float64 [M] (q[v] = sum_j x[j][v]^2, ascending j, computed
+ *   once by the caller) -> t float32 [Pb][M], the one-sample t map of the permutations p0 .. p0 + Pb - 1.  Subject j of
+ *   permutation p is negated where bit (j & 31) of bits[p - p0][j >> 5] is set (bits: uint32 [Pb][(S + 31) / 32], device), or,
+ *   with bits == NULL, where the top bit of chebgcn_aug_draw(seed, refill = 0, i = p, d = j) is set; permutation 0 is then the
+ *   identity.  Per (permutation, vertex), in float64, every operation rounded on its own (never an fma):
+ *     s = 0;  s = s + (+-x[j][v])  for j = 0 .. S - 1;     m = s / S;     d = q[v] - s * m;
+ *     t = d > 0 ? (float)(m / sqrt(d / (S * (S - 1)))) : 0         (one rounding to float32; a constant vertex gives 0)
+ *   division and square root correctly rounded: bit for bit what float64 NumPy gives (stats.map_test_host).
+ *   2 <= S <= 4096, M <= 2^24, Pb <= 65535: CHEBGCN_EUNSUPPORTED beyond, before any launch.  chebgcn_last_dispatch():
+ *   signflip_t_kernel.
+ * cluster_enhance: t float32 [Pb][M]; u = negate ? -t : t.  ptr int32 [M + 1] / idx int32 [nnz]: the graph's neighbour lists in
+ *   CSR form (device; symmetric, no diagonal: the caller builds them; idx may be NULL when nnz == 0; an entry outside [0, M) is
+ *   skipped, ptr is clamped into [0, nnz]).  Per permutation, with the caller's tables hf float32 [NH + 1] (heights, ASCENDING in i, entry 0 unused), hw
+ *   float64 [NH + 1] and ep float64 [M + 1] (all device):
+ *     MAX     out[p][v] = (double)u[v]; no graph, no tables, no status.
+ *     TFCE    n = u_max > 0 ? floor((double)u_max / step) : 0 heights; vertex v is active at height i <= n when u[v] > hf[i];
+ *             e_i(v) = the size of v's connected component among the active vertices;
+ *             out[p][v] = sum over the heights i = n, n - 1, .. 1 at which v is active, IN THAT ORDER, of ep[e_i(v)] * hw[i]:
+ *             acc = 0, acc = acc + (ep * hw), the product rounded, then the sum (float64).  No pow on the device.
+ *     EXTENT  the same with n = 1 whatever u_max (hf[1] = the forming threshold; ep[e] = e and hw[1] = 1 give the extent).
+ *   out float64 [Pb][M] or NULL; labels int32 [Pb][M] or NULL: the smallest vertex of v's component at height 1, -1 where v is
+ *   not active there; pmax float64 [Pb] or NULL: max_v out[p][v].  At least one of the three.
+ *   status: int32 [1] (device), zeroed by the caller.  The call does not synchronise and does not allocate; what only the device
+ *   can find out is reported there and the caller reads it with the result: CHEBGCN_CLUSTER_EHEIGHTS = a permutation has more
+ *   than NH heights, CHEBGCN_CLUSTER_ELOOP = a union-find loop ran past its bound of M turns.  Non-zero: the outputs are void.
+ *   Labelling is a lock-free union-find (smaller root wins: compare-and-swap hooking, path halving); no workgroup waits for
+ *   another; sizes are integer atomics; no float atomics: outputs are bit for bit reproducible and equal to the host restatement.
+ *   Arms (arm: 0 automatic, 1 on chip, 2 streamed):
+ *     on chip   M <= chebgcn_cluster_query(0): one workgroup takes one permutation through all heights with its state in LDS
+ *               (chebgcn_cluster_query(5) bytes a vertex); no workspace.  chebgcn_last_dispatch(): cluster_onchip_kernel.
+ *     streamed  any M: the state in `workspace` (chebgcn_cluster_enhance_workspace bytes, 16-byte aligned), NH heights of four
+ *               launches each whatever the permutations need (EXTENT: one).  chebgcn_last_dispatch(): cluster_prep_kernel +
+ *               cluster_hook_kernel + cluster_flatten_kernel + cluster_count_kernel + cluster_accum_kernel +
+ *               cluster_final_kernel<state>.
+ *     MAX runs cluster_final_kernel<plain> alone.
+ *   Both arms give identical outputs.  M <= 2^24, Pb <= 65535, NH <= 65536: CHEBGCN_EUNSUPPORTED beyond (and for arm 1 above
+ *   its limit), before any launch.
+ * cluster_query: 0 vertices of the on-chip arm at most, 1 subjects, 2 vertices, 3 heights, 4 permutations of a call at most,
+ *   5 bytes of state per (permutation, vertex); -1 for anything else.
+ * cluster_enhance_workspace: bytes the call would take (0: the on-chip arm, MAX, or arguments out of range). */
+enum {
+    CHEBGCN_CLUSTER_MAX = 0,
+    CHEBGCN_CLUSTER_EXTENT = 1,
+    CHEBGCN_CLUSTER_TFCE = 2
+};
+enum {
+    CHEBGCN_CLUSTER_EHEIGHTS = 1,
+    CHEBGCN_CLUSTER_ELOOP = 2
+};
+int chebgcn_cluster_query(int what);
+size_t chebgcn_cluster_enhance_workspace(int Pb, int M, int mode, int arm);
+int chebgcn_signflip_t(const float* x, const double* q, const uint32_t* bits, float* t, int S, int M, uint32_t p0, int Pb,
+                       uint32_t seed, chebgcn_stream stream);
+int chebgcn_cluster_enhance(const int32_t* ptr, const int32_t* idx, int64_t nnz, const float* t, int negate, const float* hf,
+                            const double* hw, int NH, const double* ep, double step, double* out, int32_t* labels, double* pmax,
+                            int32_t* status, void* workspace, size_t workspace_bytes, int Pb, int M, int mode, int arm,
+                            chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose
