@@ -1,0 +1,413 @@
+"""First-level general linear model: task activation maps from the event designs the decoder is trained on.
+
+``design_matrix`` turns the per-TR condition names ``match_events`` takes (or an ``(onset, duration, name)`` list) into a design:
+one HRF-convolved regressor per condition, cosine drifts, confounds, intercept.  ``first_level`` regresses every vertex of every
+staged run on its design on the device and returns, per subject, the effect, variance and t map of every contrast -- by default
+one condition against the others, in the class order of ``EventWindows.classes`` and of the attribution maps, so that
+``map_test(first_level(...).effect, A)`` and ``map_test(saliency maps, A)`` speak about the same subjects and classes.
+``first_level_host`` restates it in float64 NumPy.
+
+Condition regressors are in closed form.  With ``F_a`` the CDF of the unit-scale gamma distribution of shape ``a``, the response
+to a unit step at time 0 of the double-gamma HRF ``h = (gamma_a1 - ratio gamma_a2) / (1 - ratio)`` (SPM: 6, 16, 1/6; unit area)
+is ``G(s) = (F_a1(s) - ratio F_a2(s)) / (1 - ratio)`` for ``s >= 0`` and 0 below, so a block ``[on, off)`` contributes
+``G(t - on) - G(t - off)`` at time t: no oversampling grid, plateau 1 for long blocks.
+
+On the device a run's design enters as its thin SVD ``X = U S V^T`` of rank k (singular values above ``max(T, P) eps S_0``):
+``Q = U[:, :k]``, ``B = V[:, :k] / S[:k]``.  One pass over the scan forms ``a = Q^T y`` and ``y.y`` (chebgcn_glm_project);
+``rss = y.y - a.a``, ``b = B a`` (the minimum-norm solution), and for a contrast c ``effect = u.a`` with ``u = B^T c``,
+``variance = rss / dof * u.u`` (chebgcn_glm_finish); the runs of a subject are combined as fixed effects
+(chebgcn_glm_combine).  All of it float64 on the device, rounded once to float32: see include/chebgcn.h.
+
+Out of scope: AR(1) / prewhitened noise models (the OLS t of a single run is optimistic under temporal autocorrelation; the
+effect maps handed to ``map_test`` are not affected), temporal derivatives of the HRF, precision-weighted fixed effects, and
+returning residual series.
+
+The host-only parts need NumPy and SciPy only.
+"""
+import collections
+
+import numpy as np
+
+HRF_SPM = (6.0, 16.0, 1.0 / 6.0)
+KMAX, CMAX, PMAX, RMAX = 64, 32, 64, 65535      # chebgcn_glm_query(2), (3), (7), (8)
+ESTIMABLE_TOL = 1e-8
+
+Design = collections.namedtuple('Design', 'X columns conditions')
+Design.__doc__ = """What ``design_matrix`` returns: ``X`` float64 [T, P]; ``columns`` the P column names (the conditions, then
+``drift_1`` .., ``confound_0`` .., ``constant`` last); ``conditions`` the condition names, = the first columns, in class order."""
+
+GLMResult = collections.namedtuple('GLMResult', 'effect variance t dof groups betas')
+GLMResult.__doc__ = """What ``first_level`` returns.  ``effect``, ``variance``, ``t``: float32 [S, C, M], one map per group (subject)
+and contrast (float64 from ``first_level_host``); ``dof`` int64 [S] the residual degrees of freedom (summed over the group's
+runs); ``groups`` the S group keys in order of first appearance; ``betas`` None, or one float32 [P_r, M] per run."""
+
+
+def _is_tensor(a):
+    return type(a).__module__.split('.')[0] == 'torch'
+
+
+# ---- designs --------------------------------------------------------------------------------------------------------------------
+
+def _names(seq, what):
+    a = np.asarray(seq)
+    if isinstance(seq, str) or a.ndim != 1 or a.size == 0 or a.dtype.kind not in 'USO' \
+            or (a.dtype.kind == 'O' and not all(isinstance(n, str) for n in a)):
+        raise ValueError('design_matrix: %s must be a non-empty 1-d sequence of condition names (str), got %s %s'
+                         % (what, a.dtype, a.shape))
+    return a.astype(str)
+
+
+def step_response(s, hrf=HRF_SPM):
+    """``G(s)``: the response at time s (seconds, any shape) to a unit step at 0; the boxcar's own step for ``hrf=None``."""
+    s = np.asarray(s, np.float64)
+    if hrf is None:
+        return (s >= 0).astype(np.float64)
+    from scipy.stats import gamma
+    a1, a2, ratio = hrf
+    sp = np.maximum(s, 0.0)
+    return np.where(s >= 0, (gamma.cdf(sp, a1) - ratio * gamma.cdf(sp, a2)) / (1.0 - ratio), 0.0)
+
+
+def design_matrix(names=None, events=None, T=None, tr=0.72, conditions=None, hrf='spm', high_pass=1.0 / 128, confounds=None):
+    """The design of one run: a ``Design``.
+
+    Exactly one of ``names`` -- per-TR condition names, the format ``match_events`` takes: a maximal stretch of equal names from
+    TR i to TR j is a block ``[i tr, (j + 1) tr)`` -- and ``events`` -- a sequence of ``(onset_s, duration_s, name)``, which
+    needs ``T``.  ``conditions`` defaults to the sorted set of names other than ``'rest'`` (the order of
+    ``EventWindows.classes``); names outside ``conditions`` are left to the baseline.  ``tr``: seconds per row (0.72: HCP).
+    ``hrf``: ``'spm'`` (shapes 6 and 16, ratio 1/6), a tuple ``(a1, a2, ratio)``, or None for the plain boxcar sampled at
+    ``t_k = k tr``.  Regressors are ``x(t_k) = sum_blocks G(t_k - on) - G(t_k - off)`` in closed form (see the module).
+    ``high_pass`` (Hz): drift columns ``cos(pi (2 k + 1) j / (2 T))``, ``j = 1 .. floor(2 T tr high_pass)``; None or an order of
+    0 gives none.  ``confounds``: ``[T, Q]``, appended as given.  The intercept is the last column.  Every malformed argument
+    is a ``ValueError``."""
+    if (names is None) == (events is None):
+        raise ValueError('design_matrix: give exactly one of names (per-TR condition names) and events ((onset, duration, name))')
+    if isinstance(tr, (bool, np.bool_)) or not isinstance(tr, (int, float, np.integer, np.floating)) or not np.isfinite(tr) or tr <= 0:
+        raise ValueError('design_matrix: tr must be a positive number of seconds, got %r' % (tr,))
+    tr = float(tr)
+    if T is not None and (isinstance(T, (bool, np.bool_)) or not isinstance(T, (int, np.integer)) or T < 1):
+        raise ValueError('design_matrix: T must be an int >= 1, got %r' % (T,))
+    if isinstance(hrf, str):
+        if hrf != 'spm':
+            raise ValueError("design_matrix: hrf must be 'spm', (a1, a2, ratio) or None, got %r" % (hrf,))
+        hrf = HRF_SPM
+    elif hrf is not None:
+        try:
+            hrf = tuple(float(v) for v in hrf)
+        except (TypeError, ValueError):
+            hrf = ()
+        if len(hrf) != 3 or not all(np.isfinite(hrf)) or hrf[0] <= 0 or hrf[1] <= 0 or hrf[2] == 1.0:
+            raise ValueError("design_matrix: hrf must be 'spm', (a1, a2, ratio) with shapes > 0 and ratio != 1, or None")
+    blocks = []                                                 # (onset, offset, name), seconds
+    if names is not None:
+        names = _names(names, 'names')
+        if T is not None and int(T) != names.size:
+            raise ValueError('design_matrix: T = %d but names has %d entries' % (T, names.size))
+        T = int(names.size)
+        cuts = np.concatenate([[0], np.flatnonzero(names[1:] != names[:-1]) + 1, [T]])
+        blocks = [(i * tr, i * tr + (j - i) * tr, str(names[i])) for i, j in zip(cuts[:-1], cuts[1:])]     # as (onset, duration) gives it
+        seen = set(names.tolist())
+    else:
+        if T is None:
+            raise ValueError('design_matrix: events need T, the number of rows of the run')
+        T = int(T)
+        if isinstance(events, (str, np.ndarray)) or not hasattr(events, '__len__') or len(events) == 0:
+            raise ValueError('design_matrix: events must be a non-empty sequence of (onset_s, duration_s, name)')
+        for i, ev in enumerate(events):
+            try:
+                on, dur, name = ev
+                on, dur = float(on), float(dur)
+            except (TypeError, ValueError):
+                raise ValueError('design_matrix: event %d must be (onset_s, duration_s, name), got %r' % (i, ev)) from None
+            if not isinstance(name, str) or not np.isfinite(on) or not np.isfinite(dur) or dur < 0:
+                raise ValueError('design_matrix: event %d must be (onset_s, duration_s >= 0, name str), got %r' % (i, ev))
+            blocks.append((on, on + dur, name))
+        seen = set(b[2] for b in blocks)
+    if conditions is None:
+        conditions = sorted(seen - {'rest'})
+    elif isinstance(conditions, str) or not hasattr(conditions, '__len__') or not all(isinstance(n, str) for n in conditions):
+        raise ValueError('design_matrix: conditions must be a sequence of condition names (str), got %r' % (conditions,))
+    conditions = [str(n) for n in conditions]
+    if not conditions or len(set(conditions)) != len(conditions):
+        raise ValueError('design_matrix: conditions must be non-empty and distinct, got %r' % (conditions,))
+    order = 0
+    if high_pass is not None:
+        if isinstance(high_pass, (bool, np.bool_)) or not isinstance(high_pass, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(high_pass) or high_pass < 0:
+            raise ValueError('design_matrix: high_pass must be a frequency >= 0 in Hz or None, got %r' % (high_pass,))
+        order = int(np.floor(2.0 * T * tr * float(high_pass)))
+    Qn = 0
+    if confounds is not None:
+        confounds = np.asarray(confounds)
+        if confounds.ndim != 2 or confounds.shape[0] != T or confounds.dtype.kind not in 'fiu':
+            raise ValueError('design_matrix: confounds must be numeric [T = %d, Q], got %s %r' % (T, confounds.dtype, confounds.shape))
+        confounds = confounds.astype(np.float64)
+        if not np.isfinite(confounds).all():
+            raise ValueError('design_matrix: confounds hold non-finite values')
+        Qn = confounds.shape[1]
+    t = np.arange(T, dtype=np.float64) * tr
+    X = np.zeros((T, len(conditions) + order + Qn + 1))
+    for on, off, name in blocks:
+        if name in conditions:
+            X[:, conditions.index(name)] += step_response(t - on, hrf) - step_response(t - off, hrf)
+    k = np.arange(T, dtype=np.float64)
+    for j in range(1, order + 1):
+        X[:, len(conditions) + j - 1] = np.cos(np.pi * (2.0 * k + 1.0) * j / (2.0 * T))
+    if Qn:
+        X[:, len(conditions) + order:len(conditions) + order + Qn] = confounds
+    X[:, -1] = 1.0
+    columns = conditions + ['drift_%d' % j for j in range(1, order + 1)] + ['confound_%d' % q for q in range(Qn)] + ['constant']
+    return Design(X, columns, list(conditions))
+
+
+def contrasts_one_vs_rest(design):
+    """``[classes, P]``: +1 on a condition and ``-1 / (n - 1)`` on the others, in class order (one condition: +1 alone, the
+    condition against the baseline).  The default of ``first_level``."""
+    n, P = len(design.conditions), len(design.columns)
+    if n < 1:
+        raise ValueError('contrasts_one_vs_rest: the design has no conditions')
+    c = np.zeros((n, P))
+    c[:, :n] = -1.0 / (n - 1) if n > 1 else 0.0
+    c[np.arange(n), np.arange(n)] = 1.0
+    return c
+
+
+# ---- arguments ------------------------------------------------------------------------------------------------------------------
+
+_Run = collections.namedtuple('_Run', 'T X c rank Q B u un2')
+_Plan = collections.namedtuple('_Plan', 'runs tables M C keys members tensors')
+
+
+def _factor(X):
+    """Thin SVD of a design: ``(rank, Q [T, k], B [P, k])`` -- ``b = B (Q^T y)`` is the minimum-norm least-squares solution."""
+    U, S, Vt = np.linalg.svd(X, full_matrices=False)
+    k = int((S > max(X.shape) * np.finfo(np.float64).eps * S[0]).sum()) if S.size and S[0] > 0 else 0
+    return k, np.ascontiguousarray(U[:, :k]), np.ascontiguousarray(Vt[:k].T / S[:k])
+
+
+def _plan(runs, designs, contrasts, groups, who, limits=True):
+    """Everything that can be checked without the series' values; the per-run tables of the kernels."""
+    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
+    if single and runs.ndim != 2:
+        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
+    runs = [runs] if single else list(runs)
+    if not runs:
+        raise ValueError('%s: no runs' % who)
+    tensors = all(_is_tensor(r) for r in runs)
+    runs = [r if _is_tensor(r) else np.asarray(r) for r in runs]
+    if any(r.ndim != 2 for r in runs):
+        raise ValueError('%s: every run must be [T, M]' % who)
+    M = int(runs[0].shape[1])
+    if M < 1 or any(int(r.shape[1]) != M for r in runs):
+        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
+    if isinstance(designs, Design):
+        designs = [designs]
+    designs = list(designs)
+    if len(designs) != len(runs) or not all(isinstance(d, Design) for d in designs):
+        raise ValueError('%s: designs must hold one Design per run (%d runs, %d designs)' % (who, len(runs), len(designs)))
+    R = len(runs)
+    if groups is None:
+        groups = [0] * R
+    groups = list(groups)
+    if len(groups) != R:
+        raise ValueError('%s: groups must hold one key per run (%d runs, %d keys)' % (who, R, len(groups)))
+    keys, members = [], {}
+    for r, g in enumerate(groups):
+        try:
+            hash(g)
+        except TypeError:
+            raise ValueError('%s: group key %r of run %d is not hashable' % (who, g, r)) from None
+        if g not in members:
+            keys.append(g)
+            members[g] = []
+        members[g].append(r)
+    per_run = None
+    if contrasts is not None:
+        if isinstance(contrasts, (list, tuple)) and len(contrasts) == R and all(np.ndim(c) == 2 for c in contrasts):
+            per_run = [np.asarray(c, np.float64) for c in contrasts]
+        else:
+            c = np.atleast_2d(np.asarray(contrasts, np.float64))
+            if c.ndim != 2:
+                raise ValueError('%s: contrasts must be [C, P] (or one such array per run), got shape %r' % (who, c.shape))
+            per_run = [c] * R
+    tables = []
+    C = None
+    for r, (y, d) in enumerate(zip(runs, designs)):
+        X = np.asarray(d.X, np.float64)
+        if X.ndim != 2 or X.shape[1] < 1 or not np.isfinite(X).all():
+            raise ValueError('%s: the design of run %d must be a finite [T, P] matrix' % (who, r))
+        T, P = int(y.shape[0]), int(X.shape[1])
+        if X.shape[0] != T:
+            raise ValueError('%s: the design of run %d has %d rows, the run %d' % (who, r, X.shape[0], T))
+        c = contrasts_one_vs_rest(d) if per_run is None else per_run[r]
+        if c.shape[1] != P or c.shape[0] < 1 or not np.isfinite(c).all():
+            raise ValueError('%s: the contrasts of run %d must be finite [C, P = %d], got %r' % (who, r, P, c.shape))
+        if C is None:
+            C = int(c.shape[0])
+        if c.shape[0] != C:
+            raise ValueError('%s: run %d has %d contrasts, run 0 has %d' % (who, r, c.shape[0], C))
+        if limits and (P > PMAX or C > CMAX):
+            raise ValueError('%s: run %d has P = %d design columns and C = %d contrasts; served: P <= %d, C <= %d'
+                             % (who, r, P, C, PMAX, CMAX))
+        k, Q, B = _factor(X)
+        if T <= k:
+            raise ValueError('%s: run %d has T = %d rows and a design of rank %d: no residual degrees of freedom' % (who, r, T, k))
+        if limits and k > KMAX:
+            raise ValueError('%s: the design of run %d has rank %d; served: up to %d' % (who, r, k, KMAX))
+        proj = Q.T @ X                                          # X^+ X c = V_k V_k^T c = B (Q^T X) c
+        for i in range(C):
+            miss = np.linalg.norm(c[i] - B @ (proj @ c[i]))
+            if miss > ESTIMABLE_TOL * np.linalg.norm(c[i]) or not np.linalg.norm(c[i]) > 0:
+                raise ValueError('%s: contrast %d is not estimable in run %d (its part outside the row space of the design: %.3g '
+                                 'of its norm)' % (who, i, r, miss / max(np.linalg.norm(c[i]), 1e-300)))
+        u = c @ B                                               # [C, k]
+        tables.append(_Run(T, X, c, k, Q, B, u, (u * u).sum(axis=1)))
+    return _Plan(runs, tables, M, C, keys, [members[g] for g in keys], tensors)
+
+
+def _host_array(y, who):
+    y = (y.detach().cpu().numpy() if _is_tensor(y) else np.asarray(y))
+    if y.dtype.kind not in 'fiu':
+        raise ValueError('%s: series of dtype %s' % (who, y.dtype))
+    y = y.astype(np.float32)
+    if not np.isfinite(y).all():
+        raise ValueError('%s: series hold non-finite values' % who)
+    return y
+
+
+# ---- the host restatement -------------------------------------------------------------------------------------------------------
+
+def first_level_host(runs, designs, contrasts=None, groups=None, betas=False):
+    """``first_level`` restated in float64 NumPy (no device), without the projection trick of the kernels.  Per run:
+    ``b = lstsq(X, y)`` (minimum norm), the residuals formed explicitly, ``rss = sum res^2``, ``dof = T - rank(X)``,
+    ``sigma^2 = rss / dof``; per contrast ``effect = c.b``, ``variance = sigma^2 c pinv(X^T X) c``, ``t = effect / sqrt(variance)``
+    (0 where the variance is 0).  The runs of a group are combined as fixed effects: ``effect = mean_r effect_r``,
+    ``variance = sum_r variance_r / R_g^2``, ``dof = sum_r dof_r``.  The series are rounded to float32 first, as staging does.
+    Returns a ``GLMResult`` of float64 maps (betas float64 as well)."""
+    who = 'first_level_host'
+    pl = _plan(runs, designs, contrasts, groups, who, limits=False)
+    eff, var, dof, bs = [], [], [], []
+    for y, tb in zip(pl.runs, pl.tables):
+        y = _host_array(y, who).astype(np.float64)
+        b = np.linalg.lstsq(tb.X, y, rcond=max(tb.X.shape) * np.finfo(np.float64).eps)[0]
+        res = y - tb.X @ b
+        rss = (res * res).sum(axis=0)
+        d = tb.T - tb.rank
+        factor = np.einsum('cp,pq,cq->c', tb.c, np.linalg.pinv(tb.X.T @ tb.X, rcond=(max(tb.X.shape) * np.finfo(np.float64).eps) ** 2,
+                                                                 hermitian=True), tb.c)
+        eff.append(tb.c @ b)
+        var.append((rss / d)[None, :] * factor[:, None])
+        dof.append(d)
+        bs.append(b)
+    S = len(pl.keys)
+    effect = np.empty((S, pl.C, pl.M))
+    variance = np.empty((S, pl.C, pl.M))
+    gdof = np.empty(S, np.int64)
+    for g, mem in enumerate(pl.members):
+        se, sv = np.zeros((pl.C, pl.M)), np.zeros((pl.C, pl.M))
+        for r in mem:
+            se, sv = se + eff[r], sv + var[r]
+        effect[g] = se / len(mem)
+        variance[g] = sv / (float(len(mem)) * float(len(mem)))
+        gdof[g] = sum(dof[r] for r in mem)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        t = np.where(variance > 0, effect / np.sqrt(variance), 0.0)
+    return GLMResult(effect, variance, t, gdof, list(pl.keys), bs if betas else None)
+
+
+# ---- the device -----------------------------------------------------------------------------------------------------------------
+
+def _batch_tables(tabs, C):
+    """The tables of one batch of runs, padded with zero columns to its common k (and zero rows to its common P)."""
+    k = max(max(tb.rank for tb in tabs), 1)
+    P = max(tb.X.shape[1] for tb in tabs)
+    Q = np.zeros((sum(tb.T for tb in tabs), k))
+    U = np.zeros((len(tabs), C, k))
+    B = np.zeros((len(tabs), P, k))
+    o = 0
+    for i, tb in enumerate(tabs):
+        Q[o:o + tb.T, :tb.rank] = tb.Q
+        U[i, :, :tb.rank] = tb.u
+        B[i, :tb.X.shape[1], :tb.rank] = tb.B
+        o += tb.T
+    return Q, U, np.stack([tb.un2 for tb in tabs]), B, np.array([tb.rank for tb in tabs], np.int32)
+
+
+def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=False, batch_runs=None):
+    """Per-subject activation maps of a general linear model, on the device: a ``GLMResult``.
+
+    ``runs``: one ``[T, M]`` array or a list (any lengths, same M; NumPy arrays, or torch tensors such as
+    ``Parcellation.reduce`` returns, which are staged where they lie).  They are staged as ``[Ttot, plane_stride(M)]`` float32
+    planes with a device table of run offsets, as ``connectivity_graph`` stages them.  ``designs``: one ``Design`` per run.
+    ``contrasts``: ``[C, P]`` for every run (or one such array per run, when designs differ in width); default
+    ``contrasts_one_vs_rest`` of each design.  ``groups``: one hashable key per run -- the subject; default one group; the
+    runs of a group are combined as fixed effects (``effect`` the mean, ``variance = sum / R_g^2``, ``dof`` the sum).
+    ``batch_runs``: runs of one pass of the kernels, which bounds the float64 workspace of ``(k + 1) Mp`` values per run;
+    default from the free device memory.  The result does not depend on it, bit for bit.
+
+    Returns ``effect``, ``variance``, ``t`` float32 ``[S, C, M]`` (NumPy; torch tensors on the device if every run came as a
+    tensor), ``dof`` int64 ``[S]``, ``groups`` and, with ``betas``, one float32 ``[P_r, M]`` per run (the minimum-norm
+    solution where a design is rank deficient).  ``t`` is 0 where the variance is 0 (a vertex constant in time), never NaN.
+
+    ``ValueError`` before any launch: non-finite series, ``T_r <= rank``, a contrast that is not estimable in a run
+    (``|c - X^+ X c| > 1e-8 |c|``), design rows != run rows, mixed M, P, C or rank beyond what the kernels serve.
+
+    Out of scope: AR(1) / prewhitened noise (the OLS t of one run is optimistic under autocorrelation; effect maps are not
+    affected), temporal derivatives of the HRF, precision-weighted fixed effects, residual series."""
+    who = 'first_level'
+    pl = _plan(runs, designs, contrasts, groups, who)
+    if batch_runs is not None and (isinstance(batch_runs, (bool, np.bool_)) or not isinstance(batch_runs, (int, np.integer))
+                                   or batch_runs < 1):
+        raise ValueError('%s: batch_runs must be an int >= 1 or None, got %r' % (who, batch_runs))
+    if len(pl.keys) > RMAX:
+        raise ValueError('%s: %d groups; served: up to %d' % (who, len(pl.keys), RMAX))
+    on_device = any(_is_tensor(r) for r in pl.runs)
+    host = [None if _is_tensor(r) else _host_array(r, who) for r in pl.runs]
+    import torch
+    from . import _lib, ops
+    if device is None:
+        first = next((r for r in pl.runs if _is_tensor(r) and r.is_cuda), None)
+        dev = first.device if first is not None else torch.device('cuda', torch.cuda.current_device())
+    else:
+        dev = torch.device(device)
+    R, M, C = len(pl.runs), pl.M, pl.C
+    Mp = _lib.plane_stride(M)
+    offs = np.concatenate([[0], np.cumsum([tb.T for tb in pl.tables])]).astype(np.int64)
+    with torch.cuda.device(dev):
+        if on_device:
+            planes = torch.zeros((int(offs[-1]), Mp), dtype=torch.float32, device=dev)
+            for y, h, o in zip(pl.runs, host, offs):
+                planes[o:o + y.shape[0], :M] = (y.detach() if h is None else torch.as_tensor(h)).to(dev, torch.float32)
+            if not bool(torch.isfinite(planes).all()):
+                raise ValueError('%s: series hold non-finite values' % who)
+        else:
+            staged = np.zeros((int(offs[-1]), Mp), np.float32)
+            for h, o in zip(host, offs):
+                staged[o:o + h.shape[0], :M] = h
+            planes = torch.as_tensor(staged).to(dev)
+        if batch_runs is None:
+            kmax = max(tb.rank for tb in pl.tables)
+            free = torch.cuda.mem_get_info(dev)[0]
+            batch_runs = max(1, int(free // 4) // (8 * (kmax + 1) * Mp))
+        batch_runs = int(min(batch_runs, R, RMAX))
+        e64 = torch.empty((R, C, Mp), dtype=torch.float64, device=dev)
+        v64 = torch.empty((R, C, Mp), dtype=torch.float64, device=dev)
+        beta_out = []
+        for r0 in range(0, R, batch_runs):
+            r1 = min(r0 + batch_runs, R)
+            Q, U, un2, B, rank = (torch.as_tensor(a).to(dev) for a in _batch_tables(pl.tables[r0:r1], C))
+            rows = planes[int(offs[r0]):int(offs[r1])]
+            o = torch.as_tensor(offs[r0:r1 + 1] - offs[r0]).to(dev)
+            a, yy = ops.glm_project(rows, o, M, Q)
+            beta = ops.glm_finish(a, yy, o, rows.shape[0], rank, U, un2, M, B=B if betas else None,
+                                  out64=(e64[r0:r1], v64[r0:r1]))[3]
+            if betas:
+                beta_out += [beta[i, :tb.X.shape[1], :M] for i, tb in enumerate(pl.tables[r0:r1])]
+        gptr = np.concatenate([[0], np.cumsum([len(m) for m in pl.members])]).astype(np.int32)
+        gruns = np.concatenate([np.asarray(m, np.int32) for m in pl.members])
+        effect, variance, t = ops.glm_combine(e64, v64, torch.as_tensor(gptr).to(dev), torch.as_tensor(gruns).to(dev), M)
+        dof = np.array([sum(pl.tables[r].T - pl.tables[r].rank for r in m) for m in pl.members], np.int64)
+        if pl.tensors:
+            return GLMResult(effect, variance, t, dof, list(pl.keys), [b.contiguous() for b in beta_out] if betas else None)
+        return GLMResult(effect.cpu().numpy(), variance.cpu().numpy(), t.cpu().numpy(), dof, list(pl.keys),
+                         [b.cpu().numpy() for b in beta_out] if betas else None)

@@ -650,6 +650,114 @@ def cluster_enhance(t, mode, ptr=None, idx=None, hf=None, hw=None, ep=None, step
     return out, labels, pmax
 
 
+def glm_geometry():
+    """The constants of the GLM kernels (chebgcn_glm_query), so that callers and tests follow the tile: ``vertices`` of a
+    project workgroup, ``panel`` columns of Q of one pass over the scan, ``max_k`` / ``max_C`` / ``max_P`` served, ``split`` the
+    run length from which the time loop is cut into slices, ``slice`` the least rows of a slice, ``slices`` at most, ``max_runs``
+    of one call."""
+    q = _lib.lib().chebgcn_glm_query
+    return {'vertices': q(0), 'panel': q(1), 'max_k': q(2), 'max_C': q(3), 'split': q(4), 'slice': q(5), 'slices': q(6),
+            'max_P': q(7), 'max_runs': q(8)}
+
+
+def _dense(t, dtype, shape, what):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise _lib.ChebgcnError('%s must be a contiguous %s tensor %r, got %s %r' % (
+            what, str(dtype).split('.')[-1], tuple(shape), str(t.dtype).split('.')[-1], tuple(t.shape)))
+
+
+def glm_project(planes, run_offsets, M, Q):
+    """The projections of every run on its design's orthonormal basis (chebgcn_glm_project): ``planes`` float32 [Ttot, Mp],
+    ``run_offsets`` int64 [R + 1] and ``Q`` float64 [Ttot, k] on the device -> ``(a float64 [R, k, Mp], yy float64 [R, Mp])``
+    in one workspace (the next call on the stream reuses it).  float64 FMA chains in ascending t: include/chebgcn.h."""
+    _require_cuda(planes, run_offsets, Q)
+    if planes.dim() != 2 or planes.shape[1] != plane_stride(M) or planes.dtype != torch.float32 or not planes.is_contiguous():
+        raise _lib.ChebgcnError('glm_project: planes must be contiguous float32 [Ttot, plane_stride(M)]')
+    Ttot, Mp = int(planes.shape[0]), int(planes.shape[1])
+    R = int(run_offsets.numel()) - 1
+    if run_offsets.dtype != torch.int64 or run_offsets.dim() != 1 or R < 1 or not run_offsets.is_contiguous():
+        raise _lib.ChebgcnError('glm_project: run_offsets must be a contiguous int64 vector of R + 1 entries')
+    if Q.dim() != 2:
+        raise _lib.ChebgcnError('glm_project: Q must be float64 [Ttot, k]')
+    k = int(Q.shape[1])
+    _dense(Q, torch.float64, (Ttot, k), 'glm_project: Q')
+    lib = _lib.lib()
+    nbytes = int(lib.chebgcn_glm_workspace(R, M, k))
+    ws = _workspace(max(nbytes, 8) + 8, planes.device, 'glm')
+    ws = ws[(-ws.data_ptr()) % 8:]
+    a = ws[:8 * R * k * Mp].view(torch.float64).view(R, k, Mp) if nbytes else None
+    yy = ws[8 * R * k * Mp:8 * R * (k + 1) * Mp].view(torch.float64).view(R, Mp) if nbytes else None
+    panels = -(-k // max(glm_geometry()['panel'], 1))
+    _lib.check(_launch('glm_project', 4.0 * Ttot * Mp * panels + 8.0 * R * (k + 1) * Mp, 2.0 * Ttot * Mp * (k + 1),
+                       lambda: lib.chebgcn_glm_project(_p(planes), Ttot, _p(run_offsets), R, int(M), _p(Q), k, _p(a), _p(yy),
+                                                       _stream())), 'glm_project')
+    return a, yy
+
+
+def glm_finish(a, yy, run_offsets, Ttot, rank, U, unorm2, M, B=None, out64=None, want32=False):
+    """Residual variance and contrasts of every (run, vertex) (chebgcn_glm_finish) from what ``glm_project`` returned: ``rank``
+    int32 [R], ``U`` float64 [R, C, k], ``unorm2`` float64 [R, C], ``B`` float64 [R, P, k] or None, all on the device.
+    ``out64``: a pair of float64 [R, C, Mp] tensors that receive effect and variance (for ``glm_combine``).  Returns
+    ``(effect, variance, t)`` float32 [R, C, Mp] (``want32``, else None) and ``beta`` float32 [R, P, Mp] or None."""
+    _require_cuda(a, yy, run_offsets, rank, U, unorm2, B)
+    R, k, Mp = (int(v) for v in a.shape)
+    if Mp != plane_stride(M):
+        raise _lib.ChebgcnError('glm_finish: a must be [R, k, plane_stride(M)]')
+    _dense(a, torch.float64, (R, k, Mp), 'glm_finish: a')
+    _dense(yy, torch.float64, (R, Mp), 'glm_finish: yy')
+    _dense(run_offsets, torch.int64, (R + 1,), 'glm_finish: run_offsets')
+    _dense(rank, torch.int32, (R,), 'glm_finish: rank')
+    if U.dim() != 3:
+        raise _lib.ChebgcnError('glm_finish: U must be float64 [R, C, k]')
+    C_ = int(U.shape[1])
+    _dense(U, torch.float64, (R, C_, k), 'glm_finish: U')
+    _dense(unorm2, torch.float64, (R, C_), 'glm_finish: unorm2')
+    P = 0
+    beta = None
+    if B is not None:
+        if B.dim() != 3:
+            raise _lib.ChebgcnError('glm_finish: B must be float64 [R, P, k]')
+        P = int(B.shape[1])
+        _dense(B, torch.float64, (R, P, k), 'glm_finish: B')
+        beta = torch.empty((R, P, Mp), dtype=torch.float32, device=a.device)
+    e64 = v64 = None
+    if out64 is not None:
+        e64, v64 = out64
+        _require_cuda(e64, v64)
+        _dense(e64, torch.float64, (R, C_, Mp), 'glm_finish: out64[0]')
+        _dense(v64, torch.float64, (R, C_, Mp), 'glm_finish: out64[1]')
+    e32 = v32 = t32 = None
+    if want32:
+        e32, v32, t32 = (torch.empty((R, C_, Mp), dtype=torch.float32, device=a.device) for _ in range(3))
+    _lib.check(_launch('glm_finish', 8.0 * R * Mp * (k * (1 + C_ + P) + 1), 2.0 * R * Mp * k * (1 + C_ + P),
+                       lambda: _lib.lib().chebgcn_glm_finish(
+                           _p(a), _p(yy), _p(run_offsets), int(Ttot), _p(rank), _p(U), _p(unorm2), _p(B), R, int(M), k, C_, P,
+                           _p(e64), _p(v64), _p(e32), _p(v32), _p(t32), _p(beta), _stream())), 'glm_finish')
+    return e32, v32, t32, beta
+
+
+def glm_combine(e64, v64, group_ptr, group_runs, M):
+    """Fixed effects over the runs of every group (chebgcn_glm_combine): ``e64`` / ``v64`` float64 [R, C, Mp] from ``glm_finish``,
+    ``group_ptr`` int32 [S + 1] / ``group_runs`` int32 [nruns] on the device -> ``(effect, variance, t)`` float32 [S, C, M]."""
+    _require_cuda(e64, v64, group_ptr, group_runs)
+    R, C_, Mp = (int(v) for v in e64.shape)
+    if Mp != plane_stride(M):
+        raise _lib.ChebgcnError('glm_combine: the maps must be [R, C, plane_stride(M)]')
+    _dense(e64, torch.float64, (R, C_, Mp), 'glm_combine: effects')
+    _dense(v64, torch.float64, (R, C_, Mp), 'glm_combine: variances')
+    S = int(group_ptr.numel()) - 1
+    n = int(group_runs.numel())
+    if S < 1 or n < 1:
+        raise _lib.ChebgcnError('glm_combine: no groups')
+    _dense(group_ptr, torch.int32, (S + 1,), 'glm_combine: group_ptr')
+    _dense(group_runs, torch.int32, (n,), 'glm_combine: group_runs')
+    out = tuple(torch.empty((S, C_, M), dtype=torch.float32, device=e64.device) for _ in range(3))
+    _lib.check(_launch('glm_combine', 16.0 * n * C_ * M + 12.0 * S * C_ * M, 2.0 * n * C_ * M, lambda: _lib.lib().chebgcn_glm_combine(
+        _p(e64), _p(v64), _p(group_ptr), _p(group_runs), n, R, S, C_, int(M), _p(out[0]), _p(out[1]), _p(out[2]), _stream())),
+        'glm_combine')
+    return out
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------

@@ -921,6 +921,55 @@ int chebgcn_cluster_enhance(const int32_t* ptr, const int32_t* idx, int64_t nnz,
                             int32_t* status, void* workspace, size_t workspace_bytes, int Pb, int M, int mode, int arm,
                             chebgcn_stream stream);
 
+/* ---- first-level GLM on staged scans: projections, residual variance, contrasts (glm.first_level) ------------------------------
+ * The caller factors every run's design on the host, X = U S V^T (thin SVD, rank k_r), and hands the kernels
+ *   Q = U[:, :k_r]                        float64 [Ttot][k]: row t belongs to the run that contains t; columns [k_r, k) are zero
+ *   u = (V[:, :k_r] / S[:k_r])^T c        float64 [R][C][k] per contrast c, and unorm2 = u.u = c pinv(X^T X) c, float64 [R][C]
+ *   B = V[:, :k_r] / S[:k_r]              float64 [R][P][k] (b = B a is the minimum-norm solution), only for the coefficients
+ *   rank[r] = k_r                         int32 [R]
+ * series: float32 [Ttot][Mp(M)] = R runs concatenated, run r = rows [run_offsets[r], run_offsets[r + 1]) (int64 [R + 1], device).
+ * Every entry of run_offsets is clamped into [0, Ttot] and a descending pair is an empty run; rank[r] is clamped into [0, k];
+ * a run number of group_runs outside [0, R) is skipped: nothing read from memory is an address or a trip count unchecked.
+ * All arithmetic is float64 (a float32 sum of y.y cannot resolve rss = 2e-5 y.y, the BOLD case), no float atomics, every order
+ * fixed: outputs are bit-identical from call to call, and a (run, vertex) result does not depend on R, on M, on the other runs
+ * of the call or on how the caller cuts the runs into calls (k of the call included: zero columns are never touched).
+ *
+ * glm_project: a[r][j][m] = sum_t Q[t][j] * y[t][m] (float64 [R][k][Mp]) and yy[r][m] = sum_t y[t][m]^2 (float64 [R][Mp]), each
+ *   ONE chain acc = fma(q, y, acc) from 0 over ascending t of the run -- for a run of T >= chebgcn_glm_query(4) rows one chain
+ *   per slice: n = min(chebgcn_glm_query(6), T / chebgcn_glm_query(5)) slices of ceil(T / n) consecutive rows (a function of T
+ *   alone), the slices' sums added to the first one's in ascending order (plain float64 additions).  What the pad [M, Mp) of
+ *   series holds (NaN included) never reaches a result; the pad of a and yy is written as zero.  k above chebgcn_glm_query(1) columns runs in panels of that many
+ *   (the last one narrower), the scan re-read once per panel, yy formed in the first.  One pass otherwise.
+ *   chebgcn_last_dispatch(): glm_project_kernel<NJ> per panel, NJ = its columns, joined by " + ".
+ * glm_finish, per (run, vertex), T = the run's rows, dof = T - k_r:
+ *     ssq = 0; ssq = fma(a_j, a_j, ssq), j ascending;   rss = yy - ssq, taken as 0 where rss < 4 (T + k_r) 2^-53 yy (the
+ *     round-off of that subtraction; measured 5e-15 yy against this floor of 1.4e-13 yy at T = 284, k = 22);
+ *     sigma2 = dof > 0 ? rss / dof : 0;   per contrast  e = 0; e = fma(u_j, a_j, e), j ascending;   variance = sigma2 * unorm2;
+ *     t = variance > 0 ? e / sqrt(variance) : 0   (never NaN for finite input);   beta_p = fma chain of B[p][j] a_j likewise.
+ *   eff64 / var64: float64 [R][C][Mp] (for glm_combine); effect / variance / t: float32 [R][C][Mp], each rounded ONCE from the
+ *   float64 value; beta: float32 [R][P][Mp].  Each of the three sets may be NULL (B with beta), at least one is given.
+ *   chebgcn_last_dispatch(): glm_finish_kernel.
+ * glm_combine: fixed effects over the runs of a group.  group_ptr int32 [S + 1] / group_runs int32 [nruns] (device): group g is
+ *   the runs group_runs[group_ptr[g] .. group_ptr[g + 1]), summed in that order (the caller lists them ascending), n of them:
+ *     effect = (sum_r e_r) / n;   variance = (sum_r variance_r) / (n * n);   t = variance > 0 ? effect / sqrt(variance) : 0
+ *   float64 from eff64 / var64, ONE rounding to float32; outputs [S][C][M] contiguous (no pad).
+ *   chebgcn_last_dispatch(): glm_combine_kernel.
+ * glm_query: 0 vertices of a project workgroup, 1 columns of a panel, 2 the largest k, 3 the largest C, 4 the run length from
+ *   which the time loop is split, 5 the least rows of a slice, 6 slices at most, 7 the largest P, 8 runs of one call at most;
+ *   -1 for anything else.
+ * glm_workspace: bytes of a and yy together for R runs (yy follows a; 0: arguments out of range).
+ * Limits: k <= 64, C <= 32, P <= 64, R <= 65535 per call, S <= 65535, Ttot * Mp <= 2^39: CHEBGCN_EUNSUPPORTED beyond, before
+ * any launch, as every CHEBGCN_EINVAL (NULL, counts <= 0, pointers not aligned to their element; series to 8 bytes).  The calls neither synchronise nor allocate. */
+int chebgcn_glm_query(int what);
+size_t chebgcn_glm_workspace(int R, int M, int k);
+int chebgcn_glm_project(const float* series, int64_t Ttot, const int64_t* run_offsets, int R, int M, const double* Q, int k, double* a,
+                        double* yy, chebgcn_stream stream);
+int chebgcn_glm_finish(const double* a, const double* yy, const int64_t* run_offsets, int64_t Ttot, const int32_t* rank, const double* U,
+                       const double* unorm2, const double* B, int R, int M, int k, int C, int P, double* eff64, double* var64,
+                       float* effect, float* variance, float* t, float* beta, chebgcn_stream stream);
+int chebgcn_glm_combine(const double* eff64, const double* var64, const int32_t* group_ptr, const int32_t* group_runs, int nruns, int R,
+                        int S, int C, int M, float* effect, float* variance, float* t, chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose

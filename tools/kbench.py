@@ -4,6 +4,7 @@
     python tools/kbench.py [--B 64 256] [--fin 32] [--fout 32] [--K 5] [--iters 20]
                            [--kernels recurrence_fwd ...]
     python tools/kbench.py --parcellate [--iters 20] [--json out.json]      # the parcellation leg alone
+    python tools/kbench.py glm [--iters 20] [--json out.json]               # the first-level GLM kernels alone
 
 Times each C-ABI entry point with HIP events on the launch stream and prints achieved
 algorithmic GB/s (SURVEY.md 8d byte counts) and the fraction of the 8 TB/s HBM roofline.
@@ -125,8 +126,89 @@ def parcellate_leg(args):
             json.dump(results, f, indent=1)
 
 
+def glm_leg(args):
+    """chebgcn_glm_project and chebgcn_glm_finish at two shapes -- one HCP dtseries run (1200 x 91282, k = 40) and 256 atlas runs
+    (284 x 360, k = 22) -- each against the bytes-once HBM floor (6.29 TB/s measured copy rate, 8 TB/s spec), the float64 FMA
+    count at the vector rate (78.6 TFLOP/s: half the fp32 vector rate) and what a user would write in torch on the same device:
+    ``Q.T @ series.double()`` per run plus the residual algebra."""
+    import torch
+    from gcn_fmri_decoding_amd import _lib, ops
+    dev = torch.device('cuda:0')
+    HBM, HBM_SPEC, FMA64 = 6.29e12, 8.0e12, 78.6e12 / 2
+    results = []
+
+    def timeit(fn, iters):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        for s, e in evs:
+            s.record()
+            fn()
+            e.record()
+        torch.cuda.synchronize()
+        ms = sorted(s.elapsed_time(e) for s, e in evs)
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    def note(name, shape, t, nbytes, fmas, dispatch=''):
+        med, lo, hi = t
+        r = {'leg': name, 'shape': shape, 'median_ms': med, 'min_ms': lo, 'max_ms': hi, 'bytes': nbytes, 'fma64': fmas,
+             'hbm_floor_ms': 1e3 * nbytes / HBM, 'hbm_spec_floor_ms': 1e3 * nbytes / HBM_SPEC, 'fma_floor_ms': 1e3 * fmas / FMA64,
+             'dispatch': dispatch}
+        results.append(r)
+        print('%-22s %-22s %9.3f ms (min %8.3f, max %8.3f)  HBM floor %7.3f ms (%4.1fx)  fp64 FMA floor %7.3f ms (%4.1fx)  %s'
+              % (name, shape, med, lo, hi, r['hbm_floor_ms'], med / r['hbm_floor_ms'], r['fma_floor_ms'],
+                 med / max(r['fma_floor_ms'], 1e-9), dispatch), flush=True)
+
+    for R, T, M, k, C in ((1, 1200, 91282, 40, 4), (256, 284, 360, 22, 4)):
+        shape = '%dx%dx%d k=%d' % (R, T, M, k)
+        Mp = _lib.plane_stride(M)
+        g = torch.Generator(device=dev).manual_seed(R)
+        planes = torch.zeros(R * T, Mp, device=dev)
+        planes[:, :M] = 1e4 + 50.0 * torch.randn(R * T, M, device=dev, generator=g)
+        offs = torch.arange(R + 1, device=dev, dtype=torch.int64) * T
+        Q = torch.linalg.qr(torch.randn(R, T, k, device=dev, dtype=torch.float64, generator=g))[0].reshape(R * T, k).contiguous()
+        U = torch.randn(R, C, k, device=dev, dtype=torch.float64, generator=g)
+        un2 = (U * U).sum(dim=2)
+        rank = torch.full((R,), k, device=dev, dtype=torch.int32)
+        e64 = torch.empty(R, C, Mp, device=dev, dtype=torch.float64)
+        v64 = torch.empty_like(e64)
+        panels = -(-k // ops.glm_geometry()['panel'])
+        a, yy = ops.glm_project(planes, offs, M, Q)
+        note('glm_project', shape, timeit(lambda: ops.glm_project(planes, offs, M, Q), args.iters),
+             4.0 * R * T * Mp + 8.0 * R * (k + 1) * Mp + 8.0 * R * T * k, float(R) * T * Mp * (k + 1), _lib.last_dispatch())
+        if panels > 1:
+            print('    (%d panels: the scan is read %d times, %.3f ms at the copy rate)' % (panels, panels,
+                                                                                          1e3 * 4.0 * R * T * Mp * panels / HBM))
+        note('glm_finish', shape, timeit(lambda: ops.glm_finish(a, yy, offs, R * T, rank, U, un2, M, out64=(e64, v64)), args.iters),
+             8.0 * R * (k + 1) * Mp + 16.0 * R * C * Mp, float(R) * Mp * k * (1 + C), _lib.last_dispatch())
+        y3 = planes.view(R, T, Mp)
+        Q3 = Q.view(R, T, k)
+
+        def torch_project():
+            yd = y3.double()
+            return torch.bmm(Q3.transpose(1, 2), yd), (yd * yd).sum(dim=1)
+
+        def torch_finish(at, yt):
+            s2 = (yt - (at * at).sum(dim=1)).clamp_min(0.0) / float(T - k)
+            e = torch.bmm(U, at)
+            v = s2[:, None, :] * un2[:, :, None]
+            return e, v, e / v.sqrt()
+        at, yt = torch_project()
+        print('    max |a - torch| / max |a| = %.3e' % float((a - at).abs().max() / at.abs().max()))
+        note('torch Q.T @ y.double()', shape, timeit(torch_project, args.iters), 4.0 * R * T * Mp + 8.0 * R * (k + 1) * Mp + 8.0 * R * T * k,
+             float(R) * T * Mp * (k + 1))
+        note('torch residual algebra', shape, timeit(lambda: torch_finish(at, yt), args.iters), 8.0 * R * (k + 1) * Mp + 16.0 * R * C * Mp,
+             float(R) * Mp * k * (1 + C))
+        del planes, Q, y3, Q3, at, yt, a, yy
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('leg', nargs='?', choices=['glm'], help='glm: the first-level GLM kernels alone (ops.glm_project / glm_finish)')
     ap.add_argument('--parcellate', action='store_true', help='the parcellation leg alone (ops.parcellate at HCP size)')
     ap.add_argument('--B', type=int, nargs='+', default=[64, 256])
     ap.add_argument('--fin', type=int, default=32)
@@ -150,6 +232,8 @@ def main():
     args = ap.parse_args()
     if args.parcellate:
         return parcellate_leg(args)
+    if args.leg == 'glm':
+        return glm_leg(args)
 
     import torch
     import bench
