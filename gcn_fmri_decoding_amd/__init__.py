@@ -6,16 +6,19 @@ and ``lib_new.coarsening`` (pooling index maps), on PyTorch-ROCm tensors, with t
 arithmetic in hand-written gfx950 kernels behind the C ABI of ``include/chebgcn.h``.
 """
 from . import _lib  # noqa: F401
-from . import graph, coarsening, parcellation, filters, splits, stats, glm  # noqa: F401
+from . import graph, coarsening, parcellation, filters, splits, stats, glm, searchlight  # noqa: F401
 from .parcellation import Parcellation  # noqa: F401
 from .filters import GraphFilter  # noqa: F401
 from .stats import MapTestResult, map_test, map_test_host, sign_flips  # noqa: F401
 from .glm import (Design, GLMResult, contrasts_one_vs_rest, design_matrix, first_level,  # noqa: F401
                   first_level_host)
+# (the call itself is searchlight.searchlight: the package attribute stays the module)
+from .searchlight import SearchlightResult, searchlight_events, searchlight_host  # noqa: F401
 
 __all__ = ['graph', 'coarsening', 'parcellation', 'Parcellation', 'filters', 'GraphFilter', 'splits', 'stats', 'map_test',
            'map_test_host', 'sign_flips', 'MapTestResult', 'glm', 'Design', 'GLMResult', 'design_matrix', 'contrasts_one_vs_rest',
-           'first_level', 'first_level_host', 'models_gcn', 'ops']
+           'first_level', 'first_level_host', 'searchlight', 'SearchlightResult', 'searchlight_events', 'searchlight_host',
+           'models_gcn', 'ops']
 
 
 def __getattr__(name):

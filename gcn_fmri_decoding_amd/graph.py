@@ -286,6 +286,26 @@ def permute(L, order):
     return Lp
 
 
+def hop_balls(A, hops):
+    """The boolean CSR pattern of ``(I + A)^hops`` with sorted indices: row v lists the vertices within ``hops`` edges of v, itself
+    included (``hops = 0``: the identity).  The pattern of ``A`` is its non-zero entries, taken as given: an edge stored in one
+    direction only is walked in that direction only.  On the host; the neighbourhoods ``searchlight`` takes."""
+    if isinstance(hops, (bool, np.bool_)) or not isinstance(hops, (int, np.integer)) or hops < 0:
+        raise ValueError('hop_balls: hops must be an int >= 0, got %r' % (hops,))
+    if not sp.issparse(A) or A.shape[0] != A.shape[1] or A.shape[0] < 1:
+        raise ValueError('hop_balls: A must be a square SciPy sparse matrix')
+    n = A.shape[0]
+    step = sp.csr_matrix(A != 0, dtype=np.int32) + sp.identity(n, dtype=np.int32, format='csr')
+    step.data[:] = 1
+    balls = sp.identity(n, dtype=np.int32, format='csr')
+    for _ in range(int(hops)):
+        balls = sp.csr_matrix(balls @ step)
+        balls.data[:] = 1                                       # a pattern: path counts would overflow
+    balls = balls.astype(bool)
+    balls.sort_indices()
+    return balls
+
+
 def synthetic_graph(n_nodes=10000, k=8, levels=1, noise_level=0.01, seed=0, dtype=np.float32, knn='host'):
     """The seeded synthetic "brain" graph of the benchmark: kNN
     graph on uniform points in the unit cube, 1 % random edges, ``levels`` rounds of

@@ -758,6 +758,112 @@ def glm_combine(e64, v64, group_ptr, group_runs, M):
     return out
 
 
+def searchlight_geometry():
+    """The constants of the searchlight kernels (chebgcn_searchlight_query), so that callers and tests follow the tile: ``tile``
+    lanes of a score wave, ``centres`` of a score workgroup, ``max_C`` classes served, ``vertices`` of a spread / fit workgroup,
+    ``max_models`` of one call, ``max_tiles`` of a model's test samples, ``max_groups``; ``buckets``: the class bucket (the ``NC``
+    of ``searchlight_score_kernel<NC>``) of every class count 2 .. ``max_C``; and per bucket ``per_lane`` -- the test samples of
+    a lane: a workgroup covers ``tile * per_lane`` consecutive test samples of a model -- and ``unroll``, its neighbours in
+    flight."""
+    q = _lib.lib().chebgcn_searchlight_query
+    buckets = {c: q(100 + c) for c in range(2, q(3) + 1)}
+    widths = sorted(set(buckets.values()))
+    return {'tile': q(0), 'centres': q(1), 'max_C': q(3), 'vertices': q(4), 'max_models': q(5), 'max_tiles': q(6), 'max_groups': q(7),
+            'buckets': buckets, 'per_lane': {b: q(9) if b <= q(8) else 1 for b in widths},
+            'unroll': {b: q(10) if b <= q(8) else q(2) for b in widths}}
+
+
+def _sl_patterns(Xt, S, what):
+    if Xt.dim() != 2 or Xt.shape[1] != plane_stride(S) or Xt.dtype != torch.float32 or not Xt.is_contiguous():
+        raise _lib.ChebgcnError('%s: Xt must be contiguous float32 [M, plane_stride(S)]' % what)
+    return int(Xt.shape[0])
+
+
+def _sl_lists(ptr, idx, n, what):
+    if idx.dim() != 1 or idx.numel() < 1:
+        raise _lib.ChebgcnError('%s: empty sample lists' % what)
+    _dense(ptr, torch.int32, (n + 1,), what + ': list pointers')
+    _dense(idx, torch.int32, (int(idx.numel()),), what + ': list entries')
+    return int(idx.numel())
+
+
+def searchlight_spread(Xt, S, list_ptr, list_idx):
+    """The variance of the whole training set of every model at every vertex (chebgcn_searchlight_spread): ``Xt`` float32
+    [M, plane_stride(S)] vertex-major patterns, ``list_ptr`` int32 [NM + 1] / ``list_idx`` int32 the models' training samples,
+    on the device -> float64 [NM, M].  Two-pass float64 moments in list order: include/chebgcn.h."""
+    _require_cuda(Xt, list_ptr, list_idx)
+    M = _sl_patterns(Xt, S, 'searchlight_spread')
+    NM = int(list_ptr.numel()) - 1
+    n = _sl_lists(list_ptr, list_idx, NM, 'searchlight_spread')
+    spread = torch.empty((NM, M), dtype=torch.float64, device=Xt.device)
+    _lib.check(_launch('searchlight_spread', 8.0 * n * M + 8.0 * NM * M, 4.0 * n * M, lambda: _lib.lib().chebgcn_searchlight_spread(
+        _p(Xt), int(S), M, _p(list_ptr), _p(list_idx), n, NM, _p(spread), _stream())), 'searchlight_spread')
+    return spread
+
+
+def searchlight_fit(Xt, S, class_ptr, class_idx, C, eps, pooled=False):
+    """The naive-Bayes tables of every (model, vertex) (chebgcn_searchlight_fit): ``class_ptr`` int32 [NM * C + 1] /
+    ``class_idx`` int32 the training samples of every (model, class), ``eps`` float64 [NM] the smoothing added to every variance
+    -> ``(par float64 [NM, M, NC, 2] = (mu, 1 / (2 var)), lg float64 [NM, M, NC] = log(2 pi var) / 2)``, ``NC`` the class bucket
+    of ``C``; ``pooled``: one variance for all classes."""
+    _require_cuda(Xt, class_ptr, class_idx, eps)
+    M = _sl_patterns(Xt, S, 'searchlight_fit')
+    NM = int(eps.numel())
+    _dense(eps, torch.float64, (NM,), 'searchlight_fit: eps')
+    n = _sl_lists(class_ptr, class_idx, NM * int(C), 'searchlight_fit')
+    NC = int(_lib.lib().chebgcn_searchlight_query(100 + int(C)))
+    if NC < int(C):
+        raise _lib.ChebgcnError('searchlight_fit: C = %r classes are not served' % (C,))
+    par = torch.empty((NM, M, NC, 2), dtype=torch.float64, device=Xt.device)
+    lg = torch.empty((NM, M, NC), dtype=torch.float64, device=Xt.device)
+    _lib.check(_launch('searchlight_fit', 8.0 * n * M + 24.0 * NM * M * NC, 4.0 * n * M, lambda: _lib.lib().chebgcn_searchlight_fit(
+        _p(Xt), int(S), M, _p(class_ptr), _p(class_idx), n, NM, int(C), int(bool(pooled)), _p(eps), _p(par), _p(lg), _stream())),
+        'searchlight_fit')
+    return par, lg
+
+
+def searchlight_score(Xt, S, rowptr, colidx, u0, Ub, test_ptr, tmax, C, par, lg, logprior, sgroup, slabel, sorig, correct,
+                      scores=None, predictions=None):
+    """Score the centres ``[u0, u0 + Ub)`` (chebgcn_searchlight_score): ``rowptr`` / ``colidx`` int32 CSR of all U neighbourhoods,
+    ``test_ptr`` int32 [NM + 1] the (contiguous) test samples of every model, ``tmax`` the most of one model, ``par`` / ``lg``
+    from ``searchlight_fit``, ``logprior`` float64 [NM, NC], ``sgroup`` / ``slabel`` / ``sorig`` int32 [S].  ADDS the hits to
+    ``correct`` int32 [G, C, U] and fills ``scores`` float64 [S, C, U] / ``predictions`` uint8 [S, U] where given.  float64 in
+    the centred form, a fixed order per centre: include/chebgcn.h."""
+    _require_cuda(Xt, rowptr, colidx, test_ptr, par, lg, logprior, sgroup, slabel, sorig, correct, scores, predictions)
+    M = _sl_patterns(Xt, S, 'searchlight_score')
+    S, C, u0, Ub = int(S), int(C), int(u0), int(Ub)
+    U = int(rowptr.numel()) - 1
+    nnz = _sl_lists(rowptr, colidx, U, 'searchlight_score')
+    NM = int(test_ptr.numel()) - 1
+    _dense(test_ptr, torch.int32, (NM + 1,), 'searchlight_score: test_ptr')
+    NC = int(_lib.lib().chebgcn_searchlight_query(100 + C))
+    _dense(par, torch.float64, (NM, M, NC, 2), 'searchlight_score: par')
+    _dense(lg, torch.float64, (NM, M, NC), 'searchlight_score: lg')
+    _dense(logprior, torch.float64, (NM, NC), 'searchlight_score: logprior')
+    for t, what in ((sgroup, 'sgroup'), (slabel, 'slabel'), (sorig, 'sorig')):
+        _dense(t, torch.int32, (S,), 'searchlight_score: ' + what)
+    if correct.dim() != 3 or correct.shape[1] != C or correct.shape[2] != U:
+        raise _lib.ChebgcnError('searchlight_score: correct must be int32 [G, C, U]')
+    G = int(correct.shape[0])
+    _dense(correct, torch.int32, (G, C, U), 'searchlight_score: correct')
+    if scores is not None:
+        _dense(scores, torch.float64, (S, C, U), 'searchlight_score: scores')
+    if predictions is not None:
+        _dense(predictions, torch.uint8, (S, U), 'searchlight_score: predictions')
+    if not 0 <= u0 <= U - Ub or Ub < 1:
+        raise _lib.ChebgcnError('searchlight_score: centres [%d, %d) outside the %d rows' % (u0, u0 + Ub, U))
+    nbytes = max(8 * NM * Ub * NC, 8)
+    ws = _workspace(nbytes + 8, Xt.device, 'searchlight')
+    ws = ws[(-ws.data_ptr()) % 8:]
+    base = ws[:nbytes].view(torch.float64)
+    terms = float(S) * float(nnz) * Ub / max(U, 1)
+    _lib.check(_launch('searchlight_score', 4.0 * terms + 16.0 * NM * NC * float(nnz) * Ub / max(U, 1), 4.0 * terms * C,
+                       lambda: _lib.lib().chebgcn_searchlight_score(
+                           _p(Xt), S, M, _p(rowptr), _p(colidx), nnz, U, u0, Ub, _p(test_ptr), int(tmax), NM, C, _p(par), _p(lg),
+                           _p(logprior), _p(sgroup), _p(slabel), _p(sorig), G, _p(base), _p(correct), _p(scores), _p(predictions),
+                           _stream())), 'searchlight_score')
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------

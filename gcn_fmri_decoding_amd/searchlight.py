@@ -1,0 +1,528 @@
+"""Searchlight decoding: where in the brain is the task information?
+
+At every centre a cross-validated Gaussian naive-Bayes classifier is fed only the centre's neighbourhood, and the centre gets
+the classifier's accuracy.  ``searchlight`` does it on the device for any list of neighbourhoods -- ``graph.hop_balls`` of the
+brain graph for the classical searchlight map, one row per parcel for ROI decoding, one row of all vertices for the whole-brain
+baseline a GCN accuracy is reported against.  ``searchlight_events`` cuts the trial-mean patterns out of staged runs with
+``match_events`` first.  ``searchlight_host`` restates it in float64 NumPy, centre by centre.
+
+The fit of naive Bayes is per-vertex moments and its decision a sum over the neighbourhood, so one fit per training set serves
+every centre (chebgcn_searchlight_spread / _fit), and the work is the S x classes x sum |neighbourhood| likelihood terms of
+chebgcn_searchlight_score.  All of it float64 in the centred form ``(x - mu)^2 / (2 sigma^2)``: see include/chebgcn.h.
+
+Out of scope: classifiers with a full covariance inside the ball (LDA, SVM), label-permutation nulls per subject (group
+inference goes through ``map_test``), smoothing per ball (see ``searchlight``), temporal features beyond the trial mean, and
+any cleaning of the series.
+
+The host-only parts need NumPy and SciPy only.
+"""
+import collections
+
+import numpy as np
+import scipy.sparse as sp
+
+from .glm import _host_array, _is_tensor
+
+CMAX, NMAX, GMAX = 32, 65535, 1 << 20           # chebgcn_searchlight_query(3), (5), (7)
+SCORES_MAX_BYTES = 1 << 31                      # scores=True is refused beyond 2 GiB of float64 [S, classes, U]
+FOLD_MAX = 16                                   # block_dura at most in searchlight_events (the indexed gather's fold)
+
+SearchlightResult = collections.namedtuple('SearchlightResult', 'correct support recall accuracy groups classes scores predictions')
+SearchlightResult.__doc__ = """What ``searchlight`` returns.  ``correct`` int32 [G, classes, U]: the test samples of group g and
+class c that centre u classified correctly; ``support`` int64 [G, classes]: how many there were; ``recall`` float32
+[G, classes, U] = correct / support (0 where the support is 0, never NaN); ``accuracy`` float32 [G, U] = the group's correct
+over its samples; ``groups`` the G keys in order of first appearance; ``classes``; ``scores`` float64 [S, classes, U] joint
+log-likelihoods and ``predictions`` uint8 [S, U], in the caller's sample order, or None."""
+
+_Args = collections.namedtuple('_Args', 'X tensor S M y classes indptr indices U fold gidx keys within pooled uniform vs')
+
+
+# ---- arguments ------------------------------------------------------------------------------------------------------------------
+
+def _neighbourhoods(nb, M, who):
+    """``(indptr, indices)`` int64 of the [U, M] pattern: indices ascending, duplicates merged, values ignored."""
+    if sp.issparse(nb):
+        if nb.ndim != 2 or nb.shape[1] != M or nb.shape[0] < 1:
+            raise ValueError('%s: neighbourhoods must be a sparse pattern [U, M = %d], got shape %r' % (who, M, tuple(nb.shape)))
+        pat = sp.csr_matrix(nb, copy=True)
+        pat.data = np.ones(pat.data.shape, np.int8)             # values are ignored: a stored zero is a member
+    else:
+        tab = nb.detach().cpu().numpy() if _is_tensor(nb) else np.asarray(nb)
+        if tab.ndim != 2 or tab.shape[0] != M or tab.shape[1] < 1 or tab.dtype.kind not in 'iu':
+            raise ValueError('%s: neighbourhoods must be a SciPy sparse pattern [U, M] or an integer table [M = %d, k], got %s %r'
+                             % (who, M, tab.dtype, tuple(tab.shape)))
+        tab = tab.astype(np.int64)
+        if tab.min() < 0 or tab.max() >= M:
+            raise ValueError('%s: the neighbour table names vertices outside [0, %d)' % (who, M))
+        rows = np.repeat(np.arange(M, dtype=np.int64), tab.shape[1] + 1)        # the centre itself is added: kNN tables leave it out
+        cols = np.concatenate([np.arange(M, dtype=np.int64)[:, None], tab], axis=1).ravel()
+        pat = sp.csr_matrix((np.ones(rows.size, np.int8), (rows, cols)), shape=(M, M))
+    pat.sum_duplicates()
+    pat.sort_indices()
+    indptr, indices = pat.indptr.astype(np.int64), pat.indices.astype(np.int64)
+    empty = np.flatnonzero(np.diff(indptr) == 0)
+    if empty.size:
+        raise ValueError('%s: neighbourhood %d is empty (%d empty rows)' % (who, empty[0], empty.size))
+    return indptr, indices
+
+
+def _vector(v, S, name, who):
+    a = np.asarray(v.detach().cpu().numpy() if _is_tensor(v) else v)
+    if a.ndim != 1 or a.shape[0] != S:
+        raise ValueError('%s: %s must hold one entry per sample ([S = %d]), got shape %r' % (who, name, S, a.shape))
+    return a
+
+
+def _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
+           batch_centres, who, limits=True):
+    """Everything that can be checked without the samples' values."""
+    tensor = _is_tensor(samples)
+    X = samples if tensor else np.asarray(samples)
+    if X.ndim != 2 or X.shape[0] < 2 or X.shape[1] < 1:
+        raise ValueError('%s: samples must be [S >= 2, M >= 1], got shape %r' % (who, tuple(X.shape)))
+    if tensor:
+        if X.is_complex() or str(X.dtype) == 'torch.bool':
+            raise ValueError('%s: samples of dtype %s' % (who, X.dtype))
+    elif X.dtype.kind not in 'fiu':
+        raise ValueError('%s: samples of dtype %s' % (who, X.dtype))
+    S, M = int(X.shape[0]), int(X.shape[1])
+    for name, val in (('within', within), ('scores', scores), ('predictions', predictions)):
+        if not isinstance(val, (bool, np.bool_)):
+            raise ValueError('%s: %s must be True or False, got %r' % (who, name, val))
+    if variance not in ('class', 'pooled'):
+        raise ValueError("%s: variance must be 'class' or 'pooled', got %r" % (who, variance))
+    if priors not in ('empirical', 'uniform'):
+        raise ValueError("%s: priors must be 'empirical' or 'uniform', got %r" % (who, priors))
+    if isinstance(var_smoothing, (bool, np.bool_)) or not isinstance(var_smoothing, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(var_smoothing) or var_smoothing < 0:
+        raise ValueError('%s: var_smoothing must be a finite number >= 0, got %r' % (who, var_smoothing))
+    if batch_centres is not None and (isinstance(batch_centres, (bool, np.bool_)) or not isinstance(batch_centres, (int, np.integer))
+                                      or batch_centres < 1):
+        raise ValueError('%s: batch_centres must be an int >= 1 or None, got %r' % (who, batch_centres))
+    lab = _vector(labels, S, 'labels', who)
+    if lab.dtype.kind not in 'iuUSO':
+        raise ValueError('%s: labels of dtype %s (ints or names)' % (who, lab.dtype))
+    lab = lab.tolist()
+    try:
+        classes = sorted(set(lab)) if classes is None else list(classes)
+        code = {c: i for i, c in enumerate(classes)}
+    except TypeError:
+        raise ValueError('%s: labels and classes must be sortable and hashable' % who) from None
+    if len(code) != len(classes) or len(classes) < 2:
+        raise ValueError('%s: at least two distinct classes are needed, got %r' % (who, classes))
+    if len(classes) > (CMAX if limits else 256):
+        raise ValueError('%s: %d classes; served: up to %d' % (who, len(classes), CMAX if limits else 256))
+    outside = [v for v in lab if v not in code]
+    if outside:
+        raise ValueError('%s: label %r is not in classes %r' % (who, outside[0], classes))
+    y = np.array([code[v] for v in lab], np.int64)
+    fold = _vector(folds, S, 'folds', who)
+    if fold.dtype.kind not in 'iu':
+        raise ValueError('%s: folds must be ints, got dtype %s' % (who, fold.dtype))
+    fold = fold.astype(np.int64)
+    if groups is None:
+        groups = [0] * S
+    elif _is_tensor(groups) or isinstance(groups, np.ndarray):
+        groups = _vector(groups, S, 'groups', who).tolist()
+    groups = list(groups)
+    if len(groups) != S:
+        raise ValueError('%s: groups must hold one key per sample (%d samples, %d keys)' % (who, S, len(groups)))
+    keys, index = [], {}
+    gidx = np.empty(S, np.int64)
+    for s, g in enumerate(groups):
+        try:
+            hash(g)
+        except TypeError:
+            raise ValueError('%s: group key %r of sample %d is not hashable' % (who, g, s)) from None
+        if g not in index:
+            index[g] = len(keys)
+            keys.append(g)
+        gidx[s] = index[g]
+    if limits and len(keys) > GMAX:
+        raise ValueError('%s: %d groups; served: up to %d' % (who, len(keys), GMAX))
+    indptr, indices = _neighbourhoods(neighbourhoods, M, who)
+    U = int(indptr.size) - 1
+    if scores and 8 * S * len(classes) * U > SCORES_MAX_BYTES:
+        raise ValueError('%s: scores=True would return %d bytes ([S, classes, U] float64); refused beyond %d: score fewer centres '
+                         'per call' % (who, 8 * S * len(classes) * U, SCORES_MAX_BYTES))
+    # a class without a training sample, in a training set that has test samples
+    fvals, fidx = np.unique(fold, return_inverse=True)
+    cnt = np.zeros((len(keys), fvals.size, len(classes)), np.int64)
+    np.add.at(cnt, (gidx, fidx, y), 1)
+    if not within:
+        cnt = cnt.sum(axis=0, keepdims=True)
+    train = cnt.sum(axis=1, keepdims=True) - cnt                # [G or 1, F, C]: the training samples of the model tested on (g, f)
+    bad = np.argwhere((train == 0) & (cnt.sum(axis=2, keepdims=True) > 0))
+    if bad.size:
+        g, f, c = (int(v) for v in bad[0])
+        raise ValueError('%s: class %r has no training sample for the test samples of %sfold %d' % (
+            who, classes[c], 'group %r, ' % (keys[g],) if within else '', int(fvals[f])))
+    return _Args(X, tensor, S, M, y, classes, indptr, indices, U, fold, gidx, keys, bool(within), variance == 'pooled',
+                 priors == 'uniform', float(var_smoothing))
+
+
+def _summary(correct, support, xp):
+    """``(recall, accuracy)`` float32 from the counts: float64 quotients rounded once."""
+    if xp is np:
+        s = support.astype(np.float64)
+        recall = (correct / np.where(s > 0, s, 1.0)[:, :, None]).astype(np.float32)
+        accuracy = (correct.sum(axis=1) / np.maximum(s.sum(axis=1), 1.0)[:, None]).astype(np.float32)
+        return recall, accuracy
+    s = support.to(xp.float64)
+    recall = (correct.to(xp.float64) / xp.where(s > 0, s, xp.ones_like(s))[:, :, None]).to(xp.float32)
+    accuracy = (correct.sum(dim=1).to(xp.float64) / xp.clamp(s.sum(dim=1), min=1.0)[:, None]).to(xp.float32)
+    return recall, accuracy
+
+
+def _support(a):
+    support = np.zeros((len(a.keys), len(a.classes)), np.int64)
+    np.add.at(support, (a.gidx, a.y), 1)
+    return support
+
+
+# ---- the host restatement -------------------------------------------------------------------------------------------------------
+
+def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within=True, classes=None, variance='class',
+                     priors='empirical', var_smoothing=1e-9, scores=False, predictions=False, device=None, batch_centres=None,
+                     return_scale=False):
+    """``searchlight`` restated in float64 NumPy (no device; ``device`` and ``batch_centres`` are accepted and ignored), the
+    obvious way: per training set and per centre the ball's columns are sliced out, the class means and variances fitted on
+    them (``sum / n``, ``sum (x - mean)^2 / n``), every test sample scored with
+    ``log prior - sum_v [(x - mu)^2 / (2 var) + log(2 pi var) / 2]`` and the first maximal class taken.  The samples are rounded to
+    float32 first, as staging does.  Returns a ``SearchlightResult`` of NumPy arrays; with ``return_scale`` a pair of it and
+    ``scale`` float64 [S, classes, U] ``= |log prior| + sum_v [(x - mu)^2 / (2 var) + |log(2 pi var) / 2|]``, the magnitude an
+    error bound of a score is stated in."""
+    who = 'searchlight_host'
+    a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
+               batch_centres, who, limits=False)
+    X = _host_array(a.X, who).astype(np.float64)
+    S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
+    sc = np.empty((S, C, U))
+    scale = np.empty((S, C, U)) if return_scale else None
+    pred = np.empty((S, U), np.uint8)
+    key = a.gidx * (int(a.fold.max()) - int(a.fold.min()) + 1) + (a.fold - a.fold.min()) if a.within else a.fold
+    for k in np.unique(key):
+        test = key == k
+        train = ~test & (a.gidx == a.gidx[test][0]) if a.within else ~test
+        Xtr, ytr, Xte = X[train], a.y[train], X[test]
+        n = np.array([(ytr == c).sum() for c in range(C)], np.float64)
+        logp = np.full(C, -np.log(C)) if a.uniform else np.log(n / n.sum())
+        eps = a.vs * Xtr.var(axis=0).max()
+        for u in range(U):
+            cols = a.indices[a.indptr[u]:a.indptr[u + 1]]
+            A, T = Xtr[:, cols], Xte[:, cols]
+            mu = np.stack([A[ytr == c].sum(axis=0) / n[c] for c in range(C)])
+            ss = np.stack([((A[ytr == c] - mu[c]) ** 2).sum(axis=0) for c in range(C)])
+            var = (np.broadcast_to(ss.sum(axis=0) / n.sum(), ss.shape) if a.pooled else ss / n[:, None]) + eps
+            ok = var > 0                                        # a vertex whose smoothed variance is 0 contributes nothing
+            v = np.where(ok, var, 1.0)
+            for c in range(C):
+                q = np.where(ok[c], (T - mu[c]) ** 2 / (2.0 * v[c]), 0.0)
+                lg = np.where(ok[c], 0.5 * np.log(2.0 * np.pi * v[c]), 0.0)
+                sc[test, c, u] = logp[c] - (q + lg).sum(axis=1)
+                if return_scale:
+                    scale[test, c, u] = abs(logp[c]) + (q + np.abs(lg)).sum(axis=1)
+            pred[test, u] = np.argmax(sc[test, :, u], axis=1)
+    correct = np.zeros((G, C, U), np.int32)
+    np.add.at(correct, (a.gidx[:, None], a.y[:, None], np.arange(U)[None, :]), (pred == a.y[:, None]).astype(np.int32))
+    support = _support(a)
+    recall, accuracy = _summary(correct, support, np)
+    res = SearchlightResult(correct, support, recall, accuracy, list(a.keys), list(a.classes), sc if scores else None,
+                            pred if predictions else None)
+    return (res, scale) if return_scale else res
+
+
+# ---- the device -----------------------------------------------------------------------------------------------------------------
+
+_Plan = collections.namedtuple('_Plan', 'order test_ptr tmax list_ptr list_idx class_ptr class_idx logprior sgroup slabel NM NC')
+
+
+def _device_plan(a, NC):
+    """The tables of the kernels: the samples sorted by model (stable, so the test samples of a model are contiguous and keep
+    the caller's order), and per model its training samples in the caller's ascending order, as positions in the sorted order."""
+    C = len(a.classes)
+    _, fidx = np.unique(a.fold, return_inverse=True)
+    model = (a.gidx * (int(fidx.max()) + 1) + fidx) if a.within else fidx
+    ids, model = np.unique(model, return_inverse=True)
+    NM = int(ids.size)
+    order = np.argsort(model, kind='stable')
+    pos = np.empty(a.S, np.int64)
+    pos[order] = np.arange(a.S)
+    counts = np.bincount(model, minlength=NM)
+    test_ptr = np.concatenate([[0], np.cumsum(counts)])
+    first = order[test_ptr[:-1]]                                # one test sample of every model
+    lists, clists = [], []
+    logprior = np.zeros((NM, NC))
+    for m in range(NM):
+        train = model != m
+        if a.within:
+            train &= a.gidx == a.gidx[first[m]]
+        train = np.flatnonzero(train)
+        lists.append(pos[train])
+        per = [pos[train[a.y[train] == c]] for c in range(C)]
+        clists += per
+        n = np.array([p.size for p in per], np.float64)
+        logprior[m, :C] = -np.log(C) if a.uniform else np.log(n / n.sum())
+    ptr = lambda ls: np.concatenate([[0], np.cumsum([l.size for l in ls])]).astype(np.int32)
+    if sum(l.size for l in lists) > 2 ** 31 - 1:
+        raise ValueError('searchlight: %d models over %d samples list more than 2^31 training samples' % (NM, a.S))
+    i32 = lambda v: np.ascontiguousarray(v, np.int32)
+    return _Plan(order, i32(test_ptr), int(counts.max()), ptr(lists), i32(np.concatenate(lists)), ptr(clists),
+                 i32(np.concatenate(clists)), logprior, i32(a.gidx[order]), i32(a.y[order]), NM, NC)
+
+
+def _transposed(X, order, dev):
+    """``Xt`` float32 [M, plane_stride(S)]: the patterns vertex-major, samples in the plan's order (torch plumbing)."""
+    import torch
+    from . import _lib
+    S, M = X.shape
+    Xt = torch.zeros((M, _lib.plane_stride(S)), dtype=torch.float32, device=dev)
+    Xt[:, :S] = X[torch.as_tensor(order).to(dev)].t()
+    return Xt
+
+
+def _run(a, plan, Xt, scores, predictions, batch_centres):
+    """The launches, on the current device: spread, fit, then the centres batch by batch.  Returns device tensors."""
+    import torch
+    from . import ops
+    dev = Xt.device
+    up = lambda v: torch.as_tensor(v).to(dev)
+    S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
+    spread = ops.searchlight_spread(Xt, S, up(plan.list_ptr), up(plan.list_idx))
+    eps = a.vs * spread.max(dim=1).values
+    par, lg = ops.searchlight_fit(Xt, S, up(plan.class_ptr), up(plan.class_idx), C, eps, pooled=a.pooled)
+    correct = torch.zeros((G, C, U), dtype=torch.int32, device=dev)
+    sc = torch.empty((S, C, U), dtype=torch.float64, device=dev) if scores else None
+    pred = torch.empty((S, U), dtype=torch.uint8, device=dev) if predictions else None
+    if batch_centres is None:
+        batch_centres = max(1, (64 << 20) // (8 * plan.NM * plan.NC))           # 64 MiB of per-centre offsets per launch
+    batch_centres = int(min(batch_centres, U, (2 ** 31 - 1) // CMAX))
+    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
+    tables = [up(v) for v in (plan.test_ptr, plan.logprior, plan.sgroup, plan.slabel, plan.order.astype(np.int32))]
+    for u0 in range(0, U, batch_centres):
+        ops.searchlight_score(Xt, S, rowptr, colidx, u0, min(batch_centres, U - u0), tables[0], plan.tmax, C, par, lg, tables[1],
+                              tables[2], tables[3], tables[4], correct, scores=sc, predictions=pred)
+    return correct, sc, pred
+
+
+def _result(a, correct, sc, pred, as_tensor):
+    import torch
+    support = _support(a)
+    if as_tensor:
+        recall, accuracy = _summary(correct, torch.as_tensor(support).to(correct.device), torch)
+        return SearchlightResult(correct, support, recall, accuracy, list(a.keys), list(a.classes), sc, pred)
+    correct = correct.cpu().numpy()
+    recall, accuracy = _summary(correct, support, np)
+    return SearchlightResult(correct, support, recall, accuracy, list(a.keys), list(a.classes),
+                             None if sc is None else sc.cpu().numpy(), None if pred is None else pred.cpu().numpy())
+
+
+def _device(device, like=None):
+    import torch
+    if device is not None:
+        return torch.device(device)
+    if like is not None and like.is_cuda:
+        return like.device
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _searchlight(a, dev, scores, predictions, batch_centres, as_tensor, who):
+    if a.indices.size > 2 ** 31 - 1:
+        raise ValueError('%s: the neighbourhoods list %d vertices; served: fewer than 2^31' % (who, a.indices.size))
+    import torch
+    from . import ops
+    NC = ops.searchlight_geometry()['buckets'][len(a.classes)]
+    plan = _device_plan(a, NC)
+    if plan.NM > NMAX:
+        raise ValueError('%s: %d training sets; served: up to %d' % (who, plan.NM, NMAX))
+    with torch.cuda.device(dev):
+        if a.tensor:
+            X = a.X.detach().to(dev, torch.float32)
+            if not bool(torch.isfinite(X).all()):
+                raise ValueError('%s: samples hold non-finite values' % who)
+        else:
+            X = torch.as_tensor(a.X).to(dev)                    # (float32 and finite: the caller's _host_array)
+        correct, sc, pred = _run(a, plan, _transposed(X, plan.order, dev), scores, predictions, batch_centres)
+        return _result(a, correct, sc, pred, as_tensor)
+
+
+def searchlight(samples, labels, neighbourhoods, folds, groups=None, within=True, classes=None, variance='class', priors='empirical',
+                var_smoothing=1e-9, scores=False, predictions=False, device=None, batch_centres=None):
+    """Cross-validated Gaussian naive-Bayes accuracy at every centre, on the device: a ``SearchlightResult``.
+
+    ``samples``: ``[S, M]`` patterns, one per trial (trial means, betas); NumPy or a torch tensor; rounded to float32 as staging
+    does.  ``labels``: ``[S]`` values found in ``classes``, which defaults to the sorted set of labels (the order of
+    ``EventWindows.classes``).  ``neighbourhoods``: a SciPy sparse pattern ``[U, M]`` whose row u lists the vertices centre u
+    sees -- ``graph.hop_balls(A, 2)`` for the searchlight map, one row per parcel for ROI decoding, one full row for the
+    whole-brain baseline; values are ignored, indices are sorted ascending and duplicates merged, nothing is added.  An
+    ``[M, k]`` integer table such as ``knn_device`` returns is accepted too, and there the centre itself IS added to its row
+    (such tables leave it out).  ``folds``: ``[S]`` ints; a sample is tested by the model fitted without its fold.
+    ``groups``: ``[S]`` hashable keys -- the subject; default one group.  ``within=True``: the model for a test sample of
+    (group g, fold f) is fitted on the samples of g with fold != f (within-subject leave-one-run-out); ``within=False``: on all
+    samples with fold != f (across subjects: keep a subject in one fold, e.g. with ``splits.subject_folds``).  Either way the
+    counts are reported per group.
+
+    The model, per (training set, class c, vertex v), in float64: ``mu = sum x / n``, ``var = sum (x - mu)^2 / n`` in two
+    passes over the class's training samples in ascending sample order; ``variance='pooled'`` replaces it by
+    ``sum_c sum (x - mu_c)^2 / sum_c n_c`` (diagonal LDA).  Every variance gets ``eps = var_smoothing * max over ALL M vertices
+    of the variance of the whole training set`` added -- scikit-learn's ``GaussianNB`` rule, but with the maximum taken over
+    the whole brain instead of over the ball, so that the parameter tables stay per vertex and one fit serves every centre (on
+    a row of all vertices the two coincide); a vertex whose smoothed variance is 0 contributes nothing.  ``priors``: the class
+    frequencies of the training set (``'empirical'``) or ``'uniform'``.
+    ``score[s, c, u] = log prior_c - sum_{v in row u, ascending} [(x_sv - mu_cv)^2 / (2 var_cv) + log(2 pi var_cv) / 2]``; the
+    prediction is the first maximal class.
+
+    ``scores`` / ``predictions``: also return the float64 ``[S, classes, U]`` scores (refused beyond 2 GiB) / the uint8
+    ``[S, U]`` predictions.  ``batch_centres``: centres of one launch; the result does not depend on it, bit for bit.  The
+    maps are NumPy arrays, or device tensors if ``samples`` came as a tensor.  Group inference on the maps:
+    ``map_test(res.recall - 1 / len(res.classes), A)``.
+
+    ``ValueError`` before any launch: malformed shapes and dtypes, non-finite samples, fewer than two classes or more than 32,
+    a label outside ``classes``, an empty neighbourhood, ``var_smoothing < 0``, unknown strings, and a class without a training
+    sample in a training set that has test samples (naming the group and the fold).
+
+    Out of scope: classifiers with a full covariance in the ball (LDA, SVM), label-permutation nulls per subject (group
+    inference goes through ``map_test``), smoothing per ball, temporal features beyond the trial mean, any cleaning of the
+    series."""
+    who = 'searchlight'
+    a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
+               batch_centres, who)
+    if not a.tensor:
+        a = a._replace(X=_host_array(a.X, who))                 # non-finite values: before the device is touched
+    return _searchlight(a, _device(device, a.X if a.tensor else None), scores, predictions, batch_centres, a.tensor, who)
+
+
+# ---- from event designs ---------------------------------------------------------------------------------------------------------
+
+_MATCH_KW = ('start_trial', 'hrf_delay', 'flag_event', 'rest')
+
+
+def default_folds(groups, within=True):
+    """The folds ``searchlight_events`` gives runs by default, one per run: the run's position among the runs of its group
+    (``within``: leave-one-run-out inside every subject), or its group's index in order of first appearance (leave one subject
+    out)."""
+    seen = {}
+    out = []
+    for g in groups:
+        if g not in seen:
+            seen[g] = [len(seen), 0]
+        out.append(seen[g][1] if within else seen[g][0])
+        seen[g][1] += 1
+    return np.array(out, np.int64)
+
+
+def _events_plan(lengths, label_runs, target_name, block_dura, groups, folds, within, match_kw, who='searchlight_events'):
+    """The host part of ``searchlight_events``: ``(idx int64 [S, block_dura] rows of the concatenated runs, labels, groups and
+    folds per trial, classes)``."""
+    from . import events
+    R = len(lengths)
+    if isinstance(block_dura, (bool, np.bool_)) or not isinstance(block_dura, (int, np.integer)) or not 1 <= block_dura <= FOLD_MAX:
+        raise ValueError('%s: block_dura must be an int in [1, %d] (the rows one trial mean is made of), got %r'
+                         % (who, FOLD_MAX, block_dura))
+    if not isinstance(within, (bool, np.bool_)):
+        raise ValueError('%s: within must be True or False, got %r' % (who, within))
+    if not hasattr(label_runs, '__len__') or isinstance(label_runs, str) or len(label_runs) != R:
+        raise ValueError('%s: label_runs must hold one sequence of condition names per run (%d runs)' % (who, R))
+    groups = [0] * R if groups is None else list(groups)
+    if len(groups) != R:
+        raise ValueError('%s: groups must hold one key per run (%d runs, %d keys)' % (who, R, len(groups)))
+    for r, g in enumerate(groups):
+        try:
+            hash(g)
+        except TypeError:
+            raise ValueError('%s: group key %r of run %d is not hashable' % (who, g, r)) from None
+    if folds is None:
+        folds = default_folds(groups, within)
+    folds = np.asarray(folds)
+    if folds.shape != (R,) or folds.dtype.kind not in 'iu':
+        raise ValueError('%s: folds must hold one int per run (%d runs), got %s %r' % (who, R, folds.dtype, folds.shape))
+    ev = events.match_events(label_runs, target_name, int(block_dura), TRstep=1, **match_kw)
+    for r, T in enumerate(lengths):
+        if len(label_runs[r]) != T:
+            raise ValueError('%s: run %d has %d rows and %d condition names' % (who, r, T, len(label_runs[r])))
+    if not ev.kept:
+        raise ValueError('%s: no run yields a trial' % who)
+    offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    idx = np.concatenate([i + offs[r] for r, i in zip(ev.kept, ev.index)])
+    codes = np.concatenate(ev.labels)
+    per = [len(l) for l in ev.labels]
+    labels = np.asarray(ev.classes)[codes]
+    tg = [groups[r] for r, n in zip(ev.kept, per) for _ in range(n)]
+    tf = np.repeat(folds[ev.kept].astype(np.int64), per)
+    return np.ascontiguousarray(idx, np.int64), labels, tg, tf, list(ev.classes)
+
+
+def _stage(runs, M, dev, who):
+    """The runs (tensors, or float32 arrays already checked) as ``[Ttot, plane_stride(M)]`` float32 planes on the device, as
+    ``first_level`` stages them."""
+    import torch
+    from . import _lib
+    Mp = _lib.plane_stride(M)
+    offs = np.concatenate([[0], np.cumsum([int(r.shape[0]) for r in runs])])
+    if any(_is_tensor(r) for r in runs):
+        planes = torch.zeros((int(offs[-1]), Mp), dtype=torch.float32, device=dev)
+        for y, o in zip(runs, offs):
+            planes[o:o + y.shape[0], :M] = (y.detach() if _is_tensor(y) else torch.as_tensor(y)).to(dev, torch.float32)
+        if not bool(torch.isfinite(planes).all()):
+            raise ValueError('%s: series hold non-finite values' % who)
+        return planes
+    staged = np.zeros((int(offs[-1]), Mp), np.float32)
+    for y, o in zip(runs, offs):
+        staged[o:o + y.shape[0], :M] = y
+    return torch.as_tensor(staged).to(dev)
+
+
+def _event_patterns(planes, idx, M):
+    """One float32 pattern per trial, ``[S, M]``: the mean of the trial's rows of the staged planes
+    (chebgcn_gather_windows_indexed with one channel and ``fold`` = the rows of a trial; ``events.host_windows`` restates it)."""
+    from . import ops
+    return ops.gather_windows_indexed(planes, idx, M, 1, fold=int(idx.shape[1]))[:, 0, :M]
+
+
+def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods, groups=None, folds=None, within=True, **kw):
+    """``searchlight`` on the trials of an event design: ``runs`` (one ``[T, M]`` array or a list; NumPy or torch) are staged
+    as ``[Ttot, plane_stride(M)]`` planes as ``first_level`` stages them, ``match_events(label_runs, target_name, block_dura)``
+    cuts the trials (its keywords ``start_trial``, ``hrf_delay``, ``flag_event``, ``rest`` pass through; ``TRstep`` does not:
+    the pattern of a trial is the float32 mean of its ``block_dura <= 16`` rows, formed on the device by
+    ``ops.gather_windows_indexed(..., C=1, fold=block_dura)`` -- ``events.host_windows(run, index, fold=block_dura)`` restates
+    it bit for bit), and ``searchlight`` runs on the patterns with the classes of ``EventWindows.classes``.
+
+    ``groups``: one key per run (the subject; default one group).  ``folds``: one int per run; default ``default_folds``: with
+    ``within=True`` the run's position among its group's runs (leave-one-run-out), with ``within=False`` the group's index
+    (leave-one-subject-out).  Every other keyword is ``searchlight``'s.  Returns NumPy maps, or device tensors if every run came
+    as a tensor."""
+    who = 'searchlight_events'
+    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
+    if single and runs.ndim != 2:
+        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
+    runs = [runs] if single else [r if _is_tensor(r) else np.asarray(r) for r in runs]
+    if not runs or any(r.ndim != 2 for r in runs):
+        raise ValueError('%s: runs must be a non-empty list of [T, M] arrays' % who)
+    M = int(runs[0].shape[1])
+    if M < 1 or any(int(r.shape[1]) != M for r in runs):
+        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
+    if 'TRstep' in kw or 'classes' in kw:
+        raise ValueError('%s: TRstep and classes are not taken (one pattern per trial; the classes are sorted(set(target_name)))' % who)
+    match_kw = {k: kw.pop(k) for k in _MATCH_KW if k in kw}
+    unknown = set(kw) - {'variance', 'priors', 'var_smoothing', 'scores', 'predictions', 'device', 'batch_centres'}
+    if unknown:
+        raise ValueError('%s: unknown keyword %r' % (who, sorted(unknown)[0]))
+    if single and label_runs is not None and len(label_runs) and isinstance(label_runs[0], str):
+        label_runs = [label_runs]
+    idx, labels, tg, tf, classes = _events_plan([int(r.shape[0]) for r in runs], label_runs, target_name, block_dura, groups, folds,
+                                                within, match_kw, who)
+    device = kw.pop('device', None)
+    sl_kw = dict(variance='class', priors='empirical', var_smoothing=1e-9, scores=False, predictions=False, batch_centres=None)
+    sl_kw.update(kw)
+    # (the patterns do not exist yet: the checks run on a stand-in of their shape)
+    a = _check(np.zeros((idx.shape[0], M), np.float32), labels, neighbourhoods, tf, tg, within, classes, sl_kw['variance'],
+               sl_kw['priors'], sl_kw['var_smoothing'], sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], who)
+    runs = [r if _is_tensor(r) else _host_array(r, who) for r in runs]        # non-finite values: before the device is touched
+    import torch
+    first = next((r for r in runs if _is_tensor(r) and r.is_cuda), None)
+    dev = _device(device, first)
+    with torch.cuda.device(dev):
+        planes = _stage(runs, M, dev, who)
+        X = _event_patterns(planes, torch.as_tensor(idx).to(dev), M)
+        a = a._replace(X=X, tensor=True)
+        return _searchlight(a, dev, sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], all(_is_tensor(r) for r in runs), who)

@@ -970,6 +970,61 @@ int chebgcn_glm_finish(const double* a, const double* yy, const int64_t* run_off
 int chebgcn_glm_combine(const double* eff64, const double* var64, const int32_t* group_ptr, const int32_t* group_runs, int nruns, int R,
                         int S, int C, int M, float* effect, float* variance, float* t, chebgcn_stream stream);
 
+/* ---- searchlight decoding: cross-validated Gaussian naive Bayes at every centre (searchlight.searchlight) ------------------------
+ * The caller sorts the S samples so that the test samples of one MODEL (a training set: a (group, fold) pair, or a fold) are
+ * contiguous, and hands the kernels (all device memory)
+ *   Xt         float32 [M][Sp], Sp = chebgcn_plane_stride(S): the patterns vertex-major, sample s of vertex v at Xt[v * Sp + s].
+ *              What the pad columns [S, Sp) hold (NaN included) never reaches a result.
+ *   test_ptr   int32 [NM + 1]: the test samples of model m are the columns [test_ptr[m], test_ptr[m + 1])
+ *   lists      int32 pointer / index pairs of sample numbers: list_ptr [NM + 1] the whole training set of every model (spread),
+ *              class_ptr [NM * C + 1] the training samples of every (model, class), model-major (fit)
+ *   rowptr / colidx   int32 CSR [U + 1] / [nnz]: row u lists the vertices centre u sees, in the caller's vertex order
+ *   sgroup / slabel / sorig   int32 [S]: of sample s its group in [0, G), its class in [0, C), its number in the caller's order
+ * Every pointer-table entry is clamped into its array and a descending pair is an empty list; a sample number outside [0, S), a
+ * vertex outside [0, M), a group outside [0, G) is skipped: nothing read from memory is an address or a trip count unchecked.
+ * All arithmetic is float64 in the centred form (BOLD has mean / sd of 1e2 .. 1e4: the expanded quadratic cancels by its
+ * square), no float atomics, every order fixed: outputs are bit-identical from call to call and do not depend on how the caller
+ * cuts the centres into calls (u0, Ub) or on the other models of the call.
+ *
+ * Moments of a list at a vertex, x_i = Xt[v][list[i]], i ascending over the n entries inside [0, S):
+ *     s = 0; s = s + x_i;   mu = s / n;   ss = 0; d = x_i - mu, ss = fma(d, d, ss);   variance = ss / n     (n = 0: all 0)
+ * searchlight_spread: spread[m][v] (float64 [NM][M]) = the variance of list m at v.  The caller takes
+ *   eps[m] = var_smoothing * max_v spread[m][v] (any reduction: a maximum has no order).
+ *   chebgcn_last_dispatch(): searchlight_spread_kernel.
+ * searchlight_fit, per (model, vertex), NC = chebgcn_searchlight_query(100 + C) the class bucket (2, 4, 8, 16 or 32):
+ *     per class c < C the moments of list m * C + c;   pooled: variance_c = (sum_c ss_c, c ascending) / (sum_c n_c) for every c;
+ *     var = variance_c + eps[m];   h = 1 / (2 var);   lg = 0.5 * log(2 pi var);   h = lg = 0 where var is not > 0 (such a
+ *     vertex contributes nothing), and mu = h = lg = 0 for a class without samples and for the classes [C, NC).
+ *   par: float64 [NM][M][NC][2] = (mu, h);  lg: float64 [NM][M][NC] -- contiguous per (model, vertex), which is what a score
+ *   wave reads per neighbour.  chebgcn_last_dispatch(): searchlight_fit_kernel.
+ * searchlight_score, for the centres [u0, u0 + Ub) of the U rows:
+ *     base[m][ub][c] = logprior[m][c] - L,   L = 0; L = L + lg[m][v][c] over the entries v of row u0 + ub in ascending entry order
+ *       (float64 [NM][Ub][NC]: the caller's workspace; logprior float64 [NM][NC]);
+ *     per test sample s of model m:   a_c = 0;  t = (double)Xt[v][s] - mu,  a_c = fma(t * h, t, a_c)  over the same entries in the
+ *       same order;   score_c = base_c - a_c;   prediction = the first c < C with the largest score;
+ *     correct[sgroup[s]][slabel[s]][u] += 1 (int32 atomics: any order is the same result) where the prediction is slabel[s].
+ *   correct: int32 [G][C][U], which the call ADDS to (the caller zeroes it); scores: float64 [S][C][U] or NULL, predictions:
+ *   uint8 [S][U] or NULL, both indexed by sorig[s].  tmax: the most test samples of a model, 1 <= tmax <= S -- it sizes the
+ *   launch; samples of a model beyond its first tmax are not scored.
+ *   chebgcn_last_dispatch(): searchlight_base_kernel + searchlight_score_kernel<NC>.
+ * searchlight_query: 0 lanes of a score wave, 1 centres of a score workgroup, 2 neighbours in flight (class buckets above query
+ *   8), 3 the largest C, 4 vertices of a spread / fit workgroup, 5 models of one call at most, 6 tiles of a model at most,
+ *   7 groups at most, 8 the widest NARROW class bucket, 9 test samples of a lane in a narrow bucket (one in the others: a
+ *   workgroup covers query 0 times this many consecutive test samples of a model), 10 neighbours in flight in a narrow bucket,
+ *   100 + C the class bucket of C classes (1 <= C <= 32); -1 for anything else.  None of these reaches a result.
+ * Limits: 2 <= C <= 32, NM <= 65535, G <= 2^20, tmax <= 65535 * 64, Ub <= (2^31 - 1) / 32: CHEBGCN_EUNSUPPORTED beyond, before any
+ * launch, as every CHEBGCN_EINVAL (NULL, counts <= 0, centres outside [0, U), pointers not aligned to their element).  The calls
+ * neither synchronise nor allocate. */
+int chebgcn_searchlight_query(int what);
+int chebgcn_searchlight_spread(const float* Xt, int S, int M, const int32_t* list_ptr, const int32_t* list_idx, int nidx, int NM,
+                               double* spread, chebgcn_stream stream);
+int chebgcn_searchlight_fit(const float* Xt, int S, int M, const int32_t* class_ptr, const int32_t* class_idx, int nidx, int NM, int C,
+                            int pooled, const double* eps, double* par, double* lg, chebgcn_stream stream);
+int chebgcn_searchlight_score(const float* Xt, int S, int M, const int32_t* rowptr, const int32_t* colidx, int nnz, int U, int u0, int Ub,
+                              const int32_t* test_ptr, int tmax, int NM, int C, const double* par, const double* lg,
+                              const double* logprior, const int32_t* sgroup, const int32_t* slabel, const int32_t* sorig, int G,
+                              double* base, int32_t* correct, double* scores, uint8_t* predictions, chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose

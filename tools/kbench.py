@@ -5,6 +5,7 @@
                            [--kernels recurrence_fwd ...]
     python tools/kbench.py --parcellate [--iters 20] [--json out.json]      # the parcellation leg alone
     python tools/kbench.py glm [--iters 20] [--json out.json]               # the first-level GLM kernels alone
+    python tools/kbench.py searchlight [--iters 20] [--json out.json]       # the searchlight kernels alone
 
 Times each C-ABI entry point with HIP events on the launch stream and prints achieved
 algorithmic GB/s (SURVEY.md 8d byte counts) and the fraction of the 8 TB/s HBM roofline.
@@ -206,9 +207,83 @@ def glm_leg(args):
             json.dump(results, f, indent=1)
 
 
+def searchlight_leg(args):
+    """chebgcn_searchlight_spread / _fit / _score on the synthetic 10k-vertex kNN graph (M = 10466) with 2-hop balls: 2048
+    samples, 8 classes, 2 folds.  The score kernel issues three float64 vector instructions per (sample, class, neighbour) term
+    -- subtract, multiply, fma: 4 floating-point operations -- so its floor is the float64 vector issue rate (39.3e12 lane
+    instructions a second: the 78.6 TFLOP/s of FMAs, half the fp32 vector rate), and the bytes-once HBM floor is far below."""
+    import torch
+    from gcn_fmri_decoding_amd import _lib, graph, ops, searchlight as sl
+    dev = torch.device('cuda:0')
+    HBM, ISSUE64 = 6.29e12, 78.6e12 / 2
+    results = []
+
+    def timeit(fn, iters):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        for s, e in evs:
+            s.record()
+            fn()
+            e.record()
+        torch.cuda.synchronize()
+        ms = sorted(s.elapsed_time(e) for s, e in evs)
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    def note(name, shape, t, nbytes, instr, flops, dispatch=''):
+        med, lo, hi = t
+        r = {'leg': name, 'shape': shape, 'median_ms': med, 'min_ms': lo, 'max_ms': hi, 'bytes': nbytes, 'fp64_instructions': instr,
+             'flops': flops, 'hbm_floor_ms': 1e3 * nbytes / HBM, 'issue_floor_ms': 1e3 * instr / ISSUE64,
+             'tflops': flops / med / 1e9, 'dispatch': dispatch}
+        results.append(r)
+        print('%-20s %-30s %9.3f ms (min %8.3f, max %8.3f)  HBM floor %7.3f ms  fp64 issue floor %7.3f ms (%4.1fx)  %6.2f TFLOP/s '
+              'of 78.6  %s' % (name, shape, med, lo, hi, r['hbm_floor_ms'], r['issue_floor_ms'], med / max(r['issue_floor_ms'], 1e-9),
+                               r['tflops'], dispatch), flush=True)
+
+    S, C, F = 2048, 8, 2
+    L = graph.synthetic_graph(10000, k=8, levels=1)[0][0]
+    balls = graph.hop_balls(L, 2)
+    M, nnz = int(L.shape[0]), int(balls.nnz)
+    rs = np.random.RandomState(0)
+    y = np.arange(S) % C
+    fold = np.arange(S) // C % F
+    X = (1e4 + 50.0 * rs.randn(S, M) + 25.0 * rs.randn(C, M)[y]).astype(np.float32)
+    a = sl._check(X, y, balls, fold, None, True, None, 'class', 'empirical', 1e-9, False, False, None, 'kbench')
+    plan = sl._device_plan(a, ops.searchlight_geometry()['buckets'][C])
+    up = lambda v: torch.as_tensor(v).to(dev)
+    Xt = sl._transposed(up(X), plan.order, dev)
+    shape = 'S=%d M=%d C=%d folds=%d nnz=%d' % (S, M, C, F, nnz)
+    lptr, lidx, cptr, cidx = up(plan.list_ptr), up(plan.list_idx), up(plan.class_ptr), up(plan.class_idx)
+    ntrain = float(plan.list_idx.size)
+    note('searchlight_spread', shape, timeit(lambda: ops.searchlight_spread(Xt, S, lptr, lidx), args.iters),
+         4.0 * M * S + 8.0 * plan.NM * M, 3.0 * ntrain * M, 3.0 * ntrain * M, '')
+    print('   ', _lib.last_dispatch())
+    eps = 1e-9 * ops.searchlight_spread(Xt, S, lptr, lidx).max(dim=1).values
+    note('searchlight_fit', shape, timeit(lambda: ops.searchlight_fit(Xt, S, cptr, cidx, C, eps), args.iters),
+         4.0 * M * S + 24.0 * plan.NM * M * plan.NC, 3.0 * ntrain * M, 3.0 * ntrain * M, _lib.last_dispatch())
+    par, lg = ops.searchlight_fit(Xt, S, cptr, cidx, C, eps)
+    correct = torch.zeros((1, C, a.U), dtype=torch.int32, device=dev)
+    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
+    tabs = [up(v) for v in (plan.test_ptr, plan.logprior, plan.sgroup, plan.slabel, plan.order.astype(np.int32))]
+
+    def score():
+        ops.searchlight_score(Xt, S, rowptr, colidx, 0, a.U, tabs[0], plan.tmax, C, par, lg, tabs[1], tabs[2], tabs[3], tabs[4], correct)
+    t = timeit(score, args.iters)
+    terms = float(S) * nnz * plan.NC                            # (sample, neighbour, class) terms the kernel works through
+    note('searchlight_score', shape, t, 4.0 * M * S + 24.0 * plan.NM * M * plan.NC + 4.0 * nnz, 3.0 * terms, 4.0 * terms,
+         _lib.last_dispatch())
+    print('    balls of %.1f vertices on average (largest %d); %.3g terms; accuracy of the last pass %.3f'
+          % (nnz / float(a.U), int(np.diff(a.indptr).max()), terms, float(correct.sum()) / (args.iters + 3.0) / S / a.U))
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('leg', nargs='?', choices=['glm'], help='glm: the first-level GLM kernels alone (ops.glm_project / glm_finish)')
+    ap.add_argument('leg', nargs='?', choices=['glm', 'searchlight'],
+                    help='glm: the first-level GLM kernels alone (ops.glm_project / glm_finish); searchlight: the searchlight kernels alone')
     ap.add_argument('--parcellate', action='store_true', help='the parcellation leg alone (ops.parcellate at HCP size)')
     ap.add_argument('--B', type=int, nargs='+', default=[64, 256])
     ap.add_argument('--fin', type=int, default=32)
@@ -234,6 +309,8 @@ def main():
         return parcellate_leg(args)
     if args.leg == 'glm':
         return glm_leg(args)
+    if args.leg == 'searchlight':
+        return searchlight_leg(args)
 
     import torch
     import bench
