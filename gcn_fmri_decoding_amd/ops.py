@@ -864,6 +864,61 @@ def searchlight_score(Xt, S, rowptr, colidx, u0, Ub, test_ptr, tmax, C, par, lg,
                            _stream())), 'searchlight_score')
 
 
+def searchlight_lda_geometry():
+    """The constants of the LDA searchlight kernel (chebgcn_searchlight_lda_query): ``threads`` of a workgroup (the test samples
+    of one scoring pass), ``max_P`` the longest row served, ``tile`` training samples of a residual tile, ``max_C``, ``blocks``
+    along a side of the covariance triangle, ``max_models``, ``max_tiles``, ``max_groups``, ``narrow`` -- the class count up to
+    which the class tables on chip are narrow -- and ``buckets``: the ball bucket (the ``PB`` of ``searchlight_lda_kernel<PB>``)
+    of every row length 1 .. ``max_P``."""
+    q = _lib.lib().chebgcn_searchlight_lda_query
+    return {'threads': q(0), 'max_P': q(1), 'tile': q(2), 'max_C': q(3), 'blocks': q(4), 'max_models': q(5), 'max_tiles': q(6),
+            'max_groups': q(7), 'narrow': q(8), 'buckets': {P: q(100 + P) for P in range(1, q(1) + 1)}}
+
+
+def searchlight_lda(Xt, S, rowptr, colidx, centres, bucket, class_ptr, class_idx, test_ptr, tmax, C, par, logprior, shrinkage, sgroup,
+                    slabel, sorig, correct, scores=None, predictions=None, gamma_out=None):
+    """Shrinkage LDA at the rows ``centres`` (int32 [Ub], all of at most ``bucket`` vertices) for every model
+    (chebgcn_searchlight_lda): one workgroup per (centre, model) forms the pooled within-class covariance of the ball, shrinks
+    it (``shrinkage`` in [1e-6, 1], or negative for Ledoit-Wolf), factorises it and scores the model's test samples.  ``par``
+    float64 [NM, M, NC, 2] from ``searchlight_fit`` with ``eps = 0``; the other tables as ``searchlight_score``.  ADDS the hits
+    to ``correct`` int32 [G, C, U]; fills ``scores`` float64 [S, C, U] / ``predictions`` uint8 [S, U] / ``gamma_out`` float64
+    [NM, U] (the shrinkage used) where given.  The model and its orders: include/chebgcn.h."""
+    _require_cuda(Xt, rowptr, colidx, centres, class_ptr, class_idx, test_ptr, par, logprior, sgroup, slabel, sorig, correct, scores,
+                  predictions, gamma_out)
+    M = _sl_patterns(Xt, S, 'searchlight_lda')
+    S, C, bucket = int(S), int(C), int(bucket)
+    U = int(rowptr.numel()) - 1
+    nnz = _sl_lists(rowptr, colidx, U, 'searchlight_lda')
+    NM = int(test_ptr.numel()) - 1
+    _dense(test_ptr, torch.int32, (NM + 1,), 'searchlight_lda: test_ptr')
+    nidx = _sl_lists(class_ptr, class_idx, NM * C, 'searchlight_lda')
+    Ub = int(centres.numel())
+    if Ub < 1:
+        raise _lib.ChebgcnError('searchlight_lda: no centres')
+    _dense(centres, torch.int32, (Ub,), 'searchlight_lda: centres')
+    NC = int(_lib.lib().chebgcn_searchlight_query(100 + C))
+    _dense(par, torch.float64, (NM, M, NC, 2), 'searchlight_lda: par')
+    _dense(logprior, torch.float64, (NM, NC), 'searchlight_lda: logprior')
+    for t, what in ((sgroup, 'sgroup'), (slabel, 'slabel'), (sorig, 'sorig')):
+        _dense(t, torch.int32, (S,), 'searchlight_lda: ' + what)
+    if correct.dim() != 3 or correct.shape[1] != C or correct.shape[2] != U:
+        raise _lib.ChebgcnError('searchlight_lda: correct must be int32 [G, C, U]')
+    G = int(correct.shape[0])
+    _dense(correct, torch.int32, (G, C, U), 'searchlight_lda: correct')
+    if scores is not None:
+        _dense(scores, torch.float64, (S, C, U), 'searchlight_lda: scores')
+    if predictions is not None:
+        _dense(predictions, torch.uint8, (S, U), 'searchlight_lda: predictions')
+    if gamma_out is not None:
+        _dense(gamma_out, torch.float64, (NM, U), 'searchlight_lda: gamma_out')
+    tri = 0.5 * bucket * (bucket + 1)
+    _lib.check(_launch('searchlight_lda', 4.0 * float(nidx) * bucket * Ub + 4.0 * float(S) * bucket * Ub, float(nidx) * tri * Ub,
+                       lambda: _lib.lib().chebgcn_searchlight_lda(
+                           _p(Xt), S, M, _p(rowptr), _p(colidx), nnz, U, _p(centres), Ub, bucket, _p(class_ptr), _p(class_idx), nidx,
+                           _p(test_ptr), int(tmax), NM, C, _p(par), _p(logprior), float(shrinkage), _p(sgroup), _p(slabel), _p(sorig), G,
+                           _p(correct), _p(scores), _p(predictions), _p(gamma_out), _stream())), 'searchlight_lda')
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """Searchlight decoding: where in the brain is the task information?
 
-At every centre a cross-validated Gaussian naive-Bayes classifier is fed only the centre's neighbourhood, and the centre gets
-the classifier's accuracy.  ``searchlight`` does it on the device for any list of neighbourhoods -- ``graph.hop_balls`` of the
+At every centre a cross-validated classifier -- Gaussian naive Bayes, or shrinkage LDA with ``classifier='lda'`` -- is fed only
+the centre's neighbourhood, and the centre gets the classifier's accuracy.  ``searchlight`` does it on the device for any list of neighbourhoods -- ``graph.hop_balls`` of the
 brain graph for the classical searchlight map, one row per parcel for ROI decoding, one row of all vertices for the whole-brain
 baseline a GCN accuracy is reported against.  ``searchlight_events`` cuts the trial-mean patterns out of staged runs with
 ``match_events`` first.  ``searchlight_host`` restates it in float64 NumPy, centre by centre.
@@ -10,7 +10,14 @@ The fit of naive Bayes is per-vertex moments and its decision a sum over the nei
 every centre (chebgcn_searchlight_spread / _fit), and the work is the S x classes x sum |neighbourhood| likelihood terms of
 chebgcn_searchlight_score.  All of it float64 in the centred form ``(x - mu)^2 / (2 sigma^2)``: see include/chebgcn.h.
 
-Out of scope: classifiers with a full covariance inside the ball (LDA, SVM), label-permutation nulls per subject (group
+Naive Bayes throws away that neighbouring vertices share noise; signal that lives in a difference of correlated vertices is
+invisible to it.  ``classifier='lda'`` keeps it: every (training set, centre) pair gets its own pooled within-class covariance
+of the ball, shrunk towards a multiple of the identity (a fixed ``shrinkage`` or Ledoit-Wolf's), its Cholesky factor and its
+discriminants -- one workgroup per pair, everything on chip (chebgcn_searchlight_lda), for balls of up to ``LDA_PMAX``
+vertices.  The model is stated once, in ``searchlight``'s docstring and in include/chebgcn.h.
+
+Out of scope: iterative classifiers inside the ball (SVM), per-class covariances (QDA), balls above ``LDA_PMAX`` vertices
+with ``'lda'``, returning the discriminant weights, label-permutation nulls per subject (group
 inference goes through ``map_test``), smoothing per ball (see ``searchlight``), temporal features beyond the trial mean, and
 any cleaning of the series.
 
@@ -26,6 +33,8 @@ from .glm import _host_array, _is_tensor
 CMAX, NMAX, GMAX = 32, 65535, 1 << 20           # chebgcn_searchlight_query(3), (5), (7)
 SCORES_MAX_BYTES = 1 << 31                      # scores=True is refused beyond 2 GiB of float64 [S, classes, U]
 FOLD_MAX = 16                                   # block_dura at most in searchlight_events (the indexed gather's fold)
+LDA_PMAX = 128                                  # chebgcn_searchlight_lda_query(1): the longest row classifier='lda' serves
+SHRINK_MIN = 1e-6                               # CHEBGCN_LDA_SHRINK_MIN: the floor of the shrinkage, given or estimated
 
 SearchlightResult = collections.namedtuple('SearchlightResult', 'correct support recall accuracy groups classes scores predictions')
 SearchlightResult.__doc__ = """What ``searchlight`` returns.  ``correct`` int32 [G, classes, U]: the test samples of group g and
@@ -34,7 +43,7 @@ class c that centre u classified correctly; ``support`` int64 [G, classes]: how 
 over its samples; ``groups`` the G keys in order of first appearance; ``classes``; ``scores`` float64 [S, classes, U] joint
 log-likelihoods and ``predictions`` uint8 [S, U], in the caller's sample order, or None."""
 
-_Args = collections.namedtuple('_Args', 'X tensor S M y classes indptr indices U fold gidx keys within pooled uniform vs')
+_Args = collections.namedtuple('_Args', 'X tensor S M y classes indptr indices U fold gidx keys within pooled uniform vs lda shrink')
 
 
 # ---- arguments ------------------------------------------------------------------------------------------------------------------
@@ -74,8 +83,8 @@ def _vector(v, S, name, who):
 
 
 def _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-           batch_centres, who, limits=True):
-    """Everything that can be checked without the samples' values."""
+           batch_centres, who, limits=True, classifier='gnb', shrinkage=0.1):
+    """Everything that can be checked without the samples' values.  ``shrink`` of the result: the float, or -1.0 for ``'auto'``."""
     tensor = _is_tensor(samples)
     X = samples if tensor else np.asarray(samples)
     if X.ndim != 2 or X.shape[0] < 2 or X.shape[1] < 1:
@@ -96,6 +105,20 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
     if isinstance(var_smoothing, (bool, np.bool_)) or not isinstance(var_smoothing, (int, float, np.integer, np.floating)) \
             or not np.isfinite(var_smoothing) or var_smoothing < 0:
         raise ValueError('%s: var_smoothing must be a finite number >= 0, got %r' % (who, var_smoothing))
+    if classifier not in ('gnb', 'lda'):
+        raise ValueError("%s: classifier must be 'gnb' or 'lda', got %r" % (who, classifier))
+    auto = isinstance(shrinkage, str) and shrinkage == 'auto'
+    number = not isinstance(shrinkage, (bool, np.bool_)) and isinstance(shrinkage, (int, float, np.integer, np.floating))
+    if classifier == 'gnb':
+        if not (number and shrinkage == 0.1):
+            raise ValueError("%s: shrinkage = %r means nothing to classifier='gnb' (naive Bayes has no covariance to shrink)"
+                             % (who, shrinkage))
+    else:
+        if not auto and not (number and SHRINK_MIN <= shrinkage <= 1):
+            raise ValueError("%s: shrinkage must be a number in [%g, 1] or 'auto', got %r" % (who, SHRINK_MIN, shrinkage))
+        if variance != 'class' or not var_smoothing == 1e-9:
+            raise ValueError("%s: variance and var_smoothing mean nothing to classifier='lda' (one pooled covariance per ball, "
+                             "regularised by shrinkage): leave them at their defaults" % who)
     if batch_centres is not None and (isinstance(batch_centres, (bool, np.bool_)) or not isinstance(batch_centres, (int, np.integer))
                                       or batch_centres < 1):
         raise ValueError('%s: batch_centres must be an int >= 1 or None, got %r' % (who, batch_centres))
@@ -142,6 +165,12 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
         raise ValueError('%s: %d groups; served: up to %d' % (who, len(keys), GMAX))
     indptr, indices = _neighbourhoods(neighbourhoods, M, who)
     U = int(indptr.size) - 1
+    if classifier == 'lda':
+        length = np.diff(indptr)
+        if length.max() > LDA_PMAX:
+            row = int(np.argmax(length > LDA_PMAX))
+            raise ValueError("%s: neighbourhood %d holds %d vertices; classifier='lda' serves rows of up to %d (a covariance per "
+                             "ball): use classifier='gnb' for parcels and whole-brain rows" % (who, row, length[row], LDA_PMAX))
     if scores and 8 * S * len(classes) * U > SCORES_MAX_BYTES:
         raise ValueError('%s: scores=True would return %d bytes ([S, classes, U] float64); refused beyond %d: score fewer centres '
                          'per call' % (who, 8 * S * len(classes) * U, SCORES_MAX_BYTES))
@@ -158,7 +187,7 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
         raise ValueError('%s: class %r has no training sample for the test samples of %sfold %d' % (
             who, classes[c], 'group %r, ' % (keys[g],) if within else '', int(fvals[f])))
     return _Args(X, tensor, S, M, y, classes, indptr, indices, U, fold, gidx, keys, bool(within), variance == 'pooled',
-                 priors == 'uniform', float(var_smoothing))
+                 priors == 'uniform', float(var_smoothing), classifier == 'lda', -1.0 if auto else float(shrinkage))
 
 
 def _summary(correct, support, xp):
@@ -184,17 +213,22 @@ def _support(a):
 
 def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within=True, classes=None, variance='class',
                      priors='empirical', var_smoothing=1e-9, scores=False, predictions=False, device=None, batch_centres=None,
-                     return_scale=False):
+                     return_scale=False, classifier='gnb', shrinkage=0.1):
     """``searchlight`` restated in float64 NumPy (no device; ``device`` and ``batch_centres`` are accepted and ignored), the
     obvious way: per training set and per centre the ball's columns are sliced out, the class means and variances fitted on
     them (``sum / n``, ``sum (x - mean)^2 / n``), every test sample scored with
     ``log prior - sum_v [(x - mu)^2 / (2 var) + log(2 pi var) / 2]`` and the first maximal class taken.  The samples are rounded to
     float32 first, as staging does.  Returns a ``SearchlightResult`` of NumPy arrays; with ``return_scale`` a pair of it and
     ``scale`` float64 [S, classes, U] ``= |log prior| + sum_v [(x - mu)^2 / (2 var) + |log(2 pi var) / 2|]``, the magnitude an
-    error bound of a score is stated in."""
+    error bound of a score is stated in.
+
+    ``classifier='lda'``: the model of ``searchlight``'s docstring, per training set and per centre: the ball's columns sliced
+    out, the residuals formed with NumPy, ``scipy.linalg.cho_factor`` / ``cho_solve``, the scores.  There ``scale`` is
+    ``kappa (|log prior_c| + |d_c . w_c| / 2 + sum_v |w_cv| |x_sv - m_v|)``, ``kappa`` the 2-norm condition number of that
+    (model, centre)'s ``Sigma`` (``eigvalsh``; 1 in the degenerate case): the magnitude a float64 solve may be off by."""
     who = 'searchlight_host'
     a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-               batch_centres, who, limits=False)
+               batch_centres, who, limits=False, classifier=classifier, shrinkage=shrinkage)
     X = _host_array(a.X, who).astype(np.float64)
     S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
     sc = np.empty((S, C, U))
@@ -211,6 +245,13 @@ def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within
         for u in range(U):
             cols = a.indices[a.indptr[u]:a.indptr[u + 1]]
             A, T = Xtr[:, cols], Xte[:, cols]
+            if a.lda:
+                s_, q_ = _lda_host_ball(A, ytr, T, n, logp, a.shrink)
+                sc[test, :, u] = s_
+                if return_scale:
+                    scale[test, :, u] = q_
+                pred[test, u] = np.argmax(s_, axis=1)
+                continue
             mu = np.stack([A[ytr == c].sum(axis=0) / n[c] for c in range(C)])
             ss = np.stack([((A[ytr == c] - mu[c]) ** 2).sum(axis=0) for c in range(C)])
             var = (np.broadcast_to(ss.sum(axis=0) / n.sum(), ss.shape) if a.pooled else ss / n[:, None]) + eps
@@ -230,6 +271,60 @@ def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within
     res = SearchlightResult(correct, support, recall, accuracy, list(a.keys), list(a.classes), sc if scores else None,
                             pred if predictions else None)
     return (res, scale) if return_scale else res
+
+
+def lda_shrinkage_host(R):
+    """The Ledoit-Wolf shrinkage of ``classifier='lda'`` with ``shrinkage='auto'``, on a matrix ``R`` [n, P] of class-centred
+    residuals (float64): with ``S = R.T R / n`` and ``nu = tr S / P``,  ``beta_ = sum_k (sum_i r_ki^2)^2``,
+    ``delta_ = sum_ij S_ij^2``, ``beta = (beta_ / n - delta_) / (P n)``, ``delta = (delta_ - 2 nu tr S + P nu^2) / P``,
+    ``beta = min(beta, delta)``, ``g = beta / delta`` (0 where ``beta == 0``), clipped into ``[SHRINK_MIN, 1]`` --
+    ``sklearn.covariance.ledoit_wolf(R, assume_centered=True)[1]`` above the floor."""
+    R = np.asarray(R, np.float64)
+    if R.ndim != 2 or R.shape[0] < 1 or R.shape[1] < 1:
+        raise ValueError('lda_shrinkage_host: R must be [n >= 1, P >= 1], got shape %r' % (R.shape,))
+    n, P = R.shape
+    S = R.T @ R / n
+    tr = np.trace(S)
+    nu = tr / P
+    beta_ = float((((R ** 2).sum(axis=1)) ** 2).sum())
+    delta_ = float((S ** 2).sum())
+    beta = (beta_ / n - delta_) / (P * n)
+    delta = (delta_ - 2.0 * nu * tr + P * nu ** 2) / P
+    beta = min(beta, delta)
+    g = 0.0 if beta == 0 else beta / delta
+    return float(min(max(g, SHRINK_MIN), 1.0))
+
+
+def _lda_host_ball(A, ytr, T, n, logp, shrink):
+    """Shrinkage LDA of one (training set, ball): ``A`` [n, P] training columns, ``T`` [t, P] test columns -> ``(scores [t, C],
+    scale [t, C])``."""
+    import scipy.linalg
+    C, P = n.size, A.shape[1]
+    order = np.concatenate([np.flatnonzero(ytr == c) for c in range(C)])        # class 0's samples first, as the plan lists them
+    mu = np.stack([A[ytr == c].sum(axis=0) / n[c] for c in range(C)])
+    m = (n[:, None] * mu).sum(axis=0) / n.sum()
+    d = mu - m
+    R = (A - mu[ytr])[order]
+    S = R.T @ R / n.sum()
+    tr = np.trace(S)
+    nu = tr / P
+    g = lda_shrinkage_host(R) if shrink < 0 else shrink
+    w, kappa = np.zeros((C, P)), 1.0
+    if tr > 0:
+        Sigma = (1.0 - g) * S + g * nu * np.eye(P)
+        try:
+            w = scipy.linalg.cho_solve(scipy.linalg.cho_factor(Sigma, lower=True), d.T).T
+            ev = np.linalg.eigvalsh(Sigma)
+            kappa = float(ev[-1] / ev[0])
+        except np.linalg.LinAlgError:
+            w = np.zeros((C, P))
+        if not (np.isfinite(w).all() and np.isfinite(kappa) and kappa > 0):
+            w, kappa = np.zeros((C, P)), 1.0
+    dw = (d * w).sum(axis=1)
+    Tc = T - m
+    scores = logp - 0.5 * dw + Tc @ w.T
+    scale = kappa * (np.abs(logp) + 0.5 * np.abs(dw) + np.abs(Tc) @ np.abs(w).T)
+    return scores, scale
 
 
 # ---- the device -----------------------------------------------------------------------------------------------------------------
@@ -305,6 +400,34 @@ def _run(a, plan, Xt, scores, predictions, batch_centres):
     return correct, sc, pred
 
 
+def _run_lda(a, plan, Xt, scores, predictions, batch_centres, gamma=False):
+    """The launches of ``classifier='lda'``: fit (``eps = 0``: only its means are used), then the centres bucket by bucket of row
+    length and batch by batch.  Returns device tensors; with ``gamma`` a fourth, float64 [NM, U]: the shrinkage used."""
+    import torch
+    from . import ops
+    dev = Xt.device
+    up = lambda v: torch.as_tensor(v).to(dev)
+    S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
+    class_ptr, class_idx = up(plan.class_ptr), up(plan.class_idx)
+    par, _ = ops.searchlight_fit(Xt, S, class_ptr, class_idx, C, torch.zeros(plan.NM, dtype=torch.float64, device=dev))
+    correct = torch.zeros((G, C, U), dtype=torch.int32, device=dev)
+    sc = torch.empty((S, C, U), dtype=torch.float64, device=dev) if scores else None
+    pred = torch.empty((S, U), dtype=torch.uint8, device=dev) if predictions else None
+    gam = torch.empty((plan.NM, U), dtype=torch.float64, device=dev) if gamma else None
+    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
+    tables = [up(v) for v in (plan.test_ptr, plan.logprior, plan.sgroup, plan.slabel, plan.order.astype(np.int32))]
+    buckets = ops.searchlight_lda_geometry()['buckets']
+    of_row = np.array([buckets[int(n)] for n in np.diff(a.indptr)])
+    for bucket in sorted(set(of_row.tolist())):
+        rows = np.flatnonzero(of_row == bucket).astype(np.int32)
+        step = rows.size if batch_centres is None else int(min(batch_centres, rows.size))
+        for i in range(0, rows.size, step):
+            ops.searchlight_lda(Xt, S, rowptr, colidx, up(rows[i:i + step]), bucket, class_ptr, class_idx, tables[0], plan.tmax, C, par,
+                                tables[1], a.shrink, tables[2], tables[3], tables[4], correct, scores=sc, predictions=pred,
+                                gamma_out=gam)
+    return (correct, sc, pred, gam) if gamma else (correct, sc, pred)
+
+
 def _result(a, correct, sc, pred, as_tensor):
     import torch
     support = _support(a)
@@ -342,13 +465,14 @@ def _searchlight(a, dev, scores, predictions, batch_centres, as_tensor, who):
                 raise ValueError('%s: samples hold non-finite values' % who)
         else:
             X = torch.as_tensor(a.X).to(dev)                    # (float32 and finite: the caller's _host_array)
-        correct, sc, pred = _run(a, plan, _transposed(X, plan.order, dev), scores, predictions, batch_centres)
+        correct, sc, pred = (_run_lda if a.lda else _run)(a, plan, _transposed(X, plan.order, dev), scores, predictions, batch_centres)
         return _result(a, correct, sc, pred, as_tensor)
 
 
 def searchlight(samples, labels, neighbourhoods, folds, groups=None, within=True, classes=None, variance='class', priors='empirical',
-                var_smoothing=1e-9, scores=False, predictions=False, device=None, batch_centres=None):
-    """Cross-validated Gaussian naive-Bayes accuracy at every centre, on the device: a ``SearchlightResult``.
+                var_smoothing=1e-9, scores=False, predictions=False, device=None, batch_centres=None, classifier='gnb', shrinkage=0.1):
+    """Cross-validated accuracy of a Gaussian naive-Bayes (``classifier='gnb'``) or a shrinkage-LDA (``'lda'``) classifier at
+    every centre, on the device: a ``SearchlightResult``.
 
     ``samples``: ``[S, M]`` patterns, one per trial (trial means, betas); NumPy or a torch tensor; rounded to float32 as staging
     does.  ``labels``: ``[S]`` values found in ``classes``, which defaults to the sorted set of labels (the order of
@@ -372,21 +496,39 @@ def searchlight(samples, labels, neighbourhoods, folds, groups=None, within=True
     ``score[s, c, u] = log prior_c - sum_{v in row u, ascending} [(x_sv - mu_cv)^2 / (2 var_cv) + log(2 pi var_cv) / 2]``; the
     prediction is the first maximal class.
 
+    ``classifier='lda'``: a full covariance inside the ball, for rows of up to ``LDA_PMAX`` = 128 vertices; ``variance`` and
+    ``var_smoothing`` must stay at their defaults.  Per (training set, centre with vertices ``v_0 < ... < v_{P-1}``), in float64:
+    ``n_c`` the training samples of class c, ``n = sum n_c``; ``mu_cv`` the class means as above; ``m_v = (sum_c n_c mu_cv) / n``;
+    ``d_cv = mu_cv - m_v``; the pooled within-class covariance ``S_ij = (sum_k r_ki r_kj) / n`` over the training samples (class 0's
+    first, each class in ascending sample order), ``r_kv = x_kv - mu_{y_k, v}``; ``nu = tr S / P``;
+    ``Sigma = (1 - g) S + g nu I``; ``w_c = Sigma^-1 d_c`` by Cholesky; ``b_c = log prior_c - d_c . w_c / 2``;
+    ``score[s, c, u] = b_c + sum_v w_cv (x_sv - m_v)``; the prediction is the first maximal class.  Up to a term common to all
+    classes this is scikit-learn's ``LinearDiscriminantAnalysis(solver='lsqr', shrinkage=g).decision_function``.  As there, the
+    covariance is weighted by the empirical class frequencies whatever ``priors`` says: ``priors`` changes the intercept only.
+    ``shrinkage``: ``g``, a number in ``[SHRINK_MIN, 1]`` = [1e-6, 1], or ``'auto'``: the Ledoit-Wolf coefficient of the residuals
+    (``lda_shrinkage_host``), clipped into that range.  The floor keeps ``Sigma`` positive definite with a condition number of at
+    most about ``P / g`` -- with fewer training samples than vertices ``S`` is singular, which is the normal case -- so no
+    pivoting and no borderline decision is needed.  If ``tr S`` is not > 0 (every vertex of the ball constant within every
+    class) or a Cholesky pivot is not positive and finite, ``w = 0`` and ``b_c = log prior_c``: the prior decides, nothing is NaN.
+    ``scores`` are then discriminant values, not log-likelihoods.  With ``'gnb'`` ``shrinkage`` must stay at its default.
+
     ``scores`` / ``predictions``: also return the float64 ``[S, classes, U]`` scores (refused beyond 2 GiB) / the uint8
     ``[S, U]`` predictions.  ``batch_centres``: centres of one launch; the result does not depend on it, bit for bit.  The
     maps are NumPy arrays, or device tensors if ``samples`` came as a tensor.  Group inference on the maps:
     ``map_test(res.recall - 1 / len(res.classes), A)``.
 
     ``ValueError`` before any launch: malformed shapes and dtypes, non-finite samples, fewer than two classes or more than 32,
-    a label outside ``classes``, an empty neighbourhood, ``var_smoothing < 0``, unknown strings, and a class without a training
-    sample in a training set that has test samples (naming the group and the fold).
+    a label outside ``classes``, an empty neighbourhood, ``var_smoothing < 0``, unknown strings, a class without a training
+    sample in a training set that has test samples (naming the group and the fold); with ``'lda'`` a row of more than 128
+    vertices (naming it), a ``shrinkage`` outside ``[1e-6, 1]`` that is not ``'auto'``, ``variance`` or ``var_smoothing`` away from
+    their defaults; with ``'gnb'`` a ``shrinkage`` away from its default.
 
-    Out of scope: classifiers with a full covariance in the ball (LDA, SVM), label-permutation nulls per subject (group
-    inference goes through ``map_test``), smoothing per ball, temporal features beyond the trial mean, any cleaning of the
-    series."""
+    Out of scope: iterative classifiers in the ball (SVM), per-class covariances (QDA), ``'lda'`` on balls above 128 vertices,
+    returning the discriminant weights, label-permutation nulls per subject (group inference goes through ``map_test``),
+    smoothing per ball, temporal features beyond the trial mean, any cleaning of the series."""
     who = 'searchlight'
     a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-               batch_centres, who)
+               batch_centres, who, classifier=classifier, shrinkage=shrinkage)
     if not a.tensor:
         a = a._replace(X=_host_array(a.X, who))                 # non-finite values: before the device is touched
     return _searchlight(a, _device(device, a.X if a.tensor else None), scores, predictions, batch_centres, a.tensor, who)
@@ -489,7 +631,7 @@ def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods
 
     ``groups``: one key per run (the subject; default one group).  ``folds``: one int per run; default ``default_folds``: with
     ``within=True`` the run's position among its group's runs (leave-one-run-out), with ``within=False`` the group's index
-    (leave-one-subject-out).  Every other keyword is ``searchlight``'s.  Returns NumPy maps, or device tensors if every run came
+    (leave-one-subject-out).  Every other keyword is ``searchlight``'s, ``classifier`` and ``shrinkage`` included.  Returns NumPy maps, or device tensors if every run came
     as a tensor."""
     who = 'searchlight_events'
     single = isinstance(runs, np.ndarray) or _is_tensor(runs)
@@ -504,7 +646,7 @@ def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods
     if 'TRstep' in kw or 'classes' in kw:
         raise ValueError('%s: TRstep and classes are not taken (one pattern per trial; the classes are sorted(set(target_name)))' % who)
     match_kw = {k: kw.pop(k) for k in _MATCH_KW if k in kw}
-    unknown = set(kw) - {'variance', 'priors', 'var_smoothing', 'scores', 'predictions', 'device', 'batch_centres'}
+    unknown = set(kw) - {'variance', 'priors', 'var_smoothing', 'scores', 'predictions', 'device', 'batch_centres', 'classifier', 'shrinkage'}
     if unknown:
         raise ValueError('%s: unknown keyword %r' % (who, sorted(unknown)[0]))
     if single and label_runs is not None and len(label_runs) and isinstance(label_runs[0], str):
@@ -512,11 +654,13 @@ def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods
     idx, labels, tg, tf, classes = _events_plan([int(r.shape[0]) for r in runs], label_runs, target_name, block_dura, groups, folds,
                                                 within, match_kw, who)
     device = kw.pop('device', None)
-    sl_kw = dict(variance='class', priors='empirical', var_smoothing=1e-9, scores=False, predictions=False, batch_centres=None)
+    sl_kw = dict(variance='class', priors='empirical', var_smoothing=1e-9, scores=False, predictions=False, batch_centres=None,
+                 classifier='gnb', shrinkage=0.1)
     sl_kw.update(kw)
     # (the patterns do not exist yet: the checks run on a stand-in of their shape)
     a = _check(np.zeros((idx.shape[0], M), np.float32), labels, neighbourhoods, tf, tg, within, classes, sl_kw['variance'],
-               sl_kw['priors'], sl_kw['var_smoothing'], sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], who)
+               sl_kw['priors'], sl_kw['var_smoothing'], sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], who,
+               classifier=sl_kw['classifier'], shrinkage=sl_kw['shrinkage'])
     runs = [r if _is_tensor(r) else _host_array(r, who) for r in runs]        # non-finite values: before the device is touched
     import torch
     first = next((r for r in runs if _is_tensor(r) and r.is_cuda), None)

@@ -1025,6 +1025,50 @@ int chebgcn_searchlight_score(const float* Xt, int S, int M, const int32_t* rowp
                               const double* logprior, const int32_t* sgroup, const int32_t* slabel, const int32_t* sorig, int G,
                               double* base, int32_t* correct, double* scores, uint8_t* predictions, chebgcn_stream stream);
 
+/* ---- searchlight decoding with shrinkage LDA: a covariance, its Cholesky factor and its discriminants per (model, centre) --------
+ * (searchlight.searchlight(classifier='lda')).  The tables are those of the naive-Bayes calls above; par is what
+ * chebgcn_searchlight_fit wrote with eps = 0 (only the means par[m][v][c][0] are read), logprior float64 [NM][NC],
+ * NC = chebgcn_searchlight_query(100 + C).  centres: int32 [Ub] row numbers of this launch (one workgroup per (centre, model));
+ * bucket: 32, 64 or 128 -- a row longer than the bucket (or empty) is skipped and nothing of it is written.
+ * The model, for model m and a row of vertices v_0 < ... < v_{P-1}, P <= 128, all in float64:
+ *     n_c = entries of list m * C + c inside [0, S),  n = sum n_c;   mu_cv = par[m][v][c][0];
+ *     m_v = (a = 0; a = fma(n_c, mu_cv, a), c ascending) / n;   d_cv = mu_cv - m_v;
+ *     r_kv = (double)Xt[v][k] - mu_{c v} for the entries k of the class lists, class 0's list first, each in list order;
+ *     S_ij = (a = 0; a = fma(r_ki, r_kj, a), one chain over those samples in that order) / n;
+ *     tr = sum_i S_ii (i ascending),  nu = tr / P;
+ *     g = shrinkage, or if shrinkage < 0 the Ledoit-Wolf coefficient of the residuals:
+ *         q_k = (sum of r_ki^2 over even i ascending) + (the same over odd i),  beta_ = fma(q_k, q_k, .) in sample order,
+ *         delta_ = per i ascending fma(S_ii, S_ii, .) then fma(2, sum_{j < i} S_ij^2, .),
+ *         beta = (beta_ / n - delta_) / (P n),  delta = (delta_ - 2 nu tr + P nu^2) / P,  beta = min(beta, delta),
+ *         g = beta / delta (0 where beta == 0), clipped into [CHEBGCN_LDA_SHRINK_MIN, 1];
+ *     Sigma = (1 - g) S + g nu I;   Sigma = L L^T: element (i, j) receives fma(-L_ik, L_jk, .) for k ascending, then the
+ *         square root (i = j) or the division by L_jj -- no pivoting: the floor on g bounds the condition number by about P / g;
+ *     L y_c = d_c (k ascending), L^T w_c = y_c (k descending), each element's chain followed by the division by L_ii;
+ *     b_c = logprior[m][c] - 0.5 (a = 0; a = fma(d_cv, w_cv, a), v ascending);
+ *     score[s][c][u] = b_c + (a = 0; a = fma(w_cv, (double)Xt[v][s] - m_v, a), v ascending);  prediction = the first maximal class;
+ *     correct[sgroup[s]][slabel[s]][u] += 1 where the prediction is slabel[s] (int32 atomics).
+ *   Degenerate -- tr not > 0 (every vertex constant within every class), n = 0, or a pivot not > 0 and finite: w = 0 and
+ *   b_c = logprior[m][c]; the prior decides and nothing is NaN.  The covariance does not depend on logprior.
+ *   correct int32 [G][C][U] is ADDED to; scores float64 [S][C][U] / predictions uint8 [S][U] / gamma_out float64 [NM][U] (the g
+ *   used) or NULL.  tmax as in searchlight_score.  Guards as above; a vertex outside [0, M) is a column of zeros (its w is 0), a
+ *   centre outside [0, U) is skipped.  Every value is a function of (model, centre, lists) alone: bit-identical under any
+ *   cut of the centres into launches, any order of centres, any other rows or models in the launch.  No float atomics.
+ *   chebgcn_last_dispatch(): searchlight_lda_kernel<bucket>.
+ * searchlight_lda_query: 0 threads of a workgroup, 1 the longest row (128), 2 training samples of a residual tile, 3 the largest
+ *   C, 4 blocks along a side of the covariance triangle, 5 models at most, 6 tiles of a model at most, 7 groups at most, 8 the
+ *   class count up to which the class tables in LDS are narrow, 100 + P the bucket of a row of P vertices (1 <= P <= 128); -1
+ *   for anything else.
+ * Limits: 2 <= C <= 32, NM <= 65535, G <= 2^20, tmax <= 65535 * 64, bucket in {32, 64, 128}: CHEBGCN_EUNSUPPORTED beyond, before
+ * any launch, as every CHEBGCN_EINVAL (NULL, counts <= 0, a shrinkage that is neither negative nor in [1e-6, 1], pointers not
+ * aligned to their element).  The call neither synchronises nor allocates. */
+#define CHEBGCN_LDA_SHRINK_MIN 1e-6
+int chebgcn_searchlight_lda_query(int what);
+int chebgcn_searchlight_lda(const float* Xt, int S, int M, const int32_t* rowptr, const int32_t* colidx, int nnz, int U,
+                            const int32_t* centres, int Ub, int bucket, const int32_t* class_ptr, const int32_t* class_idx, int nidx,
+                            const int32_t* test_ptr, int tmax, int NM, int C, const double* par, const double* logprior,
+                            double shrinkage, const int32_t* sgroup, const int32_t* slabel, const int32_t* sorig, int G,
+                            int32_t* correct, double* scores, uint8_t* predictions, double* gamma_out, chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose

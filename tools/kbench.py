@@ -6,6 +6,7 @@
     python tools/kbench.py --parcellate [--iters 20] [--json out.json]      # the parcellation leg alone
     python tools/kbench.py glm [--iters 20] [--json out.json]               # the first-level GLM kernels alone
     python tools/kbench.py searchlight [--iters 20] [--json out.json]       # the searchlight kernels alone
+    python tools/kbench.py searchlight_lda [--iters 10] [--json out.json]   # the LDA searchlight kernel alone
 
 Times each C-ABI entry point with HIP events on the launch stream and prints achieved
 algorithmic GB/s (SURVEY.md 8d byte counts) and the fraction of the 8 TB/s HBM roofline.
@@ -280,10 +281,90 @@ def searchlight_leg(args):
             json.dump(results, f, indent=1)
 
 
+def searchlight_lda_leg(args):
+    """chebgcn_searchlight_lda at the shape of the searchlight leg (the synthetic 10k-vertex kNN graph, M = 10466, 2-hop balls,
+    2048 samples, 8 classes, 2 folds): one workgroup per (centre, model).  The covariance costs n P (P + 1) / 2 float64 FMAs per
+    (model, centre), n the model's training samples, so the floor is (sum over balls of P (P + 1) / 2) x (sum over models of n)
+    lane-FMAs at the float64 vector issue rate (39.3e12 lane instructions a second); factorisation, solves and scoring come on
+    top, and the HBM floor (Xt once) is far below."""
+    import torch
+    from gcn_fmri_decoding_amd import _lib, graph, ops, searchlight as sl
+    dev = torch.device('cuda:0')
+    HBM, ISSUE64 = 6.29e12, 78.6e12 / 2
+    results = []
+
+    def timeit(fn, iters):
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        for s, e in evs:
+            s.record()
+            fn()
+            e.record()
+        torch.cuda.synchronize()
+        ms = sorted(s.elapsed_time(e) for s, e in evs)
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    S, C, F = 2048, 8, 2
+    L = graph.synthetic_graph(10000, k=8, levels=1)[0][0]
+    balls = graph.hop_balls(L, 2)
+    M, nnz = int(L.shape[0]), int(balls.nnz)
+    rs = np.random.RandomState(0)
+    y = np.arange(S) % C
+    fold = np.arange(S) // C % F
+    X = (1e4 + 50.0 * rs.randn(S, M) + 25.0 * rs.randn(C, M)[y]).astype(np.float32)
+    a = sl._check(X, y, balls, fold, None, True, None, 'class', 'empirical', 1e-9, False, False, None, 'kbench', classifier='lda')
+    plan = sl._device_plan(a, ops.searchlight_geometry()['buckets'][C])
+    up = lambda v: torch.as_tensor(v).to(dev)
+    Xt = sl._transposed(up(X), plan.order, dev)
+    cptr, cidx = up(plan.class_ptr), up(plan.class_idx)
+    par, _ = ops.searchlight_fit(Xt, S, cptr, cidx, C, torch.zeros(plan.NM, dtype=torch.float64, device=dev))
+    correct = torch.zeros((1, C, a.U), dtype=torch.int32, device=dev)
+    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
+    tabs = [up(v) for v in (plan.test_ptr, plan.logprior, plan.sgroup, plan.slabel, plan.order.astype(np.int32))]
+    P = np.diff(a.indptr)
+    buckets = ops.searchlight_lda_geometry()['buckets']
+    of_row = np.array([buckets[int(n)] for n in P])
+    ntrain = float(plan.class_idx.size)                         # summed over the models
+    tri = (P * (P + 1) // 2).astype(np.float64)
+    print('balls of %.1f vertices on average (largest %d); sum P (P + 1) / 2 = %d; %d training samples over %d models: floor %.3f ms'
+          % (P.mean(), P.max(), tri.sum(), ntrain, plan.NM, 1e3 * tri.sum() * ntrain / ISSUE64), flush=True)
+    for shrink, tag in ((0.1, 'g=0.1'), (-1.0, "g='auto'")):
+        total = [0.0, 0.0]
+        for b in sorted(set(of_row.tolist())) + [0]:
+            if b:
+                launches = [(b, up(np.flatnonzero(of_row == b).astype(np.int32)))]
+                fmas = float(tri[of_row == b].sum()) * ntrain
+            else:                                               # the whole pass: every bucket's launch
+                launches = [(k, up(np.flatnonzero(of_row == k).astype(np.int32))) for k in sorted(set(of_row.tolist()))]
+                fmas = float(tri.sum()) * ntrain
+
+            def run():
+                for k, rows in launches:
+                    ops.searchlight_lda(Xt, S, rowptr, colidx, rows, k, cptr, cidx, tabs[0], plan.tmax, C, par, tabs[1], shrink, tabs[2],
+                                        tabs[3], tabs[4], correct)
+            med, lo, hi = timeit(run, args.iters)
+            n_rows = int(sum(r.numel() for _, r in launches))
+            nbytes = 4.0 * M * S + 4.0 * nnz
+            name = 'searchlight_lda ' + ('all' if not b else '<%d>' % b)
+            results.append({'leg': name, 'shape': 'S=%d M=%d C=%d folds=%d nnz=%d %s' % (S, M, C, F, nnz, tag), 'centres': n_rows,
+                            'median_ms': med, 'min_ms': lo, 'max_ms': hi, 'covariance_fma64': fmas, 'issue_floor_ms': 1e3 * fmas / ISSUE64,
+                            'hbm_floor_ms': 1e3 * nbytes / HBM, 'dispatch': _lib.last_dispatch() if b else 'every bucket'})
+            print('%-22s %-10s %6d centres %9.3f ms (min %8.3f, max %8.3f)  covariance floor %7.3f ms (%5.1fx)  %6.2f TFLOP/s of 78.6'
+                  % (name, tag, n_rows, med, lo, hi, 1e3 * fmas / ISSUE64, med / max(1e3 * fmas / ISSUE64, 1e-9), 2.0 * fmas / med / 1e9),
+                  flush=True)
+    print('    accuracy of the last pass %.3f' % (float(correct.sum()) / S / a.U / (2 * (2 + args.iters)) / 2), flush=True)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('leg', nargs='?', choices=['glm', 'searchlight'],
-                    help='glm: the first-level GLM kernels alone (ops.glm_project / glm_finish); searchlight: the searchlight kernels alone')
+    ap.add_argument('leg', nargs='?', choices=['glm', 'searchlight', 'searchlight_lda'],
+                    help='glm: the first-level GLM kernels alone (ops.glm_project / glm_finish); searchlight: the searchlight kernels alone; '
+                         'searchlight_lda: the LDA searchlight kernel alone')
     ap.add_argument('--parcellate', action='store_true', help='the parcellation leg alone (ops.parcellate at HCP size)')
     ap.add_argument('--B', type=int, nargs='+', default=[64, 256])
     ap.add_argument('--fin', type=int, default=32)
@@ -311,6 +392,8 @@ def main():
         return glm_leg(args)
     if args.leg == 'searchlight':
         return searchlight_leg(args)
+    if args.leg == 'searchlight_lda':
+        return searchlight_lda_leg(args)
 
     import torch
     import bench
