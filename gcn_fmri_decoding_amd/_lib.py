@@ -170,6 +170,8 @@ SIGNATURES = {
     'chebgcn_searchlight_lda_query': (_i, [_i]),
     'chebgcn_searchlight_lda': (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p, _i, _p, _i, _i, _i, _p, _p, C.c_double, _p, _p, _p, _i, _p,
                                      _p, _p, _p, _p]),
+    'chebgcn_searchlight_rdm_query': (_i, [_i]),
+    'chebgcn_searchlight_rdm': (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _i, _i, _p, C.c_double, _i, _p, _p, _p]),
 }
 
 _lib = None

@@ -38,31 +38,14 @@
 // Nothing read from memory is an address or a trip count unchecked: row, list and test pointers are clamped, centre numbers
 // outside [0, U) end the workgroup, sample numbers outside [0, S) are rows of zeros, a vertex outside [0, M) is a column of zeros
 // (its w is 0), group and label numbers outside their ranges add nothing.
-#include <float.h>
-#include <limits.h>
-#include <math.h>
-
-#include "common.h"
+// Stages 2 to 4 and the forward solve of stage 5 are stated in searchlight_ball.h, which searchlight_rdm.hip shares.
+#include "searchlight_ball.h"
 
 namespace chebgcn {
 
-constexpr int LDA_T = 256;                  // threads of a workgroup
-constexpr int LDA_PMAX = 128;               // the longest row
-constexpr int LDA_TS = 32;                  // training samples of a residual tile
-constexpr int LDA_NB = 16;                  // blocks along a side of the triangle
-constexpr int LDA_BLOCKS = LDA_NB * (LDA_NB + 1) / 2;       // 136 covariance threads: waves 0 .. 2
-constexpr int LDA_QW = 3;                   // the wave of the squared norms
 constexpr int LDA_SU = 16;                  // vertices of a scoring lane in flight (the loop is bound by the latency of Xt)
-constexpr int LDA_CMAX = 32;
-constexpr int LDA_NARROW = 8;               // class tables in LDS are this wide up to this many classes, LDA_CMAX beyond
-constexpr int LDA_NMAX = 65535;             // models of one call (grid.y)
 constexpr int LDA_TILES = 65535;            // 64-sample tiles of a model's test samples, as searchlight_score
 constexpr int LDA_GMAX = 1 << 20;
-constexpr double LDA_SHRINK_MIN = CHEBGCN_LDA_SHRINK_MIN;
-
-static inline int lda_bucket(int P) { return P < 1 || P > LDA_PMAX ? -1 : P <= 32 ? 32 : P <= 64 ? 64 : 128; }
-
-__device__ __forceinline__ int lda_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 struct SlLda {
     const float* Xt;            // [M][Sp]
@@ -147,9 +130,8 @@ searchlight_lda_kernel(SlLda p) {
     }
 
     // ---- 2. covariance ----
-    int bi = 0;
-    while ((bi + 1) * (bi + 2) / 2 <= tid) ++bi;
-    const int bj = tid - bi * (bi + 1) / 2;
+    int bi, bj;
+    ball_block(tid, bi, bj);
     const bool cov = tid < LDA_BLOCKS && bi * TB < P;
     const bool autog = p.shrink < 0.0;
     double a[TB][TB];
@@ -158,175 +140,26 @@ searchlight_lda_kernel(SlLda p) {
 #pragma unroll
         for (int y = 0; y < TB; ++y) a[x][y] = 0.0;
     double beta_ = 0.0;
-    // The tiles in order: class by class, 32 entries of the class's list at a time.  The loads of the next tile are issued before
-    // the arithmetic of the current one and land in LDS after it.
-    constexpr int NI = PB / (LDA_T / LDA_TS);                   // vertices a thread stages per tile
-    const int sk = tid % LDA_TS, si = tid / LDA_TS;             // its tile entry, its first vertex
-    float xr[NI];
-    unsigned live = 0;                                          // bit q: xr[q] is a value
-    auto next = [&](int& c, int& t) {                           // the tile after (c, t); c = C: none
-        if (c >= 0 && t + LDA_TS < ci1[c]) {
-            t += LDA_TS;
-            return;
-        }
-        do ++c; while (c < C && ci0[c] >= ci1[c]);
-        t = c < C ? ci0[c] : 0;
-    };
-    auto fetch = [&](int c, int t) {
-        int j = t + sk < ci1[c] ? p.cidx[t + sk] : -1;
-        if ((unsigned)j >= (unsigned)p.S) j = -1;
-        live = 0;
-#pragma unroll
-        for (int q = 0; q < NI; ++q) {
-            const int i = si + q * (LDA_T / LDA_TS);
-            const int v = i < P ? vsh[i] : -1;
-            xr[q] = 0.0f;
-            if (j >= 0 && v >= 0) {
-                xr[q] = p.Xt[(size_t)v * p.Sp + j];
-                live |= 1u << q;
-            }
-        }
-    };
-    int c = -1, t0 = 0;
-    next(c, t0);
-    if (c < C) fetch(c, t0);
-    while (c < C) {
-#pragma unroll
-        for (int q = 0; q < NI; ++q) {
-            const int i = si + q * (LDA_T / LDA_TS);
-            if (i < P) tile[sk * LD + i] = live >> q & 1 ? (double)xr[q] - dw[i * NCB + c] : 0.0;
-        }
-        const int kn = min(LDA_TS, ci1[c] - t0);
-        next(c, t0);
-        __syncthreads();
-        if (c < C) fetch(c, t0);
-        if (cov) {
-            for (int k = 0; k < kn; ++k) {
-                double ri[TB], rj[TB];
-#pragma unroll
-                for (int x = 0; x < TB; ++x) ri[x] = tile[k * LD + bi * TB + x];
-#pragma unroll
-                for (int x = 0; x < TB; ++x) rj[x] = tile[k * LD + bj * TB + x];
-#pragma unroll
-                for (int x = 0; x < TB; ++x)
-#pragma unroll
-                    for (int y = 0; y < TB; ++y) a[x][y] = fma(ri[x], rj[y], a[x][y]);
-            }
-        } else if (autog && tid >= 64 * LDA_QW) {
-            // lanes 2 k and 2 k + 1: the even and the odd vertices of entry k
-            const int k = lane >> 1, h = lane & 1;
-            double part = 0.0;
-            if (k < kn)
-                for (int i = h; i < P; i += 2) part = fma(tile[k * LD + i], tile[k * LD + i], part);
-            const double other = __shfl_xor(part, 1);
-            const double q = h ? other + part : part + other;
-            for (int kk = 0; kk < kn; ++kk) {
-                const double qk = __shfl(q, 2 * kk);
-                beta_ = fma(qk, qk, beta_);
-            }
-        }
-        __syncthreads();
-    }
-    if (cov) {
-#pragma unroll
-        for (int x = 0; x < TB; ++x)
-#pragma unroll
-            for (int y = 0; y < TB; ++y) {
-                const int i = bi * TB + x, jj = bj * TB + y;
-                if (i < P && jj <= i) Ssh[i * (i + 1) / 2 + jj] = n ? a[x][y] / (double)n : 0.0;
-            }
-    }
-    if (tid == 64 * LDA_QW) scal[0] = beta_;
-    __syncthreads();
+    ball_covariance<PB, NCB>(p.Xt, p.Sp, p.S, p.cidx, C, P, vsh, ci0, ci1, dw, tile, tid, bi, bj, cov, autog, a, beta_);
+    ball_store<PB>(Ssh, scal, P, n, tid, bi, bj, cov, a, beta_);
 
     // ---- 3. trace, shrinkage, Sigma ----
-    if (tid < P) {
-        double s = 0.0;
-        for (int jj = 0; jj < tid; ++jj) {
-            const double e = Ssh[tid * (tid + 1) / 2 + jj];
-            s = fma(e, e, s);
-        }
-        rowsq[tid] = s;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double tr = 0.0, dl = 0.0;
-        for (int i = 0; i < P; ++i) {
-            const double e = Ssh[i * (i + 1) / 2 + i];
-            tr = tr + e;
-            dl = fma(e, e, dl);
-            dl = fma(2.0, rowsq[i], dl);
-        }
-        const double nu = tr / (double)P;
-        double g = p.shrink;
-        if (autog) {
-            double beta = 0.0;
-            const double delta = (dl - 2.0 * nu * tr + (double)P * nu * nu) / (double)P;
-            if (n) beta = (scal[0] / (double)n - dl) / ((double)P * (double)n);
-            beta = fmin(beta, delta);
-            g = beta == 0.0 ? 0.0 : beta / delta;
-            g = g >= LDA_SHRINK_MIN ? (g <= 1.0 ? g : 1.0) : LDA_SHRINK_MIN;        // (a NaN cannot arise: delta = 0 forces beta <= 0)
-        }
-        scal[1] = g;
-        scal[2] = nu;
-        if (!(tr > 0.0) || n == 0) degen = 1;
-        if (p.gamma) p.gamma[(size_t)m * p.U + u] = g;
-    }
-    __syncthreads();
-    const double g = scal[1], nu = scal[2];
+    const double g = ball_shrinkage(Ssh, rowsq, scal, &degen, P, n, p.shrink, tid);
+    const double nu = scal[2];
+    if (tid == 0 && p.gamma) p.gamma[(size_t)m * p.U + u] = g;
     const bool flat = degen != 0;                               // uniform: nothing to factorise
-    for (int e = tid; e < P * (P + 1) / 2; e += LDA_T) Ssh[e] = (1.0 - g) * Ssh[e];
     for (int e = tid; e < P * NCB; e += LDA_T) {
         const double d = e % NCB < C ? dw[e] - msh[e / NCB] : 0.0;
         dw[e] = d;
         tile[e] = d;
     }
-    __syncthreads();
-    if (tid < P) Ssh[tid * (tid + 1) / 2 + tid] = Ssh[tid * (tid + 1) / 2 + tid] + g * nu;
-    __syncthreads();
+    ball_sigma(Ssh, P, g, nu, tid);
 
     if (!flat) {
         // ---- 4. Cholesky ----
-        for (int jc = 0; jc < P; ++jc) {
-            double s = 0.0;
-            if (tid >= jc && tid < P) {
-                const double* li = Ssh + tid * (tid + 1) / 2;
-                const double* lj = Ssh + jc * (jc + 1) / 2;
-                s = li[jc];
-                int k = 0;
-                for (; k + 4 <= jc; k += 4) {                   // (the loads of four steps before their chain)
-                    const double a0 = li[k], a1 = li[k + 1], a2 = li[k + 2], a3 = li[k + 3];
-                    const double b0 = lj[k], b1 = lj[k + 1], b2 = lj[k + 2], b3 = lj[k + 3];
-                    s = fma(-a0, b0, s);
-                    s = fma(-a1, b1, s);
-                    s = fma(-a2, b2, s);
-                    s = fma(-a3, b3, s);
-                }
-                for (; k < jc; ++k) s = fma(-li[k], lj[k], s);
-                if (tid == jc) {
-                    if (!(s > 0.0) || !(s <= DBL_MAX)) {
-                        degen = 1;
-                        s = 1.0;
-                    }
-                    Ssh[jc * (jc + 1) / 2 + jc] = sqrt(s);
-                }
-            }
-            __syncthreads();
-            if (tid > jc && tid < P) Ssh[tid * (tid + 1) / 2 + jc] = s / Ssh[jc * (jc + 1) / 2 + jc];
-            __syncthreads();
-        }
+        ball_cholesky(Ssh, &degen, P, tid);
         // ---- 5. the solves: thread (vertex i, class c) ----
-        if (tid < NCB) dw[tid] = dw[tid] / Ssh[0];
-        __syncthreads();
-        for (int k = 0; k + 1 < P; ++k) {
-            for (int e = tid; e < (P - 1 - k) * NCB; e += LDA_T) {
-                const int i = k + 1 + e / NCB, c = e % NCB;
-                double s = fma(-Ssh[i * (i + 1) / 2 + k], dw[k * NCB + c], dw[i * NCB + c]);
-                if (i == k + 1) s = s / Ssh[i * (i + 1) / 2 + i];
-                dw[i * NCB + c] = s;
-            }
-            __syncthreads();
-        }
+        ball_forward<NCB>(Ssh, dw, P, tid);
         if (tid < NCB) dw[(P - 1) * NCB + tid] = dw[(P - 1) * NCB + tid] / Ssh[(P - 1) * P / 2 + P - 1];
         __syncthreads();
         for (int k = P - 1; k > 0; --k) {

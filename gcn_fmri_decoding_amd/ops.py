@@ -919,6 +919,56 @@ def searchlight_lda(Xt, S, rowptr, colidx, centres, bucket, class_ptr, class_idx
                            _p(correct), _p(scores), _p(predictions), _p(gamma_out), _stream())), 'searchlight_lda')
 
 
+def searchlight_rdm_geometry():
+    """The constants of the RSA searchlight kernel (chebgcn_searchlight_rdm_query): ``threads`` of a workgroup, ``max_P`` the
+    longest row served, ``tile`` samples of a residual tile, ``max_C``, ``max_pairs`` of classes (two per thread beyond
+    ``threads``), ``max_cells`` of one call, ``narrow`` -- the class count up to which the class tables on chip are narrow -- and
+    ``buckets``: the ball bucket (the ``PB`` of ``searchlight_rdm_kernel<PB>``) of every row length 1 .. ``max_P``."""
+    q = _lib.lib().chebgcn_searchlight_rdm_query
+    return {'threads': q(0), 'max_P': q(1), 'tile': q(2), 'max_C': q(3), 'max_pairs': q(4), 'max_cells': q(5), 'narrow': q(6),
+            'buckets': {P: q(100 + P) for P in range(1, q(1) + 1)}}
+
+
+def searchlight_rdm(Xt, S, rowptr, colidx, centres, bucket, cell_ptr, class_ptr, class_idx, C, par, shrinkage, rdm, gamma_out=None):
+    """Crossnobis distances at the rows ``centres`` (int32 [Ub], all of at most ``bucket`` vertices) for every group
+    (chebgcn_searchlight_rdm): one workgroup per (centre, group) forms the covariance of the residuals about the cell means over
+    all cells of the group, shrinks it (``shrinkage`` in [1e-6, 1], or negative for Ledoit-Wolf), factorises it, whitens every
+    cell's class patterns and takes the cross-validated distances.  ``cell_ptr`` int32 [G + 1]: the contiguous cells of every
+    group; ``class_ptr`` int32 [NM * C + 1] / ``class_idx`` int32 the samples of every (cell, class); ``par`` float64
+    [NM, M, NC, 2] from ``searchlight_fit`` with one model per cell and ``eps = 0``.  Fills ``rdm`` float64 [G, C (C - 1) / 2, U]
+    and ``gamma_out`` float64 [G, U] (the shrinkage used; -1 where the ball is degenerate) at these rows.  The quantity and its
+    orders: include/chebgcn.h."""
+    _require_cuda(Xt, rowptr, colidx, centres, cell_ptr, class_ptr, class_idx, par, rdm, gamma_out)
+    M = _sl_patterns(Xt, S, 'searchlight_rdm')
+    S, C, bucket = int(S), int(C), int(bucket)
+    U = int(rowptr.numel()) - 1
+    nnz = _sl_lists(rowptr, colidx, U, 'searchlight_rdm')
+    G = int(cell_ptr.numel()) - 1
+    if G < 1:
+        raise _lib.ChebgcnError('searchlight_rdm: no groups')
+    _dense(cell_ptr, torch.int32, (G + 1,), 'searchlight_rdm: cell_ptr')
+    if par.dim() != 4:
+        raise _lib.ChebgcnError('searchlight_rdm: par must be float64 [NM, M, NC, 2]')
+    NM = int(par.shape[0])
+    nidx = _sl_lists(class_ptr, class_idx, NM * C, 'searchlight_rdm')
+    Ub = int(centres.numel())
+    if Ub < 1:
+        raise _lib.ChebgcnError('searchlight_rdm: no centres')
+    _dense(centres, torch.int32, (Ub,), 'searchlight_rdm: centres')
+    NC = int(_lib.lib().chebgcn_searchlight_query(100 + C))
+    _dense(par, torch.float64, (NM, M, NC, 2), 'searchlight_rdm: par')
+    npairs = C * (C - 1) // 2
+    _dense(rdm, torch.float64, (G, npairs, U), 'searchlight_rdm: rdm')
+    if gamma_out is not None:
+        _dense(gamma_out, torch.float64, (G, U), 'searchlight_rdm: gamma_out')
+    tri = 0.5 * bucket * (bucket + 1)
+    _lib.check(_launch('searchlight_rdm', 4.0 * float(nidx) * bucket * Ub + 16.0 * NM * bucket * C * Ub, float(nidx) * tri * Ub,
+                       lambda: _lib.lib().chebgcn_searchlight_rdm(
+                           _p(Xt), S, M, _p(rowptr), _p(colidx), nnz, U, _p(centres), Ub, bucket, _p(cell_ptr), _p(class_ptr),
+                           _p(class_idx), nidx, NM, C, _p(par), float(shrinkage), G, _p(rdm), _p(gamma_out), _stream())),
+               'searchlight_rdm')
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------

@@ -16,10 +16,17 @@ of the ball, shrunk towards a multiple of the identity (a fixed ``shrinkage`` or
 discriminants -- one workgroup per pair, everything on chip (chebgcn_searchlight_lda), for balls of up to ``LDA_PMAX``
 vertices.  The model is stated once, in ``searchlight``'s docstring and in include/chebgcn.h.
 
+Where the searchlight says WHERE the conditions can be told apart, ``crossnobis`` says HOW a region tells them apart: the
+representational dissimilarity matrix of every ball -- the cross-validated Mahalanobis distance of every pair of classes per
+(group, centre), whitened by the ball's shrunk noise covariance (chebgcn_searchlight_rdm, one workgroup per pair; the quantity
+is stated once, in ``crossnobis``'s docstring and in include/chebgcn.h).  ``compare_rdms`` turns the RDMs into maps of agreement
+with model RDMs for ``map_test``; ``crossnobis_events`` cuts the patterns from staged runs; ``crossnobis_host`` restates it
+with SciPy.
+
 Out of scope: iterative classifiers inside the ball (SVM), per-class covariances (QDA), balls above ``LDA_PMAX`` vertices
-with ``'lda'``, returning the discriminant weights, label-permutation nulls per subject (group
-inference goes through ``map_test``), smoothing per ball (see ``searchlight``), temporal features beyond the trial mean, and
-any cleaning of the series.
+with ``'lda'`` or ``crossnobis``, returning the discriminant weights, label-permutation nulls per subject (group
+inference goes through ``map_test``), smoothing per ball (see ``searchlight``), temporal features beyond the trial mean,
+any cleaning of the series, rank-based RDM comparisons (Spearman), noise ceilings and unbalanced designs in ``crossnobis``.
 
 The host-only parts need NumPy and SciPy only.
 """
@@ -82,9 +89,8 @@ def _vector(v, S, name, who):
     return a
 
 
-def _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-           batch_centres, who, limits=True, classifier='gnb', shrinkage=0.1):
-    """Everything that can be checked without the samples' values.  ``shrink`` of the result: the float, or -1.0 for ``'auto'``."""
+def _patterns(samples, who):
+    """``(X, tensor, S, M)`` of the ``[S, M]`` patterns, shape and dtype checked."""
     tensor = _is_tensor(samples)
     X = samples if tensor else np.asarray(samples)
     if X.ndim != 2 or X.shape[0] < 2 or X.shape[1] < 1:
@@ -94,34 +100,24 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
             raise ValueError('%s: samples of dtype %s' % (who, X.dtype))
     elif X.dtype.kind not in 'fiu':
         raise ValueError('%s: samples of dtype %s' % (who, X.dtype))
-    S, M = int(X.shape[0]), int(X.shape[1])
-    for name, val in (('within', within), ('scores', scores), ('predictions', predictions)):
-        if not isinstance(val, (bool, np.bool_)):
-            raise ValueError('%s: %s must be True or False, got %r' % (who, name, val))
-    if variance not in ('class', 'pooled'):
-        raise ValueError("%s: variance must be 'class' or 'pooled', got %r" % (who, variance))
-    if priors not in ('empirical', 'uniform'):
-        raise ValueError("%s: priors must be 'empirical' or 'uniform', got %r" % (who, priors))
-    if isinstance(var_smoothing, (bool, np.bool_)) or not isinstance(var_smoothing, (int, float, np.integer, np.floating)) \
-            or not np.isfinite(var_smoothing) or var_smoothing < 0:
-        raise ValueError('%s: var_smoothing must be a finite number >= 0, got %r' % (who, var_smoothing))
-    if classifier not in ('gnb', 'lda'):
-        raise ValueError("%s: classifier must be 'gnb' or 'lda', got %r" % (who, classifier))
+    return X, tensor, int(X.shape[0]), int(X.shape[1])
+
+
+def _shrink_number(shrinkage):
+    """``(auto, number)``: is ``shrinkage`` the string ``'auto'``, is it a real number."""
     auto = isinstance(shrinkage, str) and shrinkage == 'auto'
     number = not isinstance(shrinkage, (bool, np.bool_)) and isinstance(shrinkage, (int, float, np.integer, np.floating))
-    if classifier == 'gnb':
-        if not (number and shrinkage == 0.1):
-            raise ValueError("%s: shrinkage = %r means nothing to classifier='gnb' (naive Bayes has no covariance to shrink)"
-                             % (who, shrinkage))
-    else:
-        if not auto and not (number and SHRINK_MIN <= shrinkage <= 1):
-            raise ValueError("%s: shrinkage must be a number in [%g, 1] or 'auto', got %r" % (who, SHRINK_MIN, shrinkage))
-        if variance != 'class' or not var_smoothing == 1e-9:
-            raise ValueError("%s: variance and var_smoothing mean nothing to classifier='lda' (one pooled covariance per ball, "
-                             "regularised by shrinkage): leave them at their defaults" % who)
+    return auto, number
+
+
+def _batch(batch_centres, who):
     if batch_centres is not None and (isinstance(batch_centres, (bool, np.bool_)) or not isinstance(batch_centres, (int, np.integer))
                                       or batch_centres < 1):
         raise ValueError('%s: batch_centres must be an int >= 1 or None, got %r' % (who, batch_centres))
+
+
+def _coded_labels(labels, S, classes, limits, who):
+    """``(y int64 [S], classes)``: the labels as indices into ``classes`` (default: the sorted set of labels)."""
     lab = _vector(labels, S, 'labels', who)
     if lab.dtype.kind not in 'iuUSO':
         raise ValueError('%s: labels of dtype %s (ints or names)' % (who, lab.dtype))
@@ -138,11 +134,11 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
     outside = [v for v in lab if v not in code]
     if outside:
         raise ValueError('%s: label %r is not in classes %r' % (who, outside[0], classes))
-    y = np.array([code[v] for v in lab], np.int64)
-    fold = _vector(folds, S, 'folds', who)
-    if fold.dtype.kind not in 'iu':
-        raise ValueError('%s: folds must be ints, got dtype %s' % (who, fold.dtype))
-    fold = fold.astype(np.int64)
+    return np.array([code[v] for v in lab], np.int64), classes
+
+
+def _group_keys(groups, S, who):
+    """``(keys in order of first appearance, gidx int64 [S])``; ``None``: one group."""
     if groups is None:
         groups = [0] * S
     elif _is_tensor(groups) or isinstance(groups, np.ndarray):
@@ -161,6 +157,43 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
             index[g] = len(keys)
             keys.append(g)
         gidx[s] = index[g]
+    return keys, gidx
+
+
+def _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
+           batch_centres, who, limits=True, classifier='gnb', shrinkage=0.1):
+    """Everything that can be checked without the samples' values.  ``shrink`` of the result: the float, or -1.0 for ``'auto'``."""
+    X, tensor, S, M = _patterns(samples, who)
+    for name, val in (('within', within), ('scores', scores), ('predictions', predictions)):
+        if not isinstance(val, (bool, np.bool_)):
+            raise ValueError('%s: %s must be True or False, got %r' % (who, name, val))
+    if variance not in ('class', 'pooled'):
+        raise ValueError("%s: variance must be 'class' or 'pooled', got %r" % (who, variance))
+    if priors not in ('empirical', 'uniform'):
+        raise ValueError("%s: priors must be 'empirical' or 'uniform', got %r" % (who, priors))
+    if isinstance(var_smoothing, (bool, np.bool_)) or not isinstance(var_smoothing, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(var_smoothing) or var_smoothing < 0:
+        raise ValueError('%s: var_smoothing must be a finite number >= 0, got %r' % (who, var_smoothing))
+    if classifier not in ('gnb', 'lda'):
+        raise ValueError("%s: classifier must be 'gnb' or 'lda', got %r" % (who, classifier))
+    auto, number = _shrink_number(shrinkage)
+    if classifier == 'gnb':
+        if not (number and shrinkage == 0.1):
+            raise ValueError("%s: shrinkage = %r means nothing to classifier='gnb' (naive Bayes has no covariance to shrink)"
+                             % (who, shrinkage))
+    else:
+        if not auto and not (number and SHRINK_MIN <= shrinkage <= 1):
+            raise ValueError("%s: shrinkage must be a number in [%g, 1] or 'auto', got %r" % (who, SHRINK_MIN, shrinkage))
+        if variance != 'class' or not var_smoothing == 1e-9:
+            raise ValueError("%s: variance and var_smoothing mean nothing to classifier='lda' (one pooled covariance per ball, "
+                             "regularised by shrinkage): leave them at their defaults" % who)
+    _batch(batch_centres, who)
+    y, classes = _coded_labels(labels, S, classes, limits, who)
+    fold = _vector(folds, S, 'folds', who)
+    if fold.dtype.kind not in 'iu':
+        raise ValueError('%s: folds must be ints, got dtype %s' % (who, fold.dtype))
+    fold = fold.astype(np.int64)
+    keys, gidx = _group_keys(groups, S, who)
     if limits and len(keys) > GMAX:
         raise ValueError('%s: %d groups; served: up to %d' % (who, len(keys), GMAX))
     indptr, indices = _neighbourhoods(neighbourhoods, M, who)
@@ -670,3 +703,340 @@ def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods
         X = _event_patterns(planes, torch.as_tensor(idx).to(dev), M)
         a = a._replace(X=X, tensor=True)
         return _searchlight(a, dev, sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], all(_is_tensor(r) for r in runs), who)
+
+
+# ---- RSA: crossnobis distances per ball -----------------------------------------------------------------------------------------
+
+class RDMResult(collections.namedtuple('RDMResult', 'rdm shrinkage classes pairs groups folds')):
+    """What ``crossnobis`` returns.  ``rdm`` float64 [G, npairs, U]: the cross-validated Mahalanobis distance of every pair of
+    classes at every centre, per group, pairs numbered row-major over a < b (``scipy.spatial.distance.squareform``'s order),
+    ``npairs = C (C - 1) / 2``; ``shrinkage`` float64 [G, U]: the shrinkage used, -1 where the ball is degenerate (its distances
+    are 0); ``classes``; ``pairs`` int64 [npairs, 2]: the class indices (a, b) of every pair; ``groups`` the G keys in order of
+    first appearance; ``folds`` int64 [G]: the partitions of every group."""
+    __slots__ = ()
+
+    def square(self, g=0):
+        """The RDMs of group ``g`` as symmetric matrices with a zero diagonal: [U, C, C]."""
+        C, r = len(self.classes), self.rdm[g]
+        if _is_tensor(r):
+            import torch
+            out = torch.zeros((r.shape[1], C, C), dtype=r.dtype, device=r.device)
+            a, b = (torch.as_tensor(self.pairs[:, i]).to(r.device) for i in (0, 1))
+            out[:, a, b] = r.t()
+            out[:, b, a] = r.t()
+            return out
+        out = np.zeros((r.shape[1], C, C), r.dtype)
+        out[:, self.pairs[:, 0], self.pairs[:, 1]] = r.T
+        out[:, self.pairs[:, 1], self.pairs[:, 0]] = r.T
+        return out
+
+    def model_maps(self, models, method='pearson'):
+        """``compare_rdms(self.rdm, models, method)``: [G, Q, U], the maps ``map_test`` takes."""
+        return compare_rdms(self.rdm, models, method)
+
+
+_RdmArgs = collections.namedtuple('_RdmArgs', 'X tensor S M y classes indptr indices U gidx keys shrink cell cell_ptr folds')
+
+
+def _check_rdm(samples, labels, neighbourhoods, partitions, groups, classes, shrinkage, batch_centres, who, limits=True):
+    """Everything ``crossnobis`` can check without the samples' values.  ``cell`` of the result: the cell (group, partition) of
+    every sample, cells numbered group by group (order of first appearance) and partition ascending inside a group;
+    ``cell_ptr`` int64 [G + 1]; ``shrink``: the float, or -1.0 for ``'auto'``."""
+    X, tensor, S, M = _patterns(samples, who)
+    auto, number = _shrink_number(shrinkage)
+    if not auto and not (number and SHRINK_MIN <= shrinkage <= 1):
+        raise ValueError("%s: shrinkage must be a number in [%g, 1] or 'auto', got %r" % (who, SHRINK_MIN, shrinkage))
+    _batch(batch_centres, who)
+    y, classes = _coded_labels(labels, S, classes, limits, who)
+    part = _vector(partitions, S, 'partitions', who)
+    if part.dtype.kind not in 'iu':
+        raise ValueError('%s: partitions must be ints (the run a pattern comes from), got dtype %s' % (who, part.dtype))
+    part = part.astype(np.int64)
+    keys, gidx = _group_keys(groups, S, who)
+    indptr, indices = _neighbourhoods(neighbourhoods, M, who)
+    U = int(indptr.size) - 1
+    length = np.diff(indptr)
+    if length.max() > LDA_PMAX:
+        row = int(np.argmax(length > LDA_PMAX))
+        raise ValueError('%s: neighbourhood %d holds %d vertices; served: rows of up to %d (a covariance per ball)'
+                         % (who, row, length[row], LDA_PMAX))
+    pvals, pidx = np.unique(part, return_inverse=True)
+    cnt = np.zeros((len(keys), pvals.size, len(classes)), np.int64)
+    np.add.at(cnt, (gidx, pidx, y), 1)
+    present = cnt.sum(axis=2) > 0                               # [G, partitions]: the cells
+    folds = present.sum(axis=1)
+    if folds.min() < 2:
+        g = int(np.argmax(folds < 2))
+        raise ValueError('%s: group %r has only one partition (%d); a cross-validated distance needs two independent estimates'
+                         % (who, keys[g], int(pvals[np.argmax(present[g])])))
+    bad = np.argwhere(present[:, :, None] & (cnt == 0))
+    if bad.size:
+        g, f, c = (int(v) for v in bad[0])
+        raise ValueError('%s: group %r, partition %d holds no sample of class %r (unbalanced designs are not served)'
+                         % (who, keys[g], int(pvals[f]), classes[c]))
+    number_of = np.cumsum(present.ravel()).reshape(present.shape) - 1
+    cell = number_of[gidx, pidx]
+    cell_ptr = np.concatenate([[0], np.cumsum(folds)]).astype(np.int64)
+    if limits and int(cell_ptr[-1]) > NMAX:
+        raise ValueError('%s: %d (group, partition) cells; served: up to %d' % (who, int(cell_ptr[-1]), NMAX))
+    return _RdmArgs(X, tensor, S, M, y, classes, indptr, indices, U, gidx, keys, -1.0 if auto else float(shrinkage), cell, cell_ptr,
+                    folds.astype(np.int64))
+
+
+def _pairs(C):
+    return np.array([(a, b) for a in range(C) for b in range(a + 1, C)], np.int64).reshape(-1, 2)
+
+
+def crossnobis_host(samples, labels, neighbourhoods, partitions, groups=None, classes=None, shrinkage=0.1, batch_centres=None,
+                    device=None, return_scale=False):
+    """``crossnobis`` restated in float64 NumPy / SciPy (no device; ``device`` and ``batch_centres`` are accepted and ignored),
+    the obvious way: per group and per centre the ball's columns are sliced out, the cell means and the residuals about them
+    formed with NumPy, ``Sigma`` factorised with ``scipy.linalg.cho_factor`` and the cell patterns whitened with
+    ``solve_triangular``; the distance is the EXPLICIT double sum
+    ``sum_{k != l} (u_ka - u_kb) . (u_la - u_lb) / (F (F - 1) P)`` over ordered pairs of different cells.  The samples are
+    rounded to float32 first, as staging does.  Returns an ``RDMResult`` of NumPy arrays; with ``return_scale`` a pair of it
+    and ``scale`` float64 [G, npairs, U] ``= kappa (t_ab + q_ab) / (F (F - 1) P)``, ``kappa`` the 2-norm condition number of
+    that (group, centre)'s ``Sigma`` (1 where degenerate): the magnitude a float64 evaluation may be off by."""
+    import scipy.linalg
+    who = 'crossnobis_host'
+    a = _check_rdm(samples, labels, neighbourhoods, partitions, groups, classes, shrinkage, batch_centres, who, limits=False)
+    X = _host_array(a.X, who).astype(np.float64)
+    C, U, G = len(a.classes), a.U, len(a.keys)
+    pairs = _pairs(C)
+    rdm = np.zeros((G, len(pairs), U))
+    scale = np.zeros((G, len(pairs), U))
+    gam = np.full((G, U), -1.0)
+    for g in range(G):
+        cells = np.arange(a.cell_ptr[g], a.cell_ptr[g + 1])
+        F = cells.size
+        lists = [[np.flatnonzero((a.cell == k) & (a.y == c)) for c in range(C)] for k in cells]
+        order = np.concatenate([l for per in lists for l in per])              # cell ascending, class ascending, sample order
+        nkc = np.array([[l.size for l in per] for per in lists], np.float64)
+        n = nkc.sum()
+        for u in range(U):
+            cols = a.indices[a.indptr[u]:a.indptr[u + 1]]
+            P = cols.size
+            A = X[:, cols]
+            mu = np.stack([np.stack([A[l].sum(axis=0) / l.size for l in per]) for per in lists])       # [F, C, P]
+            m = (nkc[:, :, None] * mu).sum(axis=(0, 1)) / n
+            d = mu - m
+            R = np.concatenate([A[l] - mu[k, c] for k, per in enumerate(lists) for c, l in enumerate(per)])
+            assert R.shape == (order.size, P)
+            S_ = R.T @ R / n
+            tr = np.trace(S_)
+            if not tr > 0:
+                scale[g, :, u] = 0.0
+                continue
+            nu = tr / P
+            gg = lda_shrinkage_host(R) if a.shrink < 0 else a.shrink
+            Sigma = (1.0 - gg) * S_ + gg * nu * np.eye(P)
+            try:
+                L = scipy.linalg.cho_factor(Sigma, lower=True)[0]
+                w = scipy.linalg.solve_triangular(L, d.reshape(F * C, P).T, lower=True).T.reshape(F, C, P)
+                ev = np.linalg.eigvalsh(Sigma)
+                kappa = float(ev[-1] / ev[0])
+            except np.linalg.LinAlgError:
+                continue
+            if not (np.isfinite(w).all() and np.isfinite(kappa) and kappa > 0):
+                continue
+            gam[g, u] = gg
+            for i, (ca, cb) in enumerate(pairs):
+                delta = w[:, ca] - w[:, cb]                     # [F, P]
+                acc = 0.0
+                for k in range(F):
+                    for l in range(F):
+                        if k != l:
+                            acc += float(delta[k] @ delta[l])
+                rdm[g, i, u] = acc / (F * (F - 1) * P)
+                tot = delta.sum(axis=0)
+                scale[g, i, u] = kappa * (float(tot @ tot) + float((delta * delta).sum())) / (F * (F - 1) * P)
+    res = RDMResult(rdm, gam, list(a.classes), pairs, list(a.keys), a.folds.copy())
+    return (res, scale) if return_scale else res
+
+
+def compare_rdms(rdm, models, method='pearson'):
+    """How well the RDM of every (group, centre) follows each model RDM: ``rdm`` float64 [G, npairs, U] (``RDMResult.rdm``; NumPy
+    or torch), ``models`` [Q, npairs] in the same pair order (``scipy.spatial.distance.squareform(D, checks=False)`` of a C x C
+    model) -> float64 [G, Q, U], of the kind ``rdm`` is.  ``method='pearson'``: the correlation over the pairs,
+    ``sum (x - mean x)(m - mean m) / sqrt(sum (x - mean x)^2 sum (m - mean m)^2)``, 0 where the RDM or the model is constant
+    (all entries equal; with two classes always).  ``'cosine'``: ``sum x m / sqrt(sum x^2 sum m^2)``, 0 where either is all
+    zero -- crossnobis distances have a meaningful zero, so the cosine does not throw the overall separation away.  Plain float64
+    torch / NumPy, no kernel.  Group inference: ``map_test(compare_rdms(res.rdm, models)[:, q], A)``.  Spearman and other
+    rank-based comparisons are out of scope."""
+    who = 'compare_rdms'
+    if method not in ('pearson', 'cosine'):
+        raise ValueError("%s: method must be 'pearson' or 'cosine', got %r" % (who, method))
+    tensor = _is_tensor(rdm)
+    x = rdm if tensor else np.asarray(rdm, np.float64)
+    if x.ndim != 3 or x.shape[1] < 1:
+        raise ValueError('%s: rdm must be [G, npairs, U], got shape %r' % (who, tuple(x.shape)))
+    mod = np.asarray(models.detach().cpu().numpy() if _is_tensor(models) else models, np.float64)
+    if mod.ndim != 2 or mod.shape[0] < 1 or mod.shape[1] != x.shape[1] or not np.isfinite(mod).all():
+        raise ValueError('%s: models must be finite [Q >= 1, npairs = %d], got shape %r' % (who, x.shape[1], mod.shape))
+    if tensor:
+        import torch
+        x = x.to(torch.float64)
+        mod = torch.as_tensor(mod).to(x.device)
+        xp, amax, amin, sqrt, where = torch, (lambda v, ax: v.amax(dim=ax)), (lambda v, ax: v.amin(dim=ax)), torch.sqrt, torch.where
+        total, zeros = (lambda v, ax: v.sum(dim=ax)), torch.zeros_like
+    else:
+        xp, amax, amin, sqrt, where = np, (lambda v, ax: v.max(axis=ax)), (lambda v, ax: v.min(axis=ax)), np.sqrt, np.where
+        total, zeros = (lambda v, ax: v.sum(axis=ax)), np.zeros_like
+    npairs = x.shape[1]
+    if method == 'pearson':
+        dead_x = amax(x, 1) == amin(x, 1)                       # [G, U]
+        dead_m = amax(mod, 1) == amin(mod, 1)                   # [Q]
+        x = x - total(x, 1)[:, None, :] / npairs
+        mod = mod - total(mod, 1)[:, None] / npairs
+    else:
+        dead_x = amax(abs(x), 1) == 0
+        dead_m = amax(abs(mod), 1) == 0
+    num = xp.einsum('gpu,qp->gqu', x, mod)
+    den = sqrt(total(x * x, 1))[:, None, :] * sqrt(total(mod * mod, 1))[None, :, None]
+    dead = dead_x[:, None, :] | dead_m[None, :, None] | ~(den > 0)
+    return where(dead, zeros(num), num / where(dead, zeros(den) + 1.0, den))
+
+
+_RdmPlan = collections.namedtuple('_RdmPlan', 'order cell_ptr class_ptr class_idx NM')
+
+
+def _rdm_plan(a):
+    """The tables of the kernels: the samples sorted by cell (stable, so every list keeps the caller's order), and per
+    (cell, class) its samples as positions in the sorted order."""
+    C, NM = len(a.classes), int(a.cell_ptr[-1])
+    order = np.argsort(a.cell * C + a.y, kind='stable')         # cell ascending, class ascending, the caller's order inside
+    key = (a.cell * C + a.y)[order]
+    class_ptr = np.searchsorted(key, np.arange(NM * C + 1), side='left')
+    i32 = lambda v: np.ascontiguousarray(v, np.int32)
+    return _RdmPlan(order, i32(a.cell_ptr), i32(class_ptr), i32(np.arange(a.S)), NM)
+
+
+def _run_rdm(a, plan, Xt, batch_centres):
+    """The launches of ``crossnobis``: fit with one model per cell (``eps = 0``: only its means are used), then the centres bucket
+    by bucket of row length and batch by batch.  Returns device tensors ``(rdm [G, npairs, U], shrinkage [G, U])``."""
+    import torch
+    from . import ops
+    dev = Xt.device
+    up = lambda v: torch.as_tensor(v).to(dev)
+    C, U, G = len(a.classes), a.U, len(a.keys)
+    class_ptr, class_idx, cell_ptr = up(plan.class_ptr), up(plan.class_idx), up(plan.cell_ptr)
+    par, _ = ops.searchlight_fit(Xt, a.S, class_ptr, class_idx, C, torch.zeros(plan.NM, dtype=torch.float64, device=dev))
+    rdm = torch.zeros((G, C * (C - 1) // 2, U), dtype=torch.float64, device=dev)
+    gam = torch.full((G, U), -1.0, dtype=torch.float64, device=dev)
+    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
+    buckets = ops.searchlight_rdm_geometry()['buckets']
+    of_row = np.array([buckets[int(n)] for n in np.diff(a.indptr)])
+    for bucket in sorted(set(of_row.tolist())):
+        rows = np.flatnonzero(of_row == bucket).astype(np.int32)
+        step = rows.size if batch_centres is None else int(min(batch_centres, rows.size))
+        for i in range(0, rows.size, step):
+            ops.searchlight_rdm(Xt, a.S, rowptr, colidx, up(rows[i:i + step]), bucket, cell_ptr, class_ptr, class_idx, C, par, a.shrink,
+                                rdm, gamma_out=gam)
+    return rdm, gam
+
+
+def _crossnobis(a, dev, batch_centres, as_tensor, who):
+    if a.indices.size > 2 ** 31 - 1:
+        raise ValueError('%s: the neighbourhoods list %d vertices; served: fewer than 2^31' % (who, a.indices.size))
+    import torch
+    plan = _rdm_plan(a)
+    with torch.cuda.device(dev):
+        if a.tensor:
+            X = a.X.detach().to(dev, torch.float32)
+            if not bool(torch.isfinite(X).all()):
+                raise ValueError('%s: samples hold non-finite values' % who)
+        else:
+            X = torch.as_tensor(a.X).to(dev)                    # (float32 and finite: the caller's _host_array)
+        rdm, gam = _run_rdm(a, plan, _transposed(X, plan.order, dev), batch_centres)
+    if not as_tensor:
+        rdm, gam = rdm.cpu().numpy(), gam.cpu().numpy()
+    return RDMResult(rdm, gam, list(a.classes), _pairs(len(a.classes)), list(a.keys), a.folds.copy())
+
+
+def crossnobis(samples, labels, neighbourhoods, partitions, groups=None, classes=None, shrinkage=0.1, batch_centres=None, device=None):
+    """The representational dissimilarity matrix of every ball, on the device: the cross-validated Mahalanobis ("crossnobis",
+    Walther et al. 2016) distance of every pair of classes at every (group, centre) -- an ``RDMResult``.  Where ``searchlight``
+    says WHERE the conditions can be told apart, this says HOW a region tells them apart; ``compare_rdms`` turns the RDMs into
+    maps of agreement with model RDMs, which ``map_test`` takes for group inference.
+
+    ``samples`` [S, M], ``labels`` [S], ``neighbourhoods``, ``groups`` (the subject; ``None``: one group), ``classes``,
+    ``batch_centres`` and ``device`` as ``searchlight`` takes them, rows of P <= ``LDA_PMAX`` = 128 vertices
+    ``v_0 < ... < v_{P-1}``; ``partitions`` [S] ints: the run a pattern comes from.  A *cell* is a (group, partition); group g
+    has ``F_g >= 2`` cells, and every cell must hold at least one sample of every class.
+
+    The quantity, per (group g, row), everything in float64 and every order fixed; n the number of samples of g:
+
+    1. Cell means: ``mu_{k,c,v}`` the mean of class c in cell k (chebgcn_searchlight_fit with one model per cell, a chain in
+       sample order); ``m_v = (sum_{k,c} n_kc mu_kcv) / n`` (k, then c ascending); ``d_kcv = mu_kcv - m_v``.
+    2. Noise covariance of the residuals about the CELL means, ``r_sv = x_sv - mu_{k(s), y(s), v}``:
+       ``S_ij = (sum_s r_si r_sj) / n`` over the group's samples, cell ascending, class ascending, sample order;
+       ``nu = tr S / P``; ``Sigma = (1 - g) S + g nu I``.  ``shrinkage``: ``g`` in ``[SHRINK_MIN, 1]`` = [1e-6, 1], or ``'auto'``:
+       the Ledoit-Wolf coefficient of these residuals, exactly the rule of ``classifier='lda'`` (``lda_shrinkage_host(R)``).
+    3. Whitening: ``Sigma = L L^T`` by Cholesky; ``u_kc = L^-1 d_kc`` (a forward solve).
+    4. The distance of classes a < b:  ``T_c = sum_k u_kc`` (k ascending);
+       ``q_ab = sum_k sum_v (u_kav - u_kbv)^2`` (k outer, v ascending, one fma chain); ``t_ab = sum_v (T_av - T_bv)^2``;
+       ``rdm_ab = (t_ab - q_ab) / (F_g (F_g - 1) P)`` -- the mean over ordered pairs of different cells ``k != l`` of
+       ``(u_ka - u_kb) . (u_la - u_lb) / P``, which multiplies pattern differences from DIFFERENT runs only and is therefore
+       unbiased: zero on average where two classes do not differ (and negative about as often as positive there).
+    5. Degenerate balls -- ``tr S`` not > 0 or a Cholesky pivot not positive and finite: every distance of that (group, centre)
+       is 0 and its reported shrinkage is -1; nothing is NaN.
+
+    Returns NumPy arrays, or device tensors if ``samples`` came as a tensor.  The result does not depend on ``batch_centres``,
+    on the order of the rows or on what else the call holds, bit for bit.
+
+    ``ValueError`` before any launch: malformed shapes and dtypes, non-finite samples, a label outside ``classes``, an empty
+    neighbourhood, a cell that lacks a class (naming the group, the partition and the class), a group with only one partition,
+    a row of more than 128 vertices, more than 32 classes or fewer than 2, a ``shrinkage`` outside ``[1e-6, 1]`` that is not
+    ``'auto'``.
+
+    Out of scope: Spearman and other rank-based comparisons, noise ceilings, balls above 128 vertices, unbalanced designs (a
+    cell that lacks a class), label-permutation nulls."""
+    who = 'crossnobis'
+    a = _check_rdm(samples, labels, neighbourhoods, partitions, groups, classes, shrinkage, batch_centres, who)
+    if not a.tensor:
+        a = a._replace(X=_host_array(a.X, who))                 # non-finite values: before the device is touched
+    return _crossnobis(a, _device(device, a.X if a.tensor else None), batch_centres, a.tensor, who)
+
+
+def crossnobis_events(runs, label_runs, target_name, block_dura, neighbourhoods, groups=None, **kw):
+    """``crossnobis`` on the trials of an event design, the twin of ``searchlight_events``: ``runs`` are staged as planes,
+    ``match_events(label_runs, target_name, block_dura)`` cuts the trials (its keywords ``start_trial``, ``hrf_delay``,
+    ``flag_event``, ``rest`` pass through), the pattern of a trial is the float32 mean of its ``block_dura <= 16`` rows, formed
+    on the device, and ``crossnobis`` runs on the patterns with the classes of ``EventWindows.classes``.  The partition of a
+    pattern is the run it was cut from (its position in ``runs``); ``groups``: one key per run (the subject; default one group).
+    Every other keyword (``shrinkage``, ``batch_centres``, ``device``) is ``crossnobis``'s.  Returns NumPy arrays, or device
+    tensors if every run came as a tensor."""
+    who = 'crossnobis_events'
+    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
+    if single and runs.ndim != 2:
+        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
+    runs = [runs] if single else [r if _is_tensor(r) else np.asarray(r) for r in runs]
+    if not runs or any(r.ndim != 2 for r in runs):
+        raise ValueError('%s: runs must be a non-empty list of [T, M] arrays' % who)
+    M = int(runs[0].shape[1])
+    if M < 1 or any(int(r.shape[1]) != M for r in runs):
+        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
+    if 'TRstep' in kw or 'classes' in kw or 'partitions' in kw:
+        raise ValueError('%s: TRstep, classes and partitions are not taken (one pattern per trial; the classes are '
+                         'sorted(set(target_name)); the partition is the run)' % who)
+    match_kw = {k: kw.pop(k) for k in _MATCH_KW if k in kw}
+    unknown = set(kw) - {'shrinkage', 'batch_centres', 'device'}
+    if unknown:
+        raise ValueError('%s: unknown keyword %r' % (who, sorted(unknown)[0]))
+    if single and label_runs is not None and len(label_runs) and isinstance(label_runs[0], str):
+        label_runs = [label_runs]
+    idx, labels, tg, tp, classes = _events_plan([int(r.shape[0]) for r in runs], label_runs, target_name, block_dura, groups,
+                                                np.arange(len(runs)), True, match_kw, who)
+    device = kw.pop('device', None)
+    shrinkage, batch_centres = kw.get('shrinkage', 0.1), kw.get('batch_centres', None)
+    # (the patterns do not exist yet: the checks run on a stand-in of their shape)
+    a = _check_rdm(np.zeros((idx.shape[0], M), np.float32), labels, neighbourhoods, tp, tg, classes, shrinkage, batch_centres, who)
+    runs = [r if _is_tensor(r) else _host_array(r, who) for r in runs]        # non-finite values: before the device is touched
+    import torch
+    first = next((r for r in runs if _is_tensor(r) and r.is_cuda), None)
+    dev = _device(device, first)
+    with torch.cuda.device(dev):
+        planes = _stage(runs, M, dev, who)
+        X = _event_patterns(planes, torch.as_tensor(idx).to(dev), M)
+        a = a._replace(X=X, tensor=True)
+        return _crossnobis(a, dev, batch_centres, all(_is_tensor(r) for r in runs), who)

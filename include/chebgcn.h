@@ -1069,6 +1069,47 @@ int chebgcn_searchlight_lda(const float* Xt, int S, int M, const int32_t* rowptr
                             double shrinkage, const int32_t* sgroup, const int32_t* slabel, const int32_t* sorig, int G,
                             int32_t* correct, double* scores, uint8_t* predictions, double* gamma_out, chebgcn_stream stream);
 
+/* ---- RSA searchlight: the cross-validated Mahalanobis ("crossnobis") distance of every pair of classes per (group, centre) ------
+ * (searchlight.crossnobis).  A cell is a (group, partition); the NM cells are numbered group by group, cell_ptr int32 [G + 1]
+ * gives the contiguous cells of every group (device memory, clamped into [0, NM]; a group of fewer than 2 cells is skipped and
+ * nothing of it is written), class_ptr int32 [NM * C + 1] / class_idx int32 [nidx] list the samples of every (cell, class), and
+ * par is what chebgcn_searchlight_fit wrote for these lists with one "model" per cell and eps = 0 (only the means
+ * par[k][v][c][0] are read).  centres, bucket, Xt, rowptr, colidx as chebgcn_searchlight_lda.
+ * The quantity, for group g with cells k0 <= k < k1, F = k1 - k0, and a row of vertices v_0 < ... < v_{P-1}, P <= 128, in float64:
+ *     n_kc = entries of list k * C + c inside [0, S),  n = sum n_kc;   mu_kcv = par[k][v][c][0];
+ *     m_v = (a = 0; a = fma(n_kc, mu_kcv, a), k ascending, c ascending inside) / n;   d_kcv = mu_kcv - m_v;
+ *     r_sv = (double)Xt[v][s] - mu_{k c v} for the entries s of the lists, cell k0's class 0 first, c ascending inside a cell, each
+ *         list in list order: the residuals about the CELL means;
+ *     S_ij = (a = 0; a = fma(r_si, r_sj, a), one chain over those samples in that order) / n;
+ *     tr, nu, the shrinkage g (given, or Ledoit-Wolf's of these residuals where shrinkage < 0), Sigma = (1 - g) S + g nu I and
+ *         its Cholesky factor L: exactly as chebgcn_searchlight_lda states them (csrc/searchlight_ball.h holds both kernels' stages);
+ *     u_kc = L^-1 d_kc:  element i receives fma(-L_ij, u_j, .) for j ascending, then the division by L_ii;
+ *     T_cv = sum_k u_kcv, k ascending;
+ *     for classes a < b:  q_ab = (x = 0; x = fma(u_kav - u_kbv, u_kav - u_kbv, x), k outer ascending, v ascending inside),
+ *         t_ab = (x = 0; x = fma(T_av - T_bv, T_av - T_bv, x), v ascending),
+ *         rdm[g][pair][u] = (t_ab - q_ab) / (F (F - 1) P)
+ *     -- the mean over ordered pairs of different cells k != l of (u_ka - u_kb) . (u_la - u_lb) / P.  Pairs are numbered row-major
+ *     over a < b (scipy.spatial.distance.squareform's order), C (C - 1) / 2 of them.
+ *   Degenerate -- tr not > 0, n = 0, or a pivot not > 0 and finite: every distance of that (group, centre) is 0 and
+ *   gamma_out[g][u] = -1; nothing is NaN.  Otherwise gamma_out float64 [G][U] (or NULL) receives the g used.
+ *   rdm float64 [G][C (C - 1) / 2][U].  Guards as chebgcn_searchlight_lda: every pointer range is clamped, a centre outside [0, U)
+ *   is skipped, sample numbers outside [0, S) are rows of zeros and are not counted, a vertex outside [0, M) is a column of
+ *   zeros, a row longer than the bucket (or empty) is skipped with its outputs untouched.  Every value is a function of (group,
+ *   centre, lists) alone: bit-identical under any cut of the centres into launches, any order of centres, any other rows or
+ *   groups in the launch.  No float atomics.  chebgcn_last_dispatch(): searchlight_rdm_kernel<bucket>.
+ * searchlight_rdm_query: 0 threads of a workgroup, 1 the longest row (128), 2 samples of a residual tile, 3 the largest C, 4 the
+ *   most pairs of classes (496; a thread owns two beyond query 0), 5 cells at most (the models of chebgcn_searchlight_lda), 6 the
+ *   class count up to which the class tables in LDS are narrow, 100 + P the bucket of a row of P vertices; -1 for anything else.
+ * Limits: 2 <= C <= 32, NM <= 65535, bucket in {32, 64, 128}: CHEBGCN_EUNSUPPORTED beyond, before any launch, as every
+ * CHEBGCN_EINVAL (NULL, counts <= 0, a shrinkage that is neither negative nor in [1e-6, 1], pointers not aligned to their
+ * element, NM < 2 G: some group would hold fewer than 2 cells -- cell_ptr itself lives on the device and is guarded there).
+ * The call neither synchronises nor allocates. */
+int chebgcn_searchlight_rdm_query(int what);
+int chebgcn_searchlight_rdm(const float* Xt, int S, int M, const int32_t* rowptr, const int32_t* colidx, int nnz, int U,
+                            const int32_t* centres, int Ub, int bucket, const int32_t* cell_ptr, const int32_t* class_ptr,
+                            const int32_t* class_idx, int nidx, int NM, int C, const double* par, double shrinkage, int G,
+                            double* rdm, double* gamma_out, chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose

@@ -7,6 +7,7 @@
     python tools/kbench.py glm [--iters 20] [--json out.json]               # the first-level GLM kernels alone
     python tools/kbench.py searchlight [--iters 20] [--json out.json]       # the searchlight kernels alone
     python tools/kbench.py searchlight_lda [--iters 10] [--json out.json]   # the LDA searchlight kernel alone
+    python tools/kbench.py searchlight_rdm [--iters 10] [--json out.json]   # the RSA searchlight kernel alone
 
 Times each C-ABI entry point with HIP events on the launch stream and prints achieved
 algorithmic GB/s (SURVEY.md 8d byte counts) and the fraction of the 8 TB/s HBM roofline.
@@ -360,11 +361,86 @@ def searchlight_lda_leg(args):
             json.dump(results, f, indent=1)
 
 
+def searchlight_rdm_leg(args):
+    """chebgcn_searchlight_rdm at the shape of the searchlight legs (the synthetic 10k-vertex kNN graph, M = 10466, 2-hop balls,
+    2048 samples, 8 classes), with 2 and with 8 partitions: one workgroup per (centre, group).  One covariance per group serves all
+    its cells, so it costs S P (P + 1) / 2 float64 FMAs per centre whatever the number of partitions -- the floor is
+    (sum over balls of P (P + 1) / 2) x S lane-FMAs at the float64 vector issue rate (39.3e12 lane instructions a second);
+    factorisation and one forward solve per cell come on top, and the HBM floor (Xt once) is far below."""
+    import torch
+    from gcn_fmri_decoding_amd import _lib, graph, ops, searchlight as sl
+    dev = torch.device('cuda:0')
+    HBM, ISSUE64 = 6.29e12, 78.6e12 / 2
+    results = []
+
+    def timeit(fn, iters):
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+        for s, e in evs:
+            s.record()
+            fn()
+            e.record()
+        torch.cuda.synchronize()
+        ms = sorted(s.elapsed_time(e) for s, e in evs)
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    S, C = 2048, 8
+    L = graph.synthetic_graph(10000, k=8, levels=1)[0][0]
+    balls = graph.hop_balls(L, 2)
+    M, nnz = int(L.shape[0]), int(balls.nnz)
+    rs = np.random.RandomState(0)
+    y = np.arange(S) % C
+    X = (1e4 + 50.0 * rs.randn(S, M) + 25.0 * rs.randn(C, M)[y]).astype(np.float32)
+    up = lambda v: torch.as_tensor(v).to(dev)
+    for F in (2, 8):
+        part = np.arange(S) // C % F
+        a = sl._check_rdm(X, y, balls, part, None, None, 0.1, None, 'kbench')
+        plan = sl._rdm_plan(a)
+        Xt = sl._transposed(up(X), plan.order, dev)
+        cell_ptr, cptr, cidx = up(plan.cell_ptr), up(plan.class_ptr), up(plan.class_idx)
+        par, _ = ops.searchlight_fit(Xt, S, cptr, cidx, C, torch.zeros(plan.NM, dtype=torch.float64, device=dev))
+        rdm = torch.zeros((1, C * (C - 1) // 2, a.U), dtype=torch.float64, device=dev)
+        gam = torch.zeros((1, a.U), dtype=torch.float64, device=dev)
+        rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
+        P = np.diff(a.indptr)
+        buckets = ops.searchlight_rdm_geometry()['buckets']
+        of_row = np.array([buckets[int(n)] for n in P])
+        tri = (P * (P + 1) // 2).astype(np.float64)
+        if F == 2:
+            print('balls of %.1f vertices on average (largest %d); sum P (P + 1) / 2 = %d; %d samples: floor %.3f ms'
+                  % (P.mean(), P.max(), tri.sum(), S, 1e3 * tri.sum() * S / ISSUE64), flush=True)
+        for shrink, tag in ((0.1, 'g=0.1'), (-1.0, "g='auto'")):
+            for b in sorted(set(of_row.tolist())) + [0]:
+                ks = [b] if b else sorted(set(of_row.tolist()))         # 0: the whole pass, every bucket's launch
+                launches = [(k, up(np.flatnonzero(of_row == k).astype(np.int32))) for k in ks]
+                fmas = float(sum(tri[of_row == k].sum() for k in ks)) * S
+
+                def run():
+                    for k, rows in launches:
+                        ops.searchlight_rdm(Xt, S, rowptr, colidx, rows, k, cell_ptr, cptr, cidx, C, par, shrink, rdm, gamma_out=gam)
+                med, lo, hi = timeit(run, args.iters)
+                n_rows = int(sum(r.numel() for _, r in launches))
+                nbytes = 4.0 * M * S + 4.0 * nnz
+                name = 'searchlight_rdm ' + ('all' if not b else '<%d>' % b)
+                results.append({'leg': name, 'shape': 'S=%d M=%d C=%d partitions=%d nnz=%d %s' % (S, M, C, F, nnz, tag), 'centres': n_rows,
+                                'median_ms': med, 'min_ms': lo, 'max_ms': hi, 'covariance_fma64': fmas, 'issue_floor_ms': 1e3 * fmas / ISSUE64,
+                                'hbm_floor_ms': 1e3 * nbytes / HBM, 'dispatch': _lib.last_dispatch() if b else 'every bucket'})
+                print('%-22s F=%d %-10s %6d centres %9.3f ms (min %8.3f, max %8.3f)  covariance floor %7.3f ms (%5.1fx)  %6.2f TFLOP/s of 78.6'
+                      % (name, F, tag, n_rows, med, lo, hi, 1e3 * fmas / ISSUE64, med / max(1e3 * fmas / ISSUE64, 1e-9),
+                         2.0 * fmas / med / 1e9), flush=True)
+        print('    F=%d: mean distance of the last pass %.4f, degenerate balls %d' % (F, float(rdm.mean()), int((gam < 0).sum())), flush=True)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('leg', nargs='?', choices=['glm', 'searchlight', 'searchlight_lda'],
+    ap.add_argument('leg', nargs='?', choices=['glm', 'searchlight', 'searchlight_lda', 'searchlight_rdm'],
                     help='glm: the first-level GLM kernels alone (ops.glm_project / glm_finish); searchlight: the searchlight kernels alone; '
-                         'searchlight_lda: the LDA searchlight kernel alone')
+                         'searchlight_lda: the LDA searchlight kernel alone; searchlight_rdm: the RSA searchlight kernel alone')
     ap.add_argument('--parcellate', action='store_true', help='the parcellation leg alone (ops.parcellate at HCP size)')
     ap.add_argument('--B', type=int, nargs='+', default=[64, 256])
     ap.add_argument('--fin', type=int, default=32)
@@ -394,6 +470,8 @@ def main():
         return searchlight_leg(args)
     if args.leg == 'searchlight_lda':
         return searchlight_lda_leg(args)
+    if args.leg == 'searchlight_rdm':
+        return searchlight_rdm_leg(args)
 
     import torch
     import bench
