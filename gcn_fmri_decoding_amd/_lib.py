@@ -172,6 +172,9 @@ SIGNATURES = {
                                      _p, _p, _p, _p]),
     'chebgcn_searchlight_rdm_query': (_i, [_i]),
     'chebgcn_searchlight_rdm': (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _i, _i, _p, C.c_double, _i, _p, _p, _p]),
+    'chebgcn_searchlight_svm_query': (_i, [_i]),
+    'chebgcn_searchlight_svm': (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _p, _i, _i, _p, _p, _i, _p, _i, _i, _i, C.c_double, _i, C.c_double, _i,
+                                     _p, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

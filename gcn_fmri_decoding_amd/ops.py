@@ -969,6 +969,70 @@ def searchlight_rdm(Xt, S, rowptr, colidx, centres, bucket, cell_ptr, class_ptr,
                'searchlight_rdm')
 
 
+def searchlight_svm_geometry():
+    """The constants of the SVM searchlight kernel (chebgcn_searchlight_svm_query): ``threads`` of a workgroup, ``max_n`` the
+    largest training set served, ``tile`` vertices of a tile, ``max_C``, ``chunk`` test samples of a scoring chunk,
+    ``max_models``, ``max_tiles``, ``max_groups``, ``max_iter`` the largest sweep cap, ``super_tile`` vertices whose means are
+    formed at once, and ``buckets``: the sample bucket (the ``NB`` of ``searchlight_svm_kernel<NB>``) of every training-set size
+    1 .. ``max_n``."""
+    q = _lib.lib().chebgcn_searchlight_svm_query
+    return {'threads': q(0), 'max_n': q(1), 'tile': q(2), 'max_C': q(3), 'chunk': q(4), 'max_models': q(5), 'max_tiles': q(6),
+            'max_groups': q(7), 'max_iter': q(8), 'super_tile': q(9), 'buckets': {n: q(100 + n) for n in range(1, q(1) + 1)}}
+
+
+SVM_LOSSES = {'squared_hinge': 0, 'hinge': 1}
+
+
+def searchlight_svm(Xt, S, rowptr, colidx, centres, models, bucket, list_ptr, list_idx, test_ptr, tmax, C, Creg, loss, tol, max_iter,
+                    sgroup, slabel, sorig, correct, scores=None, predictions=None, sweeps=None, residual=None):
+    """A one-vs-rest linear SVM at the rows ``centres`` (int32 [Ub], of any length) for the models ``models`` (int32 [NMb], all
+    with training sets of at most ``bucket`` samples) (chebgcn_searchlight_svm): one workgroup per (centre, model) forms the
+    Gram matrix of the centred training samples, solves the dual of every class by coordinate descent (``Creg`` the SVM's ``C``,
+    ``loss`` ``'squared_hinge'`` or ``'hinge'``, at most ``max_iter`` sweeps, stopped at ``max |PG| <= tol``) and scores the
+    model's test samples.  ``list_ptr`` int32 [NM + 1] / ``list_idx`` int32: the training samples of every model; the other
+    tables as ``searchlight_score``.  ADDS the hits to ``correct`` int32 [G, C, U]; fills ``scores`` float64 [S, C, U] /
+    ``predictions`` uint8 [S, U] / ``sweeps`` int32 [NM, U] / ``residual`` float64 [NM, U] where given.  The model and its orders:
+    include/chebgcn.h."""
+    _require_cuda(Xt, rowptr, colidx, centres, models, list_ptr, list_idx, test_ptr, sgroup, slabel, sorig, correct, scores, predictions,
+                  sweeps, residual)
+    if loss not in SVM_LOSSES:
+        raise _lib.ChebgcnError("searchlight_svm: loss must be 'squared_hinge' or 'hinge', got %r" % (loss,))
+    M = _sl_patterns(Xt, S, 'searchlight_svm')
+    S, C, bucket = int(S), int(C), int(bucket)
+    U = int(rowptr.numel()) - 1
+    nnz = _sl_lists(rowptr, colidx, U, 'searchlight_svm')
+    NM = int(test_ptr.numel()) - 1
+    _dense(test_ptr, torch.int32, (NM + 1,), 'searchlight_svm: test_ptr')
+    nidx = _sl_lists(list_ptr, list_idx, NM, 'searchlight_svm')
+    Ub, NMb = int(centres.numel()), int(models.numel())
+    if Ub < 1 or NMb < 1:
+        raise _lib.ChebgcnError('searchlight_svm: no centres or no models')
+    _dense(centres, torch.int32, (Ub,), 'searchlight_svm: centres')
+    _dense(models, torch.int32, (NMb,), 'searchlight_svm: models')
+    for t, what in ((sgroup, 'sgroup'), (slabel, 'slabel'), (sorig, 'sorig')):
+        _dense(t, torch.int32, (S,), 'searchlight_svm: ' + what)
+    if correct.dim() != 3 or correct.shape[1] != C or correct.shape[2] != U:
+        raise _lib.ChebgcnError('searchlight_svm: correct must be int32 [G, C, U]')
+    G = int(correct.shape[0])
+    _dense(correct, torch.int32, (G, C, U), 'searchlight_svm: correct')
+    if scores is not None:
+        _dense(scores, torch.float64, (S, C, U), 'searchlight_svm: scores')
+    if predictions is not None:
+        _dense(predictions, torch.uint8, (S, U), 'searchlight_svm: predictions')
+    if sweeps is not None:
+        _dense(sweeps, torch.int32, (NM, U), 'searchlight_svm: sweeps')
+    if residual is not None:
+        _dense(residual, torch.float64, (NM, U), 'searchlight_svm: residual')
+    terms = float(nnz) * Ub / max(U, 1) * NMb                  # (vertex, model) pairs of the launch
+    tri = 0.5 * bucket * (bucket + 1)
+    _lib.check(_launch('searchlight_svm', 8.0 * terms * bucket + 4.0 * float(S) * float(nnz) * Ub / max(U, 1), 2.0 * terms * tri,
+                       lambda: _lib.lib().chebgcn_searchlight_svm(
+                           _p(Xt), S, M, _p(rowptr), _p(colidx), nnz, U, _p(centres), Ub, _p(models), NMb, bucket, _p(list_ptr),
+                           _p(list_idx), nidx, _p(test_ptr), int(tmax), NM, C, float(Creg), SVM_LOSSES[loss], float(tol), int(max_iter),
+                           _p(sgroup), _p(slabel), _p(sorig), G, _p(correct), _p(scores), _p(predictions), _p(sweeps), _p(residual),
+                           _stream())), 'searchlight_svm')
+
+
 # ------------------------------------------------------------------------------------
 # the graph-convolution layer
 # ------------------------------------------------------------------------------------

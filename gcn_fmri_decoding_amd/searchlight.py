@@ -16,6 +16,12 @@ of the ball, shrunk towards a multiple of the identity (a fixed ``shrinkage`` or
 discriminants -- one workgroup per pair, everything on chip (chebgcn_searchlight_lda), for balls of up to ``LDA_PMAX``
 vertices.  The model is stated once, in ``searchlight``'s docstring and in include/chebgcn.h.
 
+Between the two sits a hole: ``'lda'`` refuses rows above ``LDA_PMAX`` vertices, and naive Bayes cannot use the covariance.
+``classifier='svc'`` closes it: a one-vs-rest linear SVM per (training set, centre), solved in the dual by coordinate descent on
+the n x n Gram matrix of the training samples (chebgcn_searchlight_svm, one workgroup per pair, everything on chip).  Its state
+depends on the number of training samples (at most ``SVC_NMAX``) and not on the length of the row, so parcels of hundreds of
+vertices and the whole-brain row are served.  Convergence is reported (``return_solver=True``: a ``SolverInfo``), never hidden.
+
 Where the searchlight says WHERE the conditions can be told apart, ``crossnobis`` says HOW a region tells them apart: the
 representational dissimilarity matrix of every ball -- the cross-validated Mahalanobis distance of every pair of classes per
 (group, centre), whitened by the ball's shrunk noise covariance (chebgcn_searchlight_rdm, one workgroup per pair; the quantity
@@ -23,8 +29,9 @@ is stated once, in ``crossnobis``'s docstring and in include/chebgcn.h).  ``comp
 with model RDMs for ``map_test``; ``crossnobis_events`` cuts the patterns from staged runs; ``crossnobis_host`` restates it
 with SciPy.
 
-Out of scope: iterative classifiers inside the ball (SVM), per-class covariances (QDA), balls above ``LDA_PMAX`` vertices
-with ``'lda'`` or ``crossnobis``, returning the discriminant weights, label-permutation nulls per subject (group
+Out of scope: SVM training sets above ``SVC_NMAX`` samples (a Gram matrix in HBM), non-linear kernels, one-vs-one or
+Crammer-Singer multi-class, an unregularised bias, class weights, per-class covariances (QDA), balls above ``LDA_PMAX`` vertices
+with ``'lda'`` or ``crossnobis``, returning the discriminant or primal weights, label-permutation nulls per subject (group
 inference goes through ``map_test``), smoothing per ball (see ``searchlight``), temporal features beyond the trial mean,
 any cleaning of the series, rank-based RDM comparisons (Spearman), noise ceilings and unbalanced designs in ``crossnobis``.
 
@@ -50,7 +57,18 @@ class c that centre u classified correctly; ``support`` int64 [G, classes]: how 
 over its samples; ``groups`` the G keys in order of first appearance; ``classes``; ``scores`` float64 [S, classes, U] joint
 log-likelihoods and ``predictions`` uint8 [S, U], in the caller's sample order, or None."""
 
-_Args = collections.namedtuple('_Args', 'X tensor S M y classes indptr indices U fold gidx keys within pooled uniform vs lda shrink')
+SVC_NMAX = 128                                  # chebgcn_searchlight_svm_query(1): the largest training set classifier='svc' serves
+SVC_ITMAX = 100000                              # chebgcn_searchlight_svm_query(8): the largest max_iter
+SVC_LOSSES = ('squared_hinge', 'hinge')
+
+SolverInfo = collections.namedtuple('SolverInfo', 'sweeps residual models')
+SolverInfo.__doc__ = """What ``searchlight(classifier='svc', return_solver=True)`` returns beside the result.  ``sweeps`` int32
+[NM, U]: the most sweeps any class of that (model, centre) ran; ``residual`` float64 [NM, U]: the largest last-sweep ``max |PG|``
+over the classes -- converged where ``residual <= tol``, ended by the cap where ``sweeps == max_iter`` and ``residual > tol``;
+``models``: the ``(group key, fold)`` of every model row (``(None, fold)`` with ``within=False``)."""
+
+_Args = collections.namedtuple('_Args', 'X tensor S M y classes indptr indices U fold gidx keys within pooled uniform vs lda shrink '
+                               'svc Creg loss tol max_iter', defaults=(False, 1.0, 'squared_hinge', 1e-3, 1000))
 
 
 # ---- arguments ------------------------------------------------------------------------------------------------------------------
@@ -161,7 +179,7 @@ def _group_keys(groups, S, who):
 
 
 def _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-           batch_centres, who, limits=True, classifier='gnb', shrinkage=0.1):
+           batch_centres, who, limits=True, classifier='gnb', shrinkage=0.1, C=1.0, loss='squared_hinge', tol=1e-3, max_iter=1000):
     """Everything that can be checked without the samples' values.  ``shrink`` of the result: the float, or -1.0 for ``'auto'``."""
     X, tensor, S, M = _patterns(samples, who)
     for name, val in (('within', within), ('scores', scores), ('predictions', predictions)):
@@ -174,14 +192,33 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
     if isinstance(var_smoothing, (bool, np.bool_)) or not isinstance(var_smoothing, (int, float, np.integer, np.floating)) \
             or not np.isfinite(var_smoothing) or var_smoothing < 0:
         raise ValueError('%s: var_smoothing must be a finite number >= 0, got %r' % (who, var_smoothing))
-    if classifier not in ('gnb', 'lda'):
-        raise ValueError("%s: classifier must be 'gnb' or 'lda', got %r" % (who, classifier))
+    if classifier not in ('gnb', 'lda', 'svc'):
+        raise ValueError("%s: classifier must be 'gnb', 'lda' or 'svc', got %r" % (who, classifier))
     auto, number = _shrink_number(shrinkage)
+    real = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+    if classifier == 'svc':
+        if not (real(C) and C > 0):
+            raise ValueError('%s: C must be a finite number > 0, got %r' % (who, C))
+        if not (isinstance(loss, str) and loss in SVC_LOSSES):
+            raise ValueError("%s: loss must be 'squared_hinge' or 'hinge', got %r" % (who, loss))
+        if not (real(tol) and tol >= 0):
+            raise ValueError('%s: tol must be a finite number >= 0, got %r' % (who, tol))
+        if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, (int, np.integer)) or not 1 <= max_iter <= SVC_ITMAX:
+            raise ValueError('%s: max_iter must be an int in [1, %d], got %r' % (who, SVC_ITMAX, max_iter))
+        if priors != 'empirical':
+            raise ValueError("%s: priors = %r means nothing to classifier='svc' (an SVM has no prior to set): leave it at 'empirical'"
+                             % (who, priors))
+        if variance != 'class' or not var_smoothing == 1e-9 or not (number and shrinkage == 0.1):
+            raise ValueError("%s: variance, var_smoothing and shrinkage mean nothing to classifier='svc' (regularised by C): leave "
+                             "them at their defaults" % who)
+    elif not (real(C) and C == 1.0 and isinstance(loss, str) and loss == 'squared_hinge' and real(tol) and tol == 1e-3
+              and not isinstance(max_iter, (bool, np.bool_)) and isinstance(max_iter, (int, np.integer)) and max_iter == 1000):
+        raise ValueError("%s: C, loss, tol and max_iter belong to classifier='svc'; they mean nothing to classifier=%r" % (who, classifier))
     if classifier == 'gnb':
         if not (number and shrinkage == 0.1):
             raise ValueError("%s: shrinkage = %r means nothing to classifier='gnb' (naive Bayes has no covariance to shrink)"
                              % (who, shrinkage))
-    else:
+    elif classifier == 'lda':
         if not auto and not (number and SHRINK_MIN <= shrinkage <= 1):
             raise ValueError("%s: shrinkage must be a number in [%g, 1] or 'auto', got %r" % (who, SHRINK_MIN, shrinkage))
         if variance != 'class' or not var_smoothing == 1e-9:
@@ -203,7 +240,8 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
         if length.max() > LDA_PMAX:
             row = int(np.argmax(length > LDA_PMAX))
             raise ValueError("%s: neighbourhood %d holds %d vertices; classifier='lda' serves rows of up to %d (a covariance per "
-                             "ball): use classifier='gnb' for parcels and whole-brain rows" % (who, row, length[row], LDA_PMAX))
+                             "ball): use classifier='gnb' or, to keep the covariance, classifier='svc' for parcels and whole-brain "
+                             "rows" % (who, row, length[row], LDA_PMAX))
     if scores and 8 * S * len(classes) * U > SCORES_MAX_BYTES:
         raise ValueError('%s: scores=True would return %d bytes ([S, classes, U] float64); refused beyond %d: score fewer centres '
                          'per call' % (who, 8 * S * len(classes) * U, SCORES_MAX_BYTES))
@@ -219,8 +257,18 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
         g, f, c = (int(v) for v in bad[0])
         raise ValueError('%s: class %r has no training sample for the test samples of %sfold %d' % (
             who, classes[c], 'group %r, ' % (keys[g],) if within else '', int(fvals[f])))
+    if classifier == 'svc':
+        size = train.sum(axis=2)                                # [G or 1, F]: the samples of the training set tested on (g, f)
+        big = np.argwhere((size > SVC_NMAX) & (cnt.sum(axis=2) > 0))
+        if big.size:
+            g, f = (int(v) for v in big[0])
+            raise ValueError("%s: the training set of %sfold %d holds %d samples; classifier='svc' serves up to %d (the Gram matrix "
+                             "of the training samples stays on chip); across-subject training sets of thousands of samples are out "
+                             "of scope, so within=False is served only while n <= %d"
+                             % (who, 'group %r, ' % (keys[g],) if within else '', int(fvals[f]), size[g, f], SVC_NMAX, SVC_NMAX))
     return _Args(X, tensor, S, M, y, classes, indptr, indices, U, fold, gidx, keys, bool(within), variance == 'pooled',
-                 priors == 'uniform', float(var_smoothing), classifier == 'lda', -1.0 if auto else float(shrinkage))
+                 priors == 'uniform', float(var_smoothing), classifier == 'lda', -1.0 if auto else float(shrinkage),
+                 classifier == 'svc', float(C), loss, float(tol), int(max_iter))
 
 
 def _summary(correct, support, xp):
@@ -246,7 +294,8 @@ def _support(a):
 
 def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within=True, classes=None, variance='class',
                      priors='empirical', var_smoothing=1e-9, scores=False, predictions=False, device=None, batch_centres=None,
-                     return_scale=False, classifier='gnb', shrinkage=0.1):
+                     return_scale=False, classifier='gnb', shrinkage=0.1, C=1.0, loss='squared_hinge', tol=1e-3, max_iter=1000,
+                     return_solver=False):
     """``searchlight`` restated in float64 NumPy (no device; ``device`` and ``batch_centres`` are accepted and ignored), the
     obvious way: per training set and per centre the ball's columns are sliced out, the class means and variances fitted on
     them (``sum / n``, ``sum (x - mean)^2 / n``), every test sample scored with
@@ -258,26 +307,41 @@ def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within
     ``classifier='lda'``: the model of ``searchlight``'s docstring, per training set and per centre: the ball's columns sliced
     out, the residuals formed with NumPy, ``scipy.linalg.cho_factor`` / ``cho_solve``, the scores.  There ``scale`` is
     ``kappa (|log prior_c| + |d_c . w_c| / 2 + sum_v |w_cv| |x_sv - m_v|)``, ``kappa`` the 2-norm condition number of that
-    (model, centre)'s ``Sigma`` (``eigvalsh``; 1 in the degenerate case): the magnitude a float64 solve may be off by."""
+    (model, centre)'s ``Sigma`` (``eigvalsh``; 1 in the degenerate case): the magnitude a float64 solve may be off by.
+
+    ``classifier='svc'``: the model of ``searchlight``'s docstring with its chains as explicit loops over samples and vertices,
+    vectorised across (i, j) and across the classes; every operation a separate correctly rounded one, so the device agrees
+    with it bit for bit.  ``return_solver``: a pair of the result and a ``SolverInfo`` (``return_scale`` is not served there)."""
     who = 'searchlight_host'
     a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-               batch_centres, who, limits=False, classifier=classifier, shrinkage=shrinkage)
+               batch_centres, who, limits=False, classifier=classifier, shrinkage=shrinkage, C=C, loss=loss, tol=tol, max_iter=max_iter)
+    _solver_flag(return_solver, a, who)
+    if a.svc and return_scale:
+        raise ValueError("%s: return_scale is not served with classifier='svc' (the device agrees bit for bit)" % who)
     X = _host_array(a.X, who).astype(np.float64)
     S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
     sc = np.empty((S, C, U))
     scale = np.empty((S, C, U)) if return_scale else None
     pred = np.empty((S, U), np.uint8)
     key = a.gidx * (int(a.fold.max()) - int(a.fold.min()) + 1) + (a.fold - a.fold.min()) if a.within else a.fold
-    for k in np.unique(key):
+    model_keys = np.unique(key)
+    sweeps, residual, models = np.zeros((model_keys.size, U), np.int32), np.zeros((model_keys.size, U)), []
+    for mi, k in enumerate(model_keys):
         test = key == k
         train = ~test & (a.gidx == a.gidx[test][0]) if a.within else ~test
         Xtr, ytr, Xte = X[train], a.y[train], X[test]
+        models.append((a.keys[a.gidx[test][0]] if a.within else None, int(a.fold[test][0])))
         n = np.array([(ytr == c).sum() for c in range(C)], np.float64)
         logp = np.full(C, -np.log(C)) if a.uniform else np.log(n / n.sum())
-        eps = a.vs * Xtr.var(axis=0).max()
+        eps = 0.0 if a.svc else a.vs * Xtr.var(axis=0).max()
         for u in range(U):
             cols = a.indices[a.indptr[u]:a.indptr[u + 1]]
             A, T = Xtr[:, cols], Xte[:, cols]
+            if a.svc:
+                s_, sweeps[mi, u], residual[mi, u] = _svc_host_ball(A, ytr, T, C, a.Creg, a.loss, a.tol, a.max_iter)
+                sc[test, :, u] = s_
+                pred[test, u] = np.argmax(s_, axis=1)
+                continue
             if a.lda:
                 s_, q_ = _lda_host_ball(A, ytr, T, n, logp, a.shrink)
                 sc[test, :, u] = s_
@@ -303,7 +367,60 @@ def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within
     recall, accuracy = _summary(correct, support, np)
     res = SearchlightResult(correct, support, recall, accuracy, list(a.keys), list(a.classes), sc if scores else None,
                             pred if predictions else None)
+    if return_solver:
+        return res, SolverInfo(sweeps, residual, models)
     return (res, scale) if return_scale else res
+
+
+def _solver_flag(return_solver, a, who):
+    if not isinstance(return_solver, (bool, np.bool_)):
+        raise ValueError('%s: return_solver must be True or False, got %r' % (who, return_solver))
+    if return_solver and not a.svc:
+        raise ValueError("%s: return_solver belongs to classifier='svc' (the other classifiers have no iteration to report)" % who)
+
+
+def _svc_host_ball(A, ytr, T, C, Creg, loss, tol, max_iter):
+    """The one-vs-rest linear SVM of one (training set, row): ``A`` [n, P] training columns in list order, ``T`` [t, P] test
+    columns -> ``(scores [t, C], sweeps, residual)``.  The model of ``searchlight``'s docstring, operation by operation."""
+    n, P = A.shape
+    acc = np.zeros(P)
+    for k in range(n):                                          # m_v: one chain in list order, one division
+        acc = acc + A[k]
+    m = acc / float(n)
+    Ac, Tc = A - m, T - m
+    K, Kt = np.zeros((n, n)), np.zeros((T.shape[0], n))
+    for v in range(P):                                          # K_ij: one chain over the vertices per element
+        K = K + Ac[:, v, None] * Ac[None, :, v]
+        Kt = Kt + Tc[:, v, None] * Ac[None, :, v]
+    q = K + 1.0
+    D, Ub = (1.0 / (2.0 * Creg), np.inf) if loss == 'squared_hinge' else (0.0, Creg)
+    Qd = np.diagonal(q) + D
+    t = np.where(ytr[None, :] == np.arange(C)[:, None], 1.0, -1.0)              # [C, n]
+    alpha, g = np.zeros((C, n)), np.full((C, n), -1.0)
+    live = np.ones(C, bool)
+    sweeps, resid = np.zeros(C, np.int32), np.zeros(C)
+    for e in range(1, max_iter + 1):
+        mx = np.zeros(C)
+        for i in range(n):
+            G, ai = g[:, i].copy(), alpha[:, i].copy()
+            PG = np.where(ai == 0.0, np.minimum(G, 0.0), np.where(ai == Ub, np.maximum(G, 0.0), G))
+            act = live & (PG != 0.0)
+            if act.any():
+                an = np.minimum(np.maximum(ai[act] - G[act] / Qd[i], 0.0), Ub)
+                delta = an - ai[act]
+                g[act] = g[act] + (t[act, i, None] * t[act]) * (delta[:, None] * q[None, :, i])
+                g[act, i] = g[act, i] + delta * D
+                alpha[act, i] = an
+            mx = np.maximum(mx, np.abs(PG))
+        sweeps[live], resid[live] = e, mx[live]
+        live &= ~(mx <= tol)
+        if not live.any():
+            break
+    at = alpha * t
+    f = np.zeros((T.shape[0], C))
+    for j in range(n):                                          # the score: one chain in list order
+        f = f + at[None, :, j] * (Kt[:, j, None] + 1.0)
+    return f, int(sweeps.max()), float(resid.max())
 
 
 def lda_shrinkage_host(R):
@@ -461,6 +578,34 @@ def _run_lda(a, plan, Xt, scores, predictions, batch_centres, gamma=False):
     return (correct, sc, pred, gam) if gamma else (correct, sc, pred)
 
 
+def _run_svc(a, plan, Xt, scores, predictions, batch_centres):
+    """The launches of ``classifier='svc'``: the models bucket by bucket of training-set size, the centres batch by batch.
+    Returns device tensors: ``(correct, scores, predictions, sweeps int32 [NM, U], residual float64 [NM, U])``."""
+    import torch
+    from . import ops
+    dev = Xt.device
+    up = lambda v: torch.as_tensor(v).to(dev)
+    S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
+    correct = torch.zeros((G, C, U), dtype=torch.int32, device=dev)
+    sc = torch.empty((S, C, U), dtype=torch.float64, device=dev) if scores else None
+    pred = torch.empty((S, U), dtype=torch.uint8, device=dev) if predictions else None
+    sweeps = torch.zeros((plan.NM, U), dtype=torch.int32, device=dev)
+    residual = torch.zeros((plan.NM, U), dtype=torch.float64, device=dev)
+    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
+    list_ptr, list_idx = up(plan.list_ptr), up(plan.list_idx)
+    tables = [up(v) for v in (plan.test_ptr, plan.sgroup, plan.slabel, plan.order.astype(np.int32))]
+    buckets = ops.searchlight_svm_geometry()['buckets']
+    of_model = np.array([buckets[int(n)] for n in np.diff(plan.list_ptr)])
+    step = U if batch_centres is None else int(min(batch_centres, U))
+    for bucket in sorted(set(of_model.tolist())):
+        models = up(np.flatnonzero(of_model == bucket).astype(np.int32))
+        for u0 in range(0, U, step):
+            ops.searchlight_svm(Xt, S, rowptr, colidx, up(np.arange(u0, min(u0 + step, U), dtype=np.int32)), models, bucket, list_ptr,
+                                list_idx, tables[0], plan.tmax, C, a.Creg, a.loss, a.tol, a.max_iter, tables[1], tables[2], tables[3],
+                                correct, scores=sc, predictions=pred, sweeps=sweeps, residual=residual)
+    return correct, sc, pred, sweeps, residual
+
+
 def _result(a, correct, sc, pred, as_tensor):
     import torch
     support = _support(a)
@@ -482,7 +627,7 @@ def _device(device, like=None):
     return torch.device('cuda', torch.cuda.current_device())
 
 
-def _searchlight(a, dev, scores, predictions, batch_centres, as_tensor, who):
+def _searchlight(a, dev, scores, predictions, batch_centres, as_tensor, who, return_solver=False):
     if a.indices.size > 2 ** 31 - 1:
         raise ValueError('%s: the neighbourhoods list %d vertices; served: fewer than 2^31' % (who, a.indices.size))
     import torch
@@ -498,14 +643,25 @@ def _searchlight(a, dev, scores, predictions, batch_centres, as_tensor, who):
                 raise ValueError('%s: samples hold non-finite values' % who)
         else:
             X = torch.as_tensor(a.X).to(dev)                    # (float32 and finite: the caller's _host_array)
+        if a.svc:
+            correct, sc, pred, sweeps, residual = _run_svc(a, plan, _transposed(X, plan.order, dev), scores, predictions, batch_centres)
+            res = _result(a, correct, sc, pred, as_tensor)
+            if not return_solver:
+                return res
+            first = plan.order[plan.test_ptr[:-1]]              # one test sample of every model
+            models = [(a.keys[a.gidx[s]] if a.within else None, int(a.fold[s])) for s in first]
+            if not as_tensor:
+                sweeps, residual = sweeps.cpu().numpy(), residual.cpu().numpy()
+            return res, SolverInfo(sweeps, residual, models)
         correct, sc, pred = (_run_lda if a.lda else _run)(a, plan, _transposed(X, plan.order, dev), scores, predictions, batch_centres)
         return _result(a, correct, sc, pred, as_tensor)
 
 
 def searchlight(samples, labels, neighbourhoods, folds, groups=None, within=True, classes=None, variance='class', priors='empirical',
-                var_smoothing=1e-9, scores=False, predictions=False, device=None, batch_centres=None, classifier='gnb', shrinkage=0.1):
-    """Cross-validated accuracy of a Gaussian naive-Bayes (``classifier='gnb'``) or a shrinkage-LDA (``'lda'``) classifier at
-    every centre, on the device: a ``SearchlightResult``.
+                var_smoothing=1e-9, scores=False, predictions=False, device=None, batch_centres=None, classifier='gnb', shrinkage=0.1,
+                C=1.0, loss='squared_hinge', tol=1e-3, max_iter=1000, return_solver=False):
+    """Cross-validated accuracy of a Gaussian naive-Bayes (``classifier='gnb'``), a shrinkage-LDA (``'lda'``) or a linear-SVM
+    (``'svc'``) classifier at every centre, on the device: a ``SearchlightResult``.
 
     ``samples``: ``[S, M]`` patterns, one per trial (trial means, betas); NumPy or a torch tensor; rounded to float32 as staging
     does.  ``labels``: ``[S]`` values found in ``classes``, which defaults to the sorted set of labels (the order of
@@ -545,6 +701,31 @@ def searchlight(samples, labels, neighbourhoods, folds, groups=None, within=True
     class) or a Cholesky pivot is not positive and finite, ``w = 0`` and ``b_c = log prior_c``: the prior decides, nothing is NaN.
     ``scores`` are then discriminant values, not log-likelihoods.  With ``'gnb'`` ``shrinkage`` must stay at its default.
 
+    ``classifier='svc'``: a one-vs-rest linear SVM in its dual form, for rows of ANY length and training sets of up to
+    ``SVC_NMAX`` = 128 samples; ``priors``, ``variance``, ``var_smoothing`` and ``shrinkage`` must stay at their defaults (an SVM
+    has no prior to set).  Float64 throughout, and every operation is a separate correctly rounded multiply, add or divide --
+    nothing is fused -- so ``searchlight_host`` agrees bit for bit.  Per training set with samples ``k_0 < ... < k_{n-1}`` and per
+    row with vertices ``v_0 < ... < v_{P-1}``, P >= 1:  centring ``m_v = (x_{k_0 v} + x_{k_1 v} + ...) / n``, one chain in that
+    order, then one division;  Gram matrix ``K_ij = sum_v (x_iv - m_v)(x_jv - m_v)``, one chain over the vertices in ascending
+    order, for the training pairs and every (test sample, training sample) pair;  one-vs-rest with liblinear's regularised bias
+    (``fit_intercept=True, intercept_scaling=1``: the kernel is ``K + 1``): for class c  ``t_i = +1`` if ``y_i = c`` else ``-1``,
+    ``q_ij = K_ij + 1``, ``Q_ij = t_i t_j q_ij``;  ``loss='hinge'``: ``D = 0``, upper bound ``Ub = C``;  ``loss='squared_hinge'``:
+    ``D = 1 / (2 C)``, no upper bound;  ``Qd_i = q_ii + D`` (>= 1: no division needs a guard, there is no degenerate branch).
+    Dual coordinate descent (Hsieh et al. 2008) in fixed cyclic order, no shuffling, no shrinking of the active set:
+    ``alpha = 0``, ``g_i = -1``; sweeps e = 1 .. ``max_iter``, each visiting i = 0 .. n - 1:  ``G = g_i``;  ``PG = min(G, 0)`` if
+    ``alpha_i == 0``, ``max(G, 0)`` if ``alpha_i == Ub``, else ``G``;  if ``PG != 0``:  ``a = min(max(alpha_i - G / Qd_i, 0), Ub)``,
+    ``delta = a - alpha_i``, ``alpha_i = a``, for every j ``g_j = g_j + (t_i t_j)(delta q_ji)`` and at j = i additionally, as a
+    second addition, ``g_i = g_i + delta D``;  after a sweep, stop if the sweep's ``max |PG| <= tol``.
+    ``score[s, c, u] = sum_j (alpha_j t_j)(K_sj + 1)``, one chain in list order; the prediction is the first maximal class.  For
+    two classes the problems are mirror images and ``score[:, 1] == -score[:, 0]`` exactly.  At convergence this is
+    scikit-learn's ``LinearSVC(loss=, C=, dual=True, fit_intercept=True, intercept_scaling=1, multi_class='ovr')`` on the row's
+    columns centred by the training means; the primal is strongly convex in (w, b), so the decision values are unique.  Scaling
+    the patterns is the caller's job, and ``C`` is on the data's scale.  ``C``: finite, > 0; ``loss``: ``'squared_hinge'``
+    (scikit-learn's default) or ``'hinge'``; ``tol``: finite, >= 0; ``max_iter``: an int in [1, 100000].  Where n is much larger
+    than P and ``C >= 1`` the descent needs thousands of sweeps and the cap ends it: ``return_solver=True`` returns
+    ``(result, SolverInfo)`` with the sweeps run and the last sweep's ``max |PG|`` of every (model, centre), so that convergence
+    is reported and never hidden.  With the other classifiers these keywords must stay at their defaults.
+
     ``scores`` / ``predictions``: also return the float64 ``[S, classes, U]`` scores (refused beyond 2 GiB) / the uint8
     ``[S, U]`` predictions.  ``batch_centres``: centres of one launch; the result does not depend on it, bit for bit.  The
     maps are NumPy arrays, or device tensors if ``samples`` came as a tensor.  Group inference on the maps:
@@ -554,17 +735,24 @@ def searchlight(samples, labels, neighbourhoods, folds, groups=None, within=True
     a label outside ``classes``, an empty neighbourhood, ``var_smoothing < 0``, unknown strings, a class without a training
     sample in a training set that has test samples (naming the group and the fold); with ``'lda'`` a row of more than 128
     vertices (naming it), a ``shrinkage`` outside ``[1e-6, 1]`` that is not ``'auto'``, ``variance`` or ``var_smoothing`` away from
-    their defaults; with ``'gnb'`` a ``shrinkage`` away from its default.
+    their defaults; with ``'gnb'`` a ``shrinkage`` away from its default; with ``'svc'`` a training set of more than 128 samples
+    (naming the group, the fold and the count: across-subject training sets of thousands of samples are out of scope, so
+    ``within=False`` is served only while n <= 128), a bad ``C``, ``loss``, ``tol`` or ``max_iter``, ``priors='uniform'``,
+    ``variance``, ``var_smoothing`` or ``shrinkage`` away from their defaults; without ``'svc'`` its keywords away from theirs.
 
-    Out of scope: iterative classifiers in the ball (SVM), per-class covariances (QDA), ``'lda'`` on balls above 128 vertices,
-    returning the discriminant weights, label-permutation nulls per subject (group inference goes through ``map_test``),
-    smoothing per ball, temporal features beyond the trial mean, any cleaning of the series."""
+    Out of scope: SVM training sets above 128 samples (a Gram matrix in HBM), non-linear kernels, one-vs-one or Crammer-Singer
+    multi-class, an unregularised bias (libsvm's equality constraint), class weights, per-class covariances (QDA), ``'lda'`` on
+    balls above 128 vertices, returning the discriminant or primal weights, label-permutation nulls per subject (group inference
+    goes through ``map_test``), smoothing per ball, temporal features beyond the trial mean, any scaling or cleaning of the
+    patterns or the series."""
     who = 'searchlight'
     a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-               batch_centres, who, classifier=classifier, shrinkage=shrinkage)
+               batch_centres, who, classifier=classifier, shrinkage=shrinkage, C=C, loss=loss, tol=tol, max_iter=max_iter)
+    _solver_flag(return_solver, a, who)
     if not a.tensor:
         a = a._replace(X=_host_array(a.X, who))                 # non-finite values: before the device is touched
-    return _searchlight(a, _device(device, a.X if a.tensor else None), scores, predictions, batch_centres, a.tensor, who)
+    return _searchlight(a, _device(device, a.X if a.tensor else None), scores, predictions, batch_centres, a.tensor, who,
+                        bool(return_solver))
 
 
 # ---- from event designs ---------------------------------------------------------------------------------------------------------
@@ -664,7 +852,8 @@ def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods
 
     ``groups``: one key per run (the subject; default one group).  ``folds``: one int per run; default ``default_folds``: with
     ``within=True`` the run's position among its group's runs (leave-one-run-out), with ``within=False`` the group's index
-    (leave-one-subject-out).  Every other keyword is ``searchlight``'s, ``classifier`` and ``shrinkage`` included.  Returns NumPy maps, or device tensors if every run came
+    (leave-one-subject-out).  Every other keyword is ``searchlight``'s, ``classifier``, ``shrinkage`` and the SVM's ``C``, ``loss``, ``tol``, ``max_iter``
+    and ``return_solver`` included.  Returns NumPy maps, or device tensors if every run came
     as a tensor."""
     who = 'searchlight_events'
     single = isinstance(runs, np.ndarray) or _is_tensor(runs)
@@ -679,7 +868,8 @@ def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods
     if 'TRstep' in kw or 'classes' in kw:
         raise ValueError('%s: TRstep and classes are not taken (one pattern per trial; the classes are sorted(set(target_name)))' % who)
     match_kw = {k: kw.pop(k) for k in _MATCH_KW if k in kw}
-    unknown = set(kw) - {'variance', 'priors', 'var_smoothing', 'scores', 'predictions', 'device', 'batch_centres', 'classifier', 'shrinkage'}
+    unknown = set(kw) - {'variance', 'priors', 'var_smoothing', 'scores', 'predictions', 'device', 'batch_centres', 'classifier', 'shrinkage',
+                         'C', 'loss', 'tol', 'max_iter', 'return_solver'}
     if unknown:
         raise ValueError('%s: unknown keyword %r' % (who, sorted(unknown)[0]))
     if single and label_runs is not None and len(label_runs) and isinstance(label_runs[0], str):
@@ -688,12 +878,14 @@ def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods
                                                 within, match_kw, who)
     device = kw.pop('device', None)
     sl_kw = dict(variance='class', priors='empirical', var_smoothing=1e-9, scores=False, predictions=False, batch_centres=None,
-                 classifier='gnb', shrinkage=0.1)
+                 classifier='gnb', shrinkage=0.1, C=1.0, loss='squared_hinge', tol=1e-3, max_iter=1000, return_solver=False)
     sl_kw.update(kw)
     # (the patterns do not exist yet: the checks run on a stand-in of their shape)
     a = _check(np.zeros((idx.shape[0], M), np.float32), labels, neighbourhoods, tf, tg, within, classes, sl_kw['variance'],
                sl_kw['priors'], sl_kw['var_smoothing'], sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], who,
-               classifier=sl_kw['classifier'], shrinkage=sl_kw['shrinkage'])
+               classifier=sl_kw['classifier'], shrinkage=sl_kw['shrinkage'], C=sl_kw['C'], loss=sl_kw['loss'], tol=sl_kw['tol'],
+               max_iter=sl_kw['max_iter'])
+    _solver_flag(sl_kw['return_solver'], a, who)
     runs = [r if _is_tensor(r) else _host_array(r, who) for r in runs]        # non-finite values: before the device is touched
     import torch
     first = next((r for r in runs if _is_tensor(r) and r.is_cuda), None)
@@ -702,7 +894,8 @@ def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods
         planes = _stage(runs, M, dev, who)
         X = _event_patterns(planes, torch.as_tensor(idx).to(dev), M)
         a = a._replace(X=X, tensor=True)
-        return _searchlight(a, dev, sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], all(_is_tensor(r) for r in runs), who)
+        return _searchlight(a, dev, sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], all(_is_tensor(r) for r in runs), who,
+                            bool(sl_kw['return_solver']))
 
 
 # ---- RSA: crossnobis distances per ball -----------------------------------------------------------------------------------------

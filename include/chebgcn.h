@@ -1110,6 +1110,56 @@ int chebgcn_searchlight_rdm(const float* Xt, int S, int M, const int32_t* rowptr
                             const int32_t* class_idx, int nidx, int NM, int C, const double* par, double shrinkage, int G,
                             double* rdm, double* gamma_out, chebgcn_stream stream);
 
+/* ---- searchlight decoding with a linear SVM: one dual problem per class on the Gram matrix of every (model, centre) ---------------
+ * (searchlight.searchlight(classifier='svc')).  Xt, rowptr, colidx, centres, test_ptr, sgroup, slabel, sorig, correct, scores,
+ * predictions as chebgcn_searchlight_lda; list_ptr int32 [NM + 1] / list_idx int32 [nidx] are the training samples of every model
+ * (the lists of chebgcn_searchlight_spread), whose labels are slabel[list_idx[.]]; models: int32 [NMb] model numbers of this launch
+ * (one workgroup per (centre, model)); bucket: 32, 64 or 128 -- a model whose list is longer than the bucket (or empty) is skipped
+ * and nothing of it is written.  Rows of ANY length are served: the state on chip depends on the training set alone.
+ * The model, for model m with training samples k_0 < ... < k_{n-1} (list order), n <= 128, and a row of vertices
+ * v_0 < ... < v_{P-1}, P >= 1.  Float64 throughout, EVERY OPERATION A SEPARATE CORRECTLY ROUNDED MULTIPLY, ADD OR DIVIDE: nothing is
+ * fused (the file is compiled with contraction off), so a restatement in NumPy agrees bit for bit:
+ *     m_v = ((double)Xt[v][k_0] + (double)Xt[v][k_1] + ...) / n:  one chain in list order, then one division (formed by this
+ *         kernel; chebgcn_searchlight_fit's means are compiled with contraction on and are not used);
+ *     x_iv = (double)Xt[v][k_i] - m_v, and the same for a test sample s;
+ *     K_ij = (a = 0; a = a + x_iv x_jv, v ascending) for the training pairs (i >= j, symmetric) and every (test sample, training
+ *         sample) pair; a vertex outside [0, M) contributes nothing;
+ *     one-vs-rest with liblinear's regularised bias (fit_intercept=True, intercept_scaling=1: the kernel is K + 1).  Class c:
+ *         t_i = +1 if slabel[k_i] == c, else -1;  q_ij = K_ij + 1;  Q_ij = t_i t_j q_ij;
+ *         loss 0 (squared hinge): D = 1 / (2 C), no upper bound (Ub = +inf);   loss 1 (hinge): D = 0, Ub = C;
+ *         Qd_i = q_ii + D  (>= 1: no division needs a guard, there is no degenerate branch);
+ *     dual coordinate descent (Hsieh et al. 2008) in fixed cyclic order, no shuffling, no shrinking of the active set:
+ *         alpha = 0, g_i = -1;  sweeps e = 1 .. max_iter, each visiting i = 0 .. n - 1:
+ *             G = g_i;  PG = min(G, 0) if alpha_i == 0, max(G, 0) if alpha_i == Ub, else G;
+ *             if PG != 0:  a = min(max(alpha_i - G / Qd_i, 0), Ub);  delta = a - alpha_i;  alpha_i = a;
+ *                 for every j:  g_j = g_j + (t_i t_j) (delta q_ji);   at j = i additionally, as a second addition, g_i = g_i + delta D;
+ *         after a sweep: stop if the sweep's max |PG| <= tol;
+ *     score[s][c][u] = (a = 0; a = a + (alpha_j t_j) (K_sj + 1), j in list order);  prediction = the first maximal class;
+ *     correct[sgroup[s]][slabel[s]][u] += 1 where the prediction is slabel[s] (int32 atomics).
+ *   Two classes: the two problems are mirror images (the same Q, the same alpha), f_1 = -f_0 exactly; class 0 is solved and negated.
+ *   At convergence this is scikit-learn's LinearSVC(loss=, C=, dual=True, fit_intercept=True, intercept_scaling=1, multi_class='ovr')
+ *   on the row's columns centred by the training means.
+ *   sweeps int32 [NM][U] (or NULL): the most sweeps any class of that (model, centre) ran;  residual float64 [NM][U] (or NULL): the
+ *   largest last-sweep max |PG| over the classes.  correct is ADDED to.  Guards: every pointer range is clamped, a centre outside
+ *   [0, U) or a model outside [0, NM) is skipped, a sample number outside [0, S) is a row of zeros of the centred patterns and is
+ *   not counted in n, group and label numbers outside their ranges add nothing.  Every value is a function of (model, centre,
+ *   lists) alone: bit-identical under any cut of the centres or models into launches and any order of them.  No float atomics.
+ *   chebgcn_last_dispatch(): searchlight_svm_kernel<bucket>.
+ * searchlight_svm_query: 0 threads of a workgroup, 1 the largest training set (128), 2 vertices of a tile, 3 the largest C, 4 test
+ *   samples of a chunk, 5 models at most, 6 tiles of a model's test samples at most, 7 groups at most, 8 the largest max_iter,
+ *   9 vertices of a super-tile (the means of so many vertices are formed at once), 100 + n the bucket of a training set of n
+ *   samples (1 <= n <= 128); -1 for anything else.
+ * Limits: 2 <= C <= 32 classes, NM and NMb <= 65535, G <= 2^20, tmax <= 65535 * 64, bucket in {32, 64, 128}: CHEBGCN_EUNSUPPORTED
+ * beyond, before any launch, as every CHEBGCN_EINVAL (NULL, counts <= 0, C or tol not finite, C <= 0, tol < 0, a loss other than
+ * 0 or 1, max_iter outside [1, 100000], pointers not aligned to their element).  The call neither synchronises nor allocates. */
+int chebgcn_searchlight_svm_query(int what);
+int chebgcn_searchlight_svm(const float* Xt, int S, int M, const int32_t* rowptr, const int32_t* colidx, int nnz, int U,
+                            const int32_t* centres, int Ub, const int32_t* models, int NMb, int bucket, const int32_t* list_ptr,
+                            const int32_t* list_idx, int nidx, const int32_t* test_ptr, int tmax, int NM, int C, double Creg, int loss,
+                            double tol, int max_iter, const int32_t* sgroup, const int32_t* slabel, const int32_t* sorig, int G,
+                            int32_t* correct, double* scores, uint8_t* predictions, int32_t* sweeps, double* residual,
+                            chebgcn_stream stream);
+
 /* ---- vertex order for the ordered recurrence kernels (host only) ----
  * The reference leaves the numbering of a graph's vertices to its caller (the coarsening's tree order, coarsening.py:168-215);
  * the network is invariant under a relabelling as long as everything per-vertex follows (cgcnn.vertex_order).  A graph whose

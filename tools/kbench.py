@@ -8,6 +8,7 @@
     python tools/kbench.py searchlight [--iters 20] [--json out.json]       # the searchlight kernels alone
     python tools/kbench.py searchlight_lda [--iters 10] [--json out.json]   # the LDA searchlight kernel alone
     python tools/kbench.py searchlight_rdm [--iters 10] [--json out.json]   # the RSA searchlight kernel alone
+    python tools/kbench.py searchlight_svc [--iters 3] [--json out.json]    # the SVM searchlight kernel alone
 
 Times each C-ABI entry point with HIP events on the launch stream and prints achieved
 algorithmic GB/s (SURVEY.md 8d byte counts) and the fraction of the 8 TB/s HBM roofline.
@@ -436,11 +437,91 @@ def searchlight_rdm_leg(args):
             json.dump(results, f, indent=1)
 
 
+def searchlight_svc_leg(args):
+    """chebgcn_searchlight_svm at the shape of the other searchlight legs (the synthetic 10k-vertex kNN graph, M = 10466, 2-hop
+    balls, 2048 samples, 8 classes) but WITHIN 16 subjects of 128 samples and 2 folds each, so that a training set holds 64
+    samples: 32 models, one workgroup per (centre, model); and one parcel-sized leg: 360 rows of 300 vertices.  z-scored
+    patterns, C = 1, squared hinge, tol = 1e-3, at most 100 sweeps.  Two floors per leg.  The Gram matrix costs P n (n + 1) / 2
+    multiplies and as many adds per (model, centre) -- nothing is fused -- at the float64 vector issue rate (39.3e12 lane
+    instructions a second).  The solve is a chain: a coordinate step cannot begin before the last one's g is known, and costs at
+    least a float64 division (about ten dependent instructions), two multiplies, an add, two readlanes and an LDS read, about
+    120 cycles = 50 ns at 2.4 GHz; a (model, centre) runs ceil(C / 4) rounds of classes of (sweeps x n) steps each, and a CU
+    overlaps as many workgroups as the kernel's occupancy admits."""
+    import scipy.sparse as sp
+    import torch
+    from gcn_fmri_decoding_amd import _lib, graph, ops, searchlight as sl
+    dev = torch.device('cuda:0')
+    ISSUE64, STEP_S, CUS = 78.6e12 / 2, 50e-9, 256
+    OCC = {32: 4, 64: 2, 128: 1}                                # workgroups per CU: the compiler's report (DESIGN 4.26)
+    results = []
+    S, C, G, F, CAP = 2048, 8, 16, 2, 100
+    L = graph.synthetic_graph(10000, k=8, levels=1)[0][0]
+    M = int(L.shape[0])
+    rs = np.random.RandomState(0)
+    y = np.arange(S) % C
+    fold = np.arange(S) // C % F
+    groups = (np.arange(S) // (C * F) % G).tolist()
+    X = (rs.randn(S, M) + 0.5 * rs.randn(C, M)[y]).astype(np.float32)
+    parcels = np.zeros((360, M), np.int8)
+    for r in range(360):
+        parcels[r, rs.choice(M, 300, replace=False)] = 1
+    up = lambda v: torch.as_tensor(v).to(dev)
+    for tag, rows in (('balls', graph.hop_balls(L, 2)), ('parcels', sp.csr_matrix(parcels))):
+        a = sl._check(X, y, rows, fold, groups, True, None, 'class', 'empirical', 1e-9, False, False, None, 'kbench', classifier='svc',
+                      max_iter=CAP)
+        plan = sl._device_plan(a, ops.searchlight_geometry()['buckets'][C])
+        Xt = sl._transposed(up(X), plan.order, dev)
+        n = np.diff(plan.list_ptr)
+        bucket = int(ops.searchlight_svm_geometry()['buckets'][int(n.max())])
+        assert len(set(n.tolist())) == 1
+        correct = torch.zeros((G, C, a.U), dtype=torch.int32, device=dev)
+        sweeps = torch.zeros((plan.NM, a.U), dtype=torch.int32, device=dev)
+        resid = torch.zeros((plan.NM, a.U), dtype=torch.float64, device=dev)
+        rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
+        tabs = [up(v) for v in (plan.list_ptr, plan.list_idx, plan.test_ptr, plan.sgroup, plan.slabel, plan.order.astype(np.int32))]
+        centres, models = up(np.arange(a.U, dtype=np.int32)), up(np.arange(plan.NM, dtype=np.int32))
+
+        def run():
+            ops.searchlight_svm(Xt, S, rowptr, colidx, centres, models, bucket, tabs[0], tabs[1], tabs[2], plan.tmax, C, 1.0, 'squared_hinge',
+                                1e-3, CAP, tabs[3], tabs[4], tabs[5], correct, sweeps=sweeps, residual=resid)
+        run()
+        torch.cuda.synchronize()
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.iters)]
+        for s, e in evs:
+            s.record()
+            run()
+            e.record()
+        torch.cuda.synchronize()
+        ms = sorted(s.elapsed_time(e) for s, e in evs)
+        med, lo, hi = ms[len(ms) // 2], ms[0], ms[-1]
+        P = np.diff(a.indptr).astype(np.float64)
+        nn = float(n[0])
+        gram_ops = 2.0 * P.sum() * plan.NM * (nn * (nn + 1) / 2 + 64.0 * nn)     # the triangle and the test samples' rows (64 a model)
+        sw = sweeps.cpu().numpy().astype(np.float64)
+        steps = float((-(-C // 4)) * sw.sum() * nn)
+        chain_ms = 1e3 * steps * STEP_S / (CUS * OCC[bucket])
+        gram_ms = 1e3 * gram_ops / ISSUE64
+        conv = float((resid.cpu().numpy() <= 1e-3).mean())
+        acc = float(correct.sum()) / S / a.U / (1 + args.iters)
+        results.append({'leg': 'searchlight_svc ' + tag, 'shape': 'S=%d M=%d C=%d groups=%d folds=%d n=%d nnz=%d cap=%d' % (
+            S, M, C, G, F, int(nn), int(rows.nnz), CAP), 'centres': int(a.U), 'models': int(plan.NM), 'median_ms': med, 'min_ms': lo,
+            'max_ms': hi, 'mean_vertices': float(P.mean()), 'mean_sweeps': float(sw.mean()), 'max_sweeps': float(sw.max()),
+            'converged': conv, 'gram_floor_ms': gram_ms, 'chain_floor_ms': chain_ms, 'accuracy': acc, 'dispatch': _lib.last_dispatch()})
+        print('searchlight_svc %-8s %6d rows of %.1f vertices x %d models of n = %d: %10.3f ms (min %9.3f, max %9.3f); sweeps mean %.1f max %d, '
+              '%.4f converged; Gram floor %.3f ms, chain floor %.3f ms (%.1fx their sum); accuracy %.3f; %s'
+              % (tag, a.U, P.mean(), plan.NM, int(nn), med, lo, hi, sw.mean(), int(sw.max()), conv, gram_ms, chain_ms,
+                 med / (gram_ms + chain_ms), acc, _lib.last_dispatch()), flush=True)
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(results, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('leg', nargs='?', choices=['glm', 'searchlight', 'searchlight_lda', 'searchlight_rdm'],
+    ap.add_argument('leg', nargs='?', choices=['glm', 'searchlight', 'searchlight_lda', 'searchlight_rdm', 'searchlight_svc'],
                     help='glm: the first-level GLM kernels alone (ops.glm_project / glm_finish); searchlight: the searchlight kernels alone; '
-                         'searchlight_lda: the LDA searchlight kernel alone; searchlight_rdm: the RSA searchlight kernel alone')
+                         'searchlight_lda: the LDA searchlight kernel alone; searchlight_rdm: the RSA searchlight kernel alone; '
+                         'searchlight_svc: the SVM searchlight kernel alone')
     ap.add_argument('--parcellate', action='store_true', help='the parcellation leg alone (ops.parcellate at HCP size)')
     ap.add_argument('--B', type=int, nargs='+', default=[64, 256])
     ap.add_argument('--fin', type=int, default=32)
@@ -472,6 +553,8 @@ def main():
         return searchlight_lda_leg(args)
     if args.leg == 'searchlight_rdm':
         return searchlight_rdm_leg(args)
+    if args.leg == 'searchlight_svc':
+        return searchlight_svc_leg(args)
 
     import torch
     import bench
