@@ -23,14 +23,12 @@
 //                       operands; two samples per lane halve the scalar bytes per term.  Per (neighbour, class):
 //                       t = x - mu; acc = fma(t h, t, acc) -- one subtraction, one multiply, one fma, nothing that depends on tile,
 //                       wave or batch.  Two (wide buckets: four) neighbours' loads are issued before the arithmetic of the
-//                       first.  Then score = base - acc, the first maximal class, and correct[group][label][centre] += 1 with
-//                       int32 atomics, one per distinct (group, label) of the wave.
+//                       first.  Then score = base - acc, the first maximal class, and sl_tally (searchlight_common.h):
+//                       correct[group][label][centre] += 1 with int32 atomics, one per distinct (group, label) of the wave.
 // No float atomics anywhere.  Nothing read from memory is an address or a trip count unchecked: list and row pointers are clamped
 // into their arrays, sample and vertex numbers outside [0, S) / [0, M) are skipped, group and label numbers outside their ranges
 // add nothing.
-#include <limits.h>
-
-#include "common.h"
+#include "searchlight_common.h"
 
 namespace chebgcn {
 
@@ -51,16 +49,10 @@ constexpr int SL_U2 = CG_SL_U2;             //  flight, 0.95 with two and four, 
 constexpr int SL_U = CG_SL_U;               // neighbours of a wave in flight, wide buckets
 constexpr int sl_v(int NC) { return NC <= SL_NARROW ? SL_V2 : 1; }
 constexpr int sl_u(int NC) { return NC <= SL_NARROW ? SL_U2 : SL_U; }
-constexpr int SL_CMAX = 32;                 // classes
 constexpr int SL_T = 256;                   // threads of spread / fit / base
-constexpr int SL_NMAX = 65535;              // models of one call (grid.z; grid.y of spread / fit / base)
-constexpr int SL_TILES = 65535;             // 64-sample tiles of a model's test samples (grid.y of score)
-constexpr int SL_GMAX = 1 << 20;            // groups
 
 // the class bucket of C classes: the width of the parameter tables and the accumulators of the score kernel
 static inline int sl_bucket(int C) { return C <= 2 ? 2 : C <= 4 ? 4 : C <= 8 ? 8 : C <= 16 ? 16 : 32; }
-
-__device__ __forceinline__ int sl_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // Two-pass moments of row[list[i]], i ascending: cnt entries inside [0, S), their mean, and the sum of squared deviations from it
 __device__ __forceinline__ void sl_moments(const float* __restrict__ row, const int32_t* __restrict__ list, int n, int S, int& cnt,
@@ -254,17 +246,8 @@ searchlight_score_kernel(SlScore p) {
             }
             if (p.predictions) p.predictions[so * p.U + u] = (uint8_t)pred;
         }
-        // one atomic per distinct (group, label) of the wave's hits
         const int g = p.sgroup[s[k]], y = p.slabel[s[k]];
-        const int key = live[k] && pred == y && (unsigned)g < (unsigned)p.G ? g * p.C + y : -1;
-        unsigned long long left = __ballot(key >= 0);
-        while (left) {
-            const int leader = __builtin_ctzll(left);
-            const int kk = __builtin_amdgcn_readlane(key, leader);
-            const unsigned long long same = __ballot(key == kk);
-            if (lane == leader) atomicAdd(p.correct + (size_t)kk * p.U + u, (int)__popcll(same));
-            left &= ~same;
-        }
+        sl_tally(p.correct, live[k] && pred == y && (unsigned)g < (unsigned)p.G ? g * p.C + y : -1, p.U, u, lane);
     }
 }
 

@@ -13,10 +13,9 @@
 // said at the function.  Nothing read from memory is an address or a trip count unchecked: the callers clamp the lists.
 #pragma once
 #include <float.h>
-#include <limits.h>
 #include <math.h>
 
-#include "common.h"
+#include "searchlight_common.h"
 
 namespace chebgcn {
 
@@ -26,14 +25,10 @@ constexpr int LDA_TS = 32;                  // training samples of a residual ti
 constexpr int LDA_NB = 16;                  // blocks along a side of the triangle
 constexpr int LDA_BLOCKS = LDA_NB * (LDA_NB + 1) / 2;       // 136 covariance threads: waves 0 .. 2
 constexpr int LDA_QW = 3;                   // the wave of the squared norms
-constexpr int LDA_CMAX = 32;
-constexpr int LDA_NARROW = 8;               // class tables in LDS are this wide up to this many classes, LDA_CMAX beyond
-constexpr int LDA_NMAX = 65535;             // models of one call (grid.y)
+constexpr int LDA_NARROW = 8;               // class tables in LDS are this wide up to this many classes, SL_CMAX beyond
 constexpr double LDA_SHRINK_MIN = CHEBGCN_LDA_SHRINK_MIN;
 
 static inline int lda_bucket(int P) { return P < 1 || P > LDA_PMAX ? -1 : P <= 32 ? 32 : P <= 64 ? 64 : 128; }
-
-__device__ __forceinline__ int lda_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // The block (bi >= bj) of the triangle that thread tid owns: blocks are numbered row by row.
 __device__ __forceinline__ void ball_block(int tid, int& bi, int& bj) {

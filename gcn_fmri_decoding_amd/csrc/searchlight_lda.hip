@@ -29,8 +29,8 @@
 //      b_c = logprior_c - 0.5 (acc = 0; acc = fma(d_cv, w_cv, acc), v ascending).
 //      tr not > 0, n = 0 or a pivot not > 0 and finite:  w = 0, b = logprior -- the prior decides, nothing is NaN.
 //   6. The model's test samples, 256 per pass, a lane a sample: a_c = 0; t = (double)x - m_v; a_c = fma(w_cv, t, a_c), v ascending;
-//      score_c = b_c + a_c; the first maximal class; counts as in searchlight_score_kernel (ballot, one int32 atomic per distinct
-//      (group, label) of a wave).
+//      score_c = b_c + a_c; the first maximal class; the counts by sl_tally of searchlight_common.h (ballot, one int32 atomic per
+//      distinct (group, label) of a wave).
 // Every value is a function of (model, centre, the lists) alone: no float atomics, no order that depends on the launch.
 // Compiler report (VGPRs, its occupancy in waves per SIMD = workgroups per CU, LDS bytes; no scratch anywhere): <32, 8> 108, 4,
 // 15 816; <32, 32> 185, 2, 22 440; <64, 8> 92, 4, 39 112; <64, 32> 185, 2, 51 880; <128, 8> 219, 1, 110 280; <128, 32> 221, 1,
@@ -39,13 +39,12 @@
 // outside [0, U) end the workgroup, sample numbers outside [0, S) are rows of zeros, a vertex outside [0, M) is a column of zeros
 // (its w is 0), group and label numbers outside their ranges add nothing.
 // Stages 2 to 4 and the forward solve of stage 5 are stated in searchlight_ball.h, which searchlight_rdm.hip shares.
+#include "searchlight_common.h"
 #include "searchlight_ball.h"
 
 namespace chebgcn {
 
 constexpr int LDA_SU = 16;                  // vertices of a scoring lane in flight (the loop is bound by the latency of Xt)
-constexpr int LDA_TILES = 65535;            // 64-sample tiles of a model's test samples, as searchlight_score
-constexpr int LDA_GMAX = 1 << 20;
 
 struct SlLda {
     const float* Xt;            // [M][Sp]
@@ -93,7 +92,7 @@ searchlight_lda_kernel(SlLda p) {
     const int m = blockIdx.y;
     const int u = p.centres[blockIdx.x];
     if ((unsigned)u >= (unsigned)p.U) return;
-    const int r0 = lda_clamp(p.rowptr[u], 0, p.nnz), r1 = lda_clamp(p.rowptr[u + 1], r0, p.nnz);
+    const int r0 = sl_clamp(p.rowptr[u], 0, p.nnz), r1 = sl_clamp(p.rowptr[u + 1], r0, p.nnz);
     const int P = r1 - r0;
     if (P < 1 || P > PB) return;
     const int C = p.C;                                          // 2 <= C <= NCB: the entry point's check
@@ -105,9 +104,9 @@ searchlight_lda_kernel(SlLda p) {
     }
     if (tid < NCB) {
         ncnt[tid] = 0;
-        const int i0 = tid < C ? lda_clamp(p.cptr[m * C + tid], 0, p.nidx) : 0;
+        const int i0 = tid < C ? sl_clamp(p.cptr[m * C + tid], 0, p.nidx) : 0;
         ci0[tid] = i0;
-        ci1[tid] = tid < C ? lda_clamp(p.cptr[m * C + tid + 1], i0, p.nidx) : 0;
+        ci1[tid] = tid < C ? sl_clamp(p.cptr[m * C + tid + 1], i0, p.nidx) : 0;
     }
     if (tid == 0) degen = 0;
     __syncthreads();
@@ -185,8 +184,8 @@ searchlight_lda_kernel(SlLda p) {
     __syncthreads();
 
     // ---- 6. the test samples ----
-    const int s0 = lda_clamp(p.tptr[m], 0, p.S);
-    int t1 = lda_clamp(p.tptr[m + 1], s0, p.S);
+    const int s0 = sl_clamp(p.tptr[m], 0, p.S);
+    int t1 = sl_clamp(p.tptr[m + 1], s0, p.S);
     if (t1 - s0 > p.tmax) t1 = s0 + p.tmax;
     for (int sb = s0; sb < t1; sb += LDA_T) {
         const bool live = t1 - sb > tid;
@@ -221,7 +220,7 @@ searchlight_lda_kernel(SlLda p) {
             }
         }
         if (live) {
-            const size_t so = (size_t)lda_clamp(p.sorig[s], 0, p.S - 1);
+            const size_t so = (size_t)sl_clamp(p.sorig[s], 0, p.S - 1);
             if (p.scores) {
 #pragma unroll
                 for (int c = 0; c < NCB; ++c)
@@ -229,17 +228,8 @@ searchlight_lda_kernel(SlLda p) {
             }
             if (p.predictions) p.predictions[so * p.U + u] = (uint8_t)pred;
         }
-        // one atomic per distinct (group, label) of the wave's hits
         const int gr = p.sgroup[s], y = p.slabel[s];
-        const int key = live && pred == y && (unsigned)gr < (unsigned)p.G ? gr * C + y : -1;
-        unsigned long long left = __ballot(key >= 0);
-        while (left) {
-            const int leader = __builtin_ctzll(left);
-            const int kk = __builtin_amdgcn_readlane(key, leader);
-            const unsigned long long same = __ballot(key == kk);
-            if (lane == leader) atomicAdd(p.correct + (size_t)kk * p.U + u, (int)__popcll(same));
-            left &= ~same;
-        }
+        sl_tally(p.correct, live && pred == y && (unsigned)gr < (unsigned)p.G ? gr * C + y : -1, p.U, u, lane);
     }
 }
 
@@ -253,7 +243,7 @@ static void lda_launch(const SlLda& p, int Ub, int NM, hipStream_t stream) {
     if (p.C <= LDA_NARROW)
         hipLaunchKernelGGL((searchlight_lda_kernel<PB, LDA_NARROW>), grid, dim3(LDA_T), 0, stream, p);
     else
-        hipLaunchKernelGGL((searchlight_lda_kernel<PB, LDA_CMAX>), grid, dim3(LDA_T), 0, stream, p);
+        hipLaunchKernelGGL((searchlight_lda_kernel<PB, SL_CMAX>), grid, dim3(LDA_T), 0, stream, p);
 }
 
 }  // namespace chebgcn
@@ -265,11 +255,11 @@ extern "C" int chebgcn_searchlight_lda_query(int what) {
         case 0: return LDA_T;               // threads of a workgroup: test samples of one scoring pass
         case 1: return LDA_PMAX;            // the longest row
         case 2: return LDA_TS;              // training samples of a residual tile
-        case 3: return LDA_CMAX;            // the largest number of classes
+        case 3: return SL_CMAX;            // the largest number of classes
         case 4: return LDA_NB;              // blocks along a side of the covariance triangle: a thread owns (bucket / this)^2 elements
-        case 5: return LDA_NMAX;            // models of one call
-        case 6: return LDA_TILES;           // 64-sample tiles of a model's test samples
-        case 7: return LDA_GMAX;            // groups
+        case 5: return SL_NMAX;            // models of one call
+        case 6: return SL_TILES;           // 64-sample tiles of a model's test samples
+        case 7: return SL_GMAX;            // groups
         case 8: return LDA_NARROW;          // up to this many classes the class tables in LDS are this wide, query 3 beyond
         default:
             if (what > 100 && what <= 100 + LDA_PMAX) return lda_bucket(what - 100);       // the ball bucket of a row of what - 100
@@ -292,9 +282,9 @@ extern "C" int chebgcn_searchlight_lda(const float* Xt, int S, int M, const int3
     CG_REQUIRE(shrinkage < 0.0 || (shrinkage >= LDA_SHRINK_MIN && shrinkage <= 1.0),
                "searchlight_lda: shrinkage = %g; served: [%g, 1], or negative for Ledoit-Wolf", shrinkage, LDA_SHRINK_MIN);
     const long long tiles = ((long long)tmax + 63) / 64;
-    if (NM > LDA_NMAX || C > LDA_CMAX || G > LDA_GMAX || tiles > LDA_TILES || (bucket != 32 && bucket != 64 && bucket != 128))
+    if (NM > SL_NMAX || C > SL_CMAX || G > SL_GMAX || tiles > SL_TILES || (bucket != 32 && bucket != 64 && bucket != 128))
         return fail(CHEBGCN_EUNSUPPORTED, "searchlight_lda: NM = %d, C = %d, G = %d, tmax = %d, bucket = %d; served: NM <= %d, C <= %d, "
-                    "G <= %d, tmax <= %d, bucket 32, 64 or 128", NM, C, G, tmax, bucket, LDA_NMAX, LDA_CMAX, LDA_GMAX, LDA_TILES * 64);
+                    "G <= %d, tmax <= %d, bucket 32, 64 or 128", NM, C, G, tmax, bucket, SL_NMAX, SL_CMAX, SL_GMAX, SL_TILES * 64);
     CG_REQUIRE((((uintptr_t)Xt | (uintptr_t)rowptr | (uintptr_t)colidx | (uintptr_t)centres | (uintptr_t)class_ptr | (uintptr_t)class_idx |
                  (uintptr_t)test_ptr | (uintptr_t)sgroup | (uintptr_t)slabel | (uintptr_t)sorig | (uintptr_t)correct) & 3) == 0 &&
                    (((uintptr_t)par | (uintptr_t)logprior | (uintptr_t)scores | (uintptr_t)gamma_out) & 7) == 0,

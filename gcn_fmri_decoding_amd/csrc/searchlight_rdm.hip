@@ -24,11 +24,12 @@
 // Compiler report (VGPRs, its occupancy in waves per SIMD = workgroups per CU, LDS bytes; no scratch anywhere): DESIGN 4.25.
 // Nothing read from memory is an address or a trip count unchecked: row, cell and list pointers are clamped, centre numbers
 // outside [0, U) end the workgroup, sample numbers outside [0, S) are rows of zeros, a vertex outside [0, M) is a column of zeros.
+#include "searchlight_common.h"
 #include "searchlight_ball.h"
 
 namespace chebgcn {
 
-constexpr int RDM_PAIRS = LDA_CMAX * (LDA_CMAX - 1) / 2;        // 496: at most two pairs per thread
+constexpr int RDM_PAIRS = SL_CMAX * (SL_CMAX - 1) / 2;        // 496: at most two pairs per thread
 static_assert(RDM_PAIRS <= 2 * LDA_T, "two pairs per thread");
 
 struct SlRdm {
@@ -69,10 +70,10 @@ searchlight_rdm_kernel(SlRdm p) {
     const int grp = blockIdx.y;
     const int u = p.centres[blockIdx.x];
     if ((unsigned)u >= (unsigned)p.U) return;
-    const int r0 = lda_clamp(p.rowptr[u], 0, p.nnz), r1 = lda_clamp(p.rowptr[u + 1], r0, p.nnz);
+    const int r0 = sl_clamp(p.rowptr[u], 0, p.nnz), r1 = sl_clamp(p.rowptr[u + 1], r0, p.nnz);
     const int P = r1 - r0;
     if (P < 1 || P > PB) return;
-    const int k0 = lda_clamp(p.cell_ptr[grp], 0, p.NM), k1 = lda_clamp(p.cell_ptr[grp + 1], k0, p.NM);
+    const int k0 = sl_clamp(p.cell_ptr[grp], 0, p.NM), k1 = sl_clamp(p.cell_ptr[grp + 1], k0, p.NM);
     const int F = k1 - k0;
     if (F < 2) return;
     const int C = p.C;                                          // 2 <= C <= NCB: the entry point's check
@@ -99,9 +100,9 @@ searchlight_rdm_kernel(SlRdm p) {
     for (int k = k0; k < k1; ++k) {
         if (tid < NCB) {
             ncnt[tid] = 0;
-            const int i0 = tid < C ? lda_clamp(p.cptr[k * C + tid], 0, p.nidx) : 0;
+            const int i0 = tid < C ? sl_clamp(p.cptr[k * C + tid], 0, p.nidx) : 0;
             ci0[tid] = i0;
-            ci1[tid] = tid < C ? lda_clamp(p.cptr[k * C + tid + 1], i0, p.nidx) : 0;
+            ci1[tid] = tid < C ? sl_clamp(p.cptr[k * C + tid + 1], i0, p.nidx) : 0;
         }
         __syncthreads();
         for (int c = tid >> 6; c < C; c += LDA_T / 64) {        // a wave a class
@@ -196,7 +197,7 @@ static void rdm_launch(const SlRdm& p, int Ub, hipStream_t stream) {
     if (p.C <= LDA_NARROW)
         hipLaunchKernelGGL((searchlight_rdm_kernel<PB, LDA_NARROW>), grid, dim3(LDA_T), 0, stream, p);
     else
-        hipLaunchKernelGGL((searchlight_rdm_kernel<PB, LDA_CMAX>), grid, dim3(LDA_T), 0, stream, p);
+        hipLaunchKernelGGL((searchlight_rdm_kernel<PB, SL_CMAX>), grid, dim3(LDA_T), 0, stream, p);
 }
 
 }  // namespace chebgcn
@@ -208,9 +209,9 @@ extern "C" int chebgcn_searchlight_rdm_query(int what) {
         case 0: return LDA_T;               // threads of a workgroup
         case 1: return LDA_PMAX;            // the longest row
         case 2: return LDA_TS;              // samples of a residual tile
-        case 3: return LDA_CMAX;            // the largest number of classes
+        case 3: return SL_CMAX;            // the largest number of classes
         case 4: return RDM_PAIRS;           // the most pairs of classes: two per thread beyond query 0
-        case 5: return LDA_NMAX;            // cells of one call
+        case 5: return SL_NMAX;            // cells of one call
         case 6: return LDA_NARROW;          // up to this many classes the class tables in LDS are this wide, query 3 beyond
         default:
             if (what > 100 && what <= 100 + LDA_PMAX) return lda_bucket(what - 100);       // the ball bucket of a row of what - 100
@@ -229,9 +230,9 @@ extern "C" int chebgcn_searchlight_rdm(const float* Xt, int S, int M, const int3
                "bucket = %d)", S, M, nnz, U, Ub, nidx, NM, C, G, bucket);
     CG_REQUIRE(shrinkage < 0.0 || (shrinkage >= LDA_SHRINK_MIN && shrinkage <= 1.0),
                "searchlight_rdm: shrinkage = %g; served: [%g, 1], or negative for Ledoit-Wolf", shrinkage, LDA_SHRINK_MIN);
-    if (NM > LDA_NMAX || C > LDA_CMAX || (bucket != 32 && bucket != 64 && bucket != 128))
+    if (NM > SL_NMAX || C > SL_CMAX || (bucket != 32 && bucket != 64 && bucket != 128))
         return fail(CHEBGCN_EUNSUPPORTED, "searchlight_rdm: NM = %d, C = %d, bucket = %d; served: NM <= %d, C <= %d, bucket 32, 64 or 128",
-                    NM, C, bucket, LDA_NMAX, LDA_CMAX);
+                    NM, C, bucket, SL_NMAX, SL_CMAX);
     CG_REQUIRE(NM / 2 >= G, "searchlight_rdm: %d cells for %d groups: a group with fewer than 2 cells has no distance", NM, G);
     CG_REQUIRE((((uintptr_t)Xt | (uintptr_t)rowptr | (uintptr_t)colidx | (uintptr_t)centres | (uintptr_t)cell_ptr | (uintptr_t)class_ptr |
                  (uintptr_t)class_idx) & 3) == 0 && (((uintptr_t)par | (uintptr_t)rdm | (uintptr_t)gamma_out) & 7) == 0,

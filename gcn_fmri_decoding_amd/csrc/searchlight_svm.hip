@@ -28,14 +28,15 @@
 //      max |PG| is a max: order-free.  No barrier inside the solve.
 //   3. Scoring.  The model's test samples, 32 a chunk: K_sj of the chunk by streaming the row again in the same order (thread
 //      (4 test samples, NB / 32 training samples) in registers), then thread (test sample, class):
-//      f = (a = 0; a = a + (alpha_j t_j) (K_sj + 1), j in list order), the first maximal class, and the counts as in
-//      searchlight_score_kernel (ballot, one int32 atomic per distinct (group, label)).
+//      f = (a = 0; a = a + (alpha_j t_j) (K_sj + 1), j in list order), the first maximal class, and the counts by sl_tally of
+//      searchlight_common.h (ballot, one int32 atomic per distinct (group, label)).
 // Every value is a function of (model, centre, the lists) alone: no float atomics, no order that depends on the launch.
 // Compiler report and what bounds the kernel (the instructions of a coordinate step, not their latency): DESIGN 4.26.
 // Nothing read from memory is an address or a trip count unchecked: row, list and test pointers are clamped, centre and model
 // numbers outside their ranges end the workgroup, a sample number outside [0, S) is a row of zeros of the centred patterns and is
 // not counted in n, a vertex outside [0, M) is a column of zeros, group and label numbers outside their ranges add nothing.
 #pragma clang fp contract(off)
+#include "searchlight_common.h"
 #include "searchlight_ball.h"
 
 namespace chebgcn {
@@ -45,10 +46,6 @@ constexpr int SVM_NMAX = 128;               // the largest training set
 constexpr int SVM_TV = 16;                  // vertices of a tile
 constexpr int SVM_TC = 32;                  // test samples of a chunk
 constexpr int SVM_SUP = SVM_T;              // vertices of a super-tile: one mean per thread
-constexpr int SVM_CMAX = 32;
-constexpr int SVM_MODELS = 65535;           // models of one call (grid.y)
-constexpr int SVM_TILES = 65535;            // 64-sample tiles of a model's test samples, as searchlight_score
-constexpr int SVM_GMAX = 1 << 20;
 constexpr int SVM_ITMAX = 100000;           // sweeps at most
 constexpr int SVM_NBLK = LDA_NB;            // blocks along a side of the Gram triangle
 constexpr int SVM_BLOCKS = SVM_NBLK * (SVM_NBLK + 1) / 2;
@@ -221,19 +218,19 @@ template <int NB>
 __global__ void __launch_bounds__(SVM_T)
 searchlight_svm_kernel(SlSvm p) {
     constexpr int TB = NB / SVM_NBLK, JW = NB / 32, NJ = NB > 64 ? NB / 64 : 1, LDK = NB + 1;
-    static_assert(SVM_TV * (NB + SVM_TC) >= SVM_TC * SVM_CMAX, "the stage holds the chunk's scores");
+    static_assert(SVM_TV * (NB + SVM_TC) >= SVM_TC * SL_CMAX, "the stage holds the chunk's scores");
     static_assert(SVM_BLOCKS <= SVM_T && NB <= SVM_T && SVM_T / 64 == 4, "thread maps");
     __shared__ double Ksh[NB * (NB + 1) / 2];                   // K: element (i >= j) at i (i + 1) / 2 + j
     __shared__ double stage[SVM_TV * (NB + SVM_TC)];            // [q][j] training, then [q][s] test; afterwards scores [c][s]
     __shared__ double Kte[SVM_TC * LDK];                        // [s][j] of the chunk
-    __shared__ double ash[SVM_CMAX * NB];                       // [c][j]: alpha_j t_j
+    __shared__ double ash[SL_CMAX * NB];                       // [c][j]: alpha_j t_j
     __shared__ double msh[SVM_SUP];
     __shared__ double qd[NB];
-    __shared__ double rssh[SVM_CMAX];
+    __shared__ double rssh[SL_CMAX];
     __shared__ int vsh[SVM_SUP];
     __shared__ int lsh[NB];                                     // the training samples, -1: outside [0, S)
     __shared__ int ysh[NB];                                     // their labels
-    __shared__ int swsh[SVM_CMAX];
+    __shared__ int swsh[SL_CMAX];
     __shared__ int nvsh;
     double* const tile = stage;
     double* const ttile = stage + SVM_TV * NB;
@@ -243,9 +240,9 @@ searchlight_svm_kernel(SlSvm p) {
     const int u = p.centres[blockIdx.x];
     const int m = p.models[blockIdx.y];
     if ((unsigned)u >= (unsigned)p.U || (unsigned)m >= (unsigned)p.NM) return;
-    const int r0 = lda_clamp(p.rowptr[u], 0, p.nnz), r1 = lda_clamp(p.rowptr[u + 1], r0, p.nnz);
+    const int r0 = sl_clamp(p.rowptr[u], 0, p.nnz), r1 = sl_clamp(p.rowptr[u + 1], r0, p.nnz);
     const int P = r1 - r0;
-    const int l0 = lda_clamp(p.lptr[m], 0, p.nidx), l1 = lda_clamp(p.lptr[m + 1], l0, p.nidx);
+    const int l0 = sl_clamp(p.lptr[m], 0, p.nidx), l1 = sl_clamp(p.lptr[m + 1], l0, p.nidx);
     const int nl = l1 - l0;
     if (P < 1 || nl < 1 || nl > NB) return;
     const int C = p.C;                                          // 2 <= C <= 32: the entry point's check
@@ -376,8 +373,8 @@ searchlight_svm_kernel(SlSvm p) {
     }
 
     // ---- 3. the test samples, a chunk at a time ----
-    const int s0 = lda_clamp(p.tptr[m], 0, p.S);
-    int t1 = lda_clamp(p.tptr[m + 1], s0, p.S);
+    const int s0 = sl_clamp(p.tptr[m], 0, p.S);
+    int t1 = sl_clamp(p.tptr[m + 1], s0, p.S);
     if (t1 - s0 > p.tmax) t1 = s0 + p.tmax;
     for (int sb = s0; sb < t1; sb += SVM_TC) {
         const int ns = min(SVM_TC, t1 - sb);
@@ -419,22 +416,13 @@ searchlight_svm_kernel(SlSvm p) {
                         pred = c;
                     }
                 }
-                const size_t so = (size_t)lda_clamp(p.sorig[s], 0, p.S - 1);
+                const size_t so = (size_t)sl_clamp(p.sorig[s], 0, p.S - 1);
                 if (p.scores)
                     for (int c = 0; c < C; ++c) p.scores[(so * C + c) * p.U + u] = scsh[c * SVM_TC + tid];
                 if (p.predictions) p.predictions[so * p.U + u] = (uint8_t)pred;
             }
-            // one atomic per distinct (group, label) of the wave's hits
             const int gr = p.sgroup[s], y = p.slabel[s];
-            const int key = live && pred == y && (unsigned)gr < (unsigned)p.G ? gr * C + y : -1;
-            unsigned long long left = __ballot(key >= 0);
-            while (left) {
-                const int leader = __builtin_ctzll(left);
-                const int kk = __builtin_amdgcn_readlane(key, leader);
-                const unsigned long long same = __ballot(key == kk);
-                if (lane == leader) atomicAdd(p.correct + (size_t)kk * p.U + u, (int)__popcll(same));
-                left &= ~same;
-            }
+            sl_tally(p.correct, live && pred == y && (unsigned)gr < (unsigned)p.G ? gr * C + y : -1, p.U, u, lane);
         }
         // (the next pass begins with a barrier: the scores are read before the stage is written again)
     }
@@ -458,11 +446,11 @@ extern "C" int chebgcn_searchlight_svm_query(int what) {
         case 0: return SVM_T;               // threads of a workgroup
         case 1: return SVM_NMAX;            // the largest training set
         case 2: return SVM_TV;              // vertices of a tile
-        case 3: return SVM_CMAX;            // the largest number of classes
+        case 3: return SL_CMAX;            // the largest number of classes
         case 4: return SVM_TC;              // test samples of a chunk
-        case 5: return SVM_MODELS;          // models of one call
-        case 6: return SVM_TILES;           // 64-sample tiles of a model's test samples
-        case 7: return SVM_GMAX;            // groups
+        case 5: return SL_NMAX;          // models of one call
+        case 6: return SL_TILES;           // 64-sample tiles of a model's test samples
+        case 7: return SL_GMAX;            // groups
         case 8: return SVM_ITMAX;           // sweeps at most
         case 9: return SVM_SUP;             // vertices of a super-tile
         default:
@@ -488,11 +476,11 @@ extern "C" int chebgcn_searchlight_svm(const float* Xt, int S, int M, const int3
     CG_REQUIRE(loss == 0 || loss == 1, "searchlight_svm: loss = %d; served: 0 (squared hinge) or 1 (hinge)", loss);
     CG_REQUIRE(max_iter >= 1 && max_iter <= SVM_ITMAX, "searchlight_svm: max_iter = %d; served: 1 .. %d", max_iter, SVM_ITMAX);
     const long long tiles = ((long long)tmax + 63) / 64;
-    if (NM > SVM_MODELS || NMb > SVM_MODELS || C > SVM_CMAX || G > SVM_GMAX || tiles > SVM_TILES ||
+    if (NM > SL_NMAX || NMb > SL_NMAX || C > SL_CMAX || G > SL_GMAX || tiles > SL_TILES ||
         (bucket != 32 && bucket != 64 && bucket != 128))
         return fail(CHEBGCN_EUNSUPPORTED, "searchlight_svm: NM = %d, NMb = %d, C = %d, G = %d, tmax = %d, bucket = %d; served: NM <= %d, "
-                    "C <= %d, G <= %d, tmax <= %d, bucket 32, 64 or 128", NM, NMb, C, G, tmax, bucket, SVM_MODELS, SVM_CMAX, SVM_GMAX,
-                    SVM_TILES * 64);
+                    "C <= %d, G <= %d, tmax <= %d, bucket 32, 64 or 128", NM, NMb, C, G, tmax, bucket, SL_NMAX, SL_CMAX, SL_GMAX,
+                    SL_TILES * 64);
     CG_REQUIRE((((uintptr_t)Xt | (uintptr_t)rowptr | (uintptr_t)colidx | (uintptr_t)centres | (uintptr_t)models | (uintptr_t)list_ptr |
                  (uintptr_t)list_idx | (uintptr_t)test_ptr | (uintptr_t)sgroup | (uintptr_t)slabel | (uintptr_t)sorig |
                  (uintptr_t)correct | (uintptr_t)sweeps) & 3) == 0 && (((uintptr_t)scores | (uintptr_t)residual) & 7) == 0,

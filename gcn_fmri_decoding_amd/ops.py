@@ -787,6 +787,36 @@ def _sl_lists(ptr, idx, n, what):
     return int(idx.numel())
 
 
+def _sl_rows(rowptr, colidx, what):
+    """``(U, nnz)`` of the int32 CSR rows of all neighbourhoods."""
+    U = int(rowptr.numel()) - 1
+    return U, _sl_lists(rowptr, colidx, U, what)
+
+
+def _sl_index(t, name, what):
+    """The length of the int32 list ``t`` of the ``name`` (centres, models) of one launch."""
+    n = int(t.numel())
+    if n < 1:
+        raise _lib.ChebgcnError('%s: no %s' % (what, name))
+    _dense(t, torch.int32, (n,), '%s: %s' % (what, name))
+    return n
+
+
+def _sl_tables(S, C, U, sgroup, slabel, sorig, correct, scores, predictions, what):
+    """``G`` of ``correct`` int32 [G, C, U], after the sample tables int32 [S] and ``scores`` / ``predictions`` where given."""
+    for t, name in ((sgroup, 'sgroup'), (slabel, 'slabel'), (sorig, 'sorig')):
+        _dense(t, torch.int32, (S,), '%s: %s' % (what, name))
+    if correct.dim() != 3 or correct.shape[1] != C or correct.shape[2] != U:
+        raise _lib.ChebgcnError('%s: correct must be int32 [G, C, U]' % what)
+    G = int(correct.shape[0])
+    _dense(correct, torch.int32, (G, C, U), what + ': correct')
+    if scores is not None:
+        _dense(scores, torch.float64, (S, C, U), what + ': scores')
+    if predictions is not None:
+        _dense(predictions, torch.uint8, (S, U), what + ': predictions')
+    return G
+
+
 def searchlight_spread(Xt, S, list_ptr, list_idx):
     """The variance of the whole training set of every model at every vertex (chebgcn_searchlight_spread): ``Xt`` float32
     [M, plane_stride(S)] vertex-major patterns, ``list_ptr`` int32 [NM + 1] / ``list_idx`` int32 the models' training samples,
@@ -832,24 +862,14 @@ def searchlight_score(Xt, S, rowptr, colidx, u0, Ub, test_ptr, tmax, C, par, lg,
     _require_cuda(Xt, rowptr, colidx, test_ptr, par, lg, logprior, sgroup, slabel, sorig, correct, scores, predictions)
     M = _sl_patterns(Xt, S, 'searchlight_score')
     S, C, u0, Ub = int(S), int(C), int(u0), int(Ub)
-    U = int(rowptr.numel()) - 1
-    nnz = _sl_lists(rowptr, colidx, U, 'searchlight_score')
+    U, nnz = _sl_rows(rowptr, colidx, 'searchlight_score')
     NM = int(test_ptr.numel()) - 1
     _dense(test_ptr, torch.int32, (NM + 1,), 'searchlight_score: test_ptr')
     NC = int(_lib.lib().chebgcn_searchlight_query(100 + C))
     _dense(par, torch.float64, (NM, M, NC, 2), 'searchlight_score: par')
     _dense(lg, torch.float64, (NM, M, NC), 'searchlight_score: lg')
     _dense(logprior, torch.float64, (NM, NC), 'searchlight_score: logprior')
-    for t, what in ((sgroup, 'sgroup'), (slabel, 'slabel'), (sorig, 'sorig')):
-        _dense(t, torch.int32, (S,), 'searchlight_score: ' + what)
-    if correct.dim() != 3 or correct.shape[1] != C or correct.shape[2] != U:
-        raise _lib.ChebgcnError('searchlight_score: correct must be int32 [G, C, U]')
-    G = int(correct.shape[0])
-    _dense(correct, torch.int32, (G, C, U), 'searchlight_score: correct')
-    if scores is not None:
-        _dense(scores, torch.float64, (S, C, U), 'searchlight_score: scores')
-    if predictions is not None:
-        _dense(predictions, torch.uint8, (S, U), 'searchlight_score: predictions')
+    G = _sl_tables(S, C, U, sgroup, slabel, sorig, correct, scores, predictions, 'searchlight_score')
     if not 0 <= u0 <= U - Ub or Ub < 1:
         raise _lib.ChebgcnError('searchlight_score: centres [%d, %d) outside the %d rows' % (u0, u0 + Ub, U))
     nbytes = max(8 * NM * Ub * NC, 8)
@@ -887,28 +907,15 @@ def searchlight_lda(Xt, S, rowptr, colidx, centres, bucket, class_ptr, class_idx
                   predictions, gamma_out)
     M = _sl_patterns(Xt, S, 'searchlight_lda')
     S, C, bucket = int(S), int(C), int(bucket)
-    U = int(rowptr.numel()) - 1
-    nnz = _sl_lists(rowptr, colidx, U, 'searchlight_lda')
+    U, nnz = _sl_rows(rowptr, colidx, 'searchlight_lda')
     NM = int(test_ptr.numel()) - 1
     _dense(test_ptr, torch.int32, (NM + 1,), 'searchlight_lda: test_ptr')
     nidx = _sl_lists(class_ptr, class_idx, NM * C, 'searchlight_lda')
-    Ub = int(centres.numel())
-    if Ub < 1:
-        raise _lib.ChebgcnError('searchlight_lda: no centres')
-    _dense(centres, torch.int32, (Ub,), 'searchlight_lda: centres')
+    Ub = _sl_index(centres, 'centres', 'searchlight_lda')
     NC = int(_lib.lib().chebgcn_searchlight_query(100 + C))
     _dense(par, torch.float64, (NM, M, NC, 2), 'searchlight_lda: par')
     _dense(logprior, torch.float64, (NM, NC), 'searchlight_lda: logprior')
-    for t, what in ((sgroup, 'sgroup'), (slabel, 'slabel'), (sorig, 'sorig')):
-        _dense(t, torch.int32, (S,), 'searchlight_lda: ' + what)
-    if correct.dim() != 3 or correct.shape[1] != C or correct.shape[2] != U:
-        raise _lib.ChebgcnError('searchlight_lda: correct must be int32 [G, C, U]')
-    G = int(correct.shape[0])
-    _dense(correct, torch.int32, (G, C, U), 'searchlight_lda: correct')
-    if scores is not None:
-        _dense(scores, torch.float64, (S, C, U), 'searchlight_lda: scores')
-    if predictions is not None:
-        _dense(predictions, torch.uint8, (S, U), 'searchlight_lda: predictions')
+    G = _sl_tables(S, C, U, sgroup, slabel, sorig, correct, scores, predictions, 'searchlight_lda')
     if gamma_out is not None:
         _dense(gamma_out, torch.float64, (NM, U), 'searchlight_lda: gamma_out')
     tri = 0.5 * bucket * (bucket + 1)
@@ -941,8 +948,7 @@ def searchlight_rdm(Xt, S, rowptr, colidx, centres, bucket, cell_ptr, class_ptr,
     _require_cuda(Xt, rowptr, colidx, centres, cell_ptr, class_ptr, class_idx, par, rdm, gamma_out)
     M = _sl_patterns(Xt, S, 'searchlight_rdm')
     S, C, bucket = int(S), int(C), int(bucket)
-    U = int(rowptr.numel()) - 1
-    nnz = _sl_lists(rowptr, colidx, U, 'searchlight_rdm')
+    U, nnz = _sl_rows(rowptr, colidx, 'searchlight_rdm')
     G = int(cell_ptr.numel()) - 1
     if G < 1:
         raise _lib.ChebgcnError('searchlight_rdm: no groups')
@@ -951,10 +957,7 @@ def searchlight_rdm(Xt, S, rowptr, colidx, centres, bucket, cell_ptr, class_ptr,
         raise _lib.ChebgcnError('searchlight_rdm: par must be float64 [NM, M, NC, 2]')
     NM = int(par.shape[0])
     nidx = _sl_lists(class_ptr, class_idx, NM * C, 'searchlight_rdm')
-    Ub = int(centres.numel())
-    if Ub < 1:
-        raise _lib.ChebgcnError('searchlight_rdm: no centres')
-    _dense(centres, torch.int32, (Ub,), 'searchlight_rdm: centres')
+    Ub = _sl_index(centres, 'centres', 'searchlight_rdm')
     NC = int(_lib.lib().chebgcn_searchlight_query(100 + C))
     _dense(par, torch.float64, (NM, M, NC, 2), 'searchlight_rdm: par')
     npairs = C * (C - 1) // 2
@@ -999,26 +1002,12 @@ def searchlight_svm(Xt, S, rowptr, colidx, centres, models, bucket, list_ptr, li
         raise _lib.ChebgcnError("searchlight_svm: loss must be 'squared_hinge' or 'hinge', got %r" % (loss,))
     M = _sl_patterns(Xt, S, 'searchlight_svm')
     S, C, bucket = int(S), int(C), int(bucket)
-    U = int(rowptr.numel()) - 1
-    nnz = _sl_lists(rowptr, colidx, U, 'searchlight_svm')
+    U, nnz = _sl_rows(rowptr, colidx, 'searchlight_svm')
     NM = int(test_ptr.numel()) - 1
     _dense(test_ptr, torch.int32, (NM + 1,), 'searchlight_svm: test_ptr')
     nidx = _sl_lists(list_ptr, list_idx, NM, 'searchlight_svm')
-    Ub, NMb = int(centres.numel()), int(models.numel())
-    if Ub < 1 or NMb < 1:
-        raise _lib.ChebgcnError('searchlight_svm: no centres or no models')
-    _dense(centres, torch.int32, (Ub,), 'searchlight_svm: centres')
-    _dense(models, torch.int32, (NMb,), 'searchlight_svm: models')
-    for t, what in ((sgroup, 'sgroup'), (slabel, 'slabel'), (sorig, 'sorig')):
-        _dense(t, torch.int32, (S,), 'searchlight_svm: ' + what)
-    if correct.dim() != 3 or correct.shape[1] != C or correct.shape[2] != U:
-        raise _lib.ChebgcnError('searchlight_svm: correct must be int32 [G, C, U]')
-    G = int(correct.shape[0])
-    _dense(correct, torch.int32, (G, C, U), 'searchlight_svm: correct')
-    if scores is not None:
-        _dense(scores, torch.float64, (S, C, U), 'searchlight_svm: scores')
-    if predictions is not None:
-        _dense(predictions, torch.uint8, (S, U), 'searchlight_svm: predictions')
+    Ub, NMb = _sl_index(centres, 'centres', 'searchlight_svm'), _sl_index(models, 'models', 'searchlight_svm')
+    G = _sl_tables(S, C, U, sgroup, slabel, sorig, correct, scores, predictions, 'searchlight_svm')
     if sweeps is not None:
         _dense(sweeps, torch.int32, (NM, U), 'searchlight_svm: sweeps')
     if residual is not None:

@@ -1,10 +1,11 @@
 """Searchlight decoding: where in the brain is the task information?
 
-At every centre a cross-validated classifier -- Gaussian naive Bayes, or shrinkage LDA with ``classifier='lda'`` -- is fed only
-the centre's neighbourhood, and the centre gets the classifier's accuracy.  ``searchlight`` does it on the device for any list of neighbourhoods -- ``graph.hop_balls`` of the
-brain graph for the classical searchlight map, one row per parcel for ROI decoding, one row of all vertices for the whole-brain
-baseline a GCN accuracy is reported against.  ``searchlight_events`` cuts the trial-mean patterns out of staged runs with
-``match_events`` first.  ``searchlight_host`` restates it in float64 NumPy, centre by centre.
+At every centre a cross-validated classifier -- Gaussian naive Bayes, shrinkage LDA with ``classifier='lda'`` or a linear SVM
+with ``classifier='svc'`` -- is fed only the centre's neighbourhood, and the centre gets the classifier's accuracy.
+``searchlight`` does it on the device for any list of neighbourhoods -- ``graph.hop_balls`` of the brain graph for the classical
+searchlight map, one row per parcel for ROI decoding, one row of all vertices for the whole-brain baseline a GCN accuracy is
+reported against.  ``searchlight_events`` cuts the trial-mean patterns out of staged runs with ``match_events`` first.
+``searchlight_host`` restates it in float64 NumPy, centre by centre.
 
 The fit of naive Bayes is per-vertex moments and its decision a sum over the neighbourhood, so one fit per training set serves
 every centre (chebgcn_searchlight_spread / _fit), and the work is the S x classes x sum |neighbourhood| likelihood terms of
@@ -38,6 +39,7 @@ any cleaning of the series, rank-based RDM comparisons (Spearman), noise ceiling
 The host-only parts need NumPy and SciPy only.
 """
 import collections
+import types
 
 import numpy as np
 import scipy.sparse as sp
@@ -68,7 +70,25 @@ over the classes -- converged where ``residual <= tol``, ended by the cap where 
 ``models``: the ``(group key, fold)`` of every model row (``(None, fold)`` with ``within=False``)."""
 
 _Args = collections.namedtuple('_Args', 'X tensor S M y classes indptr indices U fold gidx keys within pooled uniform vs lda shrink '
-                               'svc Creg loss tol max_iter', defaults=(False, 1.0, 'squared_hinge', 1e-3, 1000))
+                               'svc Creg loss tol max_iter')
+
+# The classifier keywords of ``searchlight`` and their defaults, in the order ``_check`` looks at them; the keywords every
+# classifier owns; and what is said where a keyword the classifier does not own is away from its default.
+_CLF_KW = dict(C=1.0, loss='squared_hinge', tol=1e-3, max_iter=1000, priors='empirical', shrinkage=0.1, variance='class',
+               var_smoothing=1e-9)
+_SVC_KW = ('C', 'loss', 'tol', 'max_iter')
+_CLF_OWNS = {'gnb': ('priors', 'variance', 'var_smoothing'), 'lda': ('priors', 'shrinkage'), 'svc': _SVC_KW}
+_SVC_ONLY = "%(who)s: C, loss, tol and max_iter belong to classifier='svc'; they mean nothing to classifier=%(clf)r"
+_LDA_NONE = ("%(who)s: variance and var_smoothing mean nothing to classifier='lda' (one pooled covariance per ball, regularised by "
+             "shrinkage): leave them at their defaults")
+_SVC_NONE = ("%(who)s: variance, var_smoothing and shrinkage mean nothing to classifier='svc' (regularised by C): leave them at their "
+             "defaults")
+_NOT_OWNED = {
+    'gnb': dict(dict.fromkeys(_SVC_KW, _SVC_ONLY),
+                shrinkage="%(who)s: shrinkage = %(val)r means nothing to classifier='gnb' (naive Bayes has no covariance to shrink)"),
+    'lda': dict(dict.fromkeys(_SVC_KW, _SVC_ONLY), variance=_LDA_NONE, var_smoothing=_LDA_NONE),
+    'svc': dict(priors="%(who)s: priors = %(val)r means nothing to classifier='svc' (an SVM has no prior to set): leave it at "
+                       "'empirical'", shrinkage=_SVC_NONE, variance=_SVC_NONE, var_smoothing=_SVC_NONE)}
 
 
 # ---- arguments ------------------------------------------------------------------------------------------------------------------
@@ -121,17 +141,9 @@ def _patterns(samples, who):
     return X, tensor, int(X.shape[0]), int(X.shape[1])
 
 
-def _shrink_number(shrinkage):
-    """``(auto, number)``: is ``shrinkage`` the string ``'auto'``, is it a real number."""
-    auto = isinstance(shrinkage, str) and shrinkage == 'auto'
-    number = not isinstance(shrinkage, (bool, np.bool_)) and isinstance(shrinkage, (int, float, np.integer, np.floating))
-    return auto, number
-
-
-def _batch(batch_centres, who):
-    if batch_centres is not None and (isinstance(batch_centres, (bool, np.bool_)) or not isinstance(batch_centres, (int, np.integer))
-                                      or batch_centres < 1):
-        raise ValueError('%s: batch_centres must be an int >= 1 or None, got %r' % (who, batch_centres))
+def _real(v):
+    """Is ``v`` a finite real number (a bool is none)."""
+    return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and bool(np.isfinite(v))
 
 
 def _coded_labels(labels, S, classes, limits, who):
@@ -178,10 +190,53 @@ def _group_keys(groups, S, who):
     return keys, gidx
 
 
-def _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-           batch_centres, who, limits=True, classifier='gnb', shrinkage=0.1, C=1.0, loss='squared_hinge', tol=1e-3, max_iter=1000):
-    """Everything that can be checked without the samples' values.  ``shrink`` of the result: the float, or -1.0 for ``'auto'``."""
+def _front(samples, labels, neighbourhoods, vec, name, hint, groups, classes, batch_centres, who, limits):
+    """What ``_check`` and ``_check_rdm`` share, checked in this order: the patterns, ``batch_centres``, the coded labels, the integer
+    vector ``vec`` (``name``: folds or partitions), the group keys and the neighbourhoods ->
+    ``(X, tensor, S, M, y, classes, vec int64, keys, gidx, indptr, indices, U)``."""
     X, tensor, S, M = _patterns(samples, who)
+    if batch_centres is not None and (isinstance(batch_centres, (bool, np.bool_)) or not isinstance(batch_centres, (int, np.integer))
+                                      or batch_centres < 1):
+        raise ValueError('%s: batch_centres must be an int >= 1 or None, got %r' % (who, batch_centres))
+    y, classes = _coded_labels(labels, S, classes, limits, who)
+    vec = _vector(vec, S, name, who)
+    if vec.dtype.kind not in 'iu':
+        raise ValueError('%s: %s must be ints%s, got dtype %s' % (who, name, hint, vec.dtype))
+    keys, gidx = _group_keys(groups, S, who)
+    indptr, indices = _neighbourhoods(neighbourhoods, M, who)
+    if limits and indices.size > 2 ** 31 - 1:
+        raise ValueError('%s: the neighbourhoods list %d vertices; served: fewer than 2^31' % (who, indices.size))
+    return X, tensor, S, M, y, classes, vec.astype(np.int64), keys, gidx, indptr, indices, int(indptr.size) - 1
+
+
+def _at_default(name, val):
+    """Is the classifier keyword ``name`` at its default: the default's value in the default's kind (a bool is no number, a
+    float no ``max_iter``)."""
+    kind = {str: str, int: (int, np.integer), float: (int, float, np.integer, np.floating)}[type(_CLF_KW[name])]
+    return not isinstance(val, (bool, np.bool_)) and isinstance(val, kind) and val == _CLF_KW[name]
+
+
+def _own_keyword(name, val, who):
+    """Refuses a value the owner of the classifier keyword ``name`` does not serve (``variance``, ``priors`` and ``var_smoothing``
+    are checked for every classifier, before this)."""
+    if name == 'C' and not (_real(val) and val > 0):
+        raise ValueError('%s: C must be a finite number > 0, got %r' % (who, val))
+    if name == 'loss' and not (isinstance(val, str) and val in SVC_LOSSES):
+        raise ValueError("%s: loss must be 'squared_hinge' or 'hinge', got %r" % (who, val))
+    if name == 'tol' and not (_real(val) and val >= 0):
+        raise ValueError('%s: tol must be a finite number >= 0, got %r' % (who, val))
+    if name == 'max_iter' and not (_real(val) and isinstance(val, (int, np.integer)) and 1 <= val <= SVC_ITMAX):
+        raise ValueError('%s: max_iter must be an int in [1, %d], got %r' % (who, SVC_ITMAX, val))
+    if name == 'shrinkage' and not (isinstance(val, str) and val == 'auto') and not (_real(val) and SHRINK_MIN <= val <= 1):
+        raise ValueError("%s: shrinkage must be a number in [%g, 1] or 'auto', got %r" % (who, SHRINK_MIN, val))
+
+
+def _check(samples, labels, neighbourhoods, folds, groups, within, classes, scores, predictions, batch_centres, who, limits=True,
+           classifier='gnb', **kw):
+    """Everything that can be checked without the samples' values; ``kw``: the classifier keywords of ``_CLF_KW`` that are not at
+    their defaults.  ``shrink`` of the result: the float, or -1.0 for ``'auto'``."""
+    kw = dict(_CLF_KW, **kw)
+    variance, priors, var_smoothing, shrinkage = (kw[k] for k in ('variance', 'priors', 'var_smoothing', 'shrinkage'))
     for name, val in (('within', within), ('scores', scores), ('predictions', predictions)):
         if not isinstance(val, (bool, np.bool_)):
             raise ValueError('%s: %s must be True or False, got %r' % (who, name, val))
@@ -189,52 +244,19 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
         raise ValueError("%s: variance must be 'class' or 'pooled', got %r" % (who, variance))
     if priors not in ('empirical', 'uniform'):
         raise ValueError("%s: priors must be 'empirical' or 'uniform', got %r" % (who, priors))
-    if isinstance(var_smoothing, (bool, np.bool_)) or not isinstance(var_smoothing, (int, float, np.integer, np.floating)) \
-            or not np.isfinite(var_smoothing) or var_smoothing < 0:
+    if not (_real(var_smoothing) and var_smoothing >= 0):
         raise ValueError('%s: var_smoothing must be a finite number >= 0, got %r' % (who, var_smoothing))
-    if classifier not in ('gnb', 'lda', 'svc'):
+    if classifier not in tuple(_CLF_OWNS):
         raise ValueError("%s: classifier must be 'gnb', 'lda' or 'svc', got %r" % (who, classifier))
-    auto, number = _shrink_number(shrinkage)
-    real = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
-    if classifier == 'svc':
-        if not (real(C) and C > 0):
-            raise ValueError('%s: C must be a finite number > 0, got %r' % (who, C))
-        if not (isinstance(loss, str) and loss in SVC_LOSSES):
-            raise ValueError("%s: loss must be 'squared_hinge' or 'hinge', got %r" % (who, loss))
-        if not (real(tol) and tol >= 0):
-            raise ValueError('%s: tol must be a finite number >= 0, got %r' % (who, tol))
-        if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, (int, np.integer)) or not 1 <= max_iter <= SVC_ITMAX:
-            raise ValueError('%s: max_iter must be an int in [1, %d], got %r' % (who, SVC_ITMAX, max_iter))
-        if priors != 'empirical':
-            raise ValueError("%s: priors = %r means nothing to classifier='svc' (an SVM has no prior to set): leave it at 'empirical'"
-                             % (who, priors))
-        if variance != 'class' or not var_smoothing == 1e-9 or not (number and shrinkage == 0.1):
-            raise ValueError("%s: variance, var_smoothing and shrinkage mean nothing to classifier='svc' (regularised by C): leave "
-                             "them at their defaults" % who)
-    elif not (real(C) and C == 1.0 and isinstance(loss, str) and loss == 'squared_hinge' and real(tol) and tol == 1e-3
-              and not isinstance(max_iter, (bool, np.bool_)) and isinstance(max_iter, (int, np.integer)) and max_iter == 1000):
-        raise ValueError("%s: C, loss, tol and max_iter belong to classifier='svc'; they mean nothing to classifier=%r" % (who, classifier))
-    if classifier == 'gnb':
-        if not (number and shrinkage == 0.1):
-            raise ValueError("%s: shrinkage = %r means nothing to classifier='gnb' (naive Bayes has no covariance to shrink)"
-                             % (who, shrinkage))
-    elif classifier == 'lda':
-        if not auto and not (number and SHRINK_MIN <= shrinkage <= 1):
-            raise ValueError("%s: shrinkage must be a number in [%g, 1] or 'auto', got %r" % (who, SHRINK_MIN, shrinkage))
-        if variance != 'class' or not var_smoothing == 1e-9:
-            raise ValueError("%s: variance and var_smoothing mean nothing to classifier='lda' (one pooled covariance per ball, "
-                             "regularised by shrinkage): leave them at their defaults" % who)
-    _batch(batch_centres, who)
-    y, classes = _coded_labels(labels, S, classes, limits, who)
-    fold = _vector(folds, S, 'folds', who)
-    if fold.dtype.kind not in 'iu':
-        raise ValueError('%s: folds must be ints, got dtype %s' % (who, fold.dtype))
-    fold = fold.astype(np.int64)
-    keys, gidx = _group_keys(groups, S, who)
+    for name, val in kw.items():
+        if name in _CLF_OWNS[classifier]:
+            _own_keyword(name, val, who)
+        elif not _at_default(name, val):
+            raise ValueError(_NOT_OWNED[classifier][name] % {'who': who, 'clf': classifier, 'val': val})
+    X, tensor, S, M, y, classes, fold, keys, gidx, indptr, indices, U = _front(
+        samples, labels, neighbourhoods, folds, 'folds', '', groups, classes, batch_centres, who, limits)
     if limits and len(keys) > GMAX:
         raise ValueError('%s: %d groups; served: up to %d' % (who, len(keys), GMAX))
-    indptr, indices = _neighbourhoods(neighbourhoods, M, who)
-    U = int(indptr.size) - 1
     if classifier == 'lda':
         length = np.diff(indptr)
         if length.max() > LDA_PMAX:
@@ -266,9 +288,9 @@ def _check(samples, labels, neighbourhoods, folds, groups, within, classes, vari
                              "of the training samples stays on chip); across-subject training sets of thousands of samples are out "
                              "of scope, so within=False is served only while n <= %d"
                              % (who, 'group %r, ' % (keys[g],) if within else '', int(fvals[f]), size[g, f], SVC_NMAX, SVC_NMAX))
-    return _Args(X, tensor, S, M, y, classes, indptr, indices, U, fold, gidx, keys, bool(within), variance == 'pooled',
-                 priors == 'uniform', float(var_smoothing), classifier == 'lda', -1.0 if auto else float(shrinkage),
-                 classifier == 'svc', float(C), loss, float(tol), int(max_iter))
+    return _Args(X, tensor, S, M, y, classes, indptr, indices, U, fold, gidx, keys, bool(within), variance == 'pooled', priors == 'uniform',
+                 float(var_smoothing), classifier == 'lda', -1.0 if isinstance(shrinkage, str) else float(shrinkage),
+                 classifier == 'svc', float(kw['C']), kw['loss'], float(kw['tol']), int(kw['max_iter']))
 
 
 def _summary(correct, support, xp):
@@ -313,8 +335,9 @@ def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within
     vectorised across (i, j) and across the classes; every operation a separate correctly rounded one, so the device agrees
     with it bit for bit.  ``return_solver``: a pair of the result and a ``SolverInfo`` (``return_scale`` is not served there)."""
     who = 'searchlight_host'
-    a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-               batch_centres, who, limits=False, classifier=classifier, shrinkage=shrinkage, C=C, loss=loss, tol=tol, max_iter=max_iter)
+    a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, scores, predictions, batch_centres, who, limits=False,
+               classifier=classifier, variance=variance, priors=priors, var_smoothing=var_smoothing, shrinkage=shrinkage, C=C,
+               loss=loss, tol=tol, max_iter=max_iter)
     _solver_flag(return_solver, a, who)
     if a.svc and return_scale:
         raise ValueError("%s: return_scale is not served with classifier='svc' (the device agrees bit for bit)" % who)
@@ -326,6 +349,7 @@ def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within
     key = a.gidx * (int(a.fold.max()) - int(a.fold.min()) + 1) + (a.fold - a.fold.min()) if a.within else a.fold
     model_keys = np.unique(key)
     sweeps, residual, models = np.zeros((model_keys.size, U), np.int32), np.zeros((model_keys.size, U)), []
+    ball = _svc_host_ball if a.svc else _lda_host_ball if a.lda else _gnb_host_ball
     for mi, k in enumerate(model_keys):
         test = key == k
         train = ~test & (a.gidx == a.gidx[test][0]) if a.within else ~test
@@ -333,34 +357,14 @@ def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within
         models.append((a.keys[a.gidx[test][0]] if a.within else None, int(a.fold[test][0])))
         n = np.array([(ytr == c).sum() for c in range(C)], np.float64)
         logp = np.full(C, -np.log(C)) if a.uniform else np.log(n / n.sum())
-        eps = 0.0 if a.svc else a.vs * Xtr.var(axis=0).max()
+        eps = a.vs * Xtr.var(axis=0).max()
         for u in range(U):
             cols = a.indices[a.indptr[u]:a.indptr[u + 1]]
-            A, T = Xtr[:, cols], Xte[:, cols]
-            if a.svc:
-                s_, sweeps[mi, u], residual[mi, u] = _svc_host_ball(A, ytr, T, C, a.Creg, a.loss, a.tol, a.max_iter)
-                sc[test, :, u] = s_
-                pred[test, u] = np.argmax(s_, axis=1)
-                continue
-            if a.lda:
-                s_, q_ = _lda_host_ball(A, ytr, T, n, logp, a.shrink)
-                sc[test, :, u] = s_
-                if return_scale:
-                    scale[test, :, u] = q_
-                pred[test, u] = np.argmax(s_, axis=1)
-                continue
-            mu = np.stack([A[ytr == c].sum(axis=0) / n[c] for c in range(C)])
-            ss = np.stack([((A[ytr == c] - mu[c]) ** 2).sum(axis=0) for c in range(C)])
-            var = (np.broadcast_to(ss.sum(axis=0) / n.sum(), ss.shape) if a.pooled else ss / n[:, None]) + eps
-            ok = var > 0                                        # a vertex whose smoothed variance is 0 contributes nothing
-            v = np.where(ok, var, 1.0)
-            for c in range(C):
-                q = np.where(ok[c], (T - mu[c]) ** 2 / (2.0 * v[c]), 0.0)
-                lg = np.where(ok[c], 0.5 * np.log(2.0 * np.pi * v[c]), 0.0)
-                sc[test, c, u] = logp[c] - (q + lg).sum(axis=1)
-                if return_scale:
-                    scale[test, c, u] = abs(logp[c]) + (q + np.abs(lg)).sum(axis=1)
-            pred[test, u] = np.argmax(sc[test, :, u], axis=1)
+            s_, q_, sweeps[mi, u], residual[mi, u] = ball(Xtr[:, cols], ytr, Xte[:, cols], n, logp, eps, a)
+            sc[test, :, u] = s_
+            if return_scale:
+                scale[test, :, u] = q_
+            pred[test, u] = np.argmax(s_, axis=1)
     correct = np.zeros((G, C, U), np.int32)
     np.add.at(correct, (a.gidx[:, None], a.y[:, None], np.arange(U)[None, :]), (pred == a.y[:, None]).astype(np.int32))
     support = _support(a)
@@ -379,9 +383,29 @@ def _solver_flag(return_solver, a, who):
         raise ValueError("%s: return_solver belongs to classifier='svc' (the other classifiers have no iteration to report)" % who)
 
 
-def _svc_host_ball(A, ytr, T, C, Creg, loss, tol, max_iter):
-    """The one-vs-rest linear SVM of one (training set, row): ``A`` [n, P] training columns in list order, ``T`` [t, P] test
-    columns -> ``(scores [t, C], sweeps, residual)``.  The model of ``searchlight``'s docstring, operation by operation."""
+# The classifier of one (training set, row): ``A`` [n, P] training columns in list order with labels ``ytr``, ``T`` [t, P] test
+# columns, class counts ``n`` and log priors ``logp`` [C], the smoothing ``eps`` -> ``(scores, scale or None [t, C], sweeps, residual)``.
+
+def _gnb_host_ball(A, ytr, T, n, logp, eps, a):
+    """Gaussian naive Bayes: ``sum / n``, ``sum (x - mean)^2 / n``, the joint log-likelihoods."""
+    C = n.size
+    mu = np.stack([A[ytr == c].sum(axis=0) / n[c] for c in range(C)])
+    ss = np.stack([((A[ytr == c] - mu[c]) ** 2).sum(axis=0) for c in range(C)])
+    var = (np.broadcast_to(ss.sum(axis=0) / n.sum(), ss.shape) if a.pooled else ss / n[:, None]) + eps
+    ok = var > 0                                                # a vertex whose smoothed variance is 0 contributes nothing
+    v = np.where(ok, var, 1.0)
+    scores, scale = np.empty((T.shape[0], C)), np.empty((T.shape[0], C))
+    for c in range(C):
+        q = np.where(ok[c], (T - mu[c]) ** 2 / (2.0 * v[c]), 0.0)
+        lg = np.where(ok[c], 0.5 * np.log(2.0 * np.pi * v[c]), 0.0)
+        scores[:, c] = logp[c] - (q + lg).sum(axis=1)
+        scale[:, c] = abs(logp[c]) + (q + np.abs(lg)).sum(axis=1)
+    return scores, scale, 0, 0.0
+
+
+def _svc_host_ball(A, ytr, T, n, logp, eps, a):
+    """The one-vs-rest linear SVM: the model of ``searchlight``'s docstring, operation by operation; no scale."""
+    C, Creg, loss, tol, max_iter = n.size, a.Creg, a.loss, a.tol, a.max_iter
     n, P = A.shape
     acc = np.zeros(P)
     for k in range(n):                                          # m_v: one chain in list order, one division
@@ -420,7 +444,7 @@ def _svc_host_ball(A, ytr, T, C, Creg, loss, tol, max_iter):
     f = np.zeros((T.shape[0], C))
     for j in range(n):                                          # the score: one chain in list order
         f = f + at[None, :, j] * (Kt[:, j, None] + 1.0)
-    return f, int(sweeps.max()), float(resid.max())
+    return f, None, int(sweeps.max()), float(resid.max())
 
 
 def lda_shrinkage_host(R):
@@ -445,10 +469,10 @@ def lda_shrinkage_host(R):
     return float(min(max(g, SHRINK_MIN), 1.0))
 
 
-def _lda_host_ball(A, ytr, T, n, logp, shrink):
-    """Shrinkage LDA of one (training set, ball): ``A`` [n, P] training columns, ``T`` [t, P] test columns -> ``(scores [t, C],
-    scale [t, C])``."""
+def _lda_host_ball(A, ytr, T, n, logp, eps, a):
+    """Shrinkage LDA: ``scipy.linalg.cho_factor`` / ``cho_solve`` on the shrunk pooled covariance of the ball."""
     import scipy.linalg
+    shrink = a.shrink
     C, P = n.size, A.shape[1]
     order = np.concatenate([np.flatnonzero(ytr == c) for c in range(C)])        # class 0's samples first, as the plan lists them
     mu = np.stack([A[ytr == c].sum(axis=0) / n[c] for c in range(C)])
@@ -474,7 +498,7 @@ def _lda_host_ball(A, ytr, T, n, logp, shrink):
     Tc = T - m
     scores = logp - 0.5 * dw + Tc @ w.T
     scale = kappa * (np.abs(logp) + 0.5 * np.abs(dw) + np.abs(Tc) @ np.abs(w).T)
-    return scores, scale
+    return scores, scale, 0, 0.0
 
 
 # ---- the device -----------------------------------------------------------------------------------------------------------------
@@ -526,27 +550,51 @@ def _transposed(X, order, dev):
     return Xt
 
 
+def _outputs(a, dev, scores, predictions):
+    """``(correct int32 [G, C, U] of zeros, scores float64 [S, C, U] or None, predictions uint8 [S, U] or None)`` on ``dev``."""
+    import torch
+    S, C, U = a.S, len(a.classes), a.U
+    return (torch.zeros((len(a.keys), C, U), dtype=torch.int32, device=dev),
+            torch.empty((S, C, U), dtype=torch.float64, device=dev) if scores else None,
+            torch.empty((S, U), dtype=torch.uint8, device=dev) if predictions else None)
+
+
+def _upload(a, plan, dev, names):
+    """The CSR rows of the neighbourhoods (``rowptr``, ``colidx``, int32) and the tables ``names`` of the plan on ``dev``, each
+    uploaded once; ``order`` goes as int32 (the kernels' ``sorig``)."""
+    import torch
+    up = lambda v: torch.as_tensor(v).to(dev)
+    tables = {name: up(plan.order.astype(np.int32) if name == 'order' else getattr(plan, name)) for name in names.split()}
+    return types.SimpleNamespace(rowptr=up(a.indptr.astype(np.int32)), colidx=up(a.indices.astype(np.int32)), **tables)
+
+
+def _row_batches(a, buckets, batch_centres, dev):
+    """``(bucket, rows int32 on dev)``: the centres bucket by bucket of row length (``buckets``: the bucket of every length), and
+    inside a bucket batch by batch of ``batch_centres`` (``None``: the whole bucket)."""
+    import torch
+    of_row = np.array([buckets[int(n)] for n in np.diff(a.indptr)])
+    for bucket in sorted(set(of_row.tolist())):
+        rows = np.flatnonzero(of_row == bucket).astype(np.int32)
+        step = rows.size if batch_centres is None else int(min(batch_centres, rows.size))
+        for i in range(0, rows.size, step):
+            yield bucket, torch.as_tensor(rows[i:i + step]).to(dev)
+
+
 def _run(a, plan, Xt, scores, predictions, batch_centres):
     """The launches, on the current device: spread, fit, then the centres batch by batch.  Returns device tensors."""
-    import torch
     from . import ops
-    dev = Xt.device
-    up = lambda v: torch.as_tensor(v).to(dev)
-    S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
-    spread = ops.searchlight_spread(Xt, S, up(plan.list_ptr), up(plan.list_idx))
+    t = _upload(a, plan, Xt.device, 'list_ptr list_idx class_ptr class_idx test_ptr logprior sgroup slabel order')
+    S, C, U = a.S, len(a.classes), a.U
+    spread = ops.searchlight_spread(Xt, S, t.list_ptr, t.list_idx)
     eps = a.vs * spread.max(dim=1).values
-    par, lg = ops.searchlight_fit(Xt, S, up(plan.class_ptr), up(plan.class_idx), C, eps, pooled=a.pooled)
-    correct = torch.zeros((G, C, U), dtype=torch.int32, device=dev)
-    sc = torch.empty((S, C, U), dtype=torch.float64, device=dev) if scores else None
-    pred = torch.empty((S, U), dtype=torch.uint8, device=dev) if predictions else None
+    par, lg = ops.searchlight_fit(Xt, S, t.class_ptr, t.class_idx, C, eps, pooled=a.pooled)
+    correct, sc, pred = _outputs(a, Xt.device, scores, predictions)
     if batch_centres is None:
         batch_centres = max(1, (64 << 20) // (8 * plan.NM * plan.NC))           # 64 MiB of per-centre offsets per launch
     batch_centres = int(min(batch_centres, U, (2 ** 31 - 1) // CMAX))
-    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
-    tables = [up(v) for v in (plan.test_ptr, plan.logprior, plan.sgroup, plan.slabel, plan.order.astype(np.int32))]
     for u0 in range(0, U, batch_centres):
-        ops.searchlight_score(Xt, S, rowptr, colidx, u0, min(batch_centres, U - u0), tables[0], plan.tmax, C, par, lg, tables[1],
-                              tables[2], tables[3], tables[4], correct, scores=sc, predictions=pred)
+        ops.searchlight_score(Xt, S, t.rowptr, t.colidx, u0, min(batch_centres, U - u0), t.test_ptr, plan.tmax, C, par, lg, t.logprior,
+                              t.sgroup, t.slabel, t.order, correct, scores=sc, predictions=pred)
     return correct, sc, pred
 
 
@@ -556,53 +604,39 @@ def _run_lda(a, plan, Xt, scores, predictions, batch_centres, gamma=False):
     import torch
     from . import ops
     dev = Xt.device
-    up = lambda v: torch.as_tensor(v).to(dev)
-    S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
-    class_ptr, class_idx = up(plan.class_ptr), up(plan.class_idx)
-    par, _ = ops.searchlight_fit(Xt, S, class_ptr, class_idx, C, torch.zeros(plan.NM, dtype=torch.float64, device=dev))
-    correct = torch.zeros((G, C, U), dtype=torch.int32, device=dev)
-    sc = torch.empty((S, C, U), dtype=torch.float64, device=dev) if scores else None
-    pred = torch.empty((S, U), dtype=torch.uint8, device=dev) if predictions else None
-    gam = torch.empty((plan.NM, U), dtype=torch.float64, device=dev) if gamma else None
-    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
-    tables = [up(v) for v in (plan.test_ptr, plan.logprior, plan.sgroup, plan.slabel, plan.order.astype(np.int32))]
-    buckets = ops.searchlight_lda_geometry()['buckets']
-    of_row = np.array([buckets[int(n)] for n in np.diff(a.indptr)])
-    for bucket in sorted(set(of_row.tolist())):
-        rows = np.flatnonzero(of_row == bucket).astype(np.int32)
-        step = rows.size if batch_centres is None else int(min(batch_centres, rows.size))
-        for i in range(0, rows.size, step):
-            ops.searchlight_lda(Xt, S, rowptr, colidx, up(rows[i:i + step]), bucket, class_ptr, class_idx, tables[0], plan.tmax, C, par,
-                                tables[1], a.shrink, tables[2], tables[3], tables[4], correct, scores=sc, predictions=pred,
-                                gamma_out=gam)
+    t = _upload(a, plan, dev, 'class_ptr class_idx test_ptr logprior sgroup slabel order')
+    S, C = a.S, len(a.classes)
+    par, _ = ops.searchlight_fit(Xt, S, t.class_ptr, t.class_idx, C, torch.zeros(plan.NM, dtype=torch.float64, device=dev))
+    correct, sc, pred = _outputs(a, dev, scores, predictions)
+    gam = torch.empty((plan.NM, a.U), dtype=torch.float64, device=dev) if gamma else None
+    for bucket, rows in _row_batches(a, ops.searchlight_lda_geometry()['buckets'], batch_centres, dev):
+        ops.searchlight_lda(Xt, S, t.rowptr, t.colidx, rows, bucket, t.class_ptr, t.class_idx, t.test_ptr, plan.tmax, C, par,
+                            t.logprior, a.shrink, t.sgroup, t.slabel, t.order, correct, scores=sc, predictions=pred, gamma_out=gam)
     return (correct, sc, pred, gam) if gamma else (correct, sc, pred)
 
 
 def _run_svc(a, plan, Xt, scores, predictions, batch_centres):
-    """The launches of ``classifier='svc'``: the models bucket by bucket of training-set size, the centres batch by batch.
-    Returns device tensors: ``(correct, scores, predictions, sweeps int32 [NM, U], residual float64 [NM, U])``."""
+    """The launches of ``classifier='svc'``: the models bucket by bucket of training-set size, the centres batch by batch (ranges
+    of consecutive centres, every one against every model of the bucket: not the rows of ``_row_batches``).  Returns device
+    tensors: ``(correct, scores, predictions, sweeps int32 [NM, U], residual float64 [NM, U])``."""
     import torch
     from . import ops
     dev = Xt.device
     up = lambda v: torch.as_tensor(v).to(dev)
-    S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
-    correct = torch.zeros((G, C, U), dtype=torch.int32, device=dev)
-    sc = torch.empty((S, C, U), dtype=torch.float64, device=dev) if scores else None
-    pred = torch.empty((S, U), dtype=torch.uint8, device=dev) if predictions else None
+    t = _upload(a, plan, dev, 'list_ptr list_idx test_ptr sgroup slabel order')
+    S, C, U = a.S, len(a.classes), a.U
+    correct, sc, pred = _outputs(a, dev, scores, predictions)
     sweeps = torch.zeros((plan.NM, U), dtype=torch.int32, device=dev)
     residual = torch.zeros((plan.NM, U), dtype=torch.float64, device=dev)
-    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
-    list_ptr, list_idx = up(plan.list_ptr), up(plan.list_idx)
-    tables = [up(v) for v in (plan.test_ptr, plan.sgroup, plan.slabel, plan.order.astype(np.int32))]
     buckets = ops.searchlight_svm_geometry()['buckets']
     of_model = np.array([buckets[int(n)] for n in np.diff(plan.list_ptr)])
     step = U if batch_centres is None else int(min(batch_centres, U))
     for bucket in sorted(set(of_model.tolist())):
         models = up(np.flatnonzero(of_model == bucket).astype(np.int32))
         for u0 in range(0, U, step):
-            ops.searchlight_svm(Xt, S, rowptr, colidx, up(np.arange(u0, min(u0 + step, U), dtype=np.int32)), models, bucket, list_ptr,
-                                list_idx, tables[0], plan.tmax, C, a.Creg, a.loss, a.tol, a.max_iter, tables[1], tables[2], tables[3],
-                                correct, scores=sc, predictions=pred, sweeps=sweeps, residual=residual)
+            ops.searchlight_svm(Xt, S, t.rowptr, t.colidx, up(np.arange(u0, min(u0 + step, U), dtype=np.int32)), models, bucket,
+                                t.list_ptr, t.list_idx, t.test_ptr, plan.tmax, C, a.Creg, a.loss, a.tol, a.max_iter, t.sgroup,
+                                t.slabel, t.order, correct, scores=sc, predictions=pred, sweeps=sweeps, residual=residual)
     return correct, sc, pred, sweeps, residual
 
 
@@ -627,9 +661,19 @@ def _device(device, like=None):
     return torch.device('cuda', torch.cuda.current_device())
 
 
+def _staged(a, order, dev, who):
+    """``_transposed`` of the checked patterns on ``dev``, samples in ``order``; a tensor's values are checked here."""
+    import torch
+    if a.tensor:
+        X = a.X.detach().to(dev, torch.float32)
+        if not bool(torch.isfinite(X).all()):
+            raise ValueError('%s: samples hold non-finite values' % who)
+    else:
+        X = torch.as_tensor(a.X).to(dev)                        # (float32 and finite: the caller's _host_array)
+    return _transposed(X, order, dev)
+
+
 def _searchlight(a, dev, scores, predictions, batch_centres, as_tensor, who, return_solver=False):
-    if a.indices.size > 2 ** 31 - 1:
-        raise ValueError('%s: the neighbourhoods list %d vertices; served: fewer than 2^31' % (who, a.indices.size))
     import torch
     from . import ops
     NC = ops.searchlight_geometry()['buckets'][len(a.classes)]
@@ -637,14 +681,9 @@ def _searchlight(a, dev, scores, predictions, batch_centres, as_tensor, who, ret
     if plan.NM > NMAX:
         raise ValueError('%s: %d training sets; served: up to %d' % (who, plan.NM, NMAX))
     with torch.cuda.device(dev):
-        if a.tensor:
-            X = a.X.detach().to(dev, torch.float32)
-            if not bool(torch.isfinite(X).all()):
-                raise ValueError('%s: samples hold non-finite values' % who)
-        else:
-            X = torch.as_tensor(a.X).to(dev)                    # (float32 and finite: the caller's _host_array)
+        Xt = _staged(a, plan.order, dev, who)
         if a.svc:
-            correct, sc, pred, sweeps, residual = _run_svc(a, plan, _transposed(X, plan.order, dev), scores, predictions, batch_centres)
+            correct, sc, pred, sweeps, residual = _run_svc(a, plan, Xt, scores, predictions, batch_centres)
             res = _result(a, correct, sc, pred, as_tensor)
             if not return_solver:
                 return res
@@ -653,7 +692,7 @@ def _searchlight(a, dev, scores, predictions, batch_centres, as_tensor, who, ret
             if not as_tensor:
                 sweeps, residual = sweeps.cpu().numpy(), residual.cpu().numpy()
             return res, SolverInfo(sweeps, residual, models)
-        correct, sc, pred = (_run_lda if a.lda else _run)(a, plan, _transposed(X, plan.order, dev), scores, predictions, batch_centres)
+        correct, sc, pred = (_run_lda if a.lda else _run)(a, plan, Xt, scores, predictions, batch_centres)
         return _result(a, correct, sc, pred, as_tensor)
 
 
@@ -746,8 +785,9 @@ def searchlight(samples, labels, neighbourhoods, folds, groups=None, within=True
     goes through ``map_test``), smoothing per ball, temporal features beyond the trial mean, any scaling or cleaning of the
     patterns or the series."""
     who = 'searchlight'
-    a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, variance, priors, var_smoothing, scores, predictions,
-               batch_centres, who, classifier=classifier, shrinkage=shrinkage, C=C, loss=loss, tol=tol, max_iter=max_iter)
+    a = _check(samples, labels, neighbourhoods, folds, groups, within, classes, scores, predictions, batch_centres, who,
+               classifier=classifier, variance=variance, priors=priors, var_smoothing=var_smoothing, shrinkage=shrinkage, C=C,
+               loss=loss, tol=tol, max_iter=max_iter)
     _solver_flag(return_solver, a, who)
     if not a.tensor:
         a = a._replace(X=_host_array(a.X, who))                 # non-finite values: before the device is touched
@@ -842,6 +882,41 @@ def _event_patterns(planes, idx, M):
     return ops.gather_windows_indexed(planes, idx, M, 1, fold=int(idx.shape[1]))[:, 0, :M]
 
 
+def _from_events(runs, label_runs, target_name, block_dura, groups, folds, within, kw, taken, refused, check, who):
+    """What ``searchlight_events`` and ``crossnobis_events`` share: the runs as a list of ``[T, M]``; ``kw`` loses the ``match_events``
+    keywords and ``device``, may name nothing outside ``taken``, and any of ``refused[0]`` is answered with ``refused[1]``; the trials
+    of ``_events_plan`` (``folds`` as there, or a function of the number of runs); the caller's ``check(stand_in, labels, folds,
+    groups, classes)`` on a stand-in of the patterns' shape, which do not exist yet; staging and the patterns' gather.  Returns
+    ``(the checked arguments with the patterns, the device, whether every run came as a tensor)``."""
+    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
+    if single and runs.ndim != 2:
+        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
+    runs = [runs] if single else [r if _is_tensor(r) else np.asarray(r) for r in runs]
+    if not runs or any(r.ndim != 2 for r in runs):
+        raise ValueError('%s: runs must be a non-empty list of [T, M] arrays' % who)
+    M = int(runs[0].shape[1])
+    if M < 1 or any(int(r.shape[1]) != M for r in runs):
+        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
+    if any(k in kw for k in refused[0]):
+        raise ValueError(refused[1] % who)
+    match_kw = {k: kw.pop(k) for k in _MATCH_KW if k in kw}
+    unknown = set(kw) - set(taken) - {'device'}
+    if unknown:
+        raise ValueError('%s: unknown keyword %r' % (who, sorted(unknown)[0]))
+    if single and label_runs is not None and len(label_runs) and isinstance(label_runs[0], str):
+        label_runs = [label_runs]
+    idx, labels, tg, tf, classes = _events_plan([int(r.shape[0]) for r in runs], label_runs, target_name, block_dura, groups,
+                                                folds(len(runs)) if callable(folds) else folds, within, match_kw, who)
+    device = kw.pop('device', None)
+    a = check(np.zeros((idx.shape[0], M), np.float32), labels, tf, tg, classes)
+    runs = [r if _is_tensor(r) else _host_array(r, who) for r in runs]        # non-finite values: before the device is touched
+    import torch
+    dev = _device(device, next((r for r in runs if _is_tensor(r) and r.is_cuda), None))
+    with torch.cuda.device(dev):
+        X = _event_patterns(_stage(runs, M, dev, who), torch.as_tensor(idx).to(dev), M)
+    return a._replace(X=X, tensor=True), dev, all(_is_tensor(r) for r in runs)
+
+
 def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods, groups=None, folds=None, within=True, **kw):
     """``searchlight`` on the trials of an event design: ``runs`` (one ``[T, M]`` array or a list; NumPy or torch) are staged
     as ``[Ttot, plane_stride(M)]`` planes as ``first_level`` stages them, ``match_events(label_runs, target_name, block_dura)``
@@ -852,50 +927,23 @@ def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods
 
     ``groups``: one key per run (the subject; default one group).  ``folds``: one int per run; default ``default_folds``: with
     ``within=True`` the run's position among its group's runs (leave-one-run-out), with ``within=False`` the group's index
-    (leave-one-subject-out).  Every other keyword is ``searchlight``'s, ``classifier``, ``shrinkage`` and the SVM's ``C``, ``loss``, ``tol``, ``max_iter``
-    and ``return_solver`` included.  Returns NumPy maps, or device tensors if every run came
-    as a tensor."""
+    (leave-one-subject-out).  Every other keyword is ``searchlight``'s, ``classifier``, ``shrinkage`` and the SVM's ``C``,
+    ``loss``, ``tol``, ``max_iter`` and ``return_solver`` included.  Returns NumPy maps, or device tensors if every run came as a
+    tensor."""
     who = 'searchlight_events'
-    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
-    if single and runs.ndim != 2:
-        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
-    runs = [runs] if single else [r if _is_tensor(r) else np.asarray(r) for r in runs]
-    if not runs or any(r.ndim != 2 for r in runs):
-        raise ValueError('%s: runs must be a non-empty list of [T, M] arrays' % who)
-    M = int(runs[0].shape[1])
-    if M < 1 or any(int(r.shape[1]) != M for r in runs):
-        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
-    if 'TRstep' in kw or 'classes' in kw:
-        raise ValueError('%s: TRstep and classes are not taken (one pattern per trial; the classes are sorted(set(target_name)))' % who)
-    match_kw = {k: kw.pop(k) for k in _MATCH_KW if k in kw}
-    unknown = set(kw) - {'variance', 'priors', 'var_smoothing', 'scores', 'predictions', 'device', 'batch_centres', 'classifier', 'shrinkage',
-                         'C', 'loss', 'tol', 'max_iter', 'return_solver'}
-    if unknown:
-        raise ValueError('%s: unknown keyword %r' % (who, sorted(unknown)[0]))
-    if single and label_runs is not None and len(label_runs) and isinstance(label_runs[0], str):
-        label_runs = [label_runs]
-    idx, labels, tg, tf, classes = _events_plan([int(r.shape[0]) for r in runs], label_runs, target_name, block_dura, groups, folds,
-                                                within, match_kw, who)
-    device = kw.pop('device', None)
-    sl_kw = dict(variance='class', priors='empirical', var_smoothing=1e-9, scores=False, predictions=False, batch_centres=None,
-                 classifier='gnb', shrinkage=0.1, C=1.0, loss='squared_hinge', tol=1e-3, max_iter=1000, return_solver=False)
-    sl_kw.update(kw)
-    # (the patterns do not exist yet: the checks run on a stand-in of their shape)
-    a = _check(np.zeros((idx.shape[0], M), np.float32), labels, neighbourhoods, tf, tg, within, classes, sl_kw['variance'],
-               sl_kw['priors'], sl_kw['var_smoothing'], sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], who,
-               classifier=sl_kw['classifier'], shrinkage=sl_kw['shrinkage'], C=sl_kw['C'], loss=sl_kw['loss'], tol=sl_kw['tol'],
-               max_iter=sl_kw['max_iter'])
-    _solver_flag(sl_kw['return_solver'], a, who)
-    runs = [r if _is_tensor(r) else _host_array(r, who) for r in runs]        # non-finite values: before the device is touched
-    import torch
-    first = next((r for r in runs if _is_tensor(r) and r.is_cuda), None)
-    dev = _device(device, first)
-    with torch.cuda.device(dev):
-        planes = _stage(runs, M, dev, who)
-        X = _event_patterns(planes, torch.as_tensor(idx).to(dev), M)
-        a = a._replace(X=X, tensor=True)
-        return _searchlight(a, dev, sl_kw['scores'], sl_kw['predictions'], sl_kw['batch_centres'], all(_is_tensor(r) for r in runs), who,
-                            bool(sl_kw['return_solver']))
+    mine = dict(scores=False, predictions=False, batch_centres=None, return_solver=False)
+    mine.update((k, kw.pop(k)) for k in tuple(mine) if k in kw)                # kw keeps the classifier's and _from_events' keywords
+
+    def check(stand_in, labels, tf, tg, classes):
+        a = _check(stand_in, labels, neighbourhoods, tf, tg, within, classes, mine['scores'], mine['predictions'],
+                   mine['batch_centres'], who, **kw)
+        _solver_flag(mine['return_solver'], a, who)
+        return a
+    refused = '%s: TRstep and classes are not taken (one pattern per trial; the classes are sorted(set(target_name)))'
+    a, dev, as_tensor = _from_events(runs, label_runs, target_name, block_dura, groups, folds, within, kw, {'classifier', *_CLF_KW},
+                                     (('TRstep', 'classes'), refused), check, who)
+    return _searchlight(a, dev, mine['scores'], mine['predictions'], mine['batch_centres'], as_tensor, who,
+                        bool(mine['return_solver']))
 
 
 # ---- RSA: crossnobis distances per ball -----------------------------------------------------------------------------------------
@@ -935,19 +983,10 @@ def _check_rdm(samples, labels, neighbourhoods, partitions, groups, classes, shr
     """Everything ``crossnobis`` can check without the samples' values.  ``cell`` of the result: the cell (group, partition) of
     every sample, cells numbered group by group (order of first appearance) and partition ascending inside a group;
     ``cell_ptr`` int64 [G + 1]; ``shrink``: the float, or -1.0 for ``'auto'``."""
-    X, tensor, S, M = _patterns(samples, who)
-    auto, number = _shrink_number(shrinkage)
-    if not auto and not (number and SHRINK_MIN <= shrinkage <= 1):
-        raise ValueError("%s: shrinkage must be a number in [%g, 1] or 'auto', got %r" % (who, SHRINK_MIN, shrinkage))
-    _batch(batch_centres, who)
-    y, classes = _coded_labels(labels, S, classes, limits, who)
-    part = _vector(partitions, S, 'partitions', who)
-    if part.dtype.kind not in 'iu':
-        raise ValueError('%s: partitions must be ints (the run a pattern comes from), got dtype %s' % (who, part.dtype))
-    part = part.astype(np.int64)
-    keys, gidx = _group_keys(groups, S, who)
-    indptr, indices = _neighbourhoods(neighbourhoods, M, who)
-    U = int(indptr.size) - 1
+    _own_keyword('shrinkage', shrinkage, who)
+    X, tensor, S, M, y, classes, part, keys, gidx, indptr, indices, U = _front(
+        samples, labels, neighbourhoods, partitions, 'partitions', ' (the run a pattern comes from)', groups, classes, batch_centres,
+        who, limits)
     length = np.diff(indptr)
     if length.max() > LDA_PMAX:
         row = int(np.argmax(length > LDA_PMAX))
@@ -972,8 +1011,8 @@ def _check_rdm(samples, labels, neighbourhoods, partitions, groups, classes, shr
     cell_ptr = np.concatenate([[0], np.cumsum(folds)]).astype(np.int64)
     if limits and int(cell_ptr[-1]) > NMAX:
         raise ValueError('%s: %d (group, partition) cells; served: up to %d' % (who, int(cell_ptr[-1]), NMAX))
-    return _RdmArgs(X, tensor, S, M, y, classes, indptr, indices, U, gidx, keys, -1.0 if auto else float(shrinkage), cell, cell_ptr,
-                    folds.astype(np.int64))
+    return _RdmArgs(X, tensor, S, M, y, classes, indptr, indices, U, gidx, keys, -1.0 if isinstance(shrinkage, str) else float(shrinkage),
+                    cell, cell_ptr, folds.astype(np.int64))
 
 
 def _pairs(C):
@@ -1110,37 +1149,22 @@ def _run_rdm(a, plan, Xt, batch_centres):
     import torch
     from . import ops
     dev = Xt.device
-    up = lambda v: torch.as_tensor(v).to(dev)
+    t = _upload(a, plan, dev, 'class_ptr class_idx cell_ptr')
     C, U, G = len(a.classes), a.U, len(a.keys)
-    class_ptr, class_idx, cell_ptr = up(plan.class_ptr), up(plan.class_idx), up(plan.cell_ptr)
-    par, _ = ops.searchlight_fit(Xt, a.S, class_ptr, class_idx, C, torch.zeros(plan.NM, dtype=torch.float64, device=dev))
+    par, _ = ops.searchlight_fit(Xt, a.S, t.class_ptr, t.class_idx, C, torch.zeros(plan.NM, dtype=torch.float64, device=dev))
     rdm = torch.zeros((G, C * (C - 1) // 2, U), dtype=torch.float64, device=dev)
     gam = torch.full((G, U), -1.0, dtype=torch.float64, device=dev)
-    rowptr, colidx = up(a.indptr.astype(np.int32)), up(a.indices.astype(np.int32))
-    buckets = ops.searchlight_rdm_geometry()['buckets']
-    of_row = np.array([buckets[int(n)] for n in np.diff(a.indptr)])
-    for bucket in sorted(set(of_row.tolist())):
-        rows = np.flatnonzero(of_row == bucket).astype(np.int32)
-        step = rows.size if batch_centres is None else int(min(batch_centres, rows.size))
-        for i in range(0, rows.size, step):
-            ops.searchlight_rdm(Xt, a.S, rowptr, colidx, up(rows[i:i + step]), bucket, cell_ptr, class_ptr, class_idx, C, par, a.shrink,
-                                rdm, gamma_out=gam)
+    for bucket, rows in _row_batches(a, ops.searchlight_rdm_geometry()['buckets'], batch_centres, dev):
+        ops.searchlight_rdm(Xt, a.S, t.rowptr, t.colidx, rows, bucket, t.cell_ptr, t.class_ptr, t.class_idx, C, par, a.shrink, rdm,
+                            gamma_out=gam)
     return rdm, gam
 
 
 def _crossnobis(a, dev, batch_centres, as_tensor, who):
-    if a.indices.size > 2 ** 31 - 1:
-        raise ValueError('%s: the neighbourhoods list %d vertices; served: fewer than 2^31' % (who, a.indices.size))
     import torch
     plan = _rdm_plan(a)
     with torch.cuda.device(dev):
-        if a.tensor:
-            X = a.X.detach().to(dev, torch.float32)
-            if not bool(torch.isfinite(X).all()):
-                raise ValueError('%s: samples hold non-finite values' % who)
-        else:
-            X = torch.as_tensor(a.X).to(dev)                    # (float32 and finite: the caller's _host_array)
-        rdm, gam = _run_rdm(a, plan, _transposed(X, plan.order, dev), batch_centres)
+        rdm, gam = _run_rdm(a, plan, _staged(a, plan.order, dev, who), batch_centres)
     if not as_tensor:
         rdm, gam = rdm.cpu().numpy(), gam.cpu().numpy()
     return RDMResult(rdm, gam, list(a.classes), _pairs(len(a.classes)), list(a.keys), a.folds.copy())
@@ -1200,36 +1224,11 @@ def crossnobis_events(runs, label_runs, target_name, block_dura, neighbourhoods,
     Every other keyword (``shrinkage``, ``batch_centres``, ``device``) is ``crossnobis``'s.  Returns NumPy arrays, or device
     tensors if every run came as a tensor."""
     who = 'crossnobis_events'
-    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
-    if single and runs.ndim != 2:
-        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
-    runs = [runs] if single else [r if _is_tensor(r) else np.asarray(r) for r in runs]
-    if not runs or any(r.ndim != 2 for r in runs):
-        raise ValueError('%s: runs must be a non-empty list of [T, M] arrays' % who)
-    M = int(runs[0].shape[1])
-    if M < 1 or any(int(r.shape[1]) != M for r in runs):
-        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
-    if 'TRstep' in kw or 'classes' in kw or 'partitions' in kw:
-        raise ValueError('%s: TRstep, classes and partitions are not taken (one pattern per trial; the classes are '
-                         'sorted(set(target_name)); the partition is the run)' % who)
-    match_kw = {k: kw.pop(k) for k in _MATCH_KW if k in kw}
-    unknown = set(kw) - {'shrinkage', 'batch_centres', 'device'}
-    if unknown:
-        raise ValueError('%s: unknown keyword %r' % (who, sorted(unknown)[0]))
-    if single and label_runs is not None and len(label_runs) and isinstance(label_runs[0], str):
-        label_runs = [label_runs]
-    idx, labels, tg, tp, classes = _events_plan([int(r.shape[0]) for r in runs], label_runs, target_name, block_dura, groups,
-                                                np.arange(len(runs)), True, match_kw, who)
-    device = kw.pop('device', None)
     shrinkage, batch_centres = kw.get('shrinkage', 0.1), kw.get('batch_centres', None)
-    # (the patterns do not exist yet: the checks run on a stand-in of their shape)
-    a = _check_rdm(np.zeros((idx.shape[0], M), np.float32), labels, neighbourhoods, tp, tg, classes, shrinkage, batch_centres, who)
-    runs = [r if _is_tensor(r) else _host_array(r, who) for r in runs]        # non-finite values: before the device is touched
-    import torch
-    first = next((r for r in runs if _is_tensor(r) and r.is_cuda), None)
-    dev = _device(device, first)
-    with torch.cuda.device(dev):
-        planes = _stage(runs, M, dev, who)
-        X = _event_patterns(planes, torch.as_tensor(idx).to(dev), M)
-        a = a._replace(X=X, tensor=True)
-        return _crossnobis(a, dev, batch_centres, all(_is_tensor(r) for r in runs), who)
+    check = lambda stand_in, labels, tp, tg, classes: _check_rdm(stand_in, labels, neighbourhoods, tp, tg, classes, shrinkage,
+                                                                 batch_centres, who)
+    refused = ('%s: TRstep, classes and partitions are not taken (one pattern per trial; the classes are sorted(set(target_name)); the '
+               'partition is the run)')
+    a, dev, as_tensor = _from_events(runs, label_runs, target_name, block_dura, groups, np.arange, True, kw,
+                                     {'shrinkage', 'batch_centres'}, (('TRstep', 'classes', 'partitions'), refused), check, who)
+    return _crossnobis(a, dev, batch_centres, as_tensor, who)

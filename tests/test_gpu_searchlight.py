@@ -170,7 +170,7 @@ def test_nan_in_the_pad_of_the_patterns_stays_there(geo):
     X, y, fold = data(np.random.RandomState(14), 45, 33, 3, folds=3)
     balls = ring(33, 2)
     res = run_device((X, y, balls, fold), dict(scores=True, C=3), geo)
-    a = sl._check(X, y, balls, fold, None, True, None, 'class', 'empirical', 1e-9, True, False, None, 't')
+    a = sl._check(X, y, balls, fold, None, True, None, True, False, None, 't')
     plan = sl._device_plan(a, geo['buckets'][3])
     dev = torch.device('cuda')
     Xt = sl._transposed(torch.as_tensor(X).to(dev), plan.order, dev)

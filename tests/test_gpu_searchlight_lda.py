@@ -219,7 +219,7 @@ def test_nan_in_the_pad_of_the_patterns_stays_there(geo):
     X, y, fold = data(np.random.RandomState(14), 45, 33, 3, folds=3)
     balls = ring(33, 2)
     res = run_device((X, y, balls, fold), dict(scores=True), [32])
-    a = sl._check(X, y, balls, fold, None, True, None, 'class', 'empirical', 1e-9, True, False, None, 't', classifier='lda')
+    a = sl._check(X, y, balls, fold, None, True, None, True, False, None, 't', classifier='lda')
     from gcn_fmri_decoding_amd import ops
     plan = sl._device_plan(a, ops.searchlight_geometry()['buckets'][3])
     dev = torch.device('cuda')
@@ -316,7 +316,7 @@ def test_ledoit_wolf_shrinkage(geo):
     spans = [(0, 5), (0, 40), (0, 100), (115, 120), (225, 230)]
     nb = sp.csr_matrix(np.array([[float(lo <= v < hi) for v in range(M)] for lo, hi in spans]))
     against_host('searchlight_lda_auto', (X, y, nb, fold), dict(shrinkage='auto'), geo)
-    a = sl._check(X, y, nb, fold, None, True, None, 'class', 'empirical', 1e-9, False, False, None, 't', classifier='lda', shrinkage='auto')
+    a = sl._check(X, y, nb, fold, None, True, None, False, False, None, 't', classifier='lda', shrinkage='auto')
     assert a.shrink < 0
     plan = sl._device_plan(a, ops.searchlight_geometry()['buckets'][C])
     dev = torch.device('cuda')

@@ -43,6 +43,22 @@ def synthetic_atlas(V=91282, R=360, cortex=59412, seed=0, scattered=False):
     return lab
 
 
+def _timeit(fn, iters, warm):
+    """``(median, min, max)`` ms of ``iters`` event-timed calls of ``fn`` after ``warm`` untimed ones."""
+    import torch
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for s, e in evs:
+        s.record()
+        fn()
+        e.record()
+    torch.cuda.synchronize()
+    ms = sorted(s.elapsed_time(e) for s, e in evs)
+    return ms[len(ms) // 2], ms[0], ms[-1]
+
+
 def parcellate_leg(args):
     """ops.parcellate on device-resident runs of HCP size against what the parent commit could do -- torch's index_add_ on the
     device, np.add.reduceat on label-sorted columns on the host -- and Parcellation.reduce end to end from host memory."""
@@ -52,18 +68,7 @@ def parcellate_leg(args):
     dev = torch.device('cuda:0')
     results = []
 
-    def timeit(fn, iters):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-        for s, e in evs:
-            s.record()
-            fn()
-            e.record()
-        torch.cuda.synchronize()
-        ms = sorted(s.elapsed_time(e) for s, e in evs)
-        return ms[len(ms) // 2], ms[0], ms[-1]
+    timeit = lambda fn, iters: _timeit(fn, iters, 3)
 
     def wall(fn, reps):
         ts = []
@@ -141,18 +146,7 @@ def glm_leg(args):
     HBM, HBM_SPEC, FMA64 = 6.29e12, 8.0e12, 78.6e12 / 2
     results = []
 
-    def timeit(fn, iters):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-        for s, e in evs:
-            s.record()
-            fn()
-            e.record()
-        torch.cuda.synchronize()
-        ms = sorted(s.elapsed_time(e) for s, e in evs)
-        return ms[len(ms) // 2], ms[0], ms[-1]
+    timeit = lambda fn, iters: _timeit(fn, iters, 3)
 
     def note(name, shape, t, nbytes, fmas, dispatch=''):
         med, lo, hi = t
@@ -210,29 +204,36 @@ def glm_leg(args):
             json.dump(results, f, indent=1)
 
 
+def _searchlight_problem(offset=1e4, noise=50.0, signal=25.0):
+    """The problem of the searchlight legs: the synthetic 10k-vertex kNN graph (M = 10466) and its 2-hop balls, ``S = 2048`` patterns
+    of ``C = 8`` classes, ``offset + noise * N(0, 1)`` plus a class pattern of ``signal * N(0, 1)`` ->
+    ``(L, balls, M, S, C, y, X float32 [S, M], the random state after X)``."""
+    from gcn_fmri_decoding_amd import graph
+    S, C = 2048, 8
+    L = graph.synthetic_graph(10000, k=8, levels=1)[0][0]
+    M = int(L.shape[0])
+    rs = np.random.RandomState(0)
+    y = np.arange(S) % C
+    X = (offset + noise * rs.randn(S, M) + signal * rs.randn(C, M)[y]).astype(np.float32)
+    return L, graph.hop_balls(L, 2), M, S, C, y, X, rs
+
+
+def _bucket_launches(of_row, b, up):
+    """``(buckets, [(bucket, its rows int32 on the device)])`` of bucket ``b``; ``b = 0``: the whole pass, every bucket's launch."""
+    ks = [b] if b else sorted(set(of_row.tolist()))
+    return ks, [(k, up(np.flatnonzero(of_row == k).astype(np.int32))) for k in ks]
+
+
 def searchlight_leg(args):
     """chebgcn_searchlight_spread / _fit / _score on the synthetic 10k-vertex kNN graph (M = 10466) with 2-hop balls: 2048
     samples, 8 classes, 2 folds.  The score kernel issues three float64 vector instructions per (sample, class, neighbour) term
     -- subtract, multiply, fma: 4 floating-point operations -- so its floor is the float64 vector issue rate (39.3e12 lane
     instructions a second: the 78.6 TFLOP/s of FMAs, half the fp32 vector rate), and the bytes-once HBM floor is far below."""
     import torch
-    from gcn_fmri_decoding_amd import _lib, graph, ops, searchlight as sl
+    from gcn_fmri_decoding_amd import _lib, ops, searchlight as sl
     dev = torch.device('cuda:0')
     HBM, ISSUE64 = 6.29e12, 78.6e12 / 2
     results = []
-
-    def timeit(fn, iters):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-        for s, e in evs:
-            s.record()
-            fn()
-            e.record()
-        torch.cuda.synchronize()
-        ms = sorted(s.elapsed_time(e) for s, e in evs)
-        return ms[len(ms) // 2], ms[0], ms[-1]
 
     def note(name, shape, t, nbytes, instr, flops, dispatch=''):
         med, lo, hi = t
@@ -244,26 +245,21 @@ def searchlight_leg(args):
               'of 78.6  %s' % (name, shape, med, lo, hi, r['hbm_floor_ms'], r['issue_floor_ms'], med / max(r['issue_floor_ms'], 1e-9),
                                r['tflops'], dispatch), flush=True)
 
-    S, C, F = 2048, 8, 2
-    L = graph.synthetic_graph(10000, k=8, levels=1)[0][0]
-    balls = graph.hop_balls(L, 2)
-    M, nnz = int(L.shape[0]), int(balls.nnz)
-    rs = np.random.RandomState(0)
-    y = np.arange(S) % C
+    _, balls, M, S, C, y, X, _ = _searchlight_problem()
+    F, nnz = 2, int(balls.nnz)
     fold = np.arange(S) // C % F
-    X = (1e4 + 50.0 * rs.randn(S, M) + 25.0 * rs.randn(C, M)[y]).astype(np.float32)
-    a = sl._check(X, y, balls, fold, None, True, None, 'class', 'empirical', 1e-9, False, False, None, 'kbench')
+    a = sl._check(X, y, balls, fold, None, True, None, False, False, None, 'kbench')
     plan = sl._device_plan(a, ops.searchlight_geometry()['buckets'][C])
     up = lambda v: torch.as_tensor(v).to(dev)
     Xt = sl._transposed(up(X), plan.order, dev)
     shape = 'S=%d M=%d C=%d folds=%d nnz=%d' % (S, M, C, F, nnz)
     lptr, lidx, cptr, cidx = up(plan.list_ptr), up(plan.list_idx), up(plan.class_ptr), up(plan.class_idx)
     ntrain = float(plan.list_idx.size)
-    note('searchlight_spread', shape, timeit(lambda: ops.searchlight_spread(Xt, S, lptr, lidx), args.iters),
+    note('searchlight_spread', shape, _timeit(lambda: ops.searchlight_spread(Xt, S, lptr, lidx), args.iters, 3),
          4.0 * M * S + 8.0 * plan.NM * M, 3.0 * ntrain * M, 3.0 * ntrain * M, '')
     print('   ', _lib.last_dispatch())
     eps = 1e-9 * ops.searchlight_spread(Xt, S, lptr, lidx).max(dim=1).values
-    note('searchlight_fit', shape, timeit(lambda: ops.searchlight_fit(Xt, S, cptr, cidx, C, eps), args.iters),
+    note('searchlight_fit', shape, _timeit(lambda: ops.searchlight_fit(Xt, S, cptr, cidx, C, eps), args.iters, 3),
          4.0 * M * S + 24.0 * plan.NM * M * plan.NC, 3.0 * ntrain * M, 3.0 * ntrain * M, _lib.last_dispatch())
     par, lg = ops.searchlight_fit(Xt, S, cptr, cidx, C, eps)
     correct = torch.zeros((1, C, a.U), dtype=torch.int32, device=dev)
@@ -272,7 +268,7 @@ def searchlight_leg(args):
 
     def score():
         ops.searchlight_score(Xt, S, rowptr, colidx, 0, a.U, tabs[0], plan.tmax, C, par, lg, tabs[1], tabs[2], tabs[3], tabs[4], correct)
-    t = timeit(score, args.iters)
+    t = _timeit(score, args.iters, 3)
     terms = float(S) * nnz * plan.NC                            # (sample, neighbour, class) terms the kernel works through
     note('searchlight_score', shape, t, 4.0 * M * S + 24.0 * plan.NM * M * plan.NC + 4.0 * nnz, 3.0 * terms, 4.0 * terms,
          _lib.last_dispatch())
@@ -290,33 +286,14 @@ def searchlight_lda_leg(args):
     lane-FMAs at the float64 vector issue rate (39.3e12 lane instructions a second); factorisation, solves and scoring come on
     top, and the HBM floor (Xt once) is far below."""
     import torch
-    from gcn_fmri_decoding_amd import _lib, graph, ops, searchlight as sl
+    from gcn_fmri_decoding_amd import _lib, ops, searchlight as sl
     dev = torch.device('cuda:0')
     HBM, ISSUE64 = 6.29e12, 78.6e12 / 2
     results = []
-
-    def timeit(fn, iters):
-        for _ in range(2):
-            fn()
-        torch.cuda.synchronize()
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-        for s, e in evs:
-            s.record()
-            fn()
-            e.record()
-        torch.cuda.synchronize()
-        ms = sorted(s.elapsed_time(e) for s, e in evs)
-        return ms[len(ms) // 2], ms[0], ms[-1]
-
-    S, C, F = 2048, 8, 2
-    L = graph.synthetic_graph(10000, k=8, levels=1)[0][0]
-    balls = graph.hop_balls(L, 2)
-    M, nnz = int(L.shape[0]), int(balls.nnz)
-    rs = np.random.RandomState(0)
-    y = np.arange(S) % C
+    _, balls, M, S, C, y, X, _ = _searchlight_problem()
+    F, nnz = 2, int(balls.nnz)
     fold = np.arange(S) // C % F
-    X = (1e4 + 50.0 * rs.randn(S, M) + 25.0 * rs.randn(C, M)[y]).astype(np.float32)
-    a = sl._check(X, y, balls, fold, None, True, None, 'class', 'empirical', 1e-9, False, False, None, 'kbench', classifier='lda')
+    a = sl._check(X, y, balls, fold, None, True, None, False, False, None, 'kbench', classifier='lda')
     plan = sl._device_plan(a, ops.searchlight_geometry()['buckets'][C])
     up = lambda v: torch.as_tensor(v).to(dev)
     Xt = sl._transposed(up(X), plan.order, dev)
@@ -335,18 +312,14 @@ def searchlight_lda_leg(args):
     for shrink, tag in ((0.1, 'g=0.1'), (-1.0, "g='auto'")):
         total = [0.0, 0.0]
         for b in sorted(set(of_row.tolist())) + [0]:
-            if b:
-                launches = [(b, up(np.flatnonzero(of_row == b).astype(np.int32)))]
-                fmas = float(tri[of_row == b].sum()) * ntrain
-            else:                                               # the whole pass: every bucket's launch
-                launches = [(k, up(np.flatnonzero(of_row == k).astype(np.int32))) for k in sorted(set(of_row.tolist()))]
-                fmas = float(tri.sum()) * ntrain
+            ks, launches = _bucket_launches(of_row, b, up)
+            fmas = float(sum(tri[of_row == k].sum() for k in ks)) * ntrain
 
             def run():
                 for k, rows in launches:
                     ops.searchlight_lda(Xt, S, rowptr, colidx, rows, k, cptr, cidx, tabs[0], plan.tmax, C, par, tabs[1], shrink, tabs[2],
                                         tabs[3], tabs[4], correct)
-            med, lo, hi = timeit(run, args.iters)
+            med, lo, hi = _timeit(run, args.iters, 2)
             n_rows = int(sum(r.numel() for _, r in launches))
             nbytes = 4.0 * M * S + 4.0 * nnz
             name = 'searchlight_lda ' + ('all' if not b else '<%d>' % b)
@@ -369,31 +342,12 @@ def searchlight_rdm_leg(args):
     (sum over balls of P (P + 1) / 2) x S lane-FMAs at the float64 vector issue rate (39.3e12 lane instructions a second);
     factorisation and one forward solve per cell come on top, and the HBM floor (Xt once) is far below."""
     import torch
-    from gcn_fmri_decoding_amd import _lib, graph, ops, searchlight as sl
+    from gcn_fmri_decoding_amd import _lib, ops, searchlight as sl
     dev = torch.device('cuda:0')
     HBM, ISSUE64 = 6.29e12, 78.6e12 / 2
     results = []
-
-    def timeit(fn, iters):
-        for _ in range(2):
-            fn()
-        torch.cuda.synchronize()
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-        for s, e in evs:
-            s.record()
-            fn()
-            e.record()
-        torch.cuda.synchronize()
-        ms = sorted(s.elapsed_time(e) for s, e in evs)
-        return ms[len(ms) // 2], ms[0], ms[-1]
-
-    S, C = 2048, 8
-    L = graph.synthetic_graph(10000, k=8, levels=1)[0][0]
-    balls = graph.hop_balls(L, 2)
-    M, nnz = int(L.shape[0]), int(balls.nnz)
-    rs = np.random.RandomState(0)
-    y = np.arange(S) % C
-    X = (1e4 + 50.0 * rs.randn(S, M) + 25.0 * rs.randn(C, M)[y]).astype(np.float32)
+    _, balls, M, S, C, y, X, _ = _searchlight_problem()
+    nnz = int(balls.nnz)
     up = lambda v: torch.as_tensor(v).to(dev)
     for F in (2, 8):
         part = np.arange(S) // C % F
@@ -414,14 +368,13 @@ def searchlight_rdm_leg(args):
                   % (P.mean(), P.max(), tri.sum(), S, 1e3 * tri.sum() * S / ISSUE64), flush=True)
         for shrink, tag in ((0.1, 'g=0.1'), (-1.0, "g='auto'")):
             for b in sorted(set(of_row.tolist())) + [0]:
-                ks = [b] if b else sorted(set(of_row.tolist()))         # 0: the whole pass, every bucket's launch
-                launches = [(k, up(np.flatnonzero(of_row == k).astype(np.int32))) for k in ks]
+                ks, launches = _bucket_launches(of_row, b, up)
                 fmas = float(sum(tri[of_row == k].sum() for k in ks)) * S
 
                 def run():
                     for k, rows in launches:
                         ops.searchlight_rdm(Xt, S, rowptr, colidx, rows, k, cell_ptr, cptr, cidx, C, par, shrink, rdm, gamma_out=gam)
-                med, lo, hi = timeit(run, args.iters)
+                med, lo, hi = _timeit(run, args.iters, 2)
                 n_rows = int(sum(r.numel() for _, r in launches))
                 nbytes = 4.0 * M * S + 4.0 * nnz
                 name = 'searchlight_rdm ' + ('all' if not b else '<%d>' % b)
@@ -449,26 +402,21 @@ def searchlight_svc_leg(args):
     overlaps as many workgroups as the kernel's occupancy admits."""
     import scipy.sparse as sp
     import torch
-    from gcn_fmri_decoding_amd import _lib, graph, ops, searchlight as sl
+    from gcn_fmri_decoding_amd import _lib, ops, searchlight as sl
     dev = torch.device('cuda:0')
     ISSUE64, STEP_S, CUS = 78.6e12 / 2, 50e-9, 256
     OCC = {32: 4, 64: 2, 128: 1}                                # workgroups per CU: the compiler's report (DESIGN 4.26)
     results = []
-    S, C, G, F, CAP = 2048, 8, 16, 2, 100
-    L = graph.synthetic_graph(10000, k=8, levels=1)[0][0]
-    M = int(L.shape[0])
-    rs = np.random.RandomState(0)
-    y = np.arange(S) % C
+    _, balls, M, S, C, y, X, rs = _searchlight_problem(offset=0.0, noise=1.0, signal=0.5)
+    G, F, CAP = 16, 2, 100
     fold = np.arange(S) // C % F
     groups = (np.arange(S) // (C * F) % G).tolist()
-    X = (rs.randn(S, M) + 0.5 * rs.randn(C, M)[y]).astype(np.float32)
     parcels = np.zeros((360, M), np.int8)
     for r in range(360):
         parcels[r, rs.choice(M, 300, replace=False)] = 1
     up = lambda v: torch.as_tensor(v).to(dev)
-    for tag, rows in (('balls', graph.hop_balls(L, 2)), ('parcels', sp.csr_matrix(parcels))):
-        a = sl._check(X, y, rows, fold, groups, True, None, 'class', 'empirical', 1e-9, False, False, None, 'kbench', classifier='svc',
-                      max_iter=CAP)
+    for tag, rows in (('balls', balls), ('parcels', sp.csr_matrix(parcels))):
+        a = sl._check(X, y, rows, fold, groups, True, None, False, False, None, 'kbench', classifier='svc', max_iter=CAP)
         plan = sl._device_plan(a, ops.searchlight_geometry()['buckets'][C])
         Xt = sl._transposed(up(X), plan.order, dev)
         n = np.diff(plan.list_ptr)
@@ -484,16 +432,7 @@ def searchlight_svc_leg(args):
         def run():
             ops.searchlight_svm(Xt, S, rowptr, colidx, centres, models, bucket, tabs[0], tabs[1], tabs[2], plan.tmax, C, 1.0, 'squared_hinge',
                                 1e-3, CAP, tabs[3], tabs[4], tabs[5], correct, sweeps=sweeps, residual=resid)
-        run()
-        torch.cuda.synchronize()
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.iters)]
-        for s, e in evs:
-            s.record()
-            run()
-            e.record()
-        torch.cuda.synchronize()
-        ms = sorted(s.elapsed_time(e) for s, e in evs)
-        med, lo, hi = ms[len(ms) // 2], ms[0], ms[-1]
+        med, lo, hi = _timeit(run, args.iters, 1)
         P = np.diff(a.indptr).astype(np.float64)
         nn = float(n[0])
         gram_ops = 2.0 * P.sum() * plan.NM * (nn * (nn + 1) / 2 + 64.0 * nn)     # the triangle and the test samples' rows (64 a model)
