@@ -16,20 +16,31 @@ constexpr int FC_WAVES = 8;
 constexpr int FC_CHUNK = 32;   // input features per chunk of the forward's reduction
 constexpr int FC_U = 2;        // chunks a wave keeps in flight
 
-// (fc_fwd_dropout_kernel below repeats this kernel's loads, tile and sums with a sample axis and a mask: change them together.)
-// gridDim.z > 1: the reduction is also split across workgroups (chunks [z*cps, (z+1)*cps) of FC_CHUNK input features); the
-// partial tiles go to part_out[z][b][o] and fc_fwd_reduce_kernel adds them in order.
-__global__ void __launch_bounds__(FC_WAVES * 64)
-fc_fwd_kernel(const float* __restrict__ x, long long ldx, const float* __restrict__ W, const float* __restrict__ bias,
-              float* __restrict__ y, float* __restrict__ part_out, int B, int I, int O, int relu, int cps) {
+// The forward tile, one body for both kernels.  gridDim.z > 1: the reduction is also split across workgroups (chunks
+// [bz*cps, (bz+1)*cps) of FC_CHUNK input features); the partial tiles go to part_out[bz][s][b][o] and fc_fwd_reduce_kernel adds
+// them in order.  MC: S Monte-Carlo dropout samples of the layer (models_gcn.base_model.predict_mc),
+//   y[s][b][o] = act( sum_i m(s0 + s, win[b], i) * x_s[b][i] * inv_keep * W[i][o] + bias[o] ),   x_s = x + s * sx
+// (sx == 0: the S samples share one x, the first dropout site), blockIdx.z = s * nsplit + bz.  The mask is formed in registers
+// on the 16 values of x a lane holds per chunk: feature i of window w is kept iff chebgcn_aug_draw(seed, (s0 + s) *
+// CHEBGCN_MC_SITES + layer, w, i) < thresh.  A lane reads ONE row of x, so the two key words of its window are computed once,
+// before the loop.  No mask is ever stored.  Without MC there is one sample (S = 1, s = 0), no keys and no mask: sx, win, nsplit
+// and what follows it are unused.
+template <bool MC>
+__device__ __forceinline__ void
+fc_fwd_tile(const float* x, long long ldx, long long sx, const float* W, const float* bias, float* y, float* part_out,
+            const int32_t* win, int S, int B, int I, int O, int relu, int cps, int nsplit, uint32_t seed, uint32_t s0,
+            uint32_t layer, uint32_t thresh, float inv_keep) {
     __shared__ float part[FC_WAVES][32][33];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
-    const int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    const int bx = blockIdx.x, by = blockIdx.y;
+    const int s = MC ? blockIdx.z / nsplit : 0, bz = MC ? blockIdx.z - s * nsplit : blockIdx.z;
     const int o0 = bx * 32, b0 = by * 32;
     const int brow = min(b0 + c, B - 1), ocol = min(o0 + c, O - 1);
-    const float* xr = x + (size_t)brow * ldx;
+    const float* xr = MC ? x + (size_t)s * sx + (size_t)brow * ldx : x + (size_t)brow * ldx;
     const float* wc = W + ocol;
+    AugKeys keys = {};
+    if constexpr (MC) keys = aug_keys(seed, (s0 + (uint32_t)s) * CHEBGCN_MC_SITES + layer, (uint32_t)win[brow]);   // (the hash only: never an address)
     const int nchunks = (I + FC_CHUNK - 1) / FC_CHUNK;
     const int q_lo = bz * cps, q_hi = min(q_lo + cps, nchunks);
     f32x16 acc;
@@ -60,103 +71,15 @@ fc_fwd_kernel(const float* __restrict__ x, long long ldx, const float* __restric
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const bool ok = q < q_hi && k + 4 * t + j < I;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ok ? av[u][t][j] : 0.f, ok ? bv[u][t][j] : 0.f, acc, 0, 0, 0);
-                }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) part[wave][acc_row(j, h)][c] = acc[j];
-    __syncthreads();
-    for (int e = threadIdx.x; e < 32 * 32; e += FC_WAVES * 64) {
-        const int r = e >> 5, cc = e & 31;
-        float s = part[0][r][cc];
-#pragma unroll
-        for (int w = 1; w < FC_WAVES; ++w) s += part[w][r][cc];
-        if (b0 + r < B && o0 + cc < O) {
-            if (part_out) {
-                part_out[((size_t)bz * B + b0 + r) * O + o0 + cc] = s;
-            } else {
-                s += bias ? bias[o0 + cc] : 0.f;
-                y[(size_t)(b0 + r) * O + o0 + cc] = relu ? fmaxf(s, 0.f) : s;
-            }
-        }
-    }
-}
-
-__global__ void __launch_bounds__(256)
-fc_fwd_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ y, int BO, int O,
-                     int S, int relu) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= BO) return;
-    float v[16];
-    float s = 0.f;
-    for (int z0 = 0; z0 < S; z0 += 16) {                 // sixteen loads in flight, added in split order
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = part[(size_t)min(z0 + u, S - 1) * BO + e];
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-            if (z0 + u < S) s += v[u];
-    }
-    s += bias ? bias[e % O] : 0.f;
-    y[e] = relu ? fmaxf(s, 0.f) : s;
-}
-
-// fc_fwd_kernel for S Monte-Carlo dropout samples of one layer (models_gcn.base_model.predict_mc):
-//   y[s][b][o] = act( sum_i m(s0 + s, win[b], i) * x_s[b][i] * inv_keep * W[i][o] + bias[o] ),   x_s = x + s * sx
-// (sx == 0: the S samples share one x, the first dropout site).  blockIdx.z = s * nsplit + split.  The same tile, chunks, wave
-// order and split reduction as fc_fwd_kernel; the mask is formed in registers on the 16 values of x a lane holds per chunk:
-// feature i of window w is kept iff chebgcn_aug_draw(seed, (s0 + s) * CHEBGCN_MC_SITES + layer, w, i) < thresh.  A lane reads
-// ONE row of x, so the two key words of its window are computed once, before the loop.  No mask is ever stored.
-// Everything but the sample axis and the mask is fc_fwd_kernel's, line for line (whose arithmetic this file leaves as it was):
-// a change to the loads, the guards for ldx > I, the tile or the part_out layout belongs in both.
-__global__ void __launch_bounds__(FC_WAVES * 64)
-fc_fwd_dropout_kernel(const float* __restrict__ x, long long ldx, long long sx, const float* __restrict__ W,
-                      const float* __restrict__ bias, float* __restrict__ y, float* __restrict__ part_out,
-                      const int32_t* __restrict__ win, int S, int B, int I, int O, int relu, int cps, int nsplit, uint32_t seed,
-                      uint32_t s0, uint32_t layer, uint32_t thresh, float inv_keep) {
-    __shared__ float part[FC_WAVES][32][33];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = lane & 31, h = lane >> 5;
-    const int bx = blockIdx.x, by = blockIdx.y;
-    const int s = blockIdx.z / nsplit, bz = blockIdx.z - s * nsplit;
-    const int o0 = bx * 32, b0 = by * 32;
-    const int brow = min(b0 + c, B - 1), ocol = min(o0 + c, O - 1);
-    const float* xr = x + (size_t)s * sx + (size_t)brow * ldx;
-    const float* wc = W + ocol;
-    const AugKeys keys = aug_keys(seed, (s0 + (uint32_t)s) * CHEBGCN_MC_SITES + layer, (uint32_t)win[brow]);   // (the hash only: never an address)
-    const int nchunks = (I + FC_CHUNK - 1) / FC_CHUNK;
-    const int q_lo = bz * cps, q_hi = min(q_lo + cps, nchunks);
-    f32x16 acc;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-    for (int q0 = q_lo + wave; q0 < q_hi; q0 += FC_WAVES * FC_U) {
-        f32x4 av[FC_U][4];
-        float bv[FC_U][4][4];
-#pragma unroll
-        for (int u = 0; u < FC_U; ++u) {
-            const int q = q0 + FC_WAVES * u;
-            const int k = (q < q_hi ? FC_CHUNK * q : 0) + 16 * h;    // beyond the range: any readable address, multiplied by zero
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                av[u][t] = *reinterpret_cast<const f32x4*>(xr + (k + 4 * t + 3 < ldx ? k + 4 * t : 0));
-#pragma unroll
-                for (int j = 0; j < 4; ++j) bv[u][t][j] = wc[(size_t)(k + 4 * t + j < I ? k + 4 * t + j : 0) * O];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < FC_U; ++u) {
-            const int q = q0 + FC_WAVES * u;
-            const int k = FC_CHUNK * q + 16 * h;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
                     // a value past I (the tail of a row with ldx > I, a chunk past the range) never reaches the product: a select
                     const bool ok = q < q_hi && k + 4 * t + j < I;
-                    const bool kept = ok && aug_draw(keys, (uint32_t)(k + 4 * t + j)) < thresh;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kept ? __fmul_rn(av[u][t][j], inv_keep) : 0.f,
-                                                               ok ? bv[u][t][j] : 0.f, acc, 0, 0, 0);
+                    if constexpr (MC) {
+                        const bool kept = ok && aug_draw(keys, (uint32_t)(k + 4 * t + j)) < thresh;
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kept ? __fmul_rn(av[u][t][j], inv_keep) : 0.f,
+                                                                   ok ? bv[u][t][j] : 0.f, acc, 0, 0, 0);
+                    } else {
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ok ? av[u][t][j] : 0.f, ok ? bv[u][t][j] : 0.f, acc, 0, 0, 0);
+                    }
                 }
         }
     }
@@ -177,6 +100,38 @@ fc_fwd_dropout_kernel(const float* __restrict__ x, long long ldx, long long sx, 
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(FC_WAVES * 64)
+fc_fwd_kernel(const float* __restrict__ x, long long ldx, const float* __restrict__ W, const float* __restrict__ bias,
+              float* __restrict__ y, float* __restrict__ part_out, int B, int I, int O, int relu, int cps) {
+    fc_fwd_tile<false>(x, ldx, 0, W, bias, y, part_out, nullptr, 1, B, I, O, relu, cps, 1, 0, 0, 0, 0, 1.f);
+}
+
+__global__ void __launch_bounds__(FC_WAVES * 64)
+fc_fwd_dropout_kernel(const float* __restrict__ x, long long ldx, long long sx, const float* __restrict__ W,
+                      const float* __restrict__ bias, float* __restrict__ y, float* __restrict__ part_out,
+                      const int32_t* __restrict__ win, int S, int B, int I, int O, int relu, int cps, int nsplit, uint32_t seed,
+                      uint32_t s0, uint32_t layer, uint32_t thresh, float inv_keep) {
+    fc_fwd_tile<true>(x, ldx, sx, W, bias, y, part_out, win, S, B, I, O, relu, cps, nsplit, seed, s0, layer, thresh, inv_keep);
+}
+
+__global__ void __launch_bounds__(256)
+fc_fwd_reduce_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ y, int BO, int O,
+                     int S, int relu) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= BO) return;
+    float v[16];
+    float s = 0.f;
+    for (int z0 = 0; z0 < S; z0 += 16) {                 // sixteen loads in flight, added in split order
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = part[(size_t)min(z0 + u, S - 1) * BO + e];
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+            if (z0 + u < S) s += v[u];
+    }
+    s += bias ? bias[e % O] : 0.f;
+    y[e] = relu ? fmaxf(s, 0.f) : s;
 }
 
 // dW[i][o] = sum_b x[b][i] * gm[b][o],  db[o] = sum_b gm[b][o],  gm = g gated by y > 0 (ReluGrad) where y is given.
@@ -425,48 +380,9 @@ softmax_xent_kernel(const float* __restrict__ z, const LabelT* __restrict__ y, f
 
 using namespace chebgcn;
 
-// splits of the reduction across workgroups: enough workgroups for two per CU, at least 64 chunks (512 input features) each
-static int fc_splits(int B, int I, int O) {
-    const int tiles = ((O + 31) / 32) * ((B + 31) / 32);
-    int s = 512 / tiles;
-    const int by_len = (I + 511) / 512;
-    if (s > by_len) s = by_len;
-    return s < 1 ? 1 : s;
-}
-
-extern "C" int chebgcn_fc_fwd_supported(int B, int I, int O) {
-    return B > 0 && I > 0 && O > 0 && I <= (1 << 20) && (long long)B * O <= (1 << 20);
-}
-
-extern "C" size_t chebgcn_fc_fwd_workspace(int B, int I, int O) {
-    if (!chebgcn_fc_fwd_supported(B, I, O)) return 0;
-    const int S = fc_splits(B, I, O);
-    return S > 1 ? (size_t)S * B * O * sizeof(float) : 0;
-}
-
-extern "C" int chebgcn_fc_fwd(const float* x, int64_t ldx, const float* W, const float* bias, float* y, void* workspace,
-                              size_t workspace_bytes, int B, int I, int O, int relu, chebgcn_stream stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    CG_REQUIRE(x && W && y && B > 0 && I > 0 && O > 0 && ldx >= I, "fc_fwd: bad argument");
-    if (!chebgcn_fc_fwd_supported(B, I, O) || (ldx & 3) || ((uintptr_t)x & 15))
-        return CHEBGCN_EUNSUPPORTED;
-    const int S = fc_splits(B, I, O);
-    const int nchunks = (I + FC_CHUNK - 1) / FC_CHUNK, cps = (nchunks + S - 1) / S;
-    CG_REQUIRE(S == 1 || (workspace && workspace_bytes >= chebgcn_fc_fwd_workspace(B, I, O)), "fc_fwd: workspace too small");
-    dim3 grid((O + 31) / 32, (B + 31) / 32, S);
-    note_dispatch(S > 1 ? "fc_fwd_kernel<split>" : "fc_fwd_kernel");
-    if (S > 1) note_dispatch_more("fc_fwd_reduce_kernel");
-    hipLaunchKernelGGL(fc_fwd_kernel, grid, dim3(FC_WAVES * 64), 0, stream, x, (long long)ldx, W, bias, y,
-                       S > 1 ? (float*)workspace : nullptr, B, I, O, relu, cps);
-    if (S > 1)
-        hipLaunchKernelGGL(fc_fwd_reduce_kernel, dim3((B * O + 255) / 256), dim3(256), 0, stream, (const float*)workspace, bias,
-                           y, B * O, O, S, relu);
-    CG_HIP(hipGetLastError());
-    return CHEBGCN_OK;
-}
-
-// the splits of fc_fwd over the tiles of all S samples of the launch
-static int fc_dropout_splits(int S, int B, int I, int O) {
+// splits of the reduction across workgroups, over the tiles of all S samples of the launch: enough workgroups for two per CU,
+// at least 64 chunks (512 input features) each
+static int fc_splits(int S, int B, int I, int O) {
     const long long tiles = (long long)S * ((O + 31) / 32) * ((B + 31) / 32);
     long long s = 512 / tiles;
     const int by_len = (I + 511) / 512;
@@ -480,41 +396,68 @@ extern "C" int chebgcn_fc_fwd_dropout_supported(int S, int B, int I, int O) {
 
 extern "C" size_t chebgcn_fc_fwd_dropout_workspace(int S, int B, int I, int O) {
     if (!chebgcn_fc_fwd_dropout_supported(S, B, I, O)) return 0;
-    const int ns = fc_dropout_splits(S, B, I, O);
+    const int ns = fc_splits(S, B, I, O);
     return ns > 1 ? (size_t)ns * S * B * O * sizeof(float) : 0;
+}
+
+// the plain layer is one sample of the dropout one
+extern "C" int chebgcn_fc_fwd_supported(int B, int I, int O) { return chebgcn_fc_fwd_dropout_supported(1, B, I, O); }
+
+extern "C" size_t chebgcn_fc_fwd_workspace(int B, int I, int O) { return chebgcn_fc_fwd_dropout_workspace(1, B, I, O); }
+
+// Both forward entry points behind their own argument checks: win == NULL is the plain layer (S = 1), else S dropout samples.
+// `what` names the entry point in the refusal.
+static int fc_fwd_launch(const char* what, const float* x, int64_t ldx, int64_t sx, const float* W, const float* bias, float* y,
+                         void* workspace, size_t workspace_bytes, const int32_t* win, int S, int B, int I, int O, int relu,
+                         uint32_t seed, uint32_t s0, uint32_t layer, uint32_t threshold, float inv_keep, hipStream_t stream) {
+    if (!chebgcn_fc_fwd_dropout_supported(S, B, I, O) || (ldx & 3) || (sx & 3) || ((uintptr_t)x & 15))
+        return CHEBGCN_EUNSUPPORTED;
+    const int ns = fc_splits(S, B, I, O);
+    const int nchunks = (I + FC_CHUNK - 1) / FC_CHUNK, cps = (nchunks + ns - 1) / ns;
+    CG_REQUIRE(ns == 1 || (workspace && workspace_bytes >= chebgcn_fc_fwd_dropout_workspace(S, B, I, O)), "%s: workspace too small",
+               what);
+    dim3 grid((O + 31) / 32, (B + 31) / 32, S * ns);             // S * ns <= max(S, 512)
+    float* part = ns > 1 ? (float*)workspace : nullptr;
+    if (!win) {
+        note_dispatch(ns > 1 ? "fc_fwd_kernel<split>" : "fc_fwd_kernel");
+    } else if (sx == 0) {
+        note_dispatch(ns > 1 ? "fc_fwd_dropout_kernel<shared, split>" : "fc_fwd_dropout_kernel<shared>");
+    } else {
+        note_dispatch(ns > 1 ? "fc_fwd_dropout_kernel<per_sample, split>" : "fc_fwd_dropout_kernel<per_sample>");
+    }
+    if (ns > 1) note_dispatch_more("fc_fwd_reduce_kernel");
+    if (!win)
+        hipLaunchKernelGGL(fc_fwd_kernel, grid, dim3(FC_WAVES * 64), 0, stream, x, (long long)ldx, W, bias, y, part, B, I, O, relu,
+                           cps);
+    else
+        hipLaunchKernelGGL(fc_fwd_dropout_kernel, grid, dim3(FC_WAVES * 64), 0, stream, x, (long long)ldx, (long long)sx, W, bias, y,
+                           part, win, S, B, I, O, relu, cps, ns, seed, s0, layer, threshold, inv_keep);
+    if (ns > 1)
+        hipLaunchKernelGGL(fc_fwd_reduce_kernel, dim3((S * B * O + 255) / 256), dim3(256), 0, stream, (const float*)workspace,
+                           bias, y, S * B * O, O, ns, relu);
+    CG_HIP(hipGetLastError());
+    return CHEBGCN_OK;
+}
+
+extern "C" int chebgcn_fc_fwd(const float* x, int64_t ldx, const float* W, const float* bias, float* y, void* workspace,
+                              size_t workspace_bytes, int B, int I, int O, int relu, chebgcn_stream stream_) {
+    CG_REQUIRE(x && W && y && B > 0 && I > 0 && O > 0 && ldx >= I, "fc_fwd: bad argument");
+    return fc_fwd_launch("fc_fwd", x, ldx, 0, W, bias, y, workspace, workspace_bytes, nullptr, 1, B, I, O, relu, 0, 0, 0, 0, 1.f,
+                         (hipStream_t)stream_);
 }
 
 extern "C" int chebgcn_fc_fwd_dropout(const float* x, int64_t ldx, int64_t sample_stride, const float* W, const float* bias,
                                       float* y, void* workspace, size_t workspace_bytes, const int32_t* win, int S, int B, int I,
                                       int O, int relu, uint32_t seed, int s0, int layer, uint32_t threshold, float inv_keep,
                                       chebgcn_stream stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     CG_REQUIRE(x && W && y && win && S > 0 && B > 0 && I > 0 && O > 0 && ldx >= I, "fc_fwd_dropout: bad argument");
     CG_REQUIRE(sample_stride == 0 || sample_stride >= (int64_t)(B - 1) * ldx + I,
                "fc_fwd_dropout: a sample stride of %lld elements is neither 0 nor a whole [B][ldx] matrix", (long long)sample_stride);
     CG_REQUIRE(s0 >= 0 && layer >= 0 && layer < CHEBGCN_MC_SITES, "fc_fwd_dropout: bad sample number %d or dropout site %d", s0,
                layer);
     CG_REQUIRE(inv_keep >= 1.f && inv_keep < __builtin_inff(), "fc_fwd_dropout: inv_keep = 1 / keep must be a finite number >= 1");
-    if (!chebgcn_fc_fwd_dropout_supported(S, B, I, O) || (ldx & 3) || (sample_stride & 3) || ((uintptr_t)x & 15))
-        return CHEBGCN_EUNSUPPORTED;
-    const int ns = fc_dropout_splits(S, B, I, O);
-    const int nchunks = (I + FC_CHUNK - 1) / FC_CHUNK, cps = (nchunks + ns - 1) / ns;
-    CG_REQUIRE(ns == 1 || (workspace && workspace_bytes >= chebgcn_fc_fwd_dropout_workspace(S, B, I, O)),
-               "fc_fwd_dropout: workspace too small");
-    dim3 grid((O + 31) / 32, (B + 31) / 32, S * ns);             // S * ns <= max(S, 512)
-    if (sample_stride == 0)
-        note_dispatch(ns > 1 ? "fc_fwd_dropout_kernel<shared, split>" : "fc_fwd_dropout_kernel<shared>");
-    else
-        note_dispatch(ns > 1 ? "fc_fwd_dropout_kernel<per_sample, split>" : "fc_fwd_dropout_kernel<per_sample>");
-    if (ns > 1) note_dispatch_more("fc_fwd_reduce_kernel");
-    hipLaunchKernelGGL(fc_fwd_dropout_kernel, grid, dim3(FC_WAVES * 64), 0, stream, x, (long long)ldx, (long long)sample_stride, W,
-                       bias, y, ns > 1 ? (float*)workspace : nullptr, win, S, B, I, O, relu, cps, ns, seed, (uint32_t)s0,
-                       (uint32_t)layer, threshold, inv_keep);
-    if (ns > 1)
-        hipLaunchKernelGGL(fc_fwd_reduce_kernel, dim3((S * B * O + 255) / 256), dim3(256), 0, stream, (const float*)workspace,
-                           bias, y, S * B * O, O, ns, relu);
-    CG_HIP(hipGetLastError());
-    return CHEBGCN_OK;
+    return fc_fwd_launch("fc_fwd_dropout", x, ldx, sample_stride, W, bias, y, workspace, workspace_bytes, win, S, B, I, O, relu, seed,
+                         (uint32_t)s0, (uint32_t)layer, threshold, inv_keep, (hipStream_t)stream_);
 }
 
 extern "C" int chebgcn_fc_bwd(const float* x, int64_t ldx, const float* W, const float* g, const float* y, float* dW,

@@ -477,99 +477,57 @@ feature_mean_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, in
 }
 
 // ---- Adam, TensorFlow form (epsilon outside the bias correction) ------------------------
-__global__ void __launch_bounds__(256)
-adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-            float* __restrict__ v, int64_t n, float lr_t, float b1, float b2, float eps, float gscale,
-            float l2) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float pi = p[i];
-        const float gi = fmaf(l2, pi, gscale * g[i]);
-        const float mi = m[i] + (1.f - b1) * (gi - m[i]);
-        const float vi = v[i] + (1.f - b2) * (gi * gi - v[i]);
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = pi - lr_t * mi / (sqrtf(vi) + eps);
-    }
-}
-
-// the same with the step size read from device memory: a captured HIP graph of the training step replays with the
-// value the host wrote before the launch (lr_t changes every step)
-__global__ void __launch_bounds__(256)
-adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                float* __restrict__ v, int64_t n, const float* __restrict__ lr_t_dev, float b1, float b2, float eps,
-                float gscale, float l2) {
-    const float lr_t = *lr_t_dev;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float pi = p[i];
-        const float gi = fmaf(l2, pi, gscale * g[i]);
-        const float mi = m[i] + (1.f - b1) * (gi - m[i]);
-        const float vi = v[i] + (1.f - b2) * (gi * gi - v[i]);
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = pi - lr_t * mi / (sqrtf(vi) + eps);
-    }
-}
-
-// Adam as above (step size by value, or from device memory when lr_t_dev is set) that also leaves the sum of squares of the
-// PRE-update variables it walks -- the L2 term of the loss (models_gcn.py:262-266: regularization * sum tf.nn.l2_loss) -- as one
-// partial per workgroup (fixed-order tree inside the workgroup); chebgcn_loss_bookkeeping adds the partials in index order.
-__global__ void __launch_bounds__(256)
-adam_sq_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-               float lr_t_val, const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float gscale, float l2,
-               float* __restrict__ sq_part, int64_t n_reg) {      // elements [n_reg, n): no L2 term, not in the sum of squares
-    __shared__ float red[256];
-    const float lr_t = lr_t_dev ? *lr_t_dev : lr_t_val;
-    float sq = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float pi = p[i];
-        const bool rg = i < n_reg;
-        sq = rg ? fmaf(pi, pi, sq) : sq;
-        const float gi = fmaf(rg ? l2 : 0.f, pi, gscale * g[i]);
-        const float mi = m[i] + (1.f - b1) * (gi - m[i]);
-        const float vi = v[i] + (1.f - b2) * (gi * gi - v[i]);
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = pi - lr_t * mi / (sqrtf(vi) + eps);
-    }
-    red[threadIdx.x] = sq;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sq_part[blockIdx.x] = red[0];
-}
-
-// Nadam: tf.contrib.opt.NadamOptimizer (finetuning_cgcnn.training, models_gcn.py:895-933) is TF's ApplyAdam with
+// One update for every optimizer kernel.  The step size comes by value, or from device memory when lr_t_dev is set: a captured
+// HIP graph of the training step replays with the value the host wrote before the launch (lr_t changes every step).
+// Elements [0, n_reg) take the L2 term, the rest the plain update.  SQ: the kernel also leaves the sum of squares of the
+// PRE-update variables in [0, n_reg) -- the L2 term of the loss (models_gcn.py:262-266: regularization * sum tf.nn.l2_loss) -- as
+// one partial per workgroup (fixed-order tree inside the workgroup); chebgcn_loss_bookkeeping adds the partials in index order.
+// NESTEROV: tf.contrib.opt.NadamOptimizer (finetuning_cgcnn.training, models_gcn.py:895-933), TF's ApplyAdam with
 // use_nesterov = true:  m += (1-b1)(g-m);  v += (1-b2)(g^2-v);  p -= (g(1-b1) + b1 m) lr_t / (sqrt(v) + eps).
-// Everything else as adam_sq_kernel: L2 term and partial sums of squares over [0, n_reg), plain update behind.
 // (Four elements per lane in 16-byte accesses measured the same: 39.2 us for the 6.0 M variables of training.py's head.)
-__global__ void __launch_bounds__(256)
-nadam_sq_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-                float lr_t_val, const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float gscale, float l2,
-                float* __restrict__ sq_part, int64_t n_reg) {
-    __shared__ float red[256];
+template <bool NESTEROV, bool SQ>
+__device__ __forceinline__ void
+adam_update(float* p, const float* g, float* m, float* v, int64_t n, float lr_t_val, const float* lr_t_dev, float b1, float b2,
+            float eps, float gscale, float l2, float* sq_part, int64_t n_reg) {
     const float lr_t = lr_t_dev ? *lr_t_dev : lr_t_val;
     float sq = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float pi = p[i];
         const bool rg = i < n_reg;
-        sq = rg ? fmaf(pi, pi, sq) : sq;
+        if constexpr (SQ) sq = rg ? fmaf(pi, pi, sq) : sq;
         const float gi = fmaf(rg ? l2 : 0.f, pi, gscale * g[i]);
         const float mi = m[i] + (1.f - b1) * (gi - m[i]);
         const float vi = v[i] + (1.f - b2) * (gi * gi - v[i]);
         m[i] = mi;
         v[i] = vi;
-        p[i] = pi - (gi * (1.f - b1) + b1 * mi) * lr_t / (sqrtf(vi) + eps);
+        if constexpr (NESTEROV)
+            p[i] = pi - (gi * (1.f - b1) + b1 * mi) * lr_t / (sqrtf(vi) + eps);
+        else
+            p[i] = pi - lr_t * mi / (sqrtf(vi) + eps);
     }
-    red[threadIdx.x] = sq;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
+    if constexpr (SQ) {
+        __shared__ float red[256];
+        red[threadIdx.x] = sq;
         __syncthreads();
+        for (int d = 128; d > 0; d >>= 1) {
+            if ((int)threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) sq_part[blockIdx.x] = red[0];
     }
-    if (threadIdx.x == 0) sq_part[blockIdx.x] = red[0];
 }
+
+#define CHEBGCN_ADAM_KERNEL(name, NESTEROV, SQ)                                                                               \
+    __global__ void __launch_bounds__(256)                                                                                    \
+    name(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,         \
+         float lr_t_val, const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float gscale, float l2,           \
+         float* __restrict__ sq_part, int64_t n_reg) {                                                                        \
+        adam_update<NESTEROV, SQ>(p, g, m, v, n, lr_t_val, lr_t_dev, b1, b2, eps, gscale, l2, sq_part, n_reg);                \
+    }
+CHEBGCN_ADAM_KERNEL(adam_kernel, false, false)
+CHEBGCN_ADAM_KERNEL(adam_sq_kernel, false, true)
+CHEBGCN_ADAM_KERNEL(nadam_sq_kernel, true, true)
+#undef CHEBGCN_ADAM_KERNEL
 
 // loss = cross_entropy + half_reg * sum(partials);  the ExponentialMovingAverage(0.9) of the loss with its zero-debiasing
 // (models_gcn.py:269-275): ema += (1 - decay) * (loss - ema);  loss_average = ema * corr.  One wave, one launch (torch: dot x 2,
@@ -1001,72 +959,60 @@ extern "C" int chebgcn_feature_mean_bwd(const float* dy, float* dx, int B, int M
     return CHEBGCN_OK;
 }
 
-extern "C" int chebgcn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,
-                                 float beta2, float eps, float grad_scale, float l2, chebgcn_stream stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    CG_REQUIRE(p && g && m && v && n >= 0, "adam_step: bad argument");
-    if (n == 0) return CHEBGCN_OK;
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, n, lr_t, beta1, beta2,
-                       eps, grad_scale, l2);
-    CG_HIP(hipGetLastError());
-    return CHEBGCN_OK;
-}
-
-extern "C" int chebgcn_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_t_dev,
-                                     float beta1, float beta2, float eps, float grad_scale, float l2,
-                                     chebgcn_stream stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    CG_REQUIRE(p && g && m && v && lr_t_dev && n >= 0, "adam_step_dev: bad argument");
-    if (n == 0) return CHEBGCN_OK;
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adam_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, n, lr_t_dev, beta1, beta2,
-                       eps, grad_scale, l2);
-    CG_HIP(hipGetLastError());
-    return CHEBGCN_OK;
-}
-
 extern "C" int chebgcn_adam_partials(int64_t n) {
     int64_t blocks = (n + 255) / 256;
     return (int)(blocks > 4096 ? 4096 : blocks < 0 ? 0 : blocks);
 }
 
-extern "C" int chebgcn_adam_step_sq(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, const float* lr_t_dev,
-                                    float beta1, float beta2, float eps, float grad_scale, float l2, float* sq_partials,
-                                    chebgcn_stream stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    CG_REQUIRE(p && g && m && v && sq_partials && n > 0, "adam_step_sq: bad argument");
-    note_dispatch("adam_sq_kernel");
-    hipLaunchKernelGGL(adam_sq_kernel, dim3((unsigned)chebgcn_adam_partials(n)), dim3(256), 0, stream, p, g, m, v, n, lr_t, lr_t_dev,
-                       beta1, beta2, eps, grad_scale, l2, sq_partials, n);
+// every optimizer entry point behind its own argument check, its n == 0 rule and its dispatch note
+typedef void (*adam_kernel_t)(float*, const float*, float*, float*, int64_t, float, const float*, float, float, float, float,
+                              float, float*, int64_t);
+static int adam_launch(adam_kernel_t kernel, float* p, const float* g, float* m, float* v, int64_t n, int64_t n_reg, float lr_t,
+                       const float* lr_t_dev, float beta1, float beta2, float eps, float grad_scale, float l2, float* sq_partials,
+                       chebgcn_stream stream_) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)chebgcn_adam_partials(n)), dim3(256), 0, (hipStream_t)stream_, p, g, m, v, n, lr_t,
+                       lr_t_dev, beta1, beta2, eps, grad_scale, l2, sq_partials, n_reg);
     CG_HIP(hipGetLastError());
     return CHEBGCN_OK;
+}
+
+extern "C" int chebgcn_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, float beta1,
+                                 float beta2, float eps, float grad_scale, float l2, chebgcn_stream stream) {
+    CG_REQUIRE(p && g && m && v && n >= 0, "adam_step: bad argument");
+    if (n == 0) return CHEBGCN_OK;
+    return adam_launch(adam_kernel, p, g, m, v, n, n, lr_t, nullptr, beta1, beta2, eps, grad_scale, l2, nullptr, stream);
+}
+
+extern "C" int chebgcn_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_t_dev,
+                                     float beta1, float beta2, float eps, float grad_scale, float l2,
+                                     chebgcn_stream stream) {
+    CG_REQUIRE(p && g && m && v && lr_t_dev && n >= 0, "adam_step_dev: bad argument");
+    if (n == 0) return CHEBGCN_OK;
+    return adam_launch(adam_kernel, p, g, m, v, n, n, 0.f, lr_t_dev, beta1, beta2, eps, grad_scale, l2, nullptr, stream);
+}
+
+extern "C" int chebgcn_adam_step_sq(float* p, const float* g, float* m, float* v, int64_t n, float lr_t, const float* lr_t_dev,
+                                    float beta1, float beta2, float eps, float grad_scale, float l2, float* sq_partials,
+                                    chebgcn_stream stream) {
+    CG_REQUIRE(p && g && m && v && sq_partials && n > 0, "adam_step_sq: bad argument");
+    note_dispatch("adam_sq_kernel");
+    return adam_launch(adam_sq_kernel, p, g, m, v, n, n, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale, l2, sq_partials, stream);
 }
 
 extern "C" int chebgcn_adam_step_sq_all(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_reg, float lr_t,
                                         const float* lr_t_dev, float beta1, float beta2, float eps, float grad_scale, float l2,
-                                        float* sq_partials, chebgcn_stream stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                                        float* sq_partials, chebgcn_stream stream) {
     CG_REQUIRE(p && g && m && v && sq_partials && n > 0 && n_reg >= 0 && n_reg <= n, "adam_step_sq_all: bad argument");
     note_dispatch("adam_sq_kernel<all>");
-    hipLaunchKernelGGL(adam_sq_kernel, dim3((unsigned)chebgcn_adam_partials(n)), dim3(256), 0, stream, p, g, m, v, n, lr_t, lr_t_dev,
-                       beta1, beta2, eps, grad_scale, l2, sq_partials, n_reg);
-    CG_HIP(hipGetLastError());
-    return CHEBGCN_OK;
+    return adam_launch(adam_sq_kernel, p, g, m, v, n, n_reg, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale, l2, sq_partials, stream);
 }
 
 extern "C" int chebgcn_nadam_step_sq_all(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_reg, float lr_t,
                                          const float* lr_t_dev, float beta1, float beta2, float eps, float grad_scale, float l2,
-                                         float* sq_partials, chebgcn_stream stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+                                         float* sq_partials, chebgcn_stream stream) {
     CG_REQUIRE(p && g && m && v && sq_partials && n > 0 && n_reg >= 0 && n_reg <= n, "nadam_step_sq_all: bad argument");
     note_dispatch("nadam_sq_kernel<all>");
-    hipLaunchKernelGGL(nadam_sq_kernel, dim3((unsigned)chebgcn_adam_partials(n)), dim3(256), 0, stream, p, g, m, v, n, lr_t,
-                       lr_t_dev, beta1, beta2, eps, grad_scale, l2, sq_partials, n_reg);
-    CG_HIP(hipGetLastError());
-    return CHEBGCN_OK;
+    return adam_launch(nadam_sq_kernel, p, g, m, v, n, n_reg, lr_t, lr_t_dev, beta1, beta2, eps, grad_scale, l2, sq_partials, stream);
 }
 
 namespace chebgcn {

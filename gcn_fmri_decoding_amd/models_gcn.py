@@ -426,6 +426,7 @@ class base_model(Attribution, Decode, Series, Uncertainty, CrossValidate):
         if any(s.regularized for s in specs if s.group == 'convb') or not all(s.regularized for s in specs[:nr]):
             raise AssertionError('flat layout assumes regularised variables come first')
         self._n_head, self._n_reg, self._n_total = n_head, n_reg, n
+        self._n_train = n                   # the optimizer's prefix of the flat buffers (finetuning_cgcnn: shorter)
         self.regularizers = [s.name for s in specs if s.regularized]
         self.global_step = 0
         self._loss_ema = None
@@ -730,36 +731,39 @@ class base_model(Attribution, Decode, Series, Uncertainty, CrossValidate):
         sg['cache_keys'] = ops.cache_keys() - before       # scratch allocated on the capture streams: it dies with this graph
         return sg
 
+    _nadam = False          # finetuning_cgcnn: Nesterov's form of the update, which has the one-launch entry only
+
     def _apply_adam(self, grad_scale=1.0, lr_t=None, want_sq=False):
-        """TF-form Adam over the flat buffers; ``want_sq``: the pass over the regularised variables also leaves the partial sums
-        of their squares in ``self._sq_part`` (returns how many)."""
+        """The optimizer over the trainable prefix of the flat buffers: TF-form Adam (Nadam: finetuning_cgcnn, :895-933), or
+        gradient descent at the decayed rate when momentum == 0.  ``want_sq``: the pass over the regularised variables also
+        leaves the partial sums of their squares in ``self._sq_part`` (returns how many)."""
+        n, r = self._n_train, self._n_reg
         if self.momentum == 0:
             # tf.train.GradientDescentOptimizer branch (:288-289)
             lr = self.training(None, self.learning_rate, self.decay_steps, self.decay_rate, self.momentum)
             with torch.no_grad():
-                g = self._grad * grad_scale
-                g[:self._n_reg] += self.regularization * self._flat[:self._n_reg]
-                self._flat -= lr * g
-            return
+                g = self._grad[:n] * grad_scale
+                g[:r] += self.regularization * self._flat[:r]
+                self._flat[:n] -= lr * g
+            return 0
         b1, b2 = 0.9, 0.999
         if lr_t is None:
             lr_t = self._adam_lr_t(self.global_step + 1)
-        r, n = self._n_reg, self._n_total
-        nparts = 0
-        if r > 0 and want_sq:
+        if self._nadam or (r > 0 and want_sq):
             if getattr(self, '_sq_part', None) is None:
                 self._sq_part = torch.zeros(4096, dtype=torch.float32, device=self.device)
             # every variable in ONE launch: the regularised ones (weights: the first r elements of the flat buffer) with the L2 term
             # and the partial sums of their squares, the biases behind them without
-            return ops.adam_step_sq_all(self._flat, self._grad, self._adam_m, self._adam_v, r, lr_t, self._sq_part, b1, b2, 1e-8,
-                                        grad_scale, self.regularization)
-        elif r > 0:
+            step = ops.nadam_step_sq_all if self._nadam else ops.adam_step_sq_all
+            return step(self._flat[:n], self._grad[:n], self._adam_m, self._adam_v, r, lr_t, self._sq_part, b1, b2, 1e-8,
+                        grad_scale, self.regularization)
+        if r > 0:
             ops.adam_step(self._flat[:r], self._grad[:r], self._adam_m[:r], self._adam_v[:r], lr_t, b1, b2, 1e-8,
                           grad_scale, self.regularization)
         if n > r:
-            ops.adam_step(self._flat[r:], self._grad[r:], self._adam_m[r:], self._adam_v[r:], lr_t, b1, b2, 1e-8,
+            ops.adam_step(self._flat[r:n], self._grad[r:n], self._adam_m[r:], self._adam_v[r:], lr_t, b1, b2, 1e-8,
                           grad_scale, 0.0)
-        return nparts
+        return 0
 
     # ---------------------------------------------------------------- helpers
 
@@ -1744,23 +1748,7 @@ class finetuning_cgcnn(cgcnn):
         return ops.FlatFC.apply(x, W, b, self._head_order, self._M_top, relu, W.grad if direct else None,
                                 b.grad if direct else None)
 
-    def _apply_adam(self, grad_scale=1.0, lr_t=None, want_sq=False):
-        """The optimizer of :895-933 over the trainable prefix of the flat buffers: Nadam, or gradient descent at the decayed
-        rate when momentum == 0; returns the number of partial sums of squares (Nadam)."""
-        n, r = self._n_train, self._n_reg
-        if self.momentum == 0:
-            lr = self.training(None, self.learning_rate, self.decay_steps, self.decay_rate, self.momentum)
-            with torch.no_grad():
-                g = self._grad[:n] * grad_scale
-                g[:r] += self.regularization * self._flat[:r]
-                self._flat[:n] -= lr * g
-            return 0
-        if lr_t is None:
-            lr_t = self._adam_lr_t(self.global_step + 1)
-        if getattr(self, '_sq_part', None) is None:
-            self._sq_part = torch.zeros(4096, dtype=torch.float32, device=self.device)
-        return ops.nadam_step_sq_all(self._flat[:n], self._grad[:n], self._adam_m, self._adam_v, r, lr_t, self._sq_part,
-                                     0.9, 0.999, 1e-8, grad_scale, self.regularization)
+    _nadam = True           # base_model._apply_adam: the optimizer of :895-933 over the trainable prefix
 
 
 def get_best_checkpoint(best_checkpoint_dir, select_maximum_value=True):

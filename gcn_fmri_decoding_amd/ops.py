@@ -1917,6 +1917,33 @@ FC_BWD_MAX_INNER = int(os.environ.get('CHEBGCN_FC_BWD_MAX_INNER', 4096))      # 
 FC_FWD_MAX_INNER = int(os.environ.get('CHEBGCN_FC_FWD_MAX_INNER', 1 << 20))     # A/B knob for bench runs
 
 
+def _fc_fwd(rows, ld, W, b, relu, timer_name):
+    """The one launch of chebgcn_fc_fwd: ``act(rows @ W + b)``, float32 ``[B, O]``.  ``rows``: ``B`` rows of row stride ``ld``
+    floats, the first ``I = W.shape[0]`` of each the input; ``W`` and ``b`` contiguous.  The caller has asked
+    chebgcn_fc_fwd_supported.  ``timer_name``: the entry of ``ops.timers`` the launch is counted under, None for none."""
+    B, (I, O) = rows.shape[0], W.shape
+    L = _lib.lib()
+    y = torch.empty((B, O), dtype=torch.float32, device=rows.device)
+    nws = L.chebgcn_fc_fwd_workspace(B, I, O)
+    ws = _workspace(nws, rows.device, 'fc_fwd') if nws else None
+    call = lambda: L.chebgcn_fc_fwd(_p(rows), ld, _p(W), _p(b), _p(y), _p(ws), nws, B, I, O, 1 if relu else 0, _stream())
+    _lib.check(_launch(timer_name, 4.0 * (B * I + I * O + B * O), 2.0 * B * I * O, call) if timer_name else call(), 'fc_fwd')
+    return y
+
+
+def _fc_bwd(rows, ld, W, g, y, dW, db, dx, lddx, timer_name):
+    """The one launch of chebgcn_fc_bwd for ``rows`` as in ``_fc_fwd``: WRITES the weight and bias gradients into ``dW`` / ``db``
+    and the input gradient into ``dx`` (row stride ``lddx``), each where given; ReluGrad on ``y`` where given.  ``timer_name``
+    as in ``_fc_fwd``, and what a failure is reported as ('fc_bwd' without one)."""
+    B, (I, O) = rows.shape[0], W.shape
+    need_w, need_x = dW is not None, dx is not None
+    call = lambda: _lib.lib().chebgcn_fc_bwd(_p(rows), ld, _p(W), _p(g), _p(y), _p(dW), _p(db), _p(dx), lddx, B, I, O, _stream())
+    # 'fc_bwd' counts the rows as read whichever gradients are formed; 'fc_bwd_x' (no dW: the rows are not read) does not
+    nbytes = 4.0 * (B * I * ((timer_name != 'fc_bwd_x') + need_x) + I * O * (1 + need_w) + B * O)
+    _lib.check(_launch(timer_name, nbytes, 2.0 * B * I * O * (need_w + need_x), call) if timer_name else call(),
+               timer_name or 'fc_bwd')
+
+
 def fc_forward(x, W, b, relu):
     """``act(x @ W + b)`` of the head's FC layers (models_gcn.py:650-656) by the library's small-product kernel, or None
     where the product is outside its range (large or odd inner size: the caller uses the vendor GEMM).  x may be a
@@ -1925,16 +1952,9 @@ def fc_forward(x, W, b, relu):
             and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0):
         return None
     B, I = x.shape
-    O = W.shape[1]
-    L = _lib.lib()
-    if I > FC_FWD_MAX_INNER or not L.chebgcn_fc_fwd_supported(B, I, O):
+    if I > FC_FWD_MAX_INNER or not _lib.lib().chebgcn_fc_fwd_supported(B, I, W.shape[1]):
         return None
-    y = torch.empty((B, O), dtype=torch.float32, device=x.device)
-    nws = L.chebgcn_fc_fwd_workspace(B, I, O)
-    ws = _workspace(nws, x.device, 'fc_fwd') if nws else None
-    _lib.check(L.chebgcn_fc_fwd(_p(x), x.stride(0), _p(W), _p(b), _p(y), _p(ws), nws, B, I, O, 1 if relu else 0, _stream()),
-               'fc_fwd')
-    return y
+    return _fc_fwd(x, x.stride(0), W, b, relu, None)       # (outside ops.timers: the 'fc_fwd' entry is the native callers' alone)
 
 
 def fc_backward(x, W, g, y, dW, db, need_dx):
@@ -1942,59 +1962,72 @@ def fc_backward(x, W, g, y, dW, db, need_dx):
     WRITTEN into the given buffers.  Returns ``(dx,)`` (``(None,)`` unless ``need_dx``), or None where fc_forward would
     decline and nothing was launched."""
     B, I = x.shape
-    O = W.shape[1]
-    L = _lib.lib()
     if not (x.is_cuda and x.dtype == torch.float32 and x.stride(1) == 1 and W.is_contiguous() and g.is_contiguous()
             and dW.is_contiguous() and db.is_contiguous() and (y is None or y.is_contiguous())
-            and I <= FC_BWD_MAX_INNER and L.chebgcn_fc_fwd_supported(B, I, O)):
+            and I <= FC_BWD_MAX_INNER and _lib.lib().chebgcn_fc_fwd_supported(B, I, W.shape[1])):
         return None
     dx = torch.empty((B, I), dtype=torch.float32, device=x.device) if need_dx else None
-    _lib.check(L.chebgcn_fc_bwd(_p(x), x.stride(0), _p(W), _p(g), _p(y), _p(dW), _p(db), _p(dx), I, B, I, O, _stream()),
-               'fc_bwd')
+    _fc_bwd(x, x.stride(0), W, g, y, dW, db, dx, I, None)
     return (dx,)
+
+
+def _optimizer_step(entry, p, g, m, v, n_reg, lr_t, sq_partials, beta1, beta2, eps, grad_scale, l2, timer_name=None):
+    """The checks and the call of every optimizer entry point chebgcn_<entry> on flat fp32 buffers.  ``lr_t``: a Python float,
+    or a one-element float32 DEVICE tensor read when the kernel runs (the form a captured step graph replays).  ``n_reg``: None
+    for the entries without that argument.  ``sq_partials``: None for plain ``adam_step``, whose two C entry points take the
+    step size one way each and which alone accepts no elements; else the buffer of the partial sums of squares, and the number
+    of partials written is returned."""
+    sq = sq_partials is not None
+    _require_cuda(p, g, m, v, sq_partials)
+    n = p.numel()
+    if not (g.numel() == m.numel() == v.numel() == n) or (sq and n == 0) or not (n_reg is None or 0 <= n_reg <= n):
+        raise ValueError('%s: size mismatch' % entry)
+    lib = _lib.lib()
+    nparts = lib.chebgcn_adam_partials(n) if sq else None
+    if sq and (sq_partials.dtype != torch.float32 or sq_partials.numel() < nparts):
+        raise ValueError('%s: sq_partials needs %d float32' % (entry, nparts))
+    dev_lr = isinstance(lr_t, torch.Tensor)
+    if dev_lr:
+        if not sq:
+            _require_cuda(lr_t)
+        if lr_t.dtype != torch.float32 or lr_t.numel() != 1 or not lr_t.is_cuda:
+            raise ValueError('%s: a device lr_t must be one float32' % entry)
+    if sq:
+        lr = (0.0 if dev_lr else float(lr_t), _p(lr_t) if dev_lr else None)
+    else:
+        entry, lr = (entry + '_dev', (_p(lr_t),)) if dev_lr else (entry, (float(lr_t),))
+    args = ((_p(p), _p(g), _p(m), _p(v), n) + (() if n_reg is None else (int(n_reg),)) + lr
+            + (float(beta1), float(beta2), float(eps), float(grad_scale), float(l2)) + ((_p(sq_partials),) if sq else ())
+            + (_stream(),))
+    call = lambda: getattr(lib, 'chebgcn_' + entry)(*args)
+    _lib.check(_launch(timer_name, 28.0 * n, 0.0, call) if timer_name else call(), entry)     # reads p, g, m, v; writes p, m, v
+    return nparts
+
+
+def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
+    """In-place TF-form Adam on flat fp32 buffers (models_gcn.py:296).  ``lr_t``: a Python float (chebgcn_adam_step), or a
+    one-element fp32 DEVICE tensor read when the kernel runs (chebgcn_adam_step_dev)."""
+    _optimizer_step('adam_step', p, g, m, v, None, lr_t, None, beta1, beta2, eps, grad_scale, l2)
+
+
+def adam_step_sq(p, g, m, v, lr_t, sq_partials, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
+    """``adam_step`` that also leaves the per-workgroup partial sums of squares of the PRE-update ``p`` in ``sq_partials``
+    (float32, at least ``adam_partials(n)`` elements): the L2 term of the loss without a pass of its own.  Returns the
+    number of partials written."""
+    return _optimizer_step('adam_step_sq', p, g, m, v, None, lr_t, sq_partials, beta1, beta2, eps, grad_scale, l2)
 
 
 def adam_step_sq_all(p, g, m, v, n_reg, lr_t, sq_partials, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
     """``adam_step_sq`` over ALL variables in one launch: the first ``n_reg`` elements are regularised (L2 term in the gradient,
     counted in the partial sums of squares), the rest -- the biases -- take plain Adam.  Returns the number of partials."""
-    _require_cuda(p, g, m, v, sq_partials)
-    n = p.numel()
-    if not (g.numel() == m.numel() == v.numel() == n) or n == 0 or not (0 <= n_reg <= n):
-        raise ValueError('adam_step_sq_all: size mismatch')
-    lib = _lib.lib()
-    nparts = lib.chebgcn_adam_partials(n)
-    if sq_partials.dtype != torch.float32 or sq_partials.numel() < nparts:
-        raise ValueError('adam_step_sq_all: sq_partials needs %d float32' % nparts)
-    dev_lr = isinstance(lr_t, torch.Tensor)
-    if dev_lr and (lr_t.dtype != torch.float32 or lr_t.numel() != 1 or not lr_t.is_cuda):
-        raise ValueError('adam_step_sq_all: a device lr_t must be one float32')
-    _lib.check(lib.chebgcn_adam_step_sq_all(_p(p), _p(g), _p(m), _p(v), n, int(n_reg), 0.0 if dev_lr else float(lr_t),
-                                            _p(lr_t) if dev_lr else None, float(beta1), float(beta2), float(eps), float(grad_scale),
-                                            float(l2), _p(sq_partials), _stream()), 'adam_step_sq_all')
-    return nparts
+    return _optimizer_step('adam_step_sq_all', p, g, m, v, n_reg, lr_t, sq_partials, beta1, beta2, eps, grad_scale, l2)
 
 
 def nadam_step_sq_all(p, g, m, v, n_reg, lr_t, sq_partials, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
     """Nadam -- tf.contrib.opt.NadamOptimizer, TF's ApplyAdam with use_nesterov (finetuning_cgcnn, models_gcn.py:895-933) --
     over ``p`` in one launch (chebgcn_nadam_step_sq_all): the first ``n_reg`` elements take the L2 term and leave the partial
-    sums of squares of their PRE-update values in ``sq_partials``, the rest plain Nadam.  ``lr_t``: a Python float, or a
-    one-element float32 device tensor read when the kernel runs (captured step).  Returns the number of partials."""
-    _require_cuda(p, g, m, v, sq_partials)
-    n = p.numel()
-    if not (g.numel() == m.numel() == v.numel() == n) or n == 0 or not (0 <= n_reg <= n):
-        raise ValueError('nadam_step_sq_all: size mismatch')
-    lib = _lib.lib()
-    nparts = lib.chebgcn_adam_partials(n)
-    if sq_partials.dtype != torch.float32 or sq_partials.numel() < nparts:
-        raise ValueError('nadam_step_sq_all: sq_partials needs %d float32' % nparts)
-    dev_lr = isinstance(lr_t, torch.Tensor)
-    if dev_lr and (lr_t.dtype != torch.float32 or lr_t.numel() != 1 or not lr_t.is_cuda):
-        raise ValueError('nadam_step_sq_all: a device lr_t must be one float32')
-    n_bytes = 28.0 * n          # reads p, g, m, v; writes p, m, v
-    _lib.check(_launch('nadam', n_bytes, 0.0, lambda: lib.chebgcn_nadam_step_sq_all(
-        _p(p), _p(g), _p(m), _p(v), n, int(n_reg), 0.0 if dev_lr else float(lr_t), _p(lr_t) if dev_lr else None, float(beta1),
-        float(beta2), float(eps), float(grad_scale), float(l2), _p(sq_partials), _stream())), 'nadam_step_sq_all')
-    return nparts
+    sums of squares of their PRE-update values in ``sq_partials``, the rest plain Nadam.  Returns the number of partials."""
+    return _optimizer_step('nadam_step_sq_all', p, g, m, v, n_reg, lr_t, sq_partials, beta1, beta2, eps, grad_scale, l2, 'nadam')
 
 
 def planes_to_rows(planes, M, order=None, ld=None, out=None):
@@ -2045,17 +2078,11 @@ class FlatFC(torch.autograd.Function):
         I, O = M * F, W.shape[1]
         if tuple(W.shape) != (I, O) or tuple(b.shape) != (O,):
             raise ValueError('FlatFC: weights [%d, O] and bias [O] expected' % I)
-        L = _lib.lib()
-        if not L.chebgcn_fc_fwd_supported(B, I, O):
+        if not _lib.lib().chebgcn_fc_fwd_supported(B, I, O):
             raise ValueError('FlatFC: %d x %d x %d is outside the range of chebgcn_fc_fwd' % (B, I, O))
         rows = planes_to_rows(x.contiguous(), M, order)
-        ld = rows.shape[1]
-        Wc, bc = W.detach().contiguous(), b.detach().contiguous()
-        y = torch.empty((B, O), dtype=torch.float32, device=x.device)
-        nws = L.chebgcn_fc_fwd_workspace(B, I, O)
-        ws = _workspace(nws, x.device, 'fc_fwd') if nws else None
-        _lib.check(_launch('fc_fwd', 4.0 * (B * I + I * O + B * O), 2.0 * B * I * O, lambda: L.chebgcn_fc_fwd(
-            _p(rows), ld, _p(Wc), _p(bc), _p(y), _p(ws), nws, B, I, O, 1 if relu else 0, _stream())), 'fc_fwd')
+        Wc = W.detach().contiguous()
+        y = _fc_fwd(rows, rows.shape[1], Wc, b.detach().contiguous(), relu, 'fc_fwd')
         ctx.save_for_backward(rows, Wc, y if relu else None)
         ctx.cfg, ctx.order, ctx.bufs = (B, M, F, I, O), order, (gW, gb)
         return y
@@ -2075,34 +2102,10 @@ class FlatFC(torch.autograd.Function):
             _check_grad_buffer(db, (O,), 'db')
         if ctx.needs_input_grad[0]:
             drows = torch.empty(rows.shape, dtype=torch.float32, device=g.device)
-        ld = rows.shape[1]
         if need_w or drows is not None:
-            _lib.check(_launch('fc_bwd', 4.0 * (B * I * (1 + (drows is not None)) + I * O * (1 + need_w) + B * O),
-                               2.0 * B * I * O * (need_w + (drows is not None)), lambda: _lib.lib().chebgcn_fc_bwd(
-                _p(rows), ld, _p(Wc), _p(g), _p(y), _p(dW), _p(db), _p(drows), ld, B, I, O, _stream())), 'fc_bwd')
+            _fc_bwd(rows, rows.shape[1], Wc, g, y, dW, db, drows, rows.shape[1], 'fc_bwd')
         dx = rows_to_planes(drows, M, F, ctx.order) if drows is not None else None
         return (dx, None if gW is not None else dW, None if gb is not None else db, None, None, None, None, None)
-
-
-def adam_step_sq(p, g, m, v, lr_t, sq_partials, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
-    """``adam_step`` that also leaves the per-workgroup partial sums of squares of the PRE-update ``p`` in ``sq_partials``
-    (float32, at least ``adam_partials(n)`` elements): the L2 term of the loss without a pass of its own.  Returns the
-    number of partials written."""
-    _require_cuda(p, g, m, v, sq_partials)
-    n = p.numel()
-    if not (g.numel() == m.numel() == v.numel() == n) or n == 0:
-        raise ValueError('adam_step_sq: size mismatch')
-    lib = _lib.lib()
-    nparts = lib.chebgcn_adam_partials(n)
-    if sq_partials.dtype != torch.float32 or sq_partials.numel() < nparts:
-        raise ValueError('adam_step_sq: sq_partials needs %d float32' % nparts)
-    dev_lr = isinstance(lr_t, torch.Tensor)
-    if dev_lr and (lr_t.dtype != torch.float32 or lr_t.numel() != 1 or not lr_t.is_cuda):
-        raise ValueError('adam_step_sq: a device lr_t must be one float32')
-    _lib.check(lib.chebgcn_adam_step_sq(_p(p), _p(g), _p(m), _p(v), n, 0.0 if dev_lr else float(lr_t), _p(lr_t) if dev_lr else None,
-                                        float(beta1), float(beta2), float(eps), float(grad_scale), float(l2), _p(sq_partials),
-                                        _stream()), 'adam_step_sq')
-    return nparts
 
 
 def loss_bookkeeping(cross_entropy, sq_partials, nparts, half_reg, ema, corr, decay=0.9):
@@ -2115,24 +2118,6 @@ def loss_bookkeeping(cross_entropy, sq_partials, nparts, half_reg, ema, corr, de
                                                    _p(ema), float(decay), 0.0 if dev_c else float(corr), _p(corr) if dev_c else None,
                                                    None, _p(out), _stream()), 'loss_bookkeeping')
     return out
-
-
-def adam_step(p, g, m, v, lr_t, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
-    """In-place TF-form Adam on flat fp32 buffers (models_gcn.py:296).  ``lr_t``: a Python float, or a one-element
-    fp32 DEVICE tensor read when the kernel runs (chebgcn_adam_step_dev: the form a captured step graph replays)."""
-    _require_cuda(p, g, m, v)
-    n = p.numel()
-    if not (g.numel() == m.numel() == v.numel() == n):
-        raise ValueError('adam_step: size mismatch')
-    if isinstance(lr_t, torch.Tensor):
-        _require_cuda(lr_t)
-        if lr_t.dtype != torch.float32 or lr_t.numel() != 1:
-            raise ValueError('adam_step: a device lr_t must be one float32')
-        _lib.check(_lib.lib().chebgcn_adam_step_dev(_p(p), _p(g), _p(m), _p(v), n, _p(lr_t), float(beta1), float(beta2),
-                                                    float(eps), float(grad_scale), float(l2), _stream()), 'adam_step_dev')
-        return
-    _lib.check(_lib.lib().chebgcn_adam_step(_p(p), _p(g), _p(m), _p(v), n, float(lr_t), float(beta1), float(beta2),
-                                            float(eps), float(grad_scale), float(l2), _stream()), 'adam_step')
 
 
 # ------------------------------------------------------------------------------------
@@ -2164,28 +2149,19 @@ class FCInputGrad(torch.autograd.Function):
         _require_cuda(x, W, b)
         B, I = x.shape
         O = W.shape[1]
-        L = _lib.lib()
-        if not L.chebgcn_fc_fwd_supported(B, I, O):
+        if not _lib.lib().chebgcn_fc_fwd_supported(B, I, O):
             raise ValueError('saliency: the FC layer %d x %d x %d is outside the range of chebgcn_fc_fwd' % (B, I, O))
         rows = _fc_rows(x.detach())
-        Wc, bc = W.detach().contiguous(), b.detach().contiguous()
-        y = torch.empty((B, O), dtype=torch.float32, device=x.device)
-        nws = L.chebgcn_fc_fwd_workspace(B, I, O)
-        ws = _workspace(nws, x.device, 'fc_fwd') if nws else None
-        _lib.check(_launch('fc_fwd', 4.0 * (B * I + I * O + B * O), 2.0 * B * I * O, lambda: L.chebgcn_fc_fwd(
-            _p(rows), rows.stride(0), _p(Wc), _p(bc), _p(y), _p(ws), nws, B, I, O, 1 if relu else 0, _stream())), 'fc_fwd')
+        Wc = W.detach().contiguous()
+        y = _fc_fwd(rows, rows.stride(0), Wc, b.detach().contiguous(), relu, 'fc_fwd')
         ctx.save_for_backward(rows, Wc, y if relu else None)
         return y
 
     @staticmethod
     def backward(ctx, g):
         rows, Wc, y = ctx.saved_tensors
-        B, I = rows.shape
-        O = Wc.shape[1]
-        g = g.contiguous()
-        dx = torch.empty((B, I), dtype=torch.float32, device=g.device)
-        _lib.check(_launch('fc_bwd_x', 4.0 * (B * I + I * O + B * O), 2.0 * B * I * O, lambda: _lib.lib().chebgcn_fc_bwd(
-            _p(rows), rows.stride(0), _p(Wc), _p(g), _p(y), None, None, _p(dx), I, B, I, O, _stream())), 'fc_bwd_x')
+        dx = torch.empty(rows.shape, dtype=torch.float32, device=g.device)
+        _fc_bwd(rows, rows.stride(0), Wc, g.contiguous(), y, None, None, dx, rows.shape[1], 'fc_bwd_x')
         return dx, None, None, None
 
 
@@ -2402,17 +2378,10 @@ def fc_forward_native(x, W, b, relu, who):
     _require_cuda(x, W, b)
     B, I = x.shape
     O = W.shape[1]
-    L = _lib.lib()
-    if not L.chebgcn_fc_fwd_supported(B, I, O):
+    if not _lib.lib().chebgcn_fc_fwd_supported(B, I, O):
         raise ValueError('%s: the FC layer %d x %d x %d is outside the range of chebgcn_fc_fwd' % (who, B, I, O))
     rows = _fc_rows(x.detach())
-    Wc, bc = W.detach().contiguous(), b.detach().contiguous()
-    y = torch.empty((B, O), dtype=torch.float32, device=x.device)
-    nws = L.chebgcn_fc_fwd_workspace(B, I, O)
-    ws = _workspace(nws, x.device, 'fc_fwd') if nws else None
-    _lib.check(_launch('fc_fwd', 4.0 * (B * I + I * O + B * O), 2.0 * B * I * O, lambda: L.chebgcn_fc_fwd(
-        _p(rows), rows.stride(0), _p(Wc), _p(bc), _p(y), _p(ws), nws, B, I, O, 1 if relu else 0, _stream())), 'fc_fwd')
-    return y
+    return _fc_fwd(rows, rows.stride(0), W.detach().contiguous(), b.detach().contiguous(), relu, 'fc_fwd')
 
 
 def _fc_sample_rows(x):

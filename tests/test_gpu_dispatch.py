@@ -898,6 +898,67 @@ def test_adam_with_squares_and_loss_bookkeeping(ops, dev, n, dev_scalars):
     assert e_sq <= 2e-6 and e_ema <= 1e-6 and e_out <= 1e-6, (e_sq, e_ema, e_out)
 
 
+@pytest.mark.parametrize('n', [1, 255, 257, 4096 * 256 + 1])             # the last: one element past a full grid, the loop wraps
+def test_optimizer_entries_agree_where_their_definitions_coincide(ops, dev, n):
+    """The five optimizer entry points are one update: adam_step (float and device lr_t), adam_step_sq and
+    adam_step_sq_all(n_reg = n) leave the same bits; adam_step_sq_all(n_reg = r) is adam_step with the L2 term on [:r] and
+    without it on [r:], its partials the sum of squares of the pre-update [:r]; nadam_step_sq_all differs in p alone."""
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(n)
+    p0 = torch.randn(n, generator=gen, device=dev) * 0.1
+    g = torch.randn(n, generator=gen, device=dev)
+    m0 = torch.randn(n, generator=gen, device=dev) * 0.01
+    v0 = torch.rand(n, generator=gen, device=dev) * 0.01
+    lr_t, kw = 1.7e-3, dict(grad_scale=0.5, l2=5e-4)
+    lr_dev = torch.tensor([lr_t], dtype=torch.float32, device=dev)
+
+    def run(step):
+        """(p, m, v, partials or None) after ``step(p, g, m, v, part)`` on fresh copies."""
+        p, m, v, part = p0.clone(), m0.clone(), v0.clone(), torch.full((4096,), float('nan'), device=dev)
+        nparts = step(p, m, v, part)
+        assert nparts is None or nparts == min((n + 255) // 256, 4096)
+        return p, m, v, (part[:nparts] if nparts else None)
+
+    def same(a, b, what, names='pmv'):
+        for x, y, name in zip(a, b, names):
+            assert torch.equal(x, y), '%s: %s differs' % (what, name)
+
+    plain = run(lambda p, m, v, part: ops.adam_step(p, g, m, v, lr_t, **kw))
+    same(plain, run(lambda p, m, v, part: ops.adam_step(p, g, m, v, lr_dev, **kw)), 'adam_step with a device lr_t')
+    for lr in (lr_t, lr_dev):
+        same(plain, run(lambda p, m, v, part: ops.adam_step_sq(p, g, m, v, lr, part, **kw)), 'adam_step_sq')
+        same(plain, run(lambda p, m, v, part: ops.adam_step_sq_all(p, g, m, v, n, lr, part, **kw)), 'adam_step_sq_all(n_reg = n)')
+    for r in sorted({n // 3, 0, n}):
+        def two_steps(p, m, v, part):                 # (as base_model._apply_adam: an empty side is not launched)
+            if r > 0:
+                ops.adam_step(p[:r], g[:r], m[:r], v[:r], lr_t, **kw)
+            if r < n:
+                ops.adam_step(p[r:], g[r:], m[r:], v[r:], lr_t, grad_scale=0.5, l2=0.0)
+        ref = run(two_steps)
+        got = run(lambda p, m, v, part: ops.adam_step_sq_all(p, g, m, v, r, lr_t, part, **kw))
+        same(ref, got, 'adam_step_sq_all(n_reg = %d)' % r)
+        sq_ref = float((p0[:r].double() ** 2).sum())
+        sq = float(got[3].double().sum())
+        if r == 0:
+            assert bool((got[3] == 0).all()), 'no regularised element, but a partial sum of squares is not 0'
+        else:
+            print('adam_step_sq_all n %d n_reg %d: sum of squares off by %.3e of it' % (n, r, abs(sq - sq_ref) / sq_ref))
+            assert abs(sq - sq_ref) <= 2e-6 * sq_ref, (r, sq, sq_ref)
+        nadam = run(lambda p, m, v, part: ops.nadam_step_sq_all(p, g, m, v, r, lr_t, part, **kw))
+        same(got[1:], nadam[1:], 'nadam_step_sq_all(n_reg = %d) against adam_step_sq_all' % r, 'mv')
+        assert torch.equal(got[3], nadam[3]), 'nadam_step_sq_all: other partial sums of squares'
+        assert not torch.equal(got[0], nadam[0]), 'nadam_step_sq_all left the variables Adam leaves'
+    # n = 0 is a no-op of the two plain entry points (at the C ABI: an empty tensor has no address to pass)
+    from gcn_fmri_decoding_amd import _lib
+    L, P = _lib.lib(), lambda t: ctypes.c_void_p(t.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p, m, v = p0.clone(), m0.clone(), v0.clone()
+    assert L.chebgcn_adam_step(P(p), P(g), P(m), P(v), 0, lr_t, 0.9, 0.999, 1e-8, 0.5, 5e-4, stream) == 0
+    assert L.chebgcn_adam_step_dev(P(p), P(g), P(m), P(v), 0, P(lr_dev), 0.9, 0.999, 1e-8, 0.5, 5e-4, stream) == 0
+    torch.cuda.synchronize()
+    same((p, m, v), (p0, m0, v0), 'adam_step on no element')
+
+
 @pytest.mark.parametrize('n,ordered', [(300, False), (3000, False), (3000, True)])
 def test_recurrence_fwd_t_is_the_forward_recurrence_on_the_transposed_operator(ops, dev, lib, n, ordered):
     """chebgcn_recurrence_fwd_t: T_k(L~^T) x -- on a NON-symmetric operator (a Laplacian is symmetric and would not tell L~ from

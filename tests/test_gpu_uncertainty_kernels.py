@@ -31,7 +31,9 @@ import torch
 
 from conftest import record_measured
 from gcn_fmri_decoding_amd import _lib, ops, uncertainty
-from test_gpu_head_kernels import (DEV, SENTINEL, U, Guarded, _dev, _P, _stream, assert_exact, assert_same_bits, roundoff_ratio)
+from test_gpu_head_kernels import (DEV, SENTINEL, U, Guarded, _dev, _P, _stream, assert_exact, assert_same_bits, fwd_dispatch,
+                                   roundoff_ratio)
+from test_gpu_head_kernels import _fc_fwd as _fc_plain
 
 pytestmark = pytest.mark.gpu
 SEED = 0x5EED
@@ -146,7 +148,7 @@ def _x_device(c, x):
     return _dev(flat), sx
 
 
-def _fc_dropout(lib, c, xd, sx, Wd, bd, wind, relu, keep, what):
+def _fc_dropout(lib, c, xd, sx, Wd, bd, wind, relu, keep, what, seed=SEED):
     y = Guarded(c.S * c.B, c.O)
     ns = fc_splits(c)
     nws = lib.chebgcn_fc_fwd_dropout_workspace(c.S, c.B, c.I, c.O)
@@ -154,7 +156,7 @@ def _fc_dropout(lib, c, xd, sx, Wd, bd, wind, relu, keep, what):
     ws = Guarded(1, nws // 4) if nws else None
     T, inv = uncertainty.dropout_threshold(keep)
     _lib.check(lib.chebgcn_fc_fwd_dropout(_P(xd), c.ldx, sx, _P(Wd), _P(bd), _P(y.t), _P(ws.t) if ws else None, nws, _P(wind), c.S, c.B,
-                                          c.I, c.O, relu, SEED, c.s0, c.layer, T, float(inv), _stream()), 'fc_fwd_dropout')
+                                          c.I, c.O, relu, seed, c.s0, c.layer, T, float(inv), _stream()), 'fc_fwd_dropout')
     assert _lib.last_dispatch() == fc_dispatch(c), (what, _lib.last_dispatch())
     torch.cuda.synchronize()
     y.check(what + ' y')
@@ -189,6 +191,33 @@ def test_fc_forward_dropout_vs_float64(lib, c):
                 ratios['bias%d_relu%d' % (bias, relu)] = roundoff_ratio(what, got, ref, full)
                 assert_same_bits(what, got, _fc_dropout(lib, c, xd, sx, Wd, bd if bias else None, wind, relu, keep, what))
     record_measured('fc_forward_dropout_vs_float64[%s]' % fc_id(c), arm=fc_dispatch(c), splits=fc_splits(c), **ratios)
+
+
+@pytest.mark.parametrize('B,I,O,ldx', [(5, 37, 6, 40),             # no split, ragged tile, NaN row tails
+                                       (8, 1100, 12, 1100),        # three splits, through fc_fwd_reduce_kernel
+                                       (33, 64, 33, 64)])          # two tiles each way
+def test_fc_forward_dropout_that_keeps_everything_is_fc_forward(lib, B, I, O, ldx):
+    """One sample of a shared input with keep = 1 (inv_keep = 1, every draw below 2^32 - 1 kept) is chebgcn_fc_fwd bit for bit:
+    the two kernels are one tile body, the same loads, guards, wave order and split reduction.  Round-off inputs, so the order
+    of every sum shows in the last bits."""
+    c = _c(1, B, I, O, ldx)
+    win = fc_windows(c)
+    T, inv = uncertainty.dropout_threshold(1.0)
+    assert T == 2 ** 32 - 1 and inv == 1.0
+    # a draw of exactly 2^32 - 1 would be dropped: a seed under which this case has none
+    seed = next(s for s in range(SEED, SEED + 64) if uncertainty.dropout_keep(s, c.s0, c.layer, win, I, 1.0).all())
+    x, W, b = fc_inputs(c, False)
+    xd, Wd, bd = _dev(x[0]), _dev(W), _dev(b)
+    wind = torch.as_tensor(win.astype(np.uint32).view(np.int32)).to(DEV)
+    split = fc_splits(c) > 1
+    assert fwd_dispatch(B, I, O) == ('fc_fwd_kernel<split> + fc_fwd_reduce_kernel' if split else 'fc_fwd_kernel')
+    assert fc_dispatch(c) == ('fc_fwd_dropout_kernel<shared, split> + fc_fwd_reduce_kernel' if split else 'fc_fwd_dropout_kernel<shared>')
+    for relu in (1, 0):
+        what = 'fc_fwd_dropout keep 1 %s%s' % (fc_id(c), ' relu' if relu else '')
+        plain = _fc_plain(lib, c, xd, Wd, bd, relu, what + ' (plain)')                      # (both assert their dispatch strings)
+        drop = _fc_dropout(lib, c, xd, 0, Wd, bd, wind, relu, 1.0, what, seed=seed)
+        assert bool(torch.isfinite(plain).all()) and bool((plain != 0).any())
+        assert torch.equal(drop[0], plain), what + ': the dropout kernel with nothing dropped is not the plain kernel'
 
 
 def test_fc_forward_dropout_refuses_unaligned_rows(lib):
