@@ -155,6 +155,8 @@ SIGNATURES = {
     'chebgcn_cluster_query': (_i, [_i]),
     'chebgcn_cluster_enhance_workspace': (C.c_size_t, [_i, _i, _i, _i]),
     'chebgcn_signflip_t': (_i, [_p, _p, _p, _p, _i, _i, C.c_uint32, _i, C.c_uint32, _p]),
+    'chebgcn_perm_glm_query': (_i, [_i]),
+    'chebgcn_perm_glm_t': (_i, [_p, _p, _p, _p, C.c_double, _i, _p, _p, _i, _i, _i, _i, _p]),
     'chebgcn_cluster_enhance': (_i, [_p, _p, _i64, _p, _i, _p, _p, _i, _p, C.c_double, _p, _p, _p, _p, _p, C.c_size_t, _i, _i, _i,
                                      _i, _p]),
     'chebgcn_glm_query': (_i, [_i]),

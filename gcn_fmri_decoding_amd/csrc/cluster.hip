@@ -1,8 +1,11 @@
-// Permutation inference on maps (stats.map_test): sign-flip t maps and their cluster enhancement on the brain graph.
+// Permutation inference on maps (stats.map_test, stats.design_test): t maps of permutations and their cluster enhancement on the
+// brain graph.
 //
 //   signflip_t       t[p][v] of permutation p0 + p from x [S][M]: float64 on the vector ALU, every operation rounded on its own
 //                    (include/chebgcn.h states them one by one), one thread per (permutation, vertex), the S signs of the
 //                    permutation in LDS (drawn from chebgcn_aug_draw or unpacked from the caller's table).
+//   perm_glm_t       t[p][v] of one contrast of a group design whose rows permutation p permutes (stats.design_test): described
+//                    where it stands, below signflip_t.
 //   cluster_enhance  per permutation: u = +-t, the heights i = n .. 1 walked DOWNWARDS (hf[i] falls, so components only merge and
 //                    the forest of height i + 1 seeds height i), at every height the connected components of {v : u[v] > hf[i]},
 //                    their sizes, and acc[v] = acc[v] + ep[size] * hw[i] for the active vertices.
@@ -27,6 +30,8 @@
 //             counts), count, accumulate -- between one prep and one final launch.  The kernel boundary is the only barrier.
 #pragma clang fp contract(off)
 #include <limits.h>
+
+#include <utility>
 
 #include "aug_draw.h"
 #include "common.h"
@@ -185,6 +190,194 @@ signflip_t_kernel(const float* __restrict__ x, const double* __restrict__ q, con
     float tv = 0.f;
     if (d > 0.0) tv = (float)__ddiv_rn(m, __dsqrt_rn(__ddiv_rn(d, (double)S * (double)(S - 1))));
     t[(size_t)p * M + v] = tv;
+}
+
+// ---- t of a permuted design (stats.design_test) ------------------------------------------------------------------------------------
+// perm_glm_t<NJL>  the t of one contrast after the rows of the design's orthonormal basis Uf [S][r] were permuted (and subjects
+//                  negated) by the caller's table: a[k] = sum_j Uf[row(p, j)][k] * (+-e[j][v]), then ssq = a.a, num = u.a,
+//                  rss = q - ssq, t = num / sqrt(rss / dof * unorm2) -- float64, every multiply and add rounded on its own
+//                  (include/chebgcn.h states them), so that NumPy restates it to the bit.
+//                  Workgroup (PG_VB = 128 vertices, PT permutations), PG_NW waves: a lane owns TWO consecutive vertices and
+//                  PTL = pg_ptl(r) permutations, wave w the permutations [w PTL, (w + 1) PTL) of the group -- a loaded value
+//                  of e feeds PTL * NJ multiply-adds from registers, and the waves of a workgroup read the same rows of e at the
+//                  same time (the CU's cache serves three of the four).  PTL falls with the rank: the accumulators (2 PTL NJ
+//                  float64) and as many products in flight decide the occupancy, and beyond 4 waves a SIMD lost more than the
+//                  saved loads gave (measured at S = 100, M = 10242, Pb = 256): 4 at r = 1, 2 up to r = 4, then 1.
+//                  Rows of e are read vertex fastest, pg_u(NJ) rows in one go,
+//                  no load behind a branch (a lane beyond M reads vertex M - 1 and drops it; M is any number, so a lane's two
+//                  vertices are two 4-byte loads: a row of e need not start on 8 bytes).  The table entry and the row of Uf it
+//                  names are the same for every lane: both addresses are functions of the permutation, j and k alone and come
+//                  through the scalar cache; a row number >= S is clamped to S - 1 before it is an address.
+//                  r > PG_PANEL runs in column panels of PG_PANEL, e re-read per panel (L2), ssq and num carried in registers
+//                  across the panels so that k ascends overall; the LAST panel has NJL = r - PG_PANEL * (panels - 1) columns,
+//                  a template argument (no multiply-add on padding).  A (permutation, vertex) result is a function of its own
+//                  table row, e[:, v] and q[v] alone: the same bits whatever Pb, M or the batch holds.
+#ifndef CG_PERM_NW
+#define CG_PERM_NW 4
+#endif
+#ifndef CG_PERM_PTL1
+#define CG_PERM_PTL1 4
+#endif
+#ifndef CG_PERM_PTL4
+#define CG_PERM_PTL4 2
+#endif
+#ifndef CG_PERM_PTL
+#define CG_PERM_PTL 1
+#endif
+#ifndef CG_PERM_U
+#define CG_PERM_U 4
+#endif
+#ifndef CG_PERM_UWIDE
+#define CG_PERM_UWIDE 1
+#endif
+constexpr int PG_NW = CG_PERM_NW;           // waves of a workgroup: permutations side by side on one vertex tile
+constexpr int PG_V = 2;                     // consecutive vertices of a lane
+constexpr int PG_VB = 64 * PG_V;            // vertices of a workgroup
+constexpr int PG_PANEL = 16;                // columns of Uf of one pass over e
+constexpr int PG_RMAX = 64;                 // rank of a design
+// permutations of a lane, by the rank: a lane holds PTL * PG_V * min(r, PG_PANEL) float64 accumulators
+constexpr int pg_ptl(int r) { return r <= 1 ? CG_PERM_PTL1 : r <= 4 ? CG_PERM_PTL4 : CG_PERM_PTL; }
+// rows of e a lane loads in one go, by the columns of the panel
+constexpr int pg_u(int nj) { return nj <= 8 ? CG_PERM_U : CG_PERM_UWIDE; }
+constexpr int pg_pt(int r) { return PG_NW * pg_ptl(r); }    // permutations of a workgroup
+
+__device__ __forceinline__ double pg_signed(double x, uint32_t flip) {      // flip: 0 or the sign bit
+    return __hiloint2double(__double2hiint(x) ^ (int)flip, __double2loint(x));
+}
+
+// one row j of e into the accumulators of the lane's permutations: columns [k0, k0 + NJ) of the permuted rows of Uf
+template <int PTL, int NJ>
+__device__ __forceinline__ void pg_row(double (&a)[PTL][PG_V][NJ], const float (&y)[PG_V], const double* __restrict__ Ufk,
+                                       const uint32_t* const (&rw)[PTL], int j, int S, int r) {
+    double yd[PG_V];
+#pragma unroll
+    for (int v = 0; v < PG_V; ++v) yd[v] = (double)y[v];
+#pragma unroll
+    for (int i = 0; i < PTL; ++i) {
+        const uint32_t ent = rw[i][j];
+        const uint32_t row = min(ent & 0x7FFFFFFFu, (uint32_t)(S - 1));
+        const uint32_t flip = ent & 0x80000000u;
+        const double* __restrict__ ur = Ufk + (size_t)row * r;
+        double x[PG_V];
+#pragma unroll
+        for (int v = 0; v < PG_V; ++v) x[v] = pg_signed(yd[v], flip);
+#pragma unroll
+        for (int k = 0; k < NJ; ++k) {
+            const double uk = ur[k];
+#pragma unroll
+            for (int v = 0; v < PG_V; ++v) a[i][v][k] = __dadd_rn(a[i][v][k], __dmul_rn(uk, x[v]));
+        }
+    }
+}
+
+// one panel: the pass over e, then its columns' share of ssq and num (k ascending)
+template <int PTL, int NJ>
+__device__ __forceinline__ void pg_panel(double (&ssq)[PTL][PG_V], double (&num)[PTL][PG_V], const float* __restrict__ e,
+                                         const double* __restrict__ Ufk, const double* __restrict__ uk0,
+                                         const uint32_t* const (&rw)[PTL], int S, int M, int r, int i0, int i1) {
+    constexpr int PG_U = pg_u(NJ);
+    double a[PTL][PG_V][NJ];
+#pragma unroll
+    for (int i = 0; i < PTL; ++i)
+#pragma unroll
+        for (int v = 0; v < PG_V; ++v)
+#pragma unroll
+            for (int k = 0; k < NJ; ++k) a[i][v][k] = 0.0;
+    for (int j = 0; j < S; j += PG_U) {
+        float y[PG_U][PG_V];
+#pragma unroll
+        for (int s = 0; s < PG_U; ++s) {
+            const float* row = e + (size_t)min(j + s, S - 1) * M;
+            y[s][0] = row[i0];
+            y[s][1] = row[i1];
+        }
+        if (j + PG_U <= S) {
+#pragma unroll
+            for (int s = 0; s < PG_U; ++s) pg_row<PTL, NJ>(a, y[s], Ufk, rw, j + s, S, r);
+        } else {
+#pragma unroll
+            for (int s = 0; s < PG_U; ++s)
+                if (j + s < S) pg_row<PTL, NJ>(a, y[s], Ufk, rw, j + s, S, r);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NJ; ++k) {
+        const double uk = uk0[k];
+#pragma unroll
+        for (int i = 0; i < PTL; ++i)
+#pragma unroll
+            for (int v = 0; v < PG_V; ++v) {
+                ssq[i][v] = __dadd_rn(ssq[i][v], __dmul_rn(a[i][v][k], a[i][v][k]));
+                num[i][v] = __dadd_rn(num[i][v], __dmul_rn(uk, a[i][v][k]));
+            }
+    }
+}
+
+// block (PG_VB vertices, permutations [blockIdx.y PT, + PT)), PG_NW waves.  MORE: r = PG_PANEL * (panels - 1) + NJL with at least
+// one full panel before the last; else r = NJL
+template <int NJL, bool MORE>
+__global__ void __launch_bounds__(PG_NW * 64)
+perm_glm_t_kernel(const float* __restrict__ e, const double* __restrict__ q, const double* __restrict__ Uf,
+                  const double* __restrict__ u, double unorm2, double dof, const uint32_t* __restrict__ rows, float* __restrict__ t,
+                  int S, int M, int r, int Pb) {
+    constexpr int PTL = pg_ptl(MORE ? PG_PANEL + NJL : NJL);
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int m0 = blockIdx.x * PG_VB + lane * PG_V;
+    const int pb = (blockIdx.y * PG_NW + w) * PTL;
+    if (pb >= Pb) return;                                   // (the same in every lane of the wave; no barrier follows)
+    const int i0 = min(m0, M - 1), i1 = min(m0 + 1, M - 1);
+    const uint32_t* rw[PTL];                                // a permutation beyond Pb computes the last one again and stores nothing
+#pragma unroll
+    for (int i = 0; i < PTL; ++i) rw[i] = rows + (size_t)min(pb + i, Pb - 1) * S;
+    double ssq[PTL][PG_V], num[PTL][PG_V];
+#pragma unroll
+    for (int i = 0; i < PTL; ++i)
+#pragma unroll
+        for (int v = 0; v < PG_V; ++v) ssq[i][v] = num[i][v] = 0.0;
+    int k0 = 0;
+    if (MORE)
+        for (; k0 < r - NJL; k0 += PG_PANEL) pg_panel<PTL, PG_PANEL>(ssq, num, e, Uf + k0, u + k0, rw, S, M, r, i0, i1);
+    pg_panel<PTL, NJL>(ssq, num, e, Uf + k0, u + k0, rw, S, M, r, i0, i1);
+
+    const double floor_ = __dmul_rn(4.0 * (double)(S + r), 0x1p-53);
+    const double qv[PG_V] = {q[i0], q[i1]};
+#pragma unroll
+    for (int i = 0; i < PTL; ++i) {
+        if (pb + i >= Pb) break;
+#pragma unroll
+        for (int v = 0; v < PG_V; ++v) {
+            double rss = __dsub_rn(qv[v], ssq[i][v]);
+            if (rss < __dmul_rn(floor_, qv[v])) rss = 0.0;  // round-off of the subtraction (also a negative one)
+            const double var = __dmul_rn(__ddiv_rn(rss, dof), unorm2);
+            float tv = 0.f;
+            if (var > 0.0) tv = (float)__ddiv_rn(num[i][v], __dsqrt_rn(var));
+            if (m0 + v < M) t[(size_t)(pb + i) * M + m0 + v] = tv;
+        }
+    }
+}
+
+template <int NJL, bool MORE>
+static void perm_glm_launch(hipStream_t stream, const float* e, const double* q, const double* Uf, const double* u, double unorm2,
+                            double dof, const uint32_t* rows, float* t, int S, int M, int r, int Pb) {
+    static char name[48];
+    static const int named = snprintf(name, sizeof name, "perm_glm_t_kernel<%d, %s>", NJL, MORE ? "panels" : "one");
+    (void)named;
+    note_dispatch(name);
+    const int PT = pg_pt(r);
+    const dim3 grid((unsigned)((M + PG_VB - 1) / PG_VB), (unsigned)((Pb + PT - 1) / PT));
+    hipLaunchKernelGGL((perm_glm_t_kernel<NJL, MORE>), grid, dim3(PG_NW * 64), 0, stream, e, q, Uf, u, unorm2, dof, rows, t, S, M, r,
+                       Pb);
+}
+
+typedef void (*PermGlmLaunch)(hipStream_t, const float*, const double*, const double*, const double*, double, double, const uint32_t*,
+                              float*, int, int, int, int);
+template <int... NJ>
+static PermGlmLaunch perm_glm_launch_of(int r, std::integer_sequence<int, NJ...>) {
+    static const PermGlmLaunch one[] = {perm_glm_launch<NJ + 1, false>...};
+    static const PermGlmLaunch more[] = {perm_glm_launch<NJ + 1, true>...};
+    const int njl = r - PG_PANEL * ((r - 1) / PG_PANEL);
+    return (r > PG_PANEL ? more : one)[njl - 1];
 }
 
 // ---- the on-chip arm ----------------------------------------------------------------------------------------------------------------
@@ -413,6 +606,37 @@ extern "C" int chebgcn_signflip_t(const float* x, const double* q, const uint32_
     note_dispatch("signflip_t_kernel");
     const dim3 grid((unsigned)((M + CL_T - 1) / CL_T), (unsigned)Pb);
     hipLaunchKernelGGL(signflip_t_kernel, grid, dim3(CL_T), 0, (hipStream_t)stream_, x, q, bits, t, S, M, p0, seed);
+    CG_HIP(hipGetLastError());
+    return CHEBGCN_OK;
+}
+
+extern "C" int chebgcn_perm_glm_query(int what) {
+    if (what > 100 && what <= 100 + PG_RMAX) return pg_pt(what - 100);      // permutations of a workgroup at rank what - 100
+    switch (what) {
+        case 0: return PG_VB;               // vertices of a workgroup
+        case 1: return pg_pt(1);            // permutations of a workgroup at most
+        case 2: return PG_PANEL;            // columns of Uf of one pass over e
+        case 3: return PG_RMAX;             // rank of a design
+        case 4: return CL_SMAX;             // subjects
+        case 5: return CL_MMAX;             // vertices
+        case 6: return CL_PBMAX;            // permutations of one call
+        default: return -1;
+    }
+}
+
+extern "C" int chebgcn_perm_glm_t(const float* e, const double* q, const double* Uf, const double* u, double unorm2, int dof,
+                                  const uint32_t* rows, float* t, int S, int M, int r, int Pb, chebgcn_stream stream_) {
+    CG_REQUIRE(e && q && Uf && u && rows && t, "perm_glm_t: NULL argument");
+    CG_REQUIRE(S >= 2 && M >= 1 && Pb >= 1 && r >= 1, "perm_glm_t: bad shape (S = %d, M = %d, r = %d, Pb = %d)", S, M, r, Pb);
+    if (S > CL_SMAX || M > CL_MMAX || Pb > CL_PBMAX || r > PG_RMAX)
+        return fail(CHEBGCN_EUNSUPPORTED, "perm_glm_t: S = %d, M = %d, Pb = %d, r = %d; served: S <= %d, M <= %d, Pb <= %d, r <= %d", S,
+                    M, Pb, r, CL_SMAX, CL_MMAX, CL_PBMAX, PG_RMAX);
+    CG_REQUIRE(r < S && dof >= 1, "perm_glm_t: r = %d of S = %d subjects, dof = %d", r, S, dof);
+    CG_REQUIRE((((uintptr_t)e | (uintptr_t)t | (uintptr_t)rows) & 3) == 0 && (((uintptr_t)q | (uintptr_t)Uf | (uintptr_t)u) & 7) == 0,
+               "perm_glm_t: unaligned argument");
+    CG_REQUIRE(unorm2 > 0.0 && unorm2 <= 1.7976931348623157e308, "perm_glm_t: unorm2 = %g", unorm2);
+    perm_glm_launch_of(r, std::make_integer_sequence<int, PG_PANEL>())((hipStream_t)stream_, e, q, Uf, u, unorm2, (double)dof, rows, t,
+                                                                      S, M, r, Pb);
     CG_HIP(hipGetLastError());
     return CHEBGCN_OK;
 }

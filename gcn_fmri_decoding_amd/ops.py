@@ -596,6 +596,40 @@ def signflip_t(x, q, p0, Pb, seed, bits=None, out=None):
     return out
 
 
+def perm_glm_geometry(r=None):
+    """The constants of ``perm_glm_t`` (chebgcn_perm_glm_query), so that callers and tests follow the tile: ``vertices`` and
+    ``perms`` of a workgroup (at rank ``r``; None: the most at any rank), ``panel`` columns of Uf of one pass over e, ``max_r``
+    / ``max_S`` / ``max_M`` served, ``max_perms`` of one call."""
+    q = _lib.lib().chebgcn_perm_glm_query
+    return {'vertices': q(0), 'perms': q(1 if r is None else 100 + int(r)), 'panel': q(2), 'max_r': q(3), 'max_S': q(4),
+            'max_M': q(5), 'max_perms': q(6)}
+
+
+def perm_glm_t(e, q, Uf, u, unorm2, dof, rows, out=None):
+    """The t maps of one contrast under the permutations of a table (chebgcn_perm_glm_t): ``e`` float32 [S, M], ``q`` float64
+    [M], ``Uf`` float64 [S, r], ``u`` float64 [r] and ``rows`` int32 [Pb, S] (the uint32 entries of ``stats.permutations``,
+    reinterpreted) on the device, ``unorm2`` and ``dof`` numbers -> float32 [Pb, M].  The arithmetic: include/chebgcn.h."""
+    _require_cuda(e, q, Uf, u, rows, out)
+    if e.dim() != 2 or e.dtype != torch.float32 or not e.is_contiguous():
+        raise _lib.ChebgcnError('perm_glm_t: e must be contiguous float32 [S, M]')
+    S, M = int(e.shape[0]), int(e.shape[1])
+    _vec(q, torch.float64, M, 'perm_glm_t: q')
+    if Uf.dim() != 2 or Uf.dtype != torch.float64 or int(Uf.shape[0]) != S or not Uf.is_contiguous() or Uf.numel() == 0:
+        raise _lib.ChebgcnError('perm_glm_t: Uf must be contiguous float64 [%d, r]' % S)
+    r = int(Uf.shape[1])
+    _vec(u, torch.float64, r, 'perm_glm_t: u')
+    if rows.dim() != 2 or rows.dtype != torch.int32 or int(rows.shape[1]) != S or not rows.is_contiguous() or rows.numel() == 0:
+        raise _lib.ChebgcnError('perm_glm_t: rows must be contiguous int32 words [Pb, %d]' % S)
+    Pb = int(rows.shape[0])
+    if out is None:
+        out = torch.empty((Pb, M), dtype=torch.float32, device=e.device)
+    elif tuple(out.shape) != (Pb, M) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.ChebgcnError('perm_glm_t: out must be contiguous float32 [%d, %d]' % (Pb, M))
+    _lib.check(_launch('perm_glm_t', 4.0 * Pb * M + 4.0 * S * M, 4.0 * Pb * M * S * r, lambda: _lib.lib().chebgcn_perm_glm_t(
+        _p(e), _p(q), _p(Uf), _p(u), float(unorm2), int(dof), _p(rows), _p(out), S, M, r, Pb, _stream())), 'perm_glm_t')
+    return out
+
+
 def cluster_enhance_workspace(Pb, M, mode, arm=_lib.CLUSTER_AUTO):
     """Bytes of scratch ``cluster_enhance`` takes (chebgcn_cluster_enhance_workspace): 0 on chip, ``state_bytes`` per
     (permutation, vertex) streamed."""

@@ -902,7 +902,30 @@ int chebgcn_cheb_filter(const chebgcn_graph* g, const float* x, const float* coe
  *   its limit), before any launch.
  * cluster_query: 0 vertices of the on-chip arm at most, 1 subjects, 2 vertices, 3 heights, 4 permutations of a call at most,
  *   5 bytes of state per (permutation, vertex); -1 for anything else.
- * cluster_enhance_workspace: bytes the call would take (0: the on-chip arm, MAX, or arguments out of range). */
+ * cluster_enhance_workspace: bytes the call would take (0: the on-chip arm, MAX, or arguments out of range).
+ * perm_glm_t: the t map of ONE contrast of a general linear model whose design is permuted (stats.design_test, the Freedman-Lane
+ *   scheme).  The caller factors the design on the host, D = U S V^T (thin SVD, rank r), and hands the kernel
+ *     e      float32 [S][M]   the residuals of the nuisance fit, one row per subject (contiguous; M is any number)
+ *     q      float64 [M]      q[v] = sum_j e[j][v]^2, ascending j, computed once by the caller
+ *     Uf     float64 [S][r]   = U[:, :r], row-major (device)
+ *     u      float64 [r]      = Uf^T (pinv(D)^T c) (device);  unorm2 = c pinv(D^T D) c > 0 and dof = S - r >= 1 by value
+ *     rows   uint32 [Pb][S]   (device) entry [p][j]: low 31 bits = the row of Uf that meets subject j in permutation p, top bit =
+ *                             e[j] is negated.  A row number >= S is clamped to S - 1: it is never an address unchecked.
+ *   -> t float32 [Pb][M], the layout cluster_enhance takes.  Per (permutation p, vertex v), in float64, every multiply, add,
+ *   divide and square root rounded on its own (never an fma), division and square root correctly rounded:
+ *     a_k = 0;  a_k = a_k + Uf[row(p, j)][k] * (+-e[j][v])   for j = 0 .. S - 1 ascending,   k = 0 .. r - 1
+ *     ssq = 0;  ssq = ssq + a_k * a_k   k ascending;         num = 0;  num = num + u[k] * a_k   k ascending
+ *     rss = q[v] - ssq, taken as 0 where rss < (4 (S + r) 2^-53) q[v]          (the floor glm_finish uses)
+ *     var = (rss / dof) * unorm2;       t = var > 0 ? (float)(num / sqrt(var)) : 0
+ *   bit for bit what float64 NumPy gives (stats.perm_t_host), and for a (p, v) the same bits whatever Pb, M or the rest of the
+ *   table holds.  A workgroup takes chebgcn_perm_glm_query(0) vertices and (100 + r) permutations; r > (2) runs in column panels
+ *   of (2) with e re-read per panel, ssq and num carried across them.  No synchronisation, no allocation, no atomics.
+ *   2 <= S <= 4096, M <= 2^24, Pb <= 65535, r <= 64: CHEBGCN_EUNSUPPORTED beyond, before any launch; r >= S, dof < 1 or
+ *   unorm2 <= 0: CHEBGCN_EINVAL.  chebgcn_last_dispatch(): perm_glm_t_kernel<n, one | panels>, n = the columns of the last (or
+ *   only) panel.
+ * perm_glm_query: 0 vertices of a workgroup, 1 permutations of a workgroup at most, 2 columns of a panel, 3 rank, 4 subjects,
+ *   5 vertices, 6 permutations of a call at most, 100 + r (r = 1 .. 64) permutations of a workgroup at rank r; -1 for anything
+ *   else. */
 enum {
     CHEBGCN_CLUSTER_MAX = 0,
     CHEBGCN_CLUSTER_EXTENT = 1,
@@ -916,6 +939,9 @@ int chebgcn_cluster_query(int what);
 size_t chebgcn_cluster_enhance_workspace(int Pb, int M, int mode, int arm);
 int chebgcn_signflip_t(const float* x, const double* q, const uint32_t* bits, float* t, int S, int M, uint32_t p0, int Pb,
                        uint32_t seed, chebgcn_stream stream);
+int chebgcn_perm_glm_query(int what);
+int chebgcn_perm_glm_t(const float* e, const double* q, const double* Uf, const double* u, double unorm2, int dof,
+                       const uint32_t* rows, float* t, int S, int M, int r, int Pb, chebgcn_stream stream);
 int chebgcn_cluster_enhance(const int32_t* ptr, const int32_t* idx, int64_t nnz, const float* t, int negate, const float* hf,
                             const double* hw, int NH, const double* ep, double step, double* out, int32_t* labels, double* pmax,
                             int32_t* status, void* workspace, size_t workspace_bytes, int Pb, int M, int mode, int arm,
