@@ -11,7 +11,7 @@ from .parcellation import Parcellation  # noqa: F401
 from .filters import GraphFilter  # noqa: F401
 from .stats import MapTestResult, map_test, map_test_host, sign_flips  # noqa: F401
 from .stats import DesignTestResult, design_test, design_test_host, permutations, perm_t_host  # noqa: F401
-from .glm import (Design, GLMResult, contrasts_one_vs_rest, design_matrix, first_level,  # noqa: F401
+from .glm import (Design, GLMResult, GLMResultAR1, contrasts_one_vs_rest, design_matrix, first_level,  # noqa: F401
                   first_level_host)
 # (the call itself is searchlight.searchlight: the package attribute stays the module)
 from .searchlight import SearchlightResult, SolverInfo, lda_shrinkage_host, searchlight_events, searchlight_host  # noqa: F401
@@ -19,7 +19,7 @@ from .searchlight import RDMResult, compare_rdms, crossnobis, crossnobis_events,
 
 __all__ = ['graph', 'coarsening', 'parcellation', 'Parcellation', 'filters', 'GraphFilter', 'splits', 'stats', 'map_test',
            'map_test_host', 'sign_flips', 'MapTestResult', 'design_test', 'design_test_host', 'permutations', 'perm_t_host',
-           'DesignTestResult', 'glm', 'Design', 'GLMResult', 'design_matrix', 'contrasts_one_vs_rest',
+           'DesignTestResult', 'glm', 'Design', 'GLMResult', 'GLMResultAR1', 'design_matrix', 'contrasts_one_vs_rest',
            'first_level', 'first_level_host', 'searchlight', 'SearchlightResult', 'SolverInfo', 'searchlight_events', 'searchlight_host',
            'lda_shrinkage_host', 'RDMResult', 'compare_rdms', 'crossnobis', 'crossnobis_events', 'crossnobis_host', 'models_gcn', 'ops']
 

@@ -27,7 +27,7 @@ int fail(int code, const char* fmt, ...) {
 
 namespace {
 struct DispatchRecord {
-    const char* name[6];
+    const char* name[8];     // (the AR(1) projection of 64 columns runs 8 panels)
     int n;
     char joined[512];
 };
@@ -45,7 +45,7 @@ void note_dispatch(const char* name) {
 
 void note_dispatch_more(const char* name) {
     DispatchRecord& r = dispatch_record();
-    if (r.n < 6) r.name[r.n++] = name;
+    if (r.n < 8) r.name[r.n++] = name;
 }
 
 template <typename T>

@@ -18,9 +18,20 @@ On the device a run's design enters as its thin SVD ``X = U S V^T`` of rank k (s
 ``variance = rss / dof * u.u`` (chebgcn_glm_finish); the runs of a subject are combined as fixed effects
 (chebgcn_glm_combine).  All of it float64 on the device, rounded once to float32: see include/chebgcn.h.
 
-Out of scope: AR(1) / prewhitened noise models (the OLS t of a single run is optimistic under temporal autocorrelation; the
-effect maps handed to ``map_test`` are not affected), temporal derivatives of the HRF, precision-weighted fixed effects, and
-returning residual series.
+``noise='ar1'`` prewhitens: the noise of a run is a stationary AR(1) process, covariance ``sigma^2 rho^|i-j| / (1 - rho^2)``,
+and the fit is exact generalised least squares (the first row scaled, Prais-Winsten, not dropped) -- the OLS t of a single run is
+optimistic under the temporal autocorrelation of BOLD noise.  ``rho`` is estimated per (run, vertex) from the OLS residuals,
+``sum r_t r_{t-1} / sum r_t^2`` clamped to ``+-RHO_MAX``, or given for every vertex (SPM's global AR(1)).  With
+``K = (1 + rho^2) I - rho (Sh + Sh^T) - rho^2 (e_0 e_0^T + e_L e_L^T)`` (``Sh`` the one-row shift, ``L = T - 1``) everything is
+linear or bilinear in y: the pass forms ``a = Q^T y``, ``h = Qs^T y`` (``Qs = Sh Q + Sh^T Q``), ``y.y`` and the lag sum
+``sum y_t y_{t-1}`` (chebgcn_glm_project_ar1); per vertex ``rho = (S1 - a.h + a.D a / 2) / (y.y - a.a)``, ``D = Q^T Qs``, then the
+``k x k`` system ``M = (1 + rho^2) I - rho D - rho^2 E`` (``E = q_0 q_0^T + q_L q_L^T``) is factored ``M = L L^T`` and
+``z = L^-1 g``, ``w = L^-1 u`` give ``rss = y^T K y - z.z``, ``effect = w.z``, ``variance = rss / dof * w.w``, ``b = B L^-T z``
+(chebgcn_glm_finish_ar1).  ``dof`` takes no correction for estimating rho (as nilearn and SPM).
+
+Out of scope: bias correction of the estimated rho (the residual estimate is biased downward, the more so the more regressors),
+AR orders above 1, rho smoothed across vertices, temporal derivatives of the HRF, precision-weighted fixed effects, and returning
+residual series.
 
 The host-only parts need NumPy and SciPy only.
 """
@@ -31,6 +42,7 @@ import numpy as np
 HRF_SPM = (6.0, 16.0, 1.0 / 6.0)
 KMAX, CMAX, PMAX, RMAX = 64, 32, 64, 65535      # chebgcn_glm_query(2), (3), (7), (8)
 ESTIMABLE_TOL = 1e-8
+RHO_MAX = 0.99                                  # an estimated AR(1) coefficient is clamped to +- this (include/chebgcn.h)
 
 Design = collections.namedtuple('Design', 'X columns conditions')
 Design.__doc__ = """What ``design_matrix`` returns: ``X`` float64 [T, P]; ``columns`` the P column names (the conditions, then
@@ -40,6 +52,10 @@ GLMResult = collections.namedtuple('GLMResult', 'effect variance t dof groups be
 GLMResult.__doc__ = """What ``first_level`` returns.  ``effect``, ``variance``, ``t``: float32 [S, C, M], one map per group (subject)
 and contrast (float64 from ``first_level_host``); ``dof`` int64 [S] the residual degrees of freedom (summed over the group's
 runs); ``groups`` the S group keys in order of first appearance; ``betas`` None, or one float32 [P_r, M] per run."""
+
+GLMResultAR1 = collections.namedtuple('GLMResultAR1', 'effect variance t dof groups betas rho')
+GLMResultAR1.__doc__ = """What ``first_level(noise='ar1')`` returns: the fields of ``GLMResult``, then ``rho``: one float32 [M] array
+per run (a tensor where the run came as a tensor; float64 from ``first_level_host``), the AR(1) coefficient of every vertex."""
 
 
 def _is_tensor(a):
@@ -277,16 +293,67 @@ def _host_array(y, who):
 
 # ---- the host restatement -------------------------------------------------------------------------------------------------------
 
-def first_level_host(runs, designs, contrasts=None, groups=None, betas=False):
+def _noise_args(noise, rho, who):
+    if noise not in ('ols', 'ar1'):
+        raise ValueError("%s: noise must be 'ols' or 'ar1', got %r" % (who, noise))
+    if rho is None:
+        return None
+    if noise == 'ols':
+        raise ValueError("%s: rho is the coefficient of noise='ar1'; noise='ols' takes none" % who)
+    if isinstance(rho, (bool, np.bool_)) or not isinstance(rho, (int, float, np.integer, np.floating)) or not abs(float(rho)) < 1.0:
+        raise ValueError('%s: rho must be None (estimated per vertex) or a number inside (-1, 1), got %r' % (who, rho))
+    return float(rho)
+
+
+def _host_rho(res, y, T, rank):
+    """``sum r_t r_{t-1} / sum r_t^2`` of OLS residuals [T, M], clamped to ``+-RHO_MAX``; 0 where the residuals are the round-off
+    of a vertex the design explains exactly (``rss < 4 (T + rank) 2^-53 y.y``, the floor of the kernels)."""
+    rss = (res * res).sum(axis=0)
+    lag = (res[1:] * res[:-1]).sum(axis=0)
+    live = rss >= 4.0 * (T + rank) * 2.0 ** -53 * (y * y).sum(axis=0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        raw = np.where(live & (rss > 0), lag / np.where(rss > 0, rss, 1.0), 0.0)
+    return np.clip(raw, -RHO_MAX, RHO_MAX), raw
+
+
+def _host_gls(tb, y, rho):
+    """Explicit AR(1) GLS of one run, one coefficient per vertex: the ``T x T`` covariance ``rho^|i-j| / (1 - rho^2)``, its
+    Cholesky factor, X and y whitened by it, ``lstsq``, residuals formed, ``pinv`` for the contrasts.
+    ``(b [P, M], rss [M], factor [C, M])``."""
+    from scipy.linalg import cholesky, solve_triangular
+    T, P = tb.X.shape
+    eps = max(tb.X.shape) * np.finfo(np.float64).eps
+    b, rss, factor = np.empty((P, y.shape[1])), np.empty(y.shape[1]), np.empty((tb.c.shape[0], y.shape[1]))
+    lags = np.abs(np.arange(T)[:, None] - np.arange(T)[None, :])
+    for value in np.unique(rho):
+        cols = np.flatnonzero(rho == value)
+        Lc = cholesky(value ** lags / (1.0 - value * value), lower=True)
+        Xw = solve_triangular(Lc, tb.X, lower=True)
+        yw = solve_triangular(Lc, y[:, cols], lower=True)
+        bw = np.linalg.lstsq(Xw, yw, rcond=eps)[0]
+        res = yw - Xw @ bw
+        b[:, cols] = bw
+        rss[cols] = (res * res).sum(axis=0)
+        factor[:, cols] = np.einsum('cp,pq,cq->c', tb.c, np.linalg.pinv(Xw.T @ Xw, rcond=eps ** 2, hermitian=True), tb.c)[:, None]
+    return b, rss, factor
+
+
+def first_level_host(runs, designs, contrasts=None, groups=None, betas=False, noise='ols', rho=None):
     """``first_level`` restated in float64 NumPy (no device), without the projection trick of the kernels.  Per run:
     ``b = lstsq(X, y)`` (minimum norm), the residuals formed explicitly, ``rss = sum res^2``, ``dof = T - rank(X)``,
     ``sigma^2 = rss / dof``; per contrast ``effect = c.b``, ``variance = sigma^2 c pinv(X^T X) c``, ``t = effect / sqrt(variance)``
     (0 where the variance is 0).  The runs of a group are combined as fixed effects: ``effect = mean_r effect_r``,
     ``variance = sum_r variance_r / R_g^2``, ``dof = sum_r dof_r``.  The series are rounded to float32 first, as staging does.
-    Returns a ``GLMResult`` of float64 maps (betas float64 as well)."""
+    Returns a ``GLMResult`` of float64 maps (betas float64 as well).
+
+    ``noise='ar1'`` uses none of the kernels' algebra either: the OLS fit above, ``rho = sum r_t r_{t-1} / sum r_t^2`` of its
+    residuals clamped to ``+-RHO_MAX`` (or the given ``rho``), then per vertex the explicit ``T x T`` covariance, its Cholesky
+    factor, X and y whitened by it, ``lstsq``, residuals and ``pinv`` again.  Slow: meant for the sizes of the tests.  Returns a
+    ``GLMResultAR1`` (``rho`` float64 [M] per run)."""
     who = 'first_level_host'
+    rho = _noise_args(noise, rho, who)
     pl = _plan(runs, designs, contrasts, groups, who, limits=False)
-    eff, var, dof, bs = [], [], [], []
+    eff, var, dof, bs, rhos = [], [], [], [], []
     for y, tb in zip(pl.runs, pl.tables):
         y = _host_array(y, who).astype(np.float64)
         b = np.linalg.lstsq(tb.X, y, rcond=max(tb.X.shape) * np.finfo(np.float64).eps)[0]
@@ -294,9 +361,12 @@ def first_level_host(runs, designs, contrasts=None, groups=None, betas=False):
         rss = (res * res).sum(axis=0)
         d = tb.T - tb.rank
         factor = np.einsum('cp,pq,cq->c', tb.c, np.linalg.pinv(tb.X.T @ tb.X, rcond=(max(tb.X.shape) * np.finfo(np.float64).eps) ** 2,
-                                                                 hermitian=True), tb.c)
+                                                                 hermitian=True), tb.c)[:, None]
+        if noise == 'ar1':
+            rhos.append(np.full(pl.M, rho) if rho is not None else _host_rho(res, y, tb.T, tb.rank)[0])
+            b, rss, factor = _host_gls(tb, y, rhos[-1])
         eff.append(tb.c @ b)
-        var.append((rss / d)[None, :] * factor[:, None])
+        var.append((rss / d)[None, :] * factor)
         dof.append(d)
         bs.append(b)
     S = len(pl.keys)
@@ -312,6 +382,8 @@ def first_level_host(runs, designs, contrasts=None, groups=None, betas=False):
         gdof[g] = sum(dof[r] for r in mem)
     with np.errstate(divide='ignore', invalid='ignore'):
         t = np.where(variance > 0, effect / np.sqrt(variance), 0.0)
+    if noise == 'ar1':
+        return GLMResultAR1(effect, variance, t, gdof, list(pl.keys), bs if betas else None, rhos)
     return GLMResult(effect, variance, t, gdof, list(pl.keys), bs if betas else None)
 
 
@@ -333,7 +405,28 @@ def _batch_tables(tabs, C):
     return Q, U, np.stack([tb.un2 for tb in tabs]), B, np.array([tb.rank for tb in tabs], np.int32)
 
 
-def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=False, batch_runs=None):
+def _ar1_tables(tabs, k):
+    """The tables of the AR(1) fit of one batch, padded like ``_batch_tables``: ``W = [Q | Qs]`` [T, 2k] with row t of ``Qs`` =
+    ``Q[t - 1] + Q[t + 1]`` (zero beyond the ends of the run), ``D = Q^T Qs`` and ``E = q_0 q_0^T + q_L q_L^T`` [n, k, k]."""
+    W = np.zeros((sum(tb.T for tb in tabs), 2 * k))
+    D = np.zeros((len(tabs), k, k))
+    E = np.zeros((len(tabs), k, k))
+    o = 0
+    for i, tb in enumerate(tabs):
+        Q, kr = tb.Q, tb.rank
+        Qs = np.zeros_like(Q)
+        Qs[1:] += Q[:-1]
+        Qs[:-1] += Q[1:]
+        W[o:o + tb.T, :kr] = Q
+        W[o:o + tb.T, k:k + kr] = Qs
+        d = Q.T @ Qs
+        D[i, :kr, :kr] = 0.5 * (d + d.T)
+        E[i, :kr, :kr] = np.outer(Q[0], Q[0]) + np.outer(Q[-1], Q[-1])
+        o += tb.T
+    return W, D, E
+
+
+def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=False, batch_runs=None, noise='ols', rho=None):
     """Per-subject activation maps of a general linear model, on the device: a ``GLMResult``.
 
     ``runs``: one ``[T, M]`` array or a list (any lengths, same M; NumPy arrays, or torch tensors such as
@@ -342,8 +435,12 @@ def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=F
     ``contrasts``: ``[C, P]`` for every run (or one such array per run, when designs differ in width); default
     ``contrasts_one_vs_rest`` of each design.  ``groups``: one hashable key per run -- the subject; default one group; the
     runs of a group are combined as fixed effects (``effect`` the mean, ``variance = sum / R_g^2``, ``dof`` the sum).
-    ``batch_runs``: runs of one pass of the kernels, which bounds the float64 workspace of ``(k + 1) Mp`` values per run;
-    default from the free device memory.  The result does not depend on it, bit for bit.
+    ``batch_runs``: runs of one pass of the kernels, which bounds the float64 workspace of ``(k + 1) Mp`` values per run
+    (``(2 k + 2) Mp`` with ``noise='ar1'``); default from the free device memory.  The result does not depend on it, bit for bit.
+    ``noise``: ``'ols'``, or ``'ar1'`` for the prewhitened fit of the module's docstring, which returns a ``GLMResultAR1``:
+    the same fields and ``rho``, one float32 ``[M]`` map per run.  ``rho``: None estimates the coefficient per (run, vertex)
+    from the OLS residuals (clamped to ``+-RHO_MAX``; 0 at a vertex constant in time), a number inside (-1, 1) applies it to
+    every vertex of every run.  ``dof`` is ``sum (T_r - k_r)`` either way.
 
     Returns ``effect``, ``variance``, ``t`` float32 ``[S, C, M]`` (NumPy; torch tensors on the device if every run came as a
     tensor), ``dof`` int64 ``[S]``, ``groups`` and, with ``betas``, one float32 ``[P_r, M]`` per run (the minimum-norm
@@ -352,9 +449,11 @@ def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=F
     ``ValueError`` before any launch: non-finite series, ``T_r <= rank``, a contrast that is not estimable in a run
     (``|c - X^+ X c| > 1e-8 |c|``), design rows != run rows, mixed M, P, C or rank beyond what the kernels serve.
 
-    Out of scope: AR(1) / prewhitened noise (the OLS t of one run is optimistic under autocorrelation; effect maps are not
-    affected), temporal derivatives of the HRF, precision-weighted fixed effects, residual series."""
+    Out of scope: bias correction of the estimated rho, AR orders above 1, rho smoothed across vertices, temporal derivatives
+    of the HRF, precision-weighted fixed effects, residual series."""
     who = 'first_level'
+    rho = _noise_args(noise, rho, who)
+    ar1 = noise == 'ar1'
     pl = _plan(runs, designs, contrasts, groups, who)
     if batch_runs is not None and (isinstance(batch_runs, (bool, np.bool_)) or not isinstance(batch_runs, (int, np.integer))
                                    or batch_runs < 1):
@@ -388,19 +487,26 @@ def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=F
         if batch_runs is None:
             kmax = max(tb.rank for tb in pl.tables)
             free = torch.cuda.mem_get_info(dev)[0]
-            batch_runs = max(1, int(free // 4) // (8 * (kmax + 1) * Mp))
+            batch_runs = max(1, int(free // 4) // (8 * ((2 * kmax + 2) if ar1 else (kmax + 1)) * Mp))
         batch_runs = int(min(batch_runs, R, RMAX))
         e64 = torch.empty((R, C, Mp), dtype=torch.float64, device=dev)
         v64 = torch.empty((R, C, Mp), dtype=torch.float64, device=dev)
-        beta_out = []
+        beta_out, rho_out = [], []
         for r0 in range(0, R, batch_runs):
             r1 = min(r0 + batch_runs, R)
             Q, U, un2, B, rank = (torch.as_tensor(a).to(dev) for a in _batch_tables(pl.tables[r0:r1], C))
             rows = planes[int(offs[r0]):int(offs[r1])]
             o = torch.as_tensor(offs[r0:r1 + 1] - offs[r0]).to(dev)
-            a, yy = ops.glm_project(rows, o, M, Q)
-            beta = ops.glm_finish(a, yy, o, rows.shape[0], rank, U, un2, M, B=B if betas else None,
-                                  out64=(e64[r0:r1], v64[r0:r1]))[3]
+            if ar1:
+                W, D, E = (torch.as_tensor(a).to(dev) for a in _ar1_tables(pl.tables[r0:r1], int(Q.shape[1])))
+                ah, s0, s1 = ops.glm_project_ar1(rows, o, M, W)
+                beta, rmap = ops.glm_finish_ar1(ah, s0, s1, rows, W, o, rank, D, E, U, M, rho=rho, B=B if betas else None,
+                                                out64=(e64[r0:r1], v64[r0:r1]))[3:]
+                rho_out += [rmap[i, :M] for i in range(r1 - r0)]
+            else:
+                a, yy = ops.glm_project(rows, o, M, Q)
+                beta = ops.glm_finish(a, yy, o, rows.shape[0], rank, U, un2, M, B=B if betas else None,
+                                      out64=(e64[r0:r1], v64[r0:r1]))[3]
             if betas:
                 beta_out += [beta[i, :tb.X.shape[1], :M] for i, tb in enumerate(pl.tables[r0:r1])]
         gptr = np.concatenate([[0], np.cumsum([len(m) for m in pl.members])]).astype(np.int32)
@@ -408,6 +514,8 @@ def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=F
         effect, variance, t = ops.glm_combine(e64, v64, torch.as_tensor(gptr).to(dev), torch.as_tensor(gruns).to(dev), M)
         dof = np.array([sum(pl.tables[r].T - pl.tables[r].rank for r in m) for m in pl.members], np.int64)
         if pl.tensors:
-            return GLMResult(effect, variance, t, dof, list(pl.keys), [b.contiguous() for b in beta_out] if betas else None)
-        return GLMResult(effect.cpu().numpy(), variance.cpu().numpy(), t.cpu().numpy(), dof, list(pl.keys),
-                         [b.cpu().numpy() for b in beta_out] if betas else None)
+            res = GLMResult(effect, variance, t, dof, list(pl.keys), [b.contiguous() for b in beta_out] if betas else None)
+            return GLMResultAR1(*res, [x.contiguous() for x in rho_out]) if ar1 else res
+        res = GLMResult(effect.cpu().numpy(), variance.cpu().numpy(), t.cpu().numpy(), dof, list(pl.keys),
+                        [b.cpu().numpy() for b in beta_out] if betas else None)
+        return GLMResultAR1(*res, [x.cpu().numpy() for x in rho_out]) if ar1 else res

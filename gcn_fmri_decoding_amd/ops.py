@@ -792,6 +792,98 @@ def glm_combine(e64, v64, group_ptr, group_runs, M):
     return out
 
 
+def glm_ar1_geometry(k=None):
+    """The constants of the AR(1) finish kernel (chebgcn_glm_ar1_query): ``waves`` of a workgroup, ``solve`` contrasts per forward
+    solve; with a rank ``k`` also its ``bucket`` (the ``KB`` of ``glm_finish_ar1_kernel<KB>``) and the ``vertices`` of a
+    workgroup at that rank."""
+    q = _lib.lib().chebgcn_glm_ar1_query
+    out = {'waves': q(0), 'solve': q(1)}
+    if k is not None:
+        out.update(bucket=q(100 + int(k)), vertices=q(200 + int(k)))
+    return out
+
+
+def glm_project_ar1(planes, run_offsets, M, W):
+    """The sums of the AR(1) fit (chebgcn_glm_project_ar1): ``planes`` float32 [Ttot, Mp], ``run_offsets`` int64 [R + 1] and
+    ``W = [Q | Qs]`` float64 [Ttot, 2k] on the device -> ``(ah float64 [R, 2k, Mp], s0, s1 float64 [R, Mp])`` in one workspace
+    (the next call on the stream reuses it)."""
+    _require_cuda(planes, run_offsets, W)
+    if planes.dim() != 2 or planes.shape[1] != plane_stride(M) or planes.dtype != torch.float32 or not planes.is_contiguous():
+        raise _lib.ChebgcnError('glm_project_ar1: planes must be contiguous float32 [Ttot, plane_stride(M)]')
+    Ttot, Mp = int(planes.shape[0]), int(planes.shape[1])
+    R = int(run_offsets.numel()) - 1
+    if run_offsets.dtype != torch.int64 or run_offsets.dim() != 1 or R < 1 or not run_offsets.is_contiguous():
+        raise _lib.ChebgcnError('glm_project_ar1: run_offsets must be a contiguous int64 vector of R + 1 entries')
+    if W.dim() != 2 or W.shape[1] % 2:
+        raise _lib.ChebgcnError('glm_project_ar1: W must be float64 [Ttot, 2k]')
+    k = int(W.shape[1]) // 2
+    _dense(W, torch.float64, (Ttot, 2 * k), 'glm_project_ar1: W')
+    lib = _lib.lib()
+    nbytes = int(lib.chebgcn_glm_ar1_workspace(R, M, k))
+    ws = _workspace(max(nbytes, 8) + 8, planes.device, 'glm')
+    ws = ws[(-ws.data_ptr()) % 8:]
+    n = 8 * R * Mp
+    ah = ws[:2 * k * n].view(torch.float64).view(R, 2 * k, Mp) if nbytes else None
+    s0 = ws[2 * k * n:(2 * k + 1) * n].view(torch.float64).view(R, Mp) if nbytes else None
+    s1 = ws[(2 * k + 1) * n:(2 * k + 2) * n].view(torch.float64).view(R, Mp) if nbytes else None
+    panels = -(-2 * k // max(glm_geometry()['panel'], 1))
+    _lib.check(_launch('glm_project_ar1', 4.0 * Ttot * Mp * panels + 8.0 * R * (2 * k + 2) * Mp, 2.0 * Ttot * Mp * (2 * k + 2),
+                       lambda: lib.chebgcn_glm_project_ar1(_p(planes), Ttot, _p(run_offsets), R, int(M), _p(W), k, _p(ah), _p(s0),
+                                                           _p(s1), _stream())), 'glm_project_ar1')
+    return ah, s0, s1
+
+
+def glm_finish_ar1(ah, s0, s1, planes, W, run_offsets, rank, D, E, U, M, rho=None, B=None, out64=None, want32=False):
+    """The AR(1) generalised least-squares fit of every (run, vertex) (chebgcn_glm_finish_ar1) from what ``glm_project_ar1``
+    returned: ``D``, ``E`` float64 [R, k, k], ``U`` float64 [R, C, k], ``B`` float64 [R, P, k] or None, ``rank`` int32 [R].
+    ``rho``: None estimates a coefficient per (run, vertex), a float applies it everywhere.  Returns ``(effect, variance, t)``
+    float32 [R, C, Mp] (``want32``, else None), ``beta`` float32 [R, P, Mp] or None, and ``rho`` float32 [R, Mp]."""
+    _require_cuda(ah, s0, s1, planes, W, run_offsets, rank, D, E, U, B)
+    R, k2, Mp = (int(v) for v in ah.shape)
+    k = k2 // 2
+    if Mp != plane_stride(M) or k2 % 2:
+        raise _lib.ChebgcnError('glm_finish_ar1: ah must be [R, 2k, plane_stride(M)]')
+    Ttot = int(planes.shape[0])
+    _dense(ah, torch.float64, (R, 2 * k, Mp), 'glm_finish_ar1: ah')
+    _dense(s0, torch.float64, (R, Mp), 'glm_finish_ar1: s0')
+    _dense(s1, torch.float64, (R, Mp), 'glm_finish_ar1: s1')
+    _dense(planes, torch.float32, (Ttot, Mp), 'glm_finish_ar1: planes')
+    _dense(W, torch.float64, (Ttot, 2 * k), 'glm_finish_ar1: W')
+    _dense(run_offsets, torch.int64, (R + 1,), 'glm_finish_ar1: run_offsets')
+    _dense(rank, torch.int32, (R,), 'glm_finish_ar1: rank')
+    _dense(D, torch.float64, (R, k, k), 'glm_finish_ar1: D')
+    _dense(E, torch.float64, (R, k, k), 'glm_finish_ar1: E')
+    if U.dim() != 3:
+        raise _lib.ChebgcnError('glm_finish_ar1: U must be float64 [R, C, k]')
+    C_ = int(U.shape[1])
+    _dense(U, torch.float64, (R, C_, k), 'glm_finish_ar1: U')
+    P = 0
+    beta = None
+    if B is not None:
+        if B.dim() != 3:
+            raise _lib.ChebgcnError('glm_finish_ar1: B must be float64 [R, P, k]')
+        P = int(B.shape[1])
+        _dense(B, torch.float64, (R, P, k), 'glm_finish_ar1: B')
+        beta = torch.empty((R, P, Mp), dtype=torch.float32, device=ah.device)
+    e64 = v64 = None
+    if out64 is not None:
+        e64, v64 = out64
+        _require_cuda(e64, v64)
+        _dense(e64, torch.float64, (R, C_, Mp), 'glm_finish_ar1: out64[0]')
+        _dense(v64, torch.float64, (R, C_, Mp), 'glm_finish_ar1: out64[1]')
+    e32 = v32 = t32 = None
+    if want32:
+        e32, v32, t32 = (torch.empty((R, C_, Mp), dtype=torch.float32, device=ah.device) for _ in range(3))
+    rho_out = torch.empty((R, Mp), dtype=torch.float32, device=ah.device)
+    flops = 2.0 * R * Mp * (k * k * k / 6.0 + k * k * (1 + C_) / 2.0 + k * (4 + P))
+    _lib.check(_launch('glm_finish_ar1', 8.0 * R * Mp * (2 * k + 2 + 2 * C_) + 4.0 * R * Mp * (1 + P), flops,
+                       lambda: _lib.lib().chebgcn_glm_finish_ar1(
+                           _p(ah), _p(s0), _p(s1), _p(planes), _p(W), _p(run_offsets), Ttot, _p(rank), _p(D), _p(E), _p(U), _p(B),
+                           R, int(M), k, C_, P, int(rho is not None), float(rho) if rho is not None else 0.0,
+                           _p(e64), _p(v64), _p(e32), _p(v32), _p(t32), _p(beta), _p(rho_out), _stream())), 'glm_finish_ar1')
+    return e32, v32, t32, beta, rho_out
+
+
 def searchlight_geometry():
     """The constants of the searchlight kernels (chebgcn_searchlight_query), so that callers and tests follow the tile: ``tile``
     lanes of a score wave, ``centres`` of a score workgroup, ``max_C`` classes served, ``vertices`` of a spread / fit workgroup,

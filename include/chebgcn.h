@@ -996,6 +996,58 @@ int chebgcn_glm_finish(const double* a, const double* yy, const int64_t* run_off
 int chebgcn_glm_combine(const double* eff64, const double* var64, const int32_t* group_ptr, const int32_t* group_runs, int nruns, int R,
                         int S, int C, int M, float* effect, float* variance, float* t, chebgcn_stream stream);
 
+/* ---- first-level GLM with AR(1) prewhitening: generalised least squares per (run, vertex) (glm.first_level(noise='ar1')) ---------
+ * Noise covariance sigma^2 rho^|i-j| / (1 - rho^2) inside a run: exact GLS for a stationary AR(1), the first row scaled
+ * (Prais-Winsten), not dropped.  With K(rho) = (1 + rho^2) I - rho (Sh + Sh^T) - rho^2 (e_0 e_0^T + e_L e_L^T), Sh the one-row shift
+ * inside the run and L = T - 1 its last row, the fit is the least-squares fit under y^T K y.  Besides the tables of the OLS
+ * entries (Q, u, B, rank, run_offsets: as above, same clamps) the caller hands, per run,
+ *   W = [Q | Qs]        float64 [Ttot][2k]: Qs = Sh Q + Sh^T Q, row t = Q[t - 1] + Q[t + 1] with zero beyond the ends of the run;
+ *                       columns [k_r, k) and [k + k_r, 2k) are zero
+ *   D = Q^T Qs          float64 [R][k][k], symmetric;   E = q_0 q_0^T + q_L q_L^T   float64 [R][k][k] (rows 0 and L of Q)
+ * glm_project_ar1: ah[r][j][m] = sum_t W[t][j] y[t][m] (float64 [R][2k][Mp]: a = Q^T y, then h = Qs^T y), s0[r][m] = y.y and
+ *   s1[r][m] = sum_{t > first row of the run} y[t][m] y[t - 1][m] (float64 [R][Mp] each): the fma chains, the slices (a function of
+ *   T alone) and the panels of glm_project over the 2k columns; the s1 term of row t belongs to the slice of row t, the first row
+ *   of a later slice pairs with the last row of the slice before it, the first row of a run with nothing (a lag never crosses
+ *   a run boundary).  Pad columns as for glm_project.  chebgcn_last_dispatch(): glm_project_ar1_kernel<NJ> per panel, " + ".
+ * glm_finish_ar1, per (run, vertex), T the run's rows, y_0 / y_L its first and last sample (read from series; pad columns and
+ *   empty runs give 0), every sum an fma chain from 0 over ascending j < k_r unless stated:
+ *     rho_given = 0:  ssq = a.a;  rss = s0 - ssq with the floor of glm_finish;  num = (s1 - a.h) + 0.5 * a.(D a), (D a)_i its own
+ *       chain over j;  rho = num / rss clamped to +-0.99 (RHO_MAX), 0 where rss is 0.   rho_given = 1: rho as passed.
+ *     c1 = fma(rho, rho, 1), r2 = rho * rho;   M_ij = fma(-r2, E_ij, fma(-rho, D_ij, i == j ? c1 : 0))
+ *     g_i = fma(-r2, fma(q0_i, y_0, qL_i * y_L), fma(-rho, h_i, c1 * a_i));   yKy = fma(-r2, fma(y_0, y_0, y_L * y_L), fma(-2 rho, s1, c1 * s0))
+ *     Cholesky M = L L^T by columns j ascending: x_ij = M_ij, x_ij = fma(-L_ip, L_jp, x_ij) over p < j ascending;
+ *       L_jj = sqrt(x_jj), d_j = 1 / L_jj, L_ij = x_ij * d_j (a pivot not > 0 -- impossible for |rho| < 1 in exact arithmetic --
+ *       gives L_jj = d_j = 0 and a zero column, never NaN)
+ *     forward solves, columns j ascending: z_j = x_j * d_j, then x_i = fma(-L_ij, z_j, x_i) for i > j, from x = g; the same from
+ *       x = u_c for w_c;   zz = z.z, ww_c = w_c.w_c, e_c = chain of fma(w_cj, z_j, e)
+ *     rss* = yKy - zz, taken as 0 where rss* < 4 (T + k_r) 2^-53 (1 + |rho|)^4 / (1 - |rho|)^2 s0.  The floor: s0, s1, a, h carry
+ *       relative round-off (T + k_r) 2^-53 of sums bounded by y.y, and enter yKy and g with weights of at most (1 + |rho|)^2;
+ *       a backward-stable Cholesky solve is exact for M + dM, |dM| <= c k 2^-53 |M|, which moves g.M^-1 g by x^T dM x with
+ *       x = M^-1 g, |M| <= (1 + |rho|)^2 and |x|^2 <= (1 + |rho|)^2 / (1 - |rho|)^2 y.y (the eigenvalues of K lie in
+ *       [(1 - |rho|)^2, (1 + |rho|)^2]); the product of the two bounds dominates.  At rho = 0 it is the floor of glm_finish.
+ *     sigma2 = dof > 0 ? rss* / dof : 0, dof = T - k_r (no correction for estimating rho);   variance_c = sigma2 * ww_c;
+ *     t = variance > 0 ? e / sqrt(variance) : 0.   A vertex constant in time: rho = 0, variance = 0, t = 0, never NaN.
+ *     beta (with B): back substitution L^T v = z over rows q DESCENDING (v_q = x_q * d_q, x_i = fma(-L_qi, v_q, x_i) for i < q),
+ *       then beta_p = chain of fma(B[p][j], v_j, s).
+ *   Outputs as for glm_finish, plus rho_out float32 [R][Mp] (the estimate, or the given value).  Every value is rounded ONCE to
+ *   float32.  No chain depends on k of the call, on M, on the other runs or on the rank bucket: results are bit-identical under
+ *   any batching.  A given rho outside (-1, 1) (NaN included): CHEBGCN_EINVAL.
+ *   chebgcn_last_dispatch(): glm_finish_ar1_kernel<KB>, KB = chebgcn_glm_ar1_query(100 + k) the rank bucket (8, 16, 32 or 64).
+ * glm_ar1_query: 0 waves of a finish workgroup, 1 contrasts per forward solve, 100 + k the rank bucket of k, 200 + k the vertices
+ *   of a finish workgroup at that k (k in [1, 64]); -1 for anything else.
+ * glm_ar1_workspace: bytes of ah, s0 and s1 together for R runs (s0 follows ah, s1 follows s0; 0: arguments out of range).
+ * Limits, alignment and the order of the checks as for the OLS entries; series to 8 bytes for the projection, 4 for the finish.
+ * The calls neither synchronise nor allocate. */
+int chebgcn_glm_ar1_query(int what);
+size_t chebgcn_glm_ar1_workspace(int R, int M, int k);
+int chebgcn_glm_project_ar1(const float* series, int64_t Ttot, const int64_t* run_offsets, int R, int M, const double* W, int k,
+                            double* ah, double* s0, double* s1, chebgcn_stream stream);
+int chebgcn_glm_finish_ar1(const double* ah, const double* s0, const double* s1, const float* series, const double* W,
+                           const int64_t* run_offsets, int64_t Ttot, const int32_t* rank, const double* D, const double* E,
+                           const double* U, const double* B, int R, int M, int k, int C, int P, int rho_given, double rho,
+                           double* eff64, double* var64, float* effect, float* variance, float* t, float* beta, float* rho_out,
+                           chebgcn_stream stream);
+
 /* ---- searchlight decoding: cross-validated Gaussian naive Bayes at every centre (searchlight.searchlight) ------------------------
  * The caller sorts the S samples so that the test samples of one MODEL (a training set: a (group, fold) pair, or a fold) are
  * contiguous, and hands the kernels (all device memory)

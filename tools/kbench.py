@@ -5,6 +5,7 @@
                            [--kernels recurrence_fwd ...]
     python tools/kbench.py --parcellate [--iters 20] [--json out.json]      # the parcellation leg alone
     python tools/kbench.py glm [--iters 20] [--json out.json]               # the first-level GLM kernels alone
+    python tools/kbench.py glm_ar1 [--iters 20] [--json out.json]           # ... and the AR(1) pair beside them and beside torch
     python tools/kbench.py searchlight [--iters 20] [--json out.json]       # the searchlight kernels alone
     python tools/kbench.py searchlight_lda [--iters 10] [--json out.json]   # the LDA searchlight kernel alone
     python tools/kbench.py searchlight_rdm [--iters 10] [--json out.json]   # the RSA searchlight kernel alone
@@ -199,6 +200,112 @@ def glm_leg(args):
         note('torch residual algebra', shape, timeit(lambda: torch_finish(at, yt), args.iters), 8.0 * R * (k + 1) * Mp + 16.0 * R * C * Mp,
              float(R) * Mp * k * (1 + C))
         del planes, Q, y3, Q3, at, yt, a, yy
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(results, f, indent=1)
+
+
+def glm_ar1_leg(args):
+    """chebgcn_glm_project_ar1 + chebgcn_glm_finish_ar1 at the two shapes of the glm leg, beside the OLS pair on the same data and
+    the same algebra written in torch on the device (float64 bmm for the sums, batched ``torch.linalg.cholesky`` and
+    ``solve_triangular`` for the k x k systems).  Floors: the scan read once per panel at the measured copy rate, and the float64
+    FMA count at the vector rate -- 2k + 2 per scan element for the pass, k^3 / 6 + (1 + C) k^2 / 2 per vertex for the finish."""
+    import numpy as np
+    import torch
+    from gcn_fmri_decoding_amd import _lib, glm, ops
+    dev = torch.device('cuda:0')
+    HBM, FMA64 = 6.29e12, 78.6e12 / 2
+    results = []
+    timeit = lambda fn, iters: _timeit(fn, iters, 3)
+
+    def note(name, shape, t, nbytes, fmas, dispatch=''):
+        med, lo, hi = t
+        r = {'leg': name, 'shape': shape, 'median_ms': med, 'min_ms': lo, 'max_ms': hi, 'hbm_floor_ms': 1e3 * nbytes / HBM,
+             'fma_floor_ms': 1e3 * fmas / FMA64, 'dispatch': dispatch}
+        results.append(r)
+        print('%-26s %-22s %9.3f ms (min %8.3f, max %8.3f)  HBM floor %7.3f ms  fp64 FMA floor %7.3f ms  %s'
+              % (name, shape, med, lo, hi, r['hbm_floor_ms'], r['fma_floor_ms'], dispatch), flush=True)
+
+    for R, T, M, k, C in ((1, 1200, 91282, 40, 4), (256, 284, 360, 22, 4)):
+        shape = '%dx%dx%d k=%d' % (R, T, M, k)
+        Mp = _lib.plane_stride(M)
+        g = torch.Generator(device=dev).manual_seed(R)
+        planes = torch.zeros(R * T, Mp, device=dev)
+        planes[:, :M] = 1e4 + 50.0 * torch.randn(R * T, M, device=dev, generator=g)
+        offs = torch.arange(R + 1, device=dev, dtype=torch.int64) * T
+        X = torch.randn(R, T, k, device=dev, dtype=torch.float64, generator=g)
+        X[:, :, 0] = 1.0                                        # the intercept: the series' mean is in the span
+        Q3 = torch.linalg.qr(X)[0].contiguous()
+        Qs3 = torch.zeros_like(Q3)
+        Qs3[:, 1:] += Q3[:, :-1]
+        Qs3[:, :-1] += Q3[:, 1:]
+        W = torch.cat([Q3, Qs3], dim=2).reshape(R * T, 2 * k).contiguous()
+        Q = Q3.reshape(R * T, k).contiguous()
+        D = torch.bmm(Q3.transpose(1, 2), Qs3)
+        D = (0.5 * (D + D.transpose(1, 2))).contiguous()
+        E = (Q3[:, 0, :, None] * Q3[:, 0, None, :] + Q3[:, -1, :, None] * Q3[:, -1, None, :]).contiguous()
+        U = torch.randn(R, C, k, device=dev, dtype=torch.float64, generator=g)
+        un2 = (U * U).sum(dim=2)
+        rank = torch.full((R,), k, device=dev, dtype=torch.int32)
+        e64 = torch.empty(R, C, Mp, device=dev, dtype=torch.float64)
+        v64 = torch.empty_like(e64)
+        panel = ops.glm_geometry()['panel']
+        scan = 4.0 * R * T * Mp
+
+        a, yy = ops.glm_project(planes, offs, M, Q)
+        t_p = timeit(lambda: ops.glm_project(planes, offs, M, Q), args.iters)
+        note('glm_project', shape, t_p, scan * -(-k // panel), float(R) * T * Mp * (k + 1), _lib.last_dispatch())
+        t_f = timeit(lambda: ops.glm_finish(a, yy, offs, R * T, rank, U, un2, M, out64=(e64, v64)), args.iters)
+        note('glm_finish', shape, t_f, 8.0 * R * (k + 1) * Mp + 16.0 * R * C * Mp, float(R) * Mp * k * (1 + C), _lib.last_dispatch())
+
+        ah, s0, s1 = ops.glm_project_ar1(planes, offs, M, W)
+        t_pa = timeit(lambda: ops.glm_project_ar1(planes, offs, M, W), args.iters)
+        note('glm_project_ar1', shape, t_pa, scan * -(-2 * k // panel), float(R) * T * Mp * (2 * k + 2), _lib.last_dispatch())
+        fin = lambda rho: ops.glm_finish_ar1(ah, s0, s1, planes, W, offs, rank, D, E, U, M, rho=rho, out64=(e64, v64))
+        fmas = float(R) * Mp * (k ** 3 / 6.0 + (1 + C) * k * k / 2.0)
+        rho_dev, ev_dev = fin(None)[4].double(), e64.clone()
+        t_fa = timeit(lambda: fin(None), args.iters)
+        note('glm_finish_ar1 (estimated)', shape, t_fa, 8.0 * R * (2 * k + 2) * Mp + 16.0 * R * C * Mp, fmas, _lib.last_dispatch())
+        note('glm_finish_ar1 (given)', shape, timeit(lambda: fin(0.3), args.iters), 8.0 * R * (2 * k + 2) * Mp + 16.0 * R * C * Mp, fmas,
+             _lib.last_dispatch())
+        print('    AR(1) pair %.3f ms, OLS pair %.3f ms' % (t_pa[0] + t_fa[0], t_p[0] + t_f[0]))
+
+        y3 = planes.view(R, T, Mp)
+        eye = torch.eye(k, device=dev, dtype=torch.float64)
+
+        def torch_sums():
+            yd = y3.double()
+            return (torch.bmm(Q3.transpose(1, 2), yd), torch.bmm(Qs3.transpose(1, 2), yd), (yd * yd).sum(dim=1),
+                    (yd[:, 1:] * yd[:, :-1]).sum(dim=1), yd[:, 0], yd[:, -1])
+
+        def torch_fit(at, ht, S0, S1, y0, yL):
+            rss = (S0 - (at * at).sum(dim=1)).clamp_min(0.0)
+            num = S1 - (at * ht).sum(dim=1) + 0.5 * (at * torch.bmm(D, at)).sum(dim=1)
+            rho = torch.where(rss > 0, num / rss.clamp_min(1e-300), torch.zeros_like(rss)).clamp(-glm.RHO_MAX, glm.RHO_MAX)      # [R, Mp]
+            c1, r2 = 1.0 + rho * rho, rho * rho
+            Mm = c1[:, :, None, None] * eye - rho[:, :, None, None] * D[:, None] - r2[:, :, None, None] * E[:, None]              # [R, Mp, k, k]
+            gq = Q3[:, 0, :, None] * y0[:, None, :] + Q3[:, -1, :, None] * yL[:, None, :]
+            gv = (c1[:, None, :] * at - rho[:, None, :] * ht - r2[:, None, :] * gq).transpose(1, 2)                               # [R, Mp, k]
+            L = torch.linalg.cholesky(Mm)
+            rhs = torch.cat([gv[..., None], U.transpose(1, 2)[:, None].expand(R, Mp, k, C)], dim=3)
+            sol = torch.linalg.solve_triangular(L, rhs, upper=False)
+            z, w = sol[..., 0], sol[..., 1:]
+            rs = (c1 * S0 - 2.0 * rho * S1 - r2 * (y0 * y0 + yL * yL) - (z * z).sum(dim=2)).clamp_min(0.0)
+            e = (w * z[..., None]).sum(dim=2).transpose(1, 2)
+            v = (rs / float(T - k))[:, None, :] * (w * w).sum(dim=2).transpose(1, 2)
+            return e, v, e / v.sqrt(), rho
+
+        sums = torch_sums()
+        e_t, v_t, _, rho_t = torch_fit(*sums)
+        print('    max |rho - torch| = %.3e, max |effect - torch| / max |effect| = %.3e'
+              % (float((rho_dev[:, :M] - rho_t[:, :M]).abs().max()), float((ev_dev[..., :M] - e_t[..., :M]).abs().max() / e_t[..., :M].abs().max())))
+        t_ts = timeit(torch_sums, args.iters)
+        note('torch sums (bmm, float64)', shape, t_ts, scan, float(R) * T * Mp * (2 * k + 2))
+        t_tf = timeit(lambda: torch_fit(*sums), args.iters)
+        note('torch cholesky + solves', shape, t_tf, 8.0 * R * (2 * k + 2) * Mp, fmas)
+        print('    torch pair %.3f ms' % (t_ts[0] + t_tf[0]))
+        del planes, W, Q, Q3, Qs3, y3, sums, ah, s0, s1, a, yy, e_t, v_t, rho_t
+        torch.cuda.empty_cache()
     if args.json:
         with open(args.json, 'w') as f:
             json.dump(results, f, indent=1)
@@ -457,7 +564,7 @@ def searchlight_svc_leg(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('leg', nargs='?', choices=['glm', 'searchlight', 'searchlight_lda', 'searchlight_rdm', 'searchlight_svc'],
+    ap.add_argument('leg', nargs='?', choices=['glm', 'glm_ar1', 'searchlight', 'searchlight_lda', 'searchlight_rdm', 'searchlight_svc'],
                     help='glm: the first-level GLM kernels alone (ops.glm_project / glm_finish); searchlight: the searchlight kernels alone; '
                          'searchlight_lda: the LDA searchlight kernel alone; searchlight_rdm: the RSA searchlight kernel alone; '
                          'searchlight_svc: the SVM searchlight kernel alone')
@@ -486,6 +593,8 @@ def main():
         return parcellate_leg(args)
     if args.leg == 'glm':
         return glm_leg(args)
+    if args.leg == 'glm_ar1':
+        return glm_ar1_leg(args)
     if args.leg == 'searchlight':
         return searchlight_leg(args)
     if args.leg == 'searchlight_lda':
