@@ -13,6 +13,7 @@ from .stats import MapTestResult, map_test, map_test_host, sign_flips  # noqa: F
 from .stats import DesignTestResult, design_test, design_test_host, permutations, perm_t_host  # noqa: F401
 from .glm import (Design, GLMResult, GLMResultAR1, contrasts_one_vs_rest, design_matrix, first_level,  # noqa: F401
                   first_level_host)
+from .glm import TrialDesign, TrialResult, single_trial, single_trial_host, trial_design  # noqa: F401
 # (the call itself is searchlight.searchlight: the package attribute stays the module)
 from .searchlight import SearchlightResult, SolverInfo, lda_shrinkage_host, searchlight_events, searchlight_host  # noqa: F401
 from .searchlight import RDMResult, compare_rdms, crossnobis, crossnobis_events, crossnobis_host  # noqa: F401
@@ -20,7 +21,8 @@ from .searchlight import RDMResult, compare_rdms, crossnobis, crossnobis_events,
 __all__ = ['graph', 'coarsening', 'parcellation', 'Parcellation', 'filters', 'GraphFilter', 'splits', 'stats', 'map_test',
            'map_test_host', 'sign_flips', 'MapTestResult', 'design_test', 'design_test_host', 'permutations', 'perm_t_host',
            'DesignTestResult', 'glm', 'Design', 'GLMResult', 'GLMResultAR1', 'design_matrix', 'contrasts_one_vs_rest',
-           'first_level', 'first_level_host', 'searchlight', 'SearchlightResult', 'SolverInfo', 'searchlight_events', 'searchlight_host',
+           'first_level', 'first_level_host', 'TrialDesign', 'TrialResult', 'trial_design', 'single_trial', 'single_trial_host',
+           'searchlight', 'SearchlightResult', 'SolverInfo', 'searchlight_events', 'searchlight_host',
            'lda_shrinkage_host', 'RDMResult', 'compare_rdms', 'crossnobis', 'crossnobis_events', 'crossnobis_host', 'models_gcn', 'ops']
 
 

@@ -169,6 +169,8 @@ SIGNATURES = {
     'chebgcn_glm_project_ar1': (_i, [_p, _i64, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
     'chebgcn_glm_finish_ar1': (_i, [_p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, C.c_double,
                                     _p, _p, _p, _p, _p, _p, _p, _p]),
+    'chebgcn_glm_trials_query': (_i, [_i]),
+    'chebgcn_glm_trials': (_i, [_p, _i64, _p, _i, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i64, _p, _p, _p, _p]),
     'chebgcn_searchlight_query': (_i, [_i]),
     'chebgcn_searchlight_spread': (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _p]),
     'chebgcn_searchlight_fit': (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),

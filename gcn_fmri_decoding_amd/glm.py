@@ -33,6 +33,12 @@ Out of scope: bias correction of the estimated rho (the residual estimate is bia
 AR orders above 1, rho smoothed across vertices, temporal derivatives of the HRF, precision-weighted fixed effects, and returning
 residual series.
 
+``trial_design`` / ``single_trial`` give one pattern per TRIAL for the searchlight and RSA chains: the beta series by "least
+squares - separate", one GLM per trial ``[x_j | the other trials lumped per condition | nuisance]``.  The models of a run differ
+by one column swap, so one set of projections of y serves all of them (chebgcn_glm_project over ``[Qn | Z_S]``, then
+chebgcn_glm_trials, which finishes every trial where its projection was formed); ``single_trial_host`` restates it with one
+explicit fit per trial.  See ``single_trial``.
+
 The host-only parts need NumPy and SciPy only.
 """
 import collections
@@ -84,18 +90,9 @@ def step_response(s, hrf=HRF_SPM):
     return np.where(s >= 0, (gamma.cdf(sp, a1) - ratio * gamma.cdf(sp, a2)) / (1.0 - ratio), 0.0)
 
 
-def design_matrix(names=None, events=None, T=None, tr=0.72, conditions=None, hrf='spm', high_pass=1.0 / 128, confounds=None):
-    """The design of one run: a ``Design``.
-
-    Exactly one of ``names`` -- per-TR condition names, the format ``match_events`` takes: a maximal stretch of equal names from
-    TR i to TR j is a block ``[i tr, (j + 1) tr)`` -- and ``events`` -- a sequence of ``(onset_s, duration_s, name)``, which
-    needs ``T``.  ``conditions`` defaults to the sorted set of names other than ``'rest'`` (the order of
-    ``EventWindows.classes``); names outside ``conditions`` are left to the baseline.  ``tr``: seconds per row (0.72: HCP).
-    ``hrf``: ``'spm'`` (shapes 6 and 16, ratio 1/6), a tuple ``(a1, a2, ratio)``, or None for the plain boxcar sampled at
-    ``t_k = k tr``.  Regressors are ``x(t_k) = sum_blocks G(t_k - on) - G(t_k - off)`` in closed form (see the module).
-    ``high_pass`` (Hz): drift columns ``cos(pi (2 k + 1) j / (2 T))``, ``j = 1 .. floor(2 T tr high_pass)``; None or an order of
-    0 gives none.  ``confounds``: ``[T, Q]``, appended as given.  The intercept is the last column.  Every malformed argument
-    is a ``ValueError``."""
+def _design_args(names, events, T, tr, conditions, hrf, high_pass, confounds):
+    """The arguments of ``design_matrix`` checked and parsed: ``(T, tr, hrf, blocks [(onset_s, offset_s, name)], conditions,
+    drift order, confounds float64 [T, Qn] or None)``."""
     if (names is None) == (events is None):
         raise ValueError('design_matrix: give exactly one of names (per-TR condition names) and events ((onset, duration, name))')
     if isinstance(tr, (bool, np.bool_)) or not isinstance(tr, (int, float, np.integer, np.floating)) or not np.isfinite(tr) or tr <= 0:
@@ -161,19 +158,44 @@ def design_matrix(names=None, events=None, T=None, tr=0.72, conditions=None, hrf
         if not np.isfinite(confounds).all():
             raise ValueError('design_matrix: confounds hold non-finite values')
         Qn = confounds.shape[1]
+    return T, tr, hrf, blocks, conditions, order, confounds
+
+
+def _nuisance(T, order, confounds):
+    """The columns of a design that are no conditions: ``(float64 [T, order + Qn + 1], their names)`` -- cosine drifts, the
+    confounds as given, the intercept last."""
+    Qn = 0 if confounds is None else confounds.shape[1]
+    N = np.zeros((T, order + Qn + 1))
+    k = np.arange(T, dtype=np.float64)
+    for j in range(1, order + 1):
+        N[:, j - 1] = np.cos(np.pi * (2.0 * k + 1.0) * j / (2.0 * T))
+    if Qn:
+        N[:, order:order + Qn] = confounds
+    N[:, -1] = 1.0
+    return N, ['drift_%d' % j for j in range(1, order + 1)] + ['confound_%d' % q for q in range(Qn)] + ['constant']
+
+
+def design_matrix(names=None, events=None, T=None, tr=0.72, conditions=None, hrf='spm', high_pass=1.0 / 128, confounds=None):
+    """The design of one run: a ``Design``.
+
+    Exactly one of ``names`` -- per-TR condition names, the format ``match_events`` takes: a maximal stretch of equal names from
+    TR i to TR j is a block ``[i tr, (j + 1) tr)`` -- and ``events`` -- a sequence of ``(onset_s, duration_s, name)``, which
+    needs ``T``.  ``conditions`` defaults to the sorted set of names other than ``'rest'`` (the order of
+    ``EventWindows.classes``); names outside ``conditions`` are left to the baseline.  ``tr``: seconds per row (0.72: HCP).
+    ``hrf``: ``'spm'`` (shapes 6 and 16, ratio 1/6), a tuple ``(a1, a2, ratio)``, or None for the plain boxcar sampled at
+    ``t_k = k tr``.  Regressors are ``x(t_k) = sum_blocks G(t_k - on) - G(t_k - off)`` in closed form (see the module).
+    ``high_pass`` (Hz): drift columns ``cos(pi (2 k + 1) j / (2 T))``, ``j = 1 .. floor(2 T tr high_pass)``; None or an order of
+    0 gives none.  ``confounds``: ``[T, Q]``, appended as given.  The intercept is the last column.  Every malformed argument
+    is a ``ValueError``."""
+    T, tr, hrf, blocks, conditions, order, confounds = _design_args(names, events, T, tr, conditions, hrf, high_pass, confounds)
     t = np.arange(T, dtype=np.float64) * tr
-    X = np.zeros((T, len(conditions) + order + Qn + 1))
+    N, nuisance = _nuisance(T, order, confounds)
+    X = np.zeros((T, len(conditions) + N.shape[1]))
     for on, off, name in blocks:
         if name in conditions:
             X[:, conditions.index(name)] += step_response(t - on, hrf) - step_response(t - off, hrf)
-    k = np.arange(T, dtype=np.float64)
-    for j in range(1, order + 1):
-        X[:, len(conditions) + j - 1] = np.cos(np.pi * (2.0 * k + 1.0) * j / (2.0 * T))
-    if Qn:
-        X[:, len(conditions) + order:len(conditions) + order + Qn] = confounds
-    X[:, -1] = 1.0
-    columns = conditions + ['drift_%d' % j for j in range(1, order + 1)] + ['confound_%d' % q for q in range(Qn)] + ['constant']
-    return Design(X, columns, list(conditions))
+    X[:, len(conditions):] = N
+    return Design(X, conditions + nuisance, list(conditions))
 
 
 def contrasts_one_vs_rest(design):
@@ -426,6 +448,40 @@ def _ar1_tables(tabs, k):
     return W, D, E
 
 
+def _stage(runs, offs, M, device, who):
+    """The runs as ``[Ttot, plane_stride(M)]`` float32 planes on the device (tensors are staged where they lie; a non-finite
+    value is a ``ValueError``): ``(device, planes)``."""
+    on_device = any(_is_tensor(r) for r in runs)
+    host = [None if _is_tensor(r) else _host_array(r, who) for r in runs]
+    import torch
+    from . import _lib
+    if device is None:
+        first = next((r for r in runs if _is_tensor(r) and r.is_cuda), None)
+        dev = first.device if first is not None else torch.device('cuda', torch.cuda.current_device())
+    else:
+        dev = torch.device(device)
+    Mp = _lib.plane_stride(M)
+    with torch.cuda.device(dev):
+        if on_device:
+            planes = torch.zeros((int(offs[-1]), Mp), dtype=torch.float32, device=dev)
+            for y, h, o in zip(runs, host, offs):
+                planes[o:o + y.shape[0], :M] = (y.detach() if h is None else torch.as_tensor(h)).to(dev, torch.float32)
+            if not bool(torch.isfinite(planes).all()):
+                raise ValueError('%s: series hold non-finite values' % who)
+        else:
+            staged = np.zeros((int(offs[-1]), Mp), np.float32)
+            for h, o in zip(host, offs):
+                staged[o:o + h.shape[0], :M] = h
+            planes = torch.as_tensor(staged).to(dev)
+    return dev, planes
+
+
+def _batch_arg(batch_runs, who):
+    if batch_runs is not None and (isinstance(batch_runs, (bool, np.bool_)) or not isinstance(batch_runs, (int, np.integer))
+                                   or batch_runs < 1):
+        raise ValueError('%s: batch_runs must be an int >= 1 or None, got %r' % (who, batch_runs))
+
+
 def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=False, batch_runs=None, noise='ols', rho=None):
     """Per-subject activation maps of a general linear model, on the device: a ``GLMResult``.
 
@@ -455,35 +511,16 @@ def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=F
     rho = _noise_args(noise, rho, who)
     ar1 = noise == 'ar1'
     pl = _plan(runs, designs, contrasts, groups, who)
-    if batch_runs is not None and (isinstance(batch_runs, (bool, np.bool_)) or not isinstance(batch_runs, (int, np.integer))
-                                   or batch_runs < 1):
-        raise ValueError('%s: batch_runs must be an int >= 1 or None, got %r' % (who, batch_runs))
+    _batch_arg(batch_runs, who)
     if len(pl.keys) > RMAX:
         raise ValueError('%s: %d groups; served: up to %d' % (who, len(pl.keys), RMAX))
-    on_device = any(_is_tensor(r) for r in pl.runs)
-    host = [None if _is_tensor(r) else _host_array(r, who) for r in pl.runs]
     import torch
     from . import _lib, ops
-    if device is None:
-        first = next((r for r in pl.runs if _is_tensor(r) and r.is_cuda), None)
-        dev = first.device if first is not None else torch.device('cuda', torch.cuda.current_device())
-    else:
-        dev = torch.device(device)
     R, M, C = len(pl.runs), pl.M, pl.C
     Mp = _lib.plane_stride(M)
     offs = np.concatenate([[0], np.cumsum([tb.T for tb in pl.tables])]).astype(np.int64)
+    dev, planes = _stage(pl.runs, offs, M, device, who)
     with torch.cuda.device(dev):
-        if on_device:
-            planes = torch.zeros((int(offs[-1]), Mp), dtype=torch.float32, device=dev)
-            for y, h, o in zip(pl.runs, host, offs):
-                planes[o:o + y.shape[0], :M] = (y.detach() if h is None else torch.as_tensor(h)).to(dev, torch.float32)
-            if not bool(torch.isfinite(planes).all()):
-                raise ValueError('%s: series hold non-finite values' % who)
-        else:
-            staged = np.zeros((int(offs[-1]), Mp), np.float32)
-            for h, o in zip(host, offs):
-                staged[o:o + h.shape[0], :M] = h
-            planes = torch.as_tensor(staged).to(dev)
         if batch_runs is None:
             kmax = max(tb.rank for tb in pl.tables)
             free = torch.cuda.mem_get_info(dev)[0]
@@ -519,3 +556,283 @@ def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=F
         res = GLMResult(effect.cpu().numpy(), variance.cpu().numpy(), t.cpu().numpy(), dof, list(pl.keys),
                         [b.cpu().numpy() for b in beta_out] if betas else None)
         return GLMResultAR1(*res, [x.cpu().numpy() for x in rho_out]) if ar1 else res
+
+
+# ---- single-trial patterns: least squares - separate ----------------------------------------------------------------------------
+
+G1MAX, NMAX = 16, 4096                          # chebgcn_glm_trials_query(2), (4)
+
+TrialDesign = collections.namedtuple('TrialDesign', 'X trials onsets nuisance columns conditions')
+TrialDesign.__doc__ = """What ``trial_design`` returns: ``X`` float64 [T, n], one HRF regressor per trial in order of onset;
+``trials`` int64 [n], the trial's condition as an index into ``conditions``; ``onsets`` float64 [n], seconds; ``nuisance`` float64
+[T, q]: drifts, confounds, intercept last -- the non-condition columns of ``design_matrix``; ``columns`` the n + q column names
+(``<condition>_<i>`` for the i-th trial of a condition, then the nuisance names); ``conditions`` the condition names in class
+order."""
+
+
+class TrialResult(collections.namedtuple('TrialResult', 'beta variance t labels run trial onset group dof classes')):
+    """What ``single_trial`` returns.  ``beta``, ``variance``, ``t``: float32 [Ntrials, M] in run order then trial order (float64
+    from ``single_trial_host``), None for what ``outputs`` does not name; per trial ``labels`` (the condition name), ``run``,
+    ``trial`` (its index inside the run), ``onset`` (seconds), ``group`` (the run's key) and ``dof`` (int64, the residual degrees
+    of freedom of the trial's model); ``classes`` the condition names in class order."""
+    __slots__ = ()
+
+    def folds(self, within=True):
+        """One fold per trial, that of its run by ``searchlight.default_folds``: the run's position among the runs of its group
+        (``within``), or its group's index in order of first appearance."""
+        from .searchlight import default_folds
+        first = np.flatnonzero(np.concatenate([[True], self.run[1:] != self.run[:-1]]))
+        per_run = default_folds([self.group[i] for i in first], within)
+        return per_run[np.searchsorted(self.run[first], self.run)]
+
+
+def trial_design(names=None, events=None, T=None, tr=0.72, conditions=None, hrf='spm', high_pass=1.0 / 128, confounds=None):
+    """The single-trial design of one run: a ``TrialDesign``.  The arguments and their checks are those of ``design_matrix``.
+    Every block of a kept condition is one trial, in order of onset: with ``names`` a maximal stretch of equal names, with
+    ``events`` one ``(onset, duration, name)`` tuple.  A trial's regressor is the closed-form response to its own block; the
+    trial columns of a condition sum to ``design_matrix``'s column of that condition, and ``nuisance`` is its other columns."""
+    try:
+        T, tr, hrf, blocks, conditions, order, confounds = _design_args(names, events, T, tr, conditions, hrf, high_pass, confounds)
+    except ValueError as e:
+        raise ValueError(str(e).replace('design_matrix:', 'trial_design:', 1)) from None
+    kept = sorted((b for b in blocks if b[2] in conditions), key=lambda b: b[0])       # (stable: ties keep the given order)
+    t = np.arange(T, dtype=np.float64) * tr
+    X = np.zeros((T, len(kept)))
+    for i, (on, off, name) in enumerate(kept):
+        X[:, i] = step_response(t - on, hrf) - step_response(t - off, hrf)
+    codes = np.array([conditions.index(b[2]) for b in kept], np.int64)
+    N, nuisance = _nuisance(T, order, confounds)
+    seen = collections.Counter()
+    cols = []
+    for c in codes:
+        cols.append('%s_%d' % (conditions[c], seen[c]))
+        seen[c] += 1
+    return TrialDesign(X, codes, np.array([b[0] for b in kept], np.float64), N, cols + nuisance, list(conditions))
+
+
+_Trials = collections.namedtuple('_Trials', 'T n X N codes own q Qn ZX ZS keep rank w F onsets')
+_TrialPlan = collections.namedtuple('_TrialPlan', 'runs tables M G classes groups outputs tensors')
+
+
+def _others(tb, j, G):
+    """The explicit ``others`` columns of trial j of a run: ``[T, G]``, column g the sum of the trials of group g other than j."""
+    O = np.zeros((tb.T, G))
+    for i in range(tb.n):
+        if i != j:
+            O[:, tb.own[i]] += tb.X[:, i]
+    return O
+
+
+def _trial_plan(runs, designs, others, outputs, groups, who, limits=True):
+    """Everything of ``single_trial`` that can be checked without the series' values, and the per-run tables of the kernels."""
+    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
+    if single and runs.ndim != 2:
+        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
+    runs = [runs] if single else list(runs)
+    if not runs:
+        raise ValueError('%s: no runs' % who)
+    tensors = all(_is_tensor(r) for r in runs)
+    runs = [r if _is_tensor(r) else np.asarray(r) for r in runs]
+    if any(r.ndim != 2 for r in runs):
+        raise ValueError('%s: every run must be [T, M]' % who)
+    M = int(runs[0].shape[1])
+    if M < 1 or any(int(r.shape[1]) != M for r in runs):
+        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
+    if isinstance(designs, TrialDesign):
+        designs = [designs]
+    designs = list(designs)
+    R = len(runs)
+    if len(designs) != R or not all(isinstance(d, TrialDesign) for d in designs):
+        raise ValueError('%s: designs must hold one TrialDesign per run (%d runs, %d designs)' % (who, R, len(designs)))
+    if others not in ('condition', 'pooled'):
+        raise ValueError("%s: others must be 'condition' or 'pooled', got %r" % (who, others))
+    if isinstance(outputs, str):
+        outputs = (outputs,)
+    outputs = tuple(outputs)
+    if not outputs or set(outputs) - {'beta', 'variance', 't'}:
+        raise ValueError("%s: outputs must name some of 'beta', 'variance', 't', got %r" % (who, outputs))
+    groups = [0] * R if groups is None else list(groups)
+    if len(groups) != R:
+        raise ValueError('%s: groups must hold one key per run (%d runs, %d keys)' % (who, R, len(groups)))
+    for r, g in enumerate(groups):
+        try:
+            hash(g)
+        except TypeError:
+            raise ValueError('%s: group key %r of run %d is not hashable' % (who, g, r)) from None
+    classes = list(designs[0].conditions)
+    if any(list(d.conditions) != classes for d in designs):
+        raise ValueError('%s: the designs differ in their conditions; build them with the same conditions=' % who)
+    G = len(classes) if others == 'condition' else 1
+    if limits and 1 + G > G1MAX:
+        raise ValueError("%s: %d conditions; served: up to %d with others='condition' (others='pooled' takes any number)"
+                         % (who, G, G1MAX - 1))
+    eps = np.finfo(np.float64).eps
+    tables = []
+    for r, (y, d) in enumerate(zip(runs, designs)):
+        X, N, codes = np.asarray(d.X, np.float64), np.asarray(d.nuisance, np.float64), np.asarray(d.trials)
+        T = int(y.shape[0])
+        if X.ndim != 2 or N.ndim != 2 or not np.isfinite(X).all() or not np.isfinite(N).all():
+            raise ValueError('%s: the design of run %d must hold finite [T, n] trial and [T, q] nuisance columns' % (who, r))
+        if X.shape[0] != T or N.shape[0] != T:
+            raise ValueError('%s: the design of run %d has %d rows, the run %d' % (who, r, X.shape[0], T))
+        n = int(X.shape[1])
+        if n < 1:
+            raise ValueError('%s: run %d has no trials' % (who, r))
+        if codes.shape != (n,) or codes.dtype.kind not in 'iu' or (codes < 0).any() or (codes >= len(classes)).any():
+            raise ValueError('%s: trials of run %d must be [n = %d] condition indices below %d' % (who, r, n, len(classes)))
+        if limits and n > NMAX:
+            raise ValueError('%s: run %d has %d trials; served: up to %d' % (who, r, n, NMAX))
+        q, Qn = _factor(N)[:2] if N.shape[1] else (0, np.zeros((T, 0)))
+        if limits and q + G > KMAX:
+            raise ValueError('%s: run %d has nuisance rank %d and %d sums of other trials; served: q + G <= %d' % (who, r, q, G, KMAX))
+        own = codes.astype(np.int64) if others == 'condition' else np.zeros(n, np.int64)
+        ZX = X - Qn @ (Qn.T @ X)
+        ZS = np.zeros((T, G))
+        count = np.zeros(G, np.int64)
+        for j in range(n):                                      # (so that a condition of one trial has that trial's very column)
+            ZS[:, own[j]] += ZX[:, j]
+            count[own[j]] += 1
+        keep = np.zeros((n, 1 + G), bool)
+        rank = np.zeros(n, np.int32)
+        w = np.zeros((n, 1 + G))
+        F = np.zeros((n, 1 + G, 1 + G))
+        for j in range(n):
+            A = np.concatenate([ZX[:, j:j + 1], ZS], axis=1)
+            A[:, 1 + own[j]] -= ZX[:, j]
+            keep[j, 0] = True
+            keep[j, 1:] = count - (np.arange(G) == own[j]) > 0      # a column that is identically zero is dropped
+            idx = np.flatnonzero(keep[j])
+            A = A[:, idx]
+            xn = np.linalg.norm(X[:, j])
+            part = A[:, 0] - A[:, 1:] @ np.linalg.lstsq(A[:, 1:], A[:, 0], rcond=max(A.shape) * eps)[0] if idx.size > 1 else A[:, 0]
+            if not xn > 0 or np.linalg.norm(part) <= ESTIMABLE_TOL * xn:
+                raise ValueError('%s: trial %d of run %d is not estimable (the part of its regressor outside its other trials and '
+                                 'the nuisance columns: %.3g of its norm)' % (who, j, r, np.linalg.norm(part) / max(xn, 1e-300)))
+            S, Vt = np.linalg.svd(A, full_matrices=False)[1:]
+            rj = int((S > max(A.shape) * eps * S[0]).sum())
+            if T <= q + rj:
+                raise ValueError('%s: run %d has T = %d rows and trial %d a model of rank %d: no residual degrees of freedom'
+                                 % (who, r, T, j, q + rj))
+            Fk = Vt[:rj] / S[:rj, None]
+            F[j][:rj, idx] = Fk
+            w[j, idx] = Fk[:, 0] @ Fk
+            rank[j] = rj
+        tables.append(_Trials(T, n, X, N, codes, own, q, Qn, ZX, ZS, keep, rank, w, F, np.asarray(d.onsets, np.float64)))
+    return _TrialPlan(runs, tables, M, G, classes, groups, outputs, tensors)
+
+
+def _trial_result(pl, maps, dof):
+    tabs = pl.tables
+    return TrialResult(maps.get('beta'), maps.get('variance'), maps.get('t'),
+                       np.array([pl.classes[c] for tb in tabs for c in tb.codes]),
+                       np.concatenate([np.full(tb.n, r, np.int64) for r, tb in enumerate(tabs)]),
+                       np.concatenate([np.arange(tb.n, dtype=np.int64) for tb in tabs]),
+                       np.concatenate([tb.onsets for tb in tabs]),
+                       [pl.groups[r] for r, tb in enumerate(tabs) for _ in range(tb.n)], np.asarray(dof, np.int64), list(pl.classes))
+
+
+def single_trial_host(runs, designs, others='condition', outputs=('beta', 't'), groups=None, device=None, batch_runs=None):
+    """``single_trial`` restated in float64 NumPy (no device; ``device`` and ``batch_runs`` are accepted and ignored), with none
+    of the kernels' algebra: per trial the explicit design ``[x_j | others | N]`` (an ``others`` column that is identically zero
+    left out), ``lstsq``, the residuals formed, the rank by SVD, ``pinv(D^T D)[0, 0]`` for the variance factor.  The series are
+    rounded to float32 first, as staging does.  Returns a ``TrialResult`` of float64 maps."""
+    who = 'single_trial_host'
+    pl = _trial_plan(runs, designs, others, outputs, groups, who, limits=False)
+    beta, var, dof = [], [], []
+    for y, tb in zip(pl.runs, pl.tables):
+        y = _host_array(y, who).astype(np.float64)
+        for j in range(tb.n):
+            O = _others(tb, j, pl.G)
+            D = np.concatenate([tb.X[:, j:j + 1], O[:, tb.keep[j, 1:]], tb.N], axis=1)
+            eps = max(D.shape) * np.finfo(np.float64).eps
+            b = np.linalg.lstsq(D, y, rcond=eps)[0]
+            res = y - D @ b
+            d = tb.T - int(np.linalg.matrix_rank(D))
+            f = np.linalg.pinv(D.T @ D, rcond=eps ** 2, hermitian=True)[0, 0]
+            beta.append(b[0])
+            var.append((res * res).sum(axis=0) / d * f)
+            dof.append(d)
+    beta, var = np.stack(beta), np.stack(var)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        t = np.where(var > 0, beta / np.sqrt(var), 0.0)
+    maps = {k: v for k, v in (('beta', beta), ('variance', var), ('t', t)) if k in pl.outputs}
+    return _trial_result(pl, maps, dof)
+
+
+def _trial_tables(tabs, G):
+    """The tables of one batch of runs: ``Q = [Qn | Z_S | 0]`` [Tb, k] for ``glm_project``, ``Z`` [Tb, nmax], the trial offsets,
+    ``q_rank`` and the flat per-trial tables."""
+    k = max(tb.q for tb in tabs) + G
+    nmax = max(tb.n for tb in tabs)
+    Tb = sum(tb.T for tb in tabs)
+    Q, Z = np.zeros((Tb, k)), np.zeros((Tb, nmax))
+    o = 0
+    for tb in tabs:
+        Q[o:o + tb.T, :tb.q] = tb.Qn
+        Q[o:o + tb.T, tb.q:tb.q + G] = tb.ZS
+        Z[o:o + tb.T, :tb.n] = tb.ZX
+        o += tb.T
+    toffs = np.concatenate([[0], np.cumsum([tb.n for tb in tabs])]).astype(np.int64)
+    return (Q, Z, toffs, np.array([tb.q for tb in tabs], np.int32), np.concatenate([tb.own for tb in tabs]).astype(np.int32),
+            np.concatenate([tb.rank for tb in tabs]).astype(np.int32), np.concatenate([tb.w for tb in tabs]),
+            np.concatenate([tb.F for tb in tabs]))
+
+
+def single_trial(runs, designs, others='condition', outputs=('beta', 't'), groups=None, device=None, batch_runs=None):
+    """Single-trial patterns (a beta series) by "least squares - separate" (Mumford et al. 2012), on the device: a ``TrialResult``.
+
+    One GLM per trial j of a run: ``[x_j | o_j1 .. o_jG | N]`` -- the trial's own HRF regressor, the other trials lumped into one
+    regressor per condition (``others='condition'``: ``o_jg`` the sum of the trials of condition g without ``x_j``, G the number of
+    conditions) or into one regressor overall (``'pooled'``, G = 1), and the nuisance columns.  The trial's pattern is the
+    coefficient ``beta`` (or the ``t`` value) of ``x_j``: with short trials a few seconds apart the responses of neighbouring
+    trials overlap, and a mean over the trial's rows (``searchlight_events``) mixes them and keeps drift and confounds.  An
+    ``others`` column that is identically zero (a condition whose only trial is j) is dropped; the model's rank and dof follow.
+
+    ``runs``, ``groups``, ``device``, ``batch_runs`` as ``first_level`` takes them (tensors are staged where they lie and the maps
+    then stay on the device; the result does not depend on ``batch_runs``, bit for bit); ``designs``: one ``TrialDesign`` per run,
+    all with the same conditions; ``outputs``: which of ``'beta'``, ``'variance'``, ``'t'`` to form, the rest are None.  Maps are
+    float32 ``[Ntrials, M]`` in run order then trial order, so that
+    ``searchlight(res.beta, res.labels, nb, res.folds(), groups=res.group)`` and ``crossnobis`` take them as they are.
+
+    The models of a run differ by one column swap, so one pass serves them all.  With ``Qn`` an orthonormal basis of N (rank q),
+    ``S`` the G sums of the trial columns and ``Z = (I - Qn Qn^T) [X | S]``: ``an = Qn^T y``, ``c = Z_S^T y`` and ``y.y`` come from
+    chebgcn_glm_project over ``[Qn | Z_S]``, and chebgcn_glm_trials forms ``p_j = z_j^T y`` and finishes every trial where its
+    projection lies: ``d = (p_j, c_g - [g = own_j] p_j)``, ``beta = w_j . d``, ``rss = y.y - an.an - |F_j d|^2``,
+    ``variance = rss / (T - q - r_j) * w_j0`` with the vertex-independent ``H_j = D_j^T (I - Qn Qn^T) D_j``, ``w_j`` the first row
+    of its pseudo-inverse, ``r_j`` its rank and ``F_j^T F_j = H_j^+``.  float64 on the device, rounded once: include/chebgcn.h.
+
+    ``ValueError`` before any launch: non-finite series, design rows != run rows, a run without trials, a trial that is not
+    estimable (the part of ``x_j`` outside the span of its others and the nuisance ``<= 1e-8 |x_j|``, e.g. an onset beyond the
+    run), ``T <= rank``, more than 15 conditions with ``others='condition'``, ``q + G > 64``, more than 4096 trials in a run.
+
+    Out of scope: LSA (all trials in one design; up to 64 columns that is ``first_level(betas=True)`` on ``[X | N]``), AR(1)
+    noise, temporal derivatives of the HRF, and any change to ``searchlight_events`` / ``crossnobis_events``."""
+    who = 'single_trial'
+    pl = _trial_plan(runs, designs, others, outputs, groups, who)
+    _batch_arg(batch_runs, who)
+    import torch
+    from . import _lib, ops
+    R, M, G = len(pl.runs), pl.M, pl.G
+    Mp = _lib.plane_stride(M)
+    offs = np.concatenate([[0], np.cumsum([tb.T for tb in pl.tables])]).astype(np.int64)
+    dev, planes = _stage(pl.runs, offs, M, device, who)
+    with torch.cuda.device(dev):
+        if batch_runs is None:
+            kmax = max(tb.q for tb in pl.tables) + G
+            batch_runs = max(1, int(torch.cuda.mem_get_info(dev)[0] // 4) // (8 * (kmax + 1) * Mp))
+        batch_runs = int(min(batch_runs, R, RMAX))
+        parts = []
+        for r0 in range(0, R, batch_runs):
+            r1 = min(r0 + batch_runs, R)
+            Q, Z, toffs, qrank, own, rank, w, F = (torch.as_tensor(a).to(dev) for a in _trial_tables(pl.tables[r0:r1], G))
+            rows = planes[int(offs[r0]):int(offs[r1])]
+            o = torch.as_tensor(offs[r0:r1 + 1] - offs[r0]).to(dev)
+            a, yy = ops.glm_project(rows, o, M, Q)
+            parts.append(ops.glm_trials(rows, o, M, Z, toffs, a, yy, qrank, own, rank, w, F, outputs=pl.outputs))
+        maps = {}
+        for i, name in enumerate(('beta', 'variance', 't')):
+            if name in pl.outputs:
+                full = torch.cat([p[i][:, :M] for p in parts]).contiguous()
+                maps[name] = full if pl.tensors else full.cpu().numpy()
+    dof = np.concatenate([tb.T - tb.q - tb.rank.astype(np.int64) for tb in pl.tables])
+    return _trial_result(pl, maps, dof)

@@ -884,6 +884,61 @@ def glm_finish_ar1(ah, s0, s1, planes, W, run_offsets, rank, D, E, U, M, rho=Non
     return e32, v32, t32, beta, rho_out
 
 
+def glm_trials_geometry():
+    """The constants of the single-trial kernel (chebgcn_glm_trials_query): ``vertices`` of a workgroup, ``panel`` trial columns of
+    one pass over the scan, ``max_G1`` columns of a trial's model besides the nuisance (itself and the others), ``max_k`` planes of
+    common sums (q + G), ``max_trials`` of one run, ``max_runs`` of one call."""
+    q = _lib.lib().chebgcn_glm_trials_query
+    return {'vertices': q(0), 'panel': q(1), 'max_G1': q(2), 'max_k': q(3), 'max_trials': q(4), 'max_runs': q(5)}
+
+
+def glm_trials_model(Ttot, Mp, R, k, nmax, N, G1, nout):
+    """``(bytes, flops)`` of one ``glm_trials`` call as ``_launch`` counts them: per panel of trial columns the scan read once and
+    the ``k + 1`` planes of common sums read once, the ``nout`` float32 maps written once; one multiply-add per (row, vertex,
+    trial column) of the pass and the ``(1 + G)^2``-sized epilogue per (trial, vertex)."""
+    panels = -(-nmax // max(glm_trials_geometry()['panel'], 1))
+    nbytes = 4.0 * Ttot * Mp * panels + 8.0 * R * (k + 1) * Mp * panels + 4.0 * N * Mp * nout
+    return nbytes, 2.0 * Ttot * Mp * nmax + 2.0 * N * Mp * (G1 * G1 + 2 * G1 + 4)
+
+
+def glm_trials(planes, run_offsets, M, Z, trial_offsets, a, yy, q_rank, own, rank, w, F, outputs=('beta', 't')):
+    """The single-trial fits of every (run, trial, vertex) (chebgcn_glm_trials): ``planes`` float32 [Ttot, Mp], ``run_offsets``
+    int64 [R + 1], ``Z`` float64 [Ttot, nmax] the projected trial columns, ``trial_offsets`` int64 [R + 1], ``a`` float64
+    [R, k, Mp] / ``yy`` float64 [R, Mp] from ``glm_project`` over ``[Qn | Z_S]``, ``q_rank`` int32 [R], and the flat per-trial
+    tables ``own`` / ``rank`` int32 [N], ``w`` float64 [N, G1], ``F`` float64 [N, G1, G1], all on the device.  Returns
+    ``(beta, variance, t)`` float32 [N, Mp], None for what ``outputs`` does not name.  The byte model counts every panel over
+    every run's rows, which is exact when the runs have equally many trials."""
+    _require_cuda(planes, run_offsets, Z, trial_offsets, a, yy, q_rank, own, rank, w, F)
+    if planes.dim() != 2 or planes.shape[1] != plane_stride(M) or planes.dtype != torch.float32 or not planes.is_contiguous():
+        raise _lib.ChebgcnError('glm_trials: planes must be contiguous float32 [Ttot, plane_stride(M)]')
+    Ttot, Mp = int(planes.shape[0]), int(planes.shape[1])
+    R = int(run_offsets.numel()) - 1
+    if R < 1 or Z.dim() != 2 or a.dim() != 3 or w.dim() != 2:
+        raise _lib.ChebgcnError('glm_trials: run_offsets [R + 1], Z [Ttot, nmax], a [R, k, Mp] and w [N, G1] are expected')
+    nmax, k = int(Z.shape[1]), int(a.shape[1])
+    N, G1 = int(w.shape[0]), int(w.shape[1])
+    _dense(run_offsets, torch.int64, (R + 1,), 'glm_trials: run_offsets')
+    _dense(trial_offsets, torch.int64, (R + 1,), 'glm_trials: trial_offsets')
+    _dense(Z, torch.float64, (Ttot, nmax), 'glm_trials: Z')
+    _dense(a, torch.float64, (R, k, Mp), 'glm_trials: a')
+    _dense(yy, torch.float64, (R, Mp), 'glm_trials: yy')
+    _dense(q_rank, torch.int32, (R,), 'glm_trials: q_rank')
+    _dense(own, torch.int32, (N,), 'glm_trials: own')
+    _dense(rank, torch.int32, (N,), 'glm_trials: rank')
+    _dense(w, torch.float64, (N, G1), 'glm_trials: w')
+    _dense(F, torch.float64, (N, G1, G1), 'glm_trials: F')
+    unknown = set(outputs) - {'beta', 'variance', 't'}
+    if unknown or not outputs:
+        raise _lib.ChebgcnError("glm_trials: outputs must name some of 'beta', 'variance', 't', got %r" % (outputs,))
+    out = [torch.empty((N, Mp), dtype=torch.float32, device=planes.device) if name in outputs else None
+           for name in ('beta', 'variance', 't')]
+    nbytes, flops = glm_trials_model(Ttot, Mp, R, k, nmax, N, G1, len(set(outputs)))
+    _lib.check(_launch('glm_trials', nbytes, flops, lambda: _lib.lib().chebgcn_glm_trials(
+        _p(planes), Ttot, _p(run_offsets), R, int(M), _p(Z), nmax, _p(trial_offsets), _p(a), _p(yy), k, _p(q_rank), _p(own), _p(rank),
+        _p(w), _p(F), G1, N, _p(out[0]), _p(out[1]), _p(out[2]), _stream())), 'glm_trials')
+    return tuple(out)
+
+
 def searchlight_geometry():
     """The constants of the searchlight kernels (chebgcn_searchlight_query), so that callers and tests follow the tile: ``tile``
     lanes of a score wave, ``centres`` of a score workgroup, ``max_C`` classes served, ``vertices`` of a spread / fit workgroup,

@@ -1048,6 +1048,42 @@ int chebgcn_glm_finish_ar1(const double* ah, const double* s0, const double* s1,
                            double* eff64, double* var64, float* effect, float* variance, float* t, float* beta, float* rho_out,
                            chebgcn_stream stream);
 
+/* ---- single-trial patterns: least squares - separate, one GLM per trial (glm.single_trial) --------------------------------------
+ * Per run, trial j's model is [x_j | o_j1 .. o_jG | N]: its own regressor, the other trials summed per condition (G conditions;
+ * or all of them in one column, G = 1), the nuisance columns N.  The caller factors N on the host (Qn orthonormal, rank q_r), forms
+ * S = the G sums of the trial columns X and Z = (I - Qn Qn^T) [X | S], runs glm_project over the table [Qn | Z_S | 0] of k >= q_r + G
+ * columns (so of run r the planes a[r][0 .. q_r) are an = Qn^T y and a[r][q_r .. q_r + G) are c = Z_S^T y), and hands glm_trials
+ *   Z              float64 [Ttot][nmax]: row t belongs to the run that contains t; column j = z_j, zero beyond the run's trials
+ *   trial_offsets  int64 [R + 1] (device): the trials of run r are the rows [trial_offsets[r], trial_offsets[r + 1]) of the flat
+ *                  per-trial tables and of the outputs, at most nmax of them
+ *   a, yy, k       what glm_project returned for these runs;   q_rank int32 [R] = q_r
+ *   own  int32 [N]          the condition of trial i (0 when G = 1; -1: none of the sums holds the trial)
+ *   rank int32 [N]          r_i = rank of H_i = D_i^T (I - Qn Qn^T) D_i, D_i = [x_i | S_g - [g = own_i] x_i], (1 + G)^2
+ *   w    float64 [N][G1]    the first row of pinv(H_i), G1 = 1 + G
+ *   F    float64 [N][G1][G1]   any factor with F^T F = pinv(H_i), rows at and beyond r_i zero
+ * Per (trial i of run r, vertex), T the run's rows, p = z_i^T y formed like a column of glm_project (the same chains, slices
+ * and panels of chebgcn_glm_trials_query(1) trial columns; the last panel has exactly its own), float64, every sum an fma chain
+ * from 0 over ascending indices:
+ *     d_0 = p, d_{1+g} = c_g - (g == own_i ? p : 0);   beta = sum_l w_l d_l;
+ *     ssq = chain of an_j^2 over j < q_r CONTINUED by (F d)_j^2 over j < r_i, (F d)_j its own chain over l;
+ *     rss = yy - ssq, taken as 0 where rss < 4 (T + q_r + r_i) 2^-53 yy (the floor of glm_finish);   dof = T - q_r - r_i;
+ *     variance = (dof > 0 ? rss / dof : 0) * w_0;   t = variance > 0 ? beta / sqrt(variance) : 0.
+ * beta / variance / t: float32 [N][Mp], each nullable (at least one given), each value rounded ONCE; pad columns are written as
+ * zero whatever the pads of series, a and yy hold.  The trial projections are never stored: the epilogue runs in the workgroup
+ * that formed them.  Clamps: run_offsets into [0, Ttot], trial_offsets into [0, N] (a run's count to nmax), q_rank into
+ * [0, k - G], own into [-1, G), rank into [0, G1].  A (run, trial, vertex) result is the same bits whatever else the call holds,
+ * whatever M, nmax and k are.  No float atomics; the call neither synchronises nor allocates.
+ * chebgcn_last_dispatch(): glm_trials_kernel<NJ> per panel, NJ = its columns, joined by " + ".
+ * glm_trials_query: 0 vertices of a workgroup, 1 trial columns of a panel, 2 the largest G1, 3 the largest k, 4 the largest nmax,
+ *   5 runs of one call at most; -1 for anything else.
+ * Limits: G1 <= 16, k <= 64, nmax <= 4096, R <= 65535, Ttot * Mp and N * Mp <= 2^39: CHEBGCN_EUNSUPPORTED beyond, before any
+ * launch, as every CHEBGCN_EINVAL (NULL, counts <= 0, k < G, pointers not aligned to 8 bytes, the int32 tables to 4). */
+int chebgcn_glm_trials_query(int what);
+int chebgcn_glm_trials(const float* series, int64_t Ttot, const int64_t* run_offsets, int R, int M, const double* Z, int nmax,
+                       const int64_t* trial_offsets, const double* a, const double* yy, int k, const int32_t* q_rank,
+                       const int32_t* own, const int32_t* rank, const double* w, const double* F, int G1, int64_t N, float* beta,
+                       float* variance, float* t, chebgcn_stream stream);
+
 /* ---- searchlight decoding: cross-validated Gaussian naive Bayes at every centre (searchlight.searchlight) ------------------------
  * The caller sorts the S samples so that the test samples of one MODEL (a training set: a (group, fold) pair, or a fold) are
  * contiguous, and hands the kernels (all device memory)
