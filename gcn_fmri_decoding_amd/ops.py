@@ -1994,42 +1994,63 @@ def spectral_transform(x, basis, M, transpose):
     return out
 
 
+def _spectral_operands(what, **tensors):
+    """The shared entry checks of the spectral wrappers below: device tensors, fp32, of the stated rank, contiguous (a view is
+    copied, as in spectral_transform).  ``tensors``: name -> (tensor, rank).  Returns the contiguous tensors in order."""
+    _require_cuda(*(t for t, _ in tensors.values()))
+    out = []
+    for name, (t, rank) in tensors.items():
+        if t.dtype != torch.float32 or t.dim() != rank:
+            raise ValueError('%s: %s must be a %d-D fp32 tensor, got %s %s' % (what, name, rank, t.dtype, tuple(t.shape)))
+        out.append(t if t.is_contiguous() else t.contiguous())
+    return out
+
+
 def spectral_mix(xh, W, M, transpose=False):
     """The per-frequency filter: ``y[b][o][m] = sum_i W[m][o][i] xh[b][i][m]`` (``transpose``: ``sum_o W[m][o][i] dy[b][o][m]``,
-    its input gradient); ``W`` is ``[M, Fout, Fin]``."""
+    its input gradient); ``W`` is ``[M, Fout, Fin]``, ``xh`` planes ``[B, Fin, Mp]`` (``transpose``: ``[B, Fout, Mp]``)."""
+    what = 'spectral_mix_bwd_x' if transpose else 'spectral_mix_fwd'
+    xh, W = _spectral_operands(what, planes=(xh, 3), W=(W, 3))
     B, Ni, Mp = xh.shape
     _, Fout, Fin = W.shape
     No = Fin if transpose else Fout
+    if Mp != plane_stride(M) or W.shape[0] != M or Ni != (Fout if transpose else Fin):
+        raise ValueError('%s: planes %s and W %s do not agree at M = %d' % (what, tuple(xh.shape), tuple(W.shape), M))
     out = torch.empty((B, No, Mp), dtype=torch.float32, device=xh.device)
     fn = _lib.lib().chebgcn_spectral_mix_bwd_x if transpose else _lib.lib().chebgcn_spectral_mix_fwd
-    _launch('spectral_mix_bwd_x' if transpose else 'spectral_mix_fwd', 4.0 * (B * (Ni + No) * Mp + W.numel()),
-            2.0 * B * M * Fin * Fout,
-            lambda: _lib.check(fn(_p(xh), _p(W), _p(out), B, M, Fin, Fout, _stream()),
-                               'spectral_mix_bwd_x' if transpose else 'spectral_mix_fwd'))
+    _launch(what, 4.0 * (B * (Ni + No) * Mp + W.numel()), 2.0 * B * M * Fin * Fout,
+            lambda: _lib.check(fn(_p(xh), _p(W), _p(out), B, M, Fin, Fout, _stream()), what))
     return out
 
 
 def spectral_mix_bwd_w(dyh, xh, M):
     """``dW[m][o][fin] = sum_b dyh[b][o][m] xh[b][fin][m]``, summed over the windows in a fixed order."""
+    what = 'spectral_mix_bwd_w'
+    dyh, xh = _spectral_operands(what, dyh=(dyh, 3), xh=(xh, 3))
     B, Fout, Mp = dyh.shape
     Fin = xh.shape[1]
+    if Mp != plane_stride(M) or xh.shape[0] != B or xh.shape[2] != Mp:
+        raise ValueError('%s: dyh %s and xh %s do not agree at M = %d' % (what, tuple(dyh.shape), tuple(xh.shape), M))
     dW = torch.empty((M, Fout, Fin), dtype=torch.float32, device=dyh.device)
-    _launch('spectral_mix_bwd_w', 4.0 * (B * (Fin + Fout) * Mp + dW.numel()), 2.0 * B * M * Fin * Fout,
-            lambda: _lib.check(_lib.lib().chebgcn_spectral_mix_bwd_w(_p(dyh), _p(xh), _p(dW), B, M, Fin, Fout, _stream()),
-                               'spectral_mix_bwd_w'))
+    _launch(what, 4.0 * (B * (Fin + Fout) * Mp + dW.numel()), 2.0 * B * M * Fin * Fout,
+            lambda: _lib.check(_lib.lib().chebgcn_spectral_mix_bwd_w(_p(dyh), _p(xh), _p(dW), B, M, Fin, Fout, _stream()), what))
     return dW
 
 
 def spline_expand(Bs, Wk, transpose=False):
     """``W = Bs @ Wk`` ([M, K] x [K, C]); ``transpose``: ``dWk = Bs^T @ dW`` (``Wk`` is then dW [M, C])."""
+    what = 'spectral_spline_expand_bwd' if transpose else 'spectral_spline_expand'
+    Bs, Wk = _spectral_operands(what, Bs=(Bs, 2), Wk=(Wk, 2))
     M, K = Bs.shape
     C = Wk.shape[1]
+    if Wk.shape[0] != (M if transpose else K):
+        raise ValueError('%s: Bs %s and %s %s do not agree' % (what, tuple(Bs.shape), 'dW' if transpose else 'Wk', tuple(Wk.shape)))
     if transpose:
         out = torch.empty((K, C), dtype=torch.float32, device=Wk.device)
-        fn, what = _lib.lib().chebgcn_spectral_spline_expand_bwd, 'spectral_spline_expand_bwd'
+        fn = _lib.lib().chebgcn_spectral_spline_expand_bwd
     else:
         out = torch.empty((M, C), dtype=torch.float32, device=Wk.device)
-        fn, what = _lib.lib().chebgcn_spectral_spline_expand, 'spectral_spline_expand'
+        fn = _lib.lib().chebgcn_spectral_spline_expand
     _launch(what, 4.0 * (M * K + (M + K) * C), 2.0 * M * K * C,
             lambda: _lib.check(fn(_p(Bs), _p(Wk), _p(out), M, K, C, _stream()), what))
     return out
