@@ -327,6 +327,14 @@ def _noise_args(noise, rho, who):
     return float(rho)
 
 
+def _contrast_factor(c, X):
+    """``c pinv(X^T X) c`` per contrast, formed as ``|pinv(X)^T c|^2`` from the SVD of X itself.  ``pinv(X^T X)`` with the
+    squared cutoff takes the null eigenvalues of a rank-deficient design (which the product leaves at ``eps |X|^2``, far above
+    ``(max(T, P) eps)^2 |X|^2``) for real ones and returns any number, negative ones included."""
+    g = c @ np.linalg.pinv(X, rcond=max(X.shape) * np.finfo(np.float64).eps)
+    return (g * g).sum(axis=1)
+
+
 def _host_rho(res, y, T, rank):
     """``sum r_t r_{t-1} / sum r_t^2`` of OLS residuals [T, M], clamped to ``+-RHO_MAX``; 0 where the residuals are the round-off
     of a vertex the design explains exactly (``rss < 4 (T + rank) 2^-53 y.y``, the floor of the kernels)."""
@@ -356,7 +364,7 @@ def _host_gls(tb, y, rho):
         res = yw - Xw @ bw
         b[:, cols] = bw
         rss[cols] = (res * res).sum(axis=0)
-        factor[:, cols] = np.einsum('cp,pq,cq->c', tb.c, np.linalg.pinv(Xw.T @ Xw, rcond=eps ** 2, hermitian=True), tb.c)[:, None]
+        factor[:, cols] = _contrast_factor(tb.c, Xw)[:, None]
     return b, rss, factor
 
 
@@ -382,8 +390,7 @@ def first_level_host(runs, designs, contrasts=None, groups=None, betas=False, no
         res = y - tb.X @ b
         rss = (res * res).sum(axis=0)
         d = tb.T - tb.rank
-        factor = np.einsum('cp,pq,cq->c', tb.c, np.linalg.pinv(tb.X.T @ tb.X, rcond=(max(tb.X.shape) * np.finfo(np.float64).eps) ** 2,
-                                                                 hermitian=True), tb.c)[:, None]
+        factor = _contrast_factor(tb.c, tb.X)[:, None]
         if noise == 'ar1':
             rhos.append(np.full(pl.M, rho) if rho is not None else _host_rho(res, y, tb.T, tb.rank)[0])
             b, rss, factor = _host_gls(tb, y, rhos[-1])

@@ -974,6 +974,9 @@ int chebgcn_cluster_enhance(const int32_t* ptr, const int32_t* idx, int64_t nnz,
  *     t = variance > 0 ? e / sqrt(variance) : 0   (never NaN for finite input);   beta_p = fma chain of B[p][j] a_j likewise.
  *   eff64 / var64: float64 [R][C][Mp] (for glm_combine); effect / variance / t: float32 [R][C][Mp], each rounded ONCE from the
  *   float64 value; beta: float32 [R][P][Mp].  Each of the three sets may be NULL (B with beta), at least one is given.
+ *   The pad [M, Mp) of every output plane of glm_finish and of glm_finish_ar1 (rho_out included) is scratch, as the conventions
+ *   above say of every plane: it is written (with what the pads of the sums give) and nothing may be read from it; nothing
+ *   outside the [R][.][Mp] planes is written.
  *   chebgcn_last_dispatch(): glm_finish_kernel.
  * glm_combine: fixed effects over the runs of a group.  group_ptr int32 [S + 1] / group_runs int32 [nruns] (device): group g is
  *   the runs group_runs[group_ptr[g] .. group_ptr[g + 1]), summed in that order (the caller lists them ascending), n of them:
