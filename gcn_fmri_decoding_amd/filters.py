@@ -13,16 +13,13 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import graph as _graph
+from .runs import cuda_device, is_tensor
 
 KMAX = 256                      # terms of a filter at most (chebgcn_cheb_filter)
 JMAX = 8                        # filters of one launch; more are applied in groups
 CHUNK_BYTES = 256 << 20         # a slice of host rows on the device, and the scratch of one launch, at most
 ROWS_MAX = 65535                # rows of one launch of the layout kernels
 ORDER_MIN = 1024                # relabel='auto': graphs above this many vertices are tried on the ordered kernels (as cgcnn does)
-
-
-def _is_tensor(a):
-    return type(a).__module__.split('.')[0] == 'torch'
 
 
 def heat(t):
@@ -154,16 +151,16 @@ class GraphFilter:
 
     # ---- the float64 restatement ---------------------------------------------------------------------------------------------------
     def _runs(self, series):
-        single = (isinstance(series, np.ndarray) or _is_tensor(series)) and series.ndim == 2
+        single = (isinstance(series, np.ndarray) or is_tensor(series)) and series.ndim == 2
         runs = [series] if single else list(series)
         if not runs:
             raise ValueError('GraphFilter: series holds no runs')
         for r in runs:
-            if not (isinstance(r, np.ndarray) or _is_tensor(r)):
+            if not (isinstance(r, np.ndarray) or is_tensor(r)):
                 raise ValueError('GraphFilter: series must be NumPy arrays or torch tensors, not %s' % type(r).__name__)
             if r.ndim != 2 or r.shape[1] != self.M:
                 raise ValueError('GraphFilter: series must be [rows, %d] (M = L.shape[0]), got shape %r' % (self.M, tuple(r.shape)))
-            if _is_tensor(r):
+            if is_tensor(r):
                 if str(r.dtype) == 'torch.float64':
                     raise ValueError('GraphFilter: series is a float64 tensor; the filter runs in float32 -- pass series.float()')
             elif not (np.issubdtype(r.dtype, np.number) or r.dtype == bool):
@@ -180,7 +177,7 @@ class GraphFilter:
         c = self.coeffs.astype(np.float32).astype(np.float64)
         out = []
         for r in runs:
-            x = r.detach().cpu().numpy() if _is_tensor(r) else np.asarray(r)
+            x = r.detach().cpu().numpy() if is_tensor(r) else np.asarray(r)
             prev, cur = None, x.astype(np.float32).astype(np.float64).T           # T_{k-2}, T_{k-1}: [M, R]
             y = c[:, 0, None, None] * cur[None]
             for k in range(1, self.K):
@@ -226,11 +223,7 @@ class GraphFilter:
             raise ValueError('GraphFilter: out is for a single run')
         import torch
         from . import ops
-        if self.device is None:
-            on_dev = [r.device for r in runs if _is_tensor(r) and r.is_cuda]
-            dev = on_dev[0] if on_dev else torch.device('cuda', torch.cuda.current_device())
-        else:
-            dev = torch.device(self.device)
+        dev = cuda_device(self.device, next((r for r in runs if is_tensor(r) and r.is_cuda), None))
         res = []
         with torch.cuda.device(dev):
             g, order, coeff = self._tables(dev)
@@ -245,13 +238,13 @@ class GraphFilter:
                     y = torch.empty(shape, dtype=torch.float32, device=dev)
                 else:
                     y = out
-                    if (not _is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or tuple(y.shape) != shape
+                    if (not is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or tuple(y.shape) != shape
                             or (self.M > 1 and y.stride(-1) != 1)):
                         raise ValueError('GraphFilter: out must be a float32 device tensor %r with contiguous rows' % (shape,))
                 yj = y[None] if self.single else y
                 for r0 in range(0, R, rows):
                     piece = r[r0:r0 + rows]
-                    if _is_tensor(piece):
+                    if is_tensor(piece):
                         x = piece.to(torch.float32).contiguous().to(dev)
                     else:
                         x = torch.as_tensor(np.ascontiguousarray(piece, dtype=np.float32)).to(dev)

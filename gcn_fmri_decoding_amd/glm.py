@@ -45,6 +45,8 @@ import collections
 
 import numpy as np
 
+from . import runs as _runs
+
 HRF_SPM = (6.0, 16.0, 1.0 / 6.0)
 KMAX, CMAX, PMAX, RMAX = 64, 32, 64, 65535      # chebgcn_glm_query(2), (3), (7), (8)
 ESTIMABLE_TOL = 1e-8
@@ -62,10 +64,6 @@ runs); ``groups`` the S group keys in order of first appearance; ``betas`` None,
 GLMResultAR1 = collections.namedtuple('GLMResultAR1', 'effect variance t dof groups betas rho')
 GLMResultAR1.__doc__ = """What ``first_level(noise='ar1')`` returns: the fields of ``GLMResult``, then ``rho``: one float32 [M] array
 per run (a tensor where the run came as a tensor; float64 from ``first_level_host``), the AR(1) coefficient of every vertex."""
-
-
-def _is_tensor(a):
-    return type(a).__module__.split('.')[0] == 'torch'
 
 
 # ---- designs --------------------------------------------------------------------------------------------------------------------
@@ -225,40 +223,14 @@ def _factor(X):
 
 def _plan(runs, designs, contrasts, groups, who, limits=True):
     """Everything that can be checked without the series' values; the per-run tables of the kernels."""
-    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
-    if single and runs.ndim != 2:
-        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
-    runs = [runs] if single else list(runs)
-    if not runs:
-        raise ValueError('%s: no runs' % who)
-    tensors = all(_is_tensor(r) for r in runs)
-    runs = [r if _is_tensor(r) else np.asarray(r) for r in runs]
-    if any(r.ndim != 2 for r in runs):
-        raise ValueError('%s: every run must be [T, M]' % who)
-    M = int(runs[0].shape[1])
-    if M < 1 or any(int(r.shape[1]) != M for r in runs):
-        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
+    runs, _, M, tensors = _runs.as_runs(runs, who)
     if isinstance(designs, Design):
         designs = [designs]
     designs = list(designs)
     if len(designs) != len(runs) or not all(isinstance(d, Design) for d in designs):
         raise ValueError('%s: designs must hold one Design per run (%d runs, %d designs)' % (who, len(runs), len(designs)))
     R = len(runs)
-    if groups is None:
-        groups = [0] * R
-    groups = list(groups)
-    if len(groups) != R:
-        raise ValueError('%s: groups must hold one key per run (%d runs, %d keys)' % (who, R, len(groups)))
-    keys, members = [], {}
-    for r, g in enumerate(groups):
-        try:
-            hash(g)
-        except TypeError:
-            raise ValueError('%s: group key %r of run %d is not hashable' % (who, g, r)) from None
-        if g not in members:
-            keys.append(g)
-            members[g] = []
-        members[g].append(r)
+    _, keys, members = _runs.group_keys(groups, R, who)
     per_run = None
     if contrasts is not None:
         if isinstance(contrasts, (list, tuple)) and len(contrasts) == R and all(np.ndim(c) == 2 for c in contrasts):
@@ -300,17 +272,7 @@ def _plan(runs, designs, contrasts, groups, who, limits=True):
                                  'of its norm)' % (who, i, r, miss / max(np.linalg.norm(c[i]), 1e-300)))
         u = c @ B                                               # [C, k]
         tables.append(_Run(T, X, c, k, Q, B, u, (u * u).sum(axis=1)))
-    return _Plan(runs, tables, M, C, keys, [members[g] for g in keys], tensors)
-
-
-def _host_array(y, who):
-    y = (y.detach().cpu().numpy() if _is_tensor(y) else np.asarray(y))
-    if y.dtype.kind not in 'fiu':
-        raise ValueError('%s: series of dtype %s' % (who, y.dtype))
-    y = y.astype(np.float32)
-    if not np.isfinite(y).all():
-        raise ValueError('%s: series hold non-finite values' % who)
-    return y
+    return _Plan(runs, tables, M, C, keys, members, tensors)
 
 
 # ---- the host restatement -------------------------------------------------------------------------------------------------------
@@ -385,7 +347,7 @@ def first_level_host(runs, designs, contrasts=None, groups=None, betas=False, no
     pl = _plan(runs, designs, contrasts, groups, who, limits=False)
     eff, var, dof, bs, rhos = [], [], [], [], []
     for y, tb in zip(pl.runs, pl.tables):
-        y = _host_array(y, who).astype(np.float64)
+        y = _runs.host_array(y, who).astype(np.float64)
         b = np.linalg.lstsq(tb.X, y, rcond=max(tb.X.shape) * np.finfo(np.float64).eps)[0]
         res = y - tb.X @ b
         rss = (res * res).sum(axis=0)
@@ -455,34 +417,6 @@ def _ar1_tables(tabs, k):
     return W, D, E
 
 
-def _stage(runs, offs, M, device, who):
-    """The runs as ``[Ttot, plane_stride(M)]`` float32 planes on the device (tensors are staged where they lie; a non-finite
-    value is a ``ValueError``): ``(device, planes)``."""
-    on_device = any(_is_tensor(r) for r in runs)
-    host = [None if _is_tensor(r) else _host_array(r, who) for r in runs]
-    import torch
-    from . import _lib
-    if device is None:
-        first = next((r for r in runs if _is_tensor(r) and r.is_cuda), None)
-        dev = first.device if first is not None else torch.device('cuda', torch.cuda.current_device())
-    else:
-        dev = torch.device(device)
-    Mp = _lib.plane_stride(M)
-    with torch.cuda.device(dev):
-        if on_device:
-            planes = torch.zeros((int(offs[-1]), Mp), dtype=torch.float32, device=dev)
-            for y, h, o in zip(runs, host, offs):
-                planes[o:o + y.shape[0], :M] = (y.detach() if h is None else torch.as_tensor(h)).to(dev, torch.float32)
-            if not bool(torch.isfinite(planes).all()):
-                raise ValueError('%s: series hold non-finite values' % who)
-        else:
-            staged = np.zeros((int(offs[-1]), Mp), np.float32)
-            for h, o in zip(host, offs):
-                staged[o:o + h.shape[0], :M] = h
-            planes = torch.as_tensor(staged).to(dev)
-    return dev, planes
-
-
 def _batch_arg(batch_runs, who):
     if batch_runs is not None and (isinstance(batch_runs, (bool, np.bool_)) or not isinstance(batch_runs, (int, np.integer))
                                    or batch_runs < 1):
@@ -494,7 +428,7 @@ def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=F
 
     ``runs``: one ``[T, M]`` array or a list (any lengths, same M; NumPy arrays, or torch tensors such as
     ``Parcellation.reduce`` returns, which are staged where they lie).  They are staged as ``[Ttot, plane_stride(M)]`` float32
-    planes with a device table of run offsets, as ``connectivity_graph`` stages them.  ``designs``: one ``Design`` per run.
+    planes with a device table of run offsets (``runs.stage``, as for ``connectivity_graph``).  ``designs``: one ``Design`` per run.
     ``contrasts``: ``[C, P]`` for every run (or one such array per run, when designs differ in width); default
     ``contrasts_one_vs_rest`` of each design.  ``groups``: one hashable key per run -- the subject; default one group; the
     runs of a group are combined as fixed effects (``effect`` the mean, ``variance = sum / R_g^2``, ``dof`` the sum).
@@ -525,22 +459,15 @@ def first_level(runs, designs, contrasts=None, groups=None, device=None, betas=F
     from . import _lib, ops
     R, M, C = len(pl.runs), pl.M, pl.C
     Mp = _lib.plane_stride(M)
-    offs = np.concatenate([[0], np.cumsum([tb.T for tb in pl.tables])]).astype(np.int64)
-    dev, planes = _stage(pl.runs, offs, M, device, who)
+    dev, planes = _runs.stage(pl.runs, M, device, who)
     with torch.cuda.device(dev):
-        if batch_runs is None:
-            kmax = max(tb.rank for tb in pl.tables)
-            free = torch.cuda.mem_get_info(dev)[0]
-            batch_runs = max(1, int(free // 4) // (8 * ((2 * kmax + 2) if ar1 else (kmax + 1)) * Mp))
-        batch_runs = int(min(batch_runs, R, RMAX))
+        kmax = max(tb.rank for tb in pl.tables)
+        batch_runs = _runs.batch_size(batch_runs, R, RMAX, 8 * ((2 * kmax + 2) if ar1 else (kmax + 1)) * Mp, dev)
         e64 = torch.empty((R, C, Mp), dtype=torch.float64, device=dev)
         v64 = torch.empty((R, C, Mp), dtype=torch.float64, device=dev)
         beta_out, rho_out = [], []
-        for r0 in range(0, R, batch_runs):
-            r1 = min(r0 + batch_runs, R)
+        for r0, r1, rows, o in _runs.batches(planes, _runs.offsets(pl.runs), batch_runs):
             Q, U, un2, B, rank = (torch.as_tensor(a).to(dev) for a in _batch_tables(pl.tables[r0:r1], C))
-            rows = planes[int(offs[r0]):int(offs[r1])]
-            o = torch.as_tensor(offs[r0:r1 + 1] - offs[r0]).to(dev)
             if ar1:
                 W, D, E = (torch.as_tensor(a).to(dev) for a in _ar1_tables(pl.tables[r0:r1], int(Q.shape[1])))
                 ah, s0, s1 = ops.glm_project_ar1(rows, o, M, W)
@@ -632,19 +559,7 @@ def _others(tb, j, G):
 
 def _trial_plan(runs, designs, others, outputs, groups, who, limits=True):
     """Everything of ``single_trial`` that can be checked without the series' values, and the per-run tables of the kernels."""
-    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
-    if single and runs.ndim != 2:
-        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
-    runs = [runs] if single else list(runs)
-    if not runs:
-        raise ValueError('%s: no runs' % who)
-    tensors = all(_is_tensor(r) for r in runs)
-    runs = [r if _is_tensor(r) else np.asarray(r) for r in runs]
-    if any(r.ndim != 2 for r in runs):
-        raise ValueError('%s: every run must be [T, M]' % who)
-    M = int(runs[0].shape[1])
-    if M < 1 or any(int(r.shape[1]) != M for r in runs):
-        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
+    runs, _, M, tensors = _runs.as_runs(runs, who)
     if isinstance(designs, TrialDesign):
         designs = [designs]
     designs = list(designs)
@@ -658,14 +573,7 @@ def _trial_plan(runs, designs, others, outputs, groups, who, limits=True):
     outputs = tuple(outputs)
     if not outputs or set(outputs) - {'beta', 'variance', 't'}:
         raise ValueError("%s: outputs must name some of 'beta', 'variance', 't', got %r" % (who, outputs))
-    groups = [0] * R if groups is None else list(groups)
-    if len(groups) != R:
-        raise ValueError('%s: groups must hold one key per run (%d runs, %d keys)' % (who, R, len(groups)))
-    for r, g in enumerate(groups):
-        try:
-            hash(g)
-        except TypeError:
-            raise ValueError('%s: group key %r of run %d is not hashable' % (who, g, r)) from None
+    groups = _runs.group_keys(groups, R, who)[0]
     classes = list(designs[0].conditions)
     if any(list(d.conditions) != classes for d in designs):
         raise ValueError('%s: the designs differ in their conditions; build them with the same conditions=' % who)
@@ -747,7 +655,7 @@ def single_trial_host(runs, designs, others='condition', outputs=('beta', 't'), 
     pl = _trial_plan(runs, designs, others, outputs, groups, who, limits=False)
     beta, var, dof = [], [], []
     for y, tb in zip(pl.runs, pl.tables):
-        y = _host_array(y, who).astype(np.float64)
+        y = _runs.host_array(y, who).astype(np.float64)
         for j in range(tb.n):
             O = _others(tb, j, pl.G)
             D = np.concatenate([tb.X[:, j:j + 1], O[:, tb.keep[j, 1:]], tb.N], axis=1)
@@ -821,19 +729,12 @@ def single_trial(runs, designs, others='condition', outputs=('beta', 't'), group
     from . import _lib, ops
     R, M, G = len(pl.runs), pl.M, pl.G
     Mp = _lib.plane_stride(M)
-    offs = np.concatenate([[0], np.cumsum([tb.T for tb in pl.tables])]).astype(np.int64)
-    dev, planes = _stage(pl.runs, offs, M, device, who)
+    dev, planes = _runs.stage(pl.runs, M, device, who)
     with torch.cuda.device(dev):
-        if batch_runs is None:
-            kmax = max(tb.q for tb in pl.tables) + G
-            batch_runs = max(1, int(torch.cuda.mem_get_info(dev)[0] // 4) // (8 * (kmax + 1) * Mp))
-        batch_runs = int(min(batch_runs, R, RMAX))
+        batch_runs = _runs.batch_size(batch_runs, R, RMAX, 8 * (max(tb.q for tb in pl.tables) + G + 1) * Mp, dev)
         parts = []
-        for r0 in range(0, R, batch_runs):
-            r1 = min(r0 + batch_runs, R)
+        for r0, r1, rows, o in _runs.batches(planes, _runs.offsets(pl.runs), batch_runs):
             Q, Z, toffs, qrank, own, rank, w, F = (torch.as_tensor(a).to(dev) for a in _trial_tables(pl.tables[r0:r1], G))
-            rows = planes[int(offs[r0]):int(offs[r1])]
-            o = torch.as_tensor(offs[r0:r1 + 1] - offs[r0]).to(dev)
             a, yy = ops.glm_project(rows, o, M, Q)
             parts.append(ops.glm_trials(rows, o, M, Z, toffs, a, yy, qrank, own, rank, w, F, outputs=pl.outputs))
         maps = {}

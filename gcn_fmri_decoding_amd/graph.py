@@ -13,6 +13,8 @@ return the same ``[N, k]`` tables as ``distance_sklearn_metrics`` without the N 
 import numpy as np
 import scipy.sparse as sp
 
+from . import runs as _runs
+
 
 def distance_sklearn_metrics(z, k=4, metric='euclidean'):
     """Exact k nearest neighbours from the full distance matrix (graph.py:9-17).
@@ -59,13 +61,6 @@ def _knn_check(N, k):
         raise ValueError('k = %d neighbours need more than %d vertices' % (k, N))
 
 
-def _cuda_device(device):
-    import torch
-    if device is None:
-        return torch.device('cuda', torch.cuda.current_device())
-    return torch.device(device)
-
-
 def knn_device(z, k=4, metric='euclidean', device=None):
     """``distance_sklearn_metrics`` on the device (chebgcn_knn), without the N x N matrix: ``z`` [N, D] features, ``metric``
     'euclidean', 'cosine' or 'correlation'.  Returns (d float32 [N, k] ascending, idx int64 [N, k]) on the host, ready for
@@ -89,7 +84,7 @@ def knn_device(z, k=4, metric='euclidean', device=None):
         raise ValueError('knn_device: z holds non-finite values')
     import torch
     from . import _lib, ops
-    dev = _cuda_device(device)
+    dev = _runs.cuda_device(device)
     planes = np.zeros((D, _lib.plane_stride(N)), np.float32)
     planes[:, :N] = z.T
     with torch.cuda.device(dev):
@@ -107,42 +102,17 @@ def connectivity_graph(series, k=8, device=None, return_sigma=False):
     correlation 0 with everything in that run).  Returns (d, idx) with ``d = 1 - r`` float32 [M, k] ascending and idx int64,
     as ``knn_device``; with ``return_sigma`` also the mean of the whole matrix r (diagonal included), the reference's kernel
     width for its RSFC graph (model.py:126).  Tangent-space and partial correlation are out of scope."""
-    def is_tensor(r):
-        return type(r).__module__.split('.')[0] == 'torch'
-
-    runs = [series] if (isinstance(series, np.ndarray) or is_tensor(series)) and series.ndim == 2 else list(series)
-    if not runs:
-        raise ValueError('connectivity_graph: no runs')
-    on_device = any(is_tensor(r) for r in runs)
-    runs = [r if is_tensor(r) else np.asarray(r) for r in runs]
-    if any(r.ndim != 2 for r in runs):
-        raise ValueError('connectivity_graph: every run must be [T, M]')
-    M = runs[0].shape[1]
-    if any(r.shape[1] != M for r in runs):
-        raise ValueError('connectivity_graph: runs differ in the number of vertices')
-    if any(r.shape[0] < 2 for r in runs):
-        raise ValueError('connectivity_graph: a run needs at least two time points')
+    who = 'connectivity_graph'
+    if (isinstance(series, np.ndarray) or _runs.is_tensor(series)) and series.ndim != 2:
+        series = list(series)                                   # (a stack [R, T, M] is taken as R runs)
+    runs, _, M, _ = _runs.as_runs(series, who, min_rows=2, min_cols=0, width='runs differ in the number of vertices',
+                                  rows='a run needs at least two time points')
     _knn_check(M, k)
-    runs = [r if is_tensor(r) else np.ascontiguousarray(r, dtype=np.float32) for r in runs]
-    if not all(np.isfinite(r).all() for r in runs if not is_tensor(r)):
-        raise ValueError('connectivity_graph: series hold non-finite values')
+    dev, planes = _runs.stage(runs, M, device, who, any_dtype=True)
     import torch
     from . import _lib, ops
-    dev = _cuda_device(device)
-    offs = np.concatenate([[0], np.cumsum([r.shape[0] for r in runs])]).astype(np.int64)
-    if on_device:                       # tensors (Parcellation.reduce gives them on the device) are staged where they lie
-        planes = torch.zeros((int(offs[-1]), _lib.plane_stride(M)), dtype=torch.float32, device=dev)
-        for r, o in zip(runs, offs):
-            planes[o:o + r.shape[0], :M] = (r if is_tensor(r) else torch.as_tensor(r)).to(dev, torch.float32)
-        if not bool(torch.isfinite(planes).all()):
-            raise ValueError('connectivity_graph: series hold non-finite values')
-    else:
-        planes = np.zeros((int(offs[-1]), _lib.plane_stride(M)), np.float32)
-        for r, o in zip(runs, offs):
-            planes[o:o + r.shape[0], :M] = r
     with torch.cuda.device(dev):
-        zn = ops.series_normalise(torch.as_tensor(planes).to(dev), torch.as_tensor(offs).to(dev), M,
-                                  scale=1.0 / np.sqrt(len(runs)))
+        zn = ops.series_normalise(planes, torch.as_tensor(_runs.offsets(runs)).to(dev), M, scale=1.0 / np.sqrt(len(runs)))
         d, idx = ops.knn(zn, M, int(k), _lib.KNN_DOT)
         out = (d.cpu().numpy(), idx.cpu().numpy().astype(np.int64))
         if return_sigma:

@@ -434,17 +434,22 @@ def knn(planes, N, k, metric):
     return dist, idx
 
 
+def _staged_runs(planes, run_offsets, M, what):
+    """``(Ttot, Mp, R)`` of staged runs: ``planes`` contiguous float32 [Ttot, plane_stride(M)], ``run_offsets`` int64 [R + 1]."""
+    if planes.dim() != 2 or planes.shape[1] != plane_stride(M) or planes.dtype != torch.float32 or not planes.is_contiguous():
+        raise _lib.ChebgcnError('%s: planes must be contiguous float32 [Ttot, plane_stride(M)]' % what)
+    R = int(run_offsets.numel()) - 1
+    if run_offsets.dtype != torch.int64 or run_offsets.dim() != 1 or R < 1 or not run_offsets.is_contiguous():
+        raise _lib.ChebgcnError('%s: run_offsets must be a contiguous int64 vector of R + 1 entries' % what)
+    return int(planes.shape[0]), int(planes.shape[1]), R
+
+
 def series_normalise(planes, run_offsets, M, scale=1.0, out=None):
     """Every run of a staged series centred and scaled to norm ``scale`` per vertex inside that run
     (chebgcn_series_normalise): ``planes`` [Ttot, Mp] fp32, ``run_offsets`` int64 [R + 1] on the device (run r = rows
     [run_offsets[r], run_offsets[r + 1]), checked by the caller) -> [Ttot, Mp]; a vertex constant in a run is zero there."""
     _require_cuda(planes, run_offsets, out)
-    if planes.dim() != 2 or planes.shape[1] != plane_stride(M) or planes.dtype != torch.float32 or not planes.is_contiguous():
-        raise _lib.ChebgcnError('series_normalise: planes must be contiguous float32 [Ttot, plane_stride(M)]')
-    Ttot, Mp = planes.shape
-    R = int(run_offsets.numel()) - 1
-    if run_offsets.dtype != torch.int64 or run_offsets.dim() != 1 or R < 1 or not run_offsets.is_contiguous():
-        raise _lib.ChebgcnError('series_normalise: run_offsets must be a contiguous int64 vector of R + 1 entries')
+    Ttot, Mp, R = _staged_runs(planes, run_offsets, M, 'series_normalise')
     o = run_offsets.cpu().numpy()           # one small download: the kernel trusts the table, so it is checked here
     if o[0] != 0 or o[-1] != Ttot or (np.diff(o) < 1).any():
         raise _lib.ChebgcnError('series_normalise: run_offsets must ascend from 0 to Ttot')
@@ -705,12 +710,7 @@ def glm_project(planes, run_offsets, M, Q):
     ``run_offsets`` int64 [R + 1] and ``Q`` float64 [Ttot, k] on the device -> ``(a float64 [R, k, Mp], yy float64 [R, Mp])``
     in one workspace (the next call on the stream reuses it).  float64 FMA chains in ascending t: include/chebgcn.h."""
     _require_cuda(planes, run_offsets, Q)
-    if planes.dim() != 2 or planes.shape[1] != plane_stride(M) or planes.dtype != torch.float32 or not planes.is_contiguous():
-        raise _lib.ChebgcnError('glm_project: planes must be contiguous float32 [Ttot, plane_stride(M)]')
-    Ttot, Mp = int(planes.shape[0]), int(planes.shape[1])
-    R = int(run_offsets.numel()) - 1
-    if run_offsets.dtype != torch.int64 or run_offsets.dim() != 1 or R < 1 or not run_offsets.is_contiguous():
-        raise _lib.ChebgcnError('glm_project: run_offsets must be a contiguous int64 vector of R + 1 entries')
+    Ttot, Mp, R = _staged_runs(planes, run_offsets, M, 'glm_project')
     if Q.dim() != 2:
         raise _lib.ChebgcnError('glm_project: Q must be float64 [Ttot, k]')
     k = int(Q.shape[1])
@@ -728,6 +728,34 @@ def glm_project(planes, run_offsets, M, Q):
     return a, yy
 
 
+def _finish_tables(what, R, k, Mp, U, B, out64, want32, dev):
+    """What the two finish kernels share: ``U`` float64 [R, C, k] and ``B`` float64 [R, P, k] or None checked, ``out64`` (a pair
+    of float64 [R, C, Mp], or None) checked, and the float32 outputs allocated:
+    ``(C, P, e64, v64, e32, v32, t32 (None without want32), beta [R, P, Mp] or None)``."""
+    if U.dim() != 3:
+        raise _lib.ChebgcnError('%s: U must be float64 [R, C, k]' % what)
+    C_ = int(U.shape[1])
+    _dense(U, torch.float64, (R, C_, k), what + ': U')
+    P = 0
+    beta = None
+    if B is not None:
+        if B.dim() != 3:
+            raise _lib.ChebgcnError('%s: B must be float64 [R, P, k]' % what)
+        P = int(B.shape[1])
+        _dense(B, torch.float64, (R, P, k), what + ': B')
+        beta = torch.empty((R, P, Mp), dtype=torch.float32, device=dev)
+    e64 = v64 = None
+    if out64 is not None:
+        e64, v64 = out64
+        _require_cuda(e64, v64)
+        _dense(e64, torch.float64, (R, C_, Mp), what + ': out64[0]')
+        _dense(v64, torch.float64, (R, C_, Mp), what + ': out64[1]')
+    e32 = v32 = t32 = None
+    if want32:
+        e32, v32, t32 = (torch.empty((R, C_, Mp), dtype=torch.float32, device=dev) for _ in range(3))
+    return C_, P, e64, v64, e32, v32, t32, beta
+
+
 def glm_finish(a, yy, run_offsets, Ttot, rank, U, unorm2, M, B=None, out64=None, want32=False):
     """Residual variance and contrasts of every (run, vertex) (chebgcn_glm_finish) from what ``glm_project`` returned: ``rank``
     int32 [R], ``U`` float64 [R, C, k], ``unorm2`` float64 [R, C], ``B`` float64 [R, P, k] or None, all on the device.
@@ -741,28 +769,8 @@ def glm_finish(a, yy, run_offsets, Ttot, rank, U, unorm2, M, B=None, out64=None,
     _dense(yy, torch.float64, (R, Mp), 'glm_finish: yy')
     _dense(run_offsets, torch.int64, (R + 1,), 'glm_finish: run_offsets')
     _dense(rank, torch.int32, (R,), 'glm_finish: rank')
-    if U.dim() != 3:
-        raise _lib.ChebgcnError('glm_finish: U must be float64 [R, C, k]')
-    C_ = int(U.shape[1])
-    _dense(U, torch.float64, (R, C_, k), 'glm_finish: U')
+    C_, P, e64, v64, e32, v32, t32, beta = _finish_tables('glm_finish', R, k, Mp, U, B, out64, want32, a.device)
     _dense(unorm2, torch.float64, (R, C_), 'glm_finish: unorm2')
-    P = 0
-    beta = None
-    if B is not None:
-        if B.dim() != 3:
-            raise _lib.ChebgcnError('glm_finish: B must be float64 [R, P, k]')
-        P = int(B.shape[1])
-        _dense(B, torch.float64, (R, P, k), 'glm_finish: B')
-        beta = torch.empty((R, P, Mp), dtype=torch.float32, device=a.device)
-    e64 = v64 = None
-    if out64 is not None:
-        e64, v64 = out64
-        _require_cuda(e64, v64)
-        _dense(e64, torch.float64, (R, C_, Mp), 'glm_finish: out64[0]')
-        _dense(v64, torch.float64, (R, C_, Mp), 'glm_finish: out64[1]')
-    e32 = v32 = t32 = None
-    if want32:
-        e32, v32, t32 = (torch.empty((R, C_, Mp), dtype=torch.float32, device=a.device) for _ in range(3))
     _lib.check(_launch('glm_finish', 8.0 * R * Mp * (k * (1 + C_ + P) + 1), 2.0 * R * Mp * k * (1 + C_ + P),
                        lambda: _lib.lib().chebgcn_glm_finish(
                            _p(a), _p(yy), _p(run_offsets), int(Ttot), _p(rank), _p(U), _p(unorm2), _p(B), R, int(M), k, C_, P,
@@ -808,12 +816,7 @@ def glm_project_ar1(planes, run_offsets, M, W):
     ``W = [Q | Qs]`` float64 [Ttot, 2k] on the device -> ``(ah float64 [R, 2k, Mp], s0, s1 float64 [R, Mp])`` in one workspace
     (the next call on the stream reuses it)."""
     _require_cuda(planes, run_offsets, W)
-    if planes.dim() != 2 or planes.shape[1] != plane_stride(M) or planes.dtype != torch.float32 or not planes.is_contiguous():
-        raise _lib.ChebgcnError('glm_project_ar1: planes must be contiguous float32 [Ttot, plane_stride(M)]')
-    Ttot, Mp = int(planes.shape[0]), int(planes.shape[1])
-    R = int(run_offsets.numel()) - 1
-    if run_offsets.dtype != torch.int64 or run_offsets.dim() != 1 or R < 1 or not run_offsets.is_contiguous():
-        raise _lib.ChebgcnError('glm_project_ar1: run_offsets must be a contiguous int64 vector of R + 1 entries')
+    Ttot, Mp, R = _staged_runs(planes, run_offsets, M, 'glm_project_ar1')
     if W.dim() != 2 or W.shape[1] % 2:
         raise _lib.ChebgcnError('glm_project_ar1: W must be float64 [Ttot, 2k]')
     k = int(W.shape[1]) // 2
@@ -853,27 +856,7 @@ def glm_finish_ar1(ah, s0, s1, planes, W, run_offsets, rank, D, E, U, M, rho=Non
     _dense(rank, torch.int32, (R,), 'glm_finish_ar1: rank')
     _dense(D, torch.float64, (R, k, k), 'glm_finish_ar1: D')
     _dense(E, torch.float64, (R, k, k), 'glm_finish_ar1: E')
-    if U.dim() != 3:
-        raise _lib.ChebgcnError('glm_finish_ar1: U must be float64 [R, C, k]')
-    C_ = int(U.shape[1])
-    _dense(U, torch.float64, (R, C_, k), 'glm_finish_ar1: U')
-    P = 0
-    beta = None
-    if B is not None:
-        if B.dim() != 3:
-            raise _lib.ChebgcnError('glm_finish_ar1: B must be float64 [R, P, k]')
-        P = int(B.shape[1])
-        _dense(B, torch.float64, (R, P, k), 'glm_finish_ar1: B')
-        beta = torch.empty((R, P, Mp), dtype=torch.float32, device=ah.device)
-    e64 = v64 = None
-    if out64 is not None:
-        e64, v64 = out64
-        _require_cuda(e64, v64)
-        _dense(e64, torch.float64, (R, C_, Mp), 'glm_finish_ar1: out64[0]')
-        _dense(v64, torch.float64, (R, C_, Mp), 'glm_finish_ar1: out64[1]')
-    e32 = v32 = t32 = None
-    if want32:
-        e32, v32, t32 = (torch.empty((R, C_, Mp), dtype=torch.float32, device=ah.device) for _ in range(3))
+    C_, P, e64, v64, e32, v32, t32, beta = _finish_tables('glm_finish_ar1', R, k, Mp, U, B, out64, want32, ah.device)
     rho_out = torch.empty((R, Mp), dtype=torch.float32, device=ah.device)
     flops = 2.0 * R * Mp * (k * k * k / 6.0 + k * k * (1 + C_) / 2.0 + k * (4 + P))
     _lib.check(_launch('glm_finish_ar1', 8.0 * R * Mp * (2 * k + 2 + 2 * C_) + 4.0 * R * Mp * (1 + P), flops,
@@ -909,15 +892,11 @@ def glm_trials(planes, run_offsets, M, Z, trial_offsets, a, yy, q_rank, own, ran
     ``(beta, variance, t)`` float32 [N, Mp], None for what ``outputs`` does not name.  The byte model counts every panel over
     every run's rows, which is exact when the runs have equally many trials."""
     _require_cuda(planes, run_offsets, Z, trial_offsets, a, yy, q_rank, own, rank, w, F)
-    if planes.dim() != 2 or planes.shape[1] != plane_stride(M) or planes.dtype != torch.float32 or not planes.is_contiguous():
-        raise _lib.ChebgcnError('glm_trials: planes must be contiguous float32 [Ttot, plane_stride(M)]')
-    Ttot, Mp = int(planes.shape[0]), int(planes.shape[1])
-    R = int(run_offsets.numel()) - 1
-    if R < 1 or Z.dim() != 2 or a.dim() != 3 or w.dim() != 2:
-        raise _lib.ChebgcnError('glm_trials: run_offsets [R + 1], Z [Ttot, nmax], a [R, k, Mp] and w [N, G1] are expected')
+    Ttot, Mp, R = _staged_runs(planes, run_offsets, M, 'glm_trials')
+    if Z.dim() != 2 or a.dim() != 3 or w.dim() != 2:
+        raise _lib.ChebgcnError('glm_trials: Z [Ttot, nmax], a [R, k, Mp] and w [N, G1] are expected')
     nmax, k = int(Z.shape[1]), int(a.shape[1])
     N, G1 = int(w.shape[0]), int(w.shape[1])
-    _dense(run_offsets, torch.int64, (R + 1,), 'glm_trials: run_offsets')
     _dense(trial_offsets, torch.int64, (R + 1,), 'glm_trials: trial_offsets')
     _dense(Z, torch.float64, (Ttot, nmax), 'glm_trials: Z')
     _dense(a, torch.float64, (R, k, Mp), 'glm_trials: a')

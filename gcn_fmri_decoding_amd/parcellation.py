@@ -13,13 +13,11 @@ rounded division.  ``reduce_host`` performs the same operations in float32 NumPy
 """
 import numpy as np
 
+from .runs import cuda_device, is_tensor
+
 MODES = ('mean', 'sum')
 RMAX = 65535
 CHUNK_BYTES = 256 << 20         # a slice of host rows on the device at most
-
-
-def _is_tensor(a):
-    return type(a).__module__.split('.')[0] == 'torch'
 
 
 class Parcellation:
@@ -102,7 +100,7 @@ class Parcellation:
         runs, single = self._runs(series)
         out = []
         for r in runs:
-            x = r.detach().cpu().numpy() if _is_tensor(r) else np.asarray(r)
+            x = r.detach().cpu().numpy() if is_tensor(r) else np.asarray(r)
             x = x.astype(np.float32, copy=False)
             with np.errstate(invalid='ignore', over='ignore'):
                 acc = self._sum_in_order(x, self.weights)
@@ -117,12 +115,12 @@ class Parcellation:
 
     # ---- the device -------------------------------------------------------------------------------------------------------------
     def _runs(self, series):
-        single = (isinstance(series, np.ndarray) or _is_tensor(series)) and series.ndim == 2
+        single = (isinstance(series, np.ndarray) or is_tensor(series)) and series.ndim == 2
         runs = [series] if single else list(series)
         if not runs:
             raise ValueError('Parcellation: no runs')
         for r in runs:
-            if not (isinstance(r, np.ndarray) or _is_tensor(r)):
+            if not (isinstance(r, np.ndarray) or is_tensor(r)):
                 raise ValueError('Parcellation: a run must be a NumPy array or a torch tensor, not %s' % type(r).__name__)
             if r.ndim != 2 or r.shape[1] != self.V:
                 raise ValueError('Parcellation: every run must be [T, %d], got shape %r' % (self.V, tuple(r.shape)))
@@ -158,11 +156,7 @@ class Parcellation:
         runs, single = self._runs(series)
         import torch
         from . import ops
-        if device is None:
-            on_dev = [r.device for r in runs if _is_tensor(r) and r.is_cuda]
-            dev = on_dev[0] if on_dev else torch.device('cuda', torch.cuda.current_device())
-        else:
-            dev = torch.device(device)
+        dev = cuda_device(device, next((r for r in runs if is_tensor(r) and r.is_cuda), None))
         m = MODES.index(mode)
         out = []
         with torch.cuda.device(dev):
@@ -170,7 +164,7 @@ class Parcellation:
             for r in runs:
                 T = int(r.shape[0])
                 res = torch.empty((T, self.R), dtype=torch.float32, device=dev)
-                if _is_tensor(r) and r.is_cuda:
+                if is_tensor(r) and r.is_cuda:
                     x = r.to(dev, torch.float32)
                     if x.stride(1) != 1 and self.V > 1:
                         x = x.contiguous()
@@ -178,7 +172,7 @@ class Parcellation:
                 else:
                     for t0 in range(0, T, chunk_rows):
                         piece = r[t0:t0 + chunk_rows]
-                        if _is_tensor(piece):
+                        if is_tensor(piece):
                             x = piece.to(torch.float32).contiguous().to(dev)
                         else:
                             x = torch.as_tensor(np.ascontiguousarray(piece, dtype=np.float32)).to(dev)
@@ -191,7 +185,7 @@ class Parcellation:
         ``occlusion_maps``, ``gradcam_maps``) -> ``[V]`` or ``[B, V]`` float32 with ``out[b, v] = maps[b, region_of[v]]`` and
         ``fill`` on the background.  A NumPy array gives a NumPy array (indexing on the host), a device tensor a device tensor
         (chebgcn_parcel_expand); a host tensor comes back as a host tensor."""
-        tensor = _is_tensor(maps)
+        tensor = is_tensor(maps)
         if not tensor:
             maps = np.asarray(maps)
         if maps.ndim not in (1, 2) or maps.shape[-1] != self.R:

@@ -44,7 +44,8 @@ import types
 import numpy as np
 import scipy.sparse as sp
 
-from .glm import _host_array, _is_tensor
+from . import runs as _runs
+from .runs import host_array, is_tensor
 
 CMAX, NMAX, GMAX = 32, 65535, 1 << 20           # chebgcn_searchlight_query(3), (5), (7)
 SCORES_MAX_BYTES = 1 << 31                      # scores=True is refused beyond 2 GiB of float64 [S, classes, U]
@@ -101,7 +102,7 @@ def _neighbourhoods(nb, M, who):
         pat = sp.csr_matrix(nb, copy=True)
         pat.data = np.ones(pat.data.shape, np.int8)             # values are ignored: a stored zero is a member
     else:
-        tab = nb.detach().cpu().numpy() if _is_tensor(nb) else np.asarray(nb)
+        tab = nb.detach().cpu().numpy() if is_tensor(nb) else np.asarray(nb)
         if tab.ndim != 2 or tab.shape[0] != M or tab.shape[1] < 1 or tab.dtype.kind not in 'iu':
             raise ValueError('%s: neighbourhoods must be a SciPy sparse pattern [U, M] or an integer table [M = %d, k], got %s %r'
                              % (who, M, tab.dtype, tuple(tab.shape)))
@@ -121,7 +122,7 @@ def _neighbourhoods(nb, M, who):
 
 
 def _vector(v, S, name, who):
-    a = np.asarray(v.detach().cpu().numpy() if _is_tensor(v) else v)
+    a = np.asarray(v.detach().cpu().numpy() if is_tensor(v) else v)
     if a.ndim != 1 or a.shape[0] != S:
         raise ValueError('%s: %s must hold one entry per sample ([S = %d]), got shape %r' % (who, name, S, a.shape))
     return a
@@ -129,7 +130,7 @@ def _vector(v, S, name, who):
 
 def _patterns(samples, who):
     """``(X, tensor, S, M)`` of the ``[S, M]`` patterns, shape and dtype checked."""
-    tensor = _is_tensor(samples)
+    tensor = is_tensor(samples)
     X = samples if tensor else np.asarray(samples)
     if X.ndim != 2 or X.shape[0] < 2 or X.shape[1] < 1:
         raise ValueError('%s: samples must be [S >= 2, M >= 1], got shape %r' % (who, tuple(X.shape)))
@@ -169,24 +170,12 @@ def _coded_labels(labels, S, classes, limits, who):
 
 def _group_keys(groups, S, who):
     """``(keys in order of first appearance, gidx int64 [S])``; ``None``: one group."""
-    if groups is None:
-        groups = [0] * S
-    elif _is_tensor(groups) or isinstance(groups, np.ndarray):
+    if is_tensor(groups) or isinstance(groups, np.ndarray):
         groups = _vector(groups, S, 'groups', who).tolist()
-    groups = list(groups)
-    if len(groups) != S:
-        raise ValueError('%s: groups must hold one key per sample (%d samples, %d keys)' % (who, S, len(groups)))
-    keys, index = [], {}
+    _, keys, members = _runs.group_keys(groups, S, who, 'sample')
     gidx = np.empty(S, np.int64)
-    for s, g in enumerate(groups):
-        try:
-            hash(g)
-        except TypeError:
-            raise ValueError('%s: group key %r of sample %d is not hashable' % (who, g, s)) from None
-        if g not in index:
-            index[g] = len(keys)
-            keys.append(g)
-        gidx[s] = index[g]
+    for g, m in enumerate(members):
+        gidx[m] = g
     return keys, gidx
 
 
@@ -341,7 +330,7 @@ def searchlight_host(samples, labels, neighbourhoods, folds, groups=None, within
     _solver_flag(return_solver, a, who)
     if a.svc and return_scale:
         raise ValueError("%s: return_scale is not served with classifier='svc' (the device agrees bit for bit)" % who)
-    X = _host_array(a.X, who).astype(np.float64)
+    X = host_array(a.X, who).astype(np.float64)
     S, C, U, G = a.S, len(a.classes), a.U, len(a.keys)
     sc = np.empty((S, C, U))
     scale = np.empty((S, C, U)) if return_scale else None
@@ -652,15 +641,6 @@ def _result(a, correct, sc, pred, as_tensor):
                              None if sc is None else sc.cpu().numpy(), None if pred is None else pred.cpu().numpy())
 
 
-def _device(device, like=None):
-    import torch
-    if device is not None:
-        return torch.device(device)
-    if like is not None and like.is_cuda:
-        return like.device
-    return torch.device('cuda', torch.cuda.current_device())
-
-
 def _staged(a, order, dev, who):
     """``_transposed`` of the checked patterns on ``dev``, samples in ``order``; a tensor's values are checked here."""
     import torch
@@ -669,7 +649,7 @@ def _staged(a, order, dev, who):
         if not bool(torch.isfinite(X).all()):
             raise ValueError('%s: samples hold non-finite values' % who)
     else:
-        X = torch.as_tensor(a.X).to(dev)                        # (float32 and finite: the caller's _host_array)
+        X = torch.as_tensor(a.X).to(dev)                        # (float32 and finite: the caller's host_array)
     return _transposed(X, order, dev)
 
 
@@ -790,8 +770,8 @@ def searchlight(samples, labels, neighbourhoods, folds, groups=None, within=True
                loss=loss, tol=tol, max_iter=max_iter)
     _solver_flag(return_solver, a, who)
     if not a.tensor:
-        a = a._replace(X=_host_array(a.X, who))                 # non-finite values: before the device is touched
-    return _searchlight(a, _device(device, a.X if a.tensor else None), scores, predictions, batch_centres, a.tensor, who,
+        a = a._replace(X=host_array(a.X, who))                  # non-finite values: before the device is touched
+    return _searchlight(a, _runs.cuda_device(device, a.X), scores, predictions, batch_centres, a.tensor, who,
                         bool(return_solver))
 
 
@@ -826,14 +806,7 @@ def _events_plan(lengths, label_runs, target_name, block_dura, groups, folds, wi
         raise ValueError('%s: within must be True or False, got %r' % (who, within))
     if not hasattr(label_runs, '__len__') or isinstance(label_runs, str) or len(label_runs) != R:
         raise ValueError('%s: label_runs must hold one sequence of condition names per run (%d runs)' % (who, R))
-    groups = [0] * R if groups is None else list(groups)
-    if len(groups) != R:
-        raise ValueError('%s: groups must hold one key per run (%d runs, %d keys)' % (who, R, len(groups)))
-    for r, g in enumerate(groups):
-        try:
-            hash(g)
-        except TypeError:
-            raise ValueError('%s: group key %r of run %d is not hashable' % (who, g, r)) from None
+    groups = _runs.group_keys(groups, R, who)[0]
     if folds is None:
         folds = default_folds(groups, within)
     folds = np.asarray(folds)
@@ -855,26 +828,6 @@ def _events_plan(lengths, label_runs, target_name, block_dura, groups, folds, wi
     return np.ascontiguousarray(idx, np.int64), labels, tg, tf, list(ev.classes)
 
 
-def _stage(runs, M, dev, who):
-    """The runs (tensors, or float32 arrays already checked) as ``[Ttot, plane_stride(M)]`` float32 planes on the device, as
-    ``first_level`` stages them."""
-    import torch
-    from . import _lib
-    Mp = _lib.plane_stride(M)
-    offs = np.concatenate([[0], np.cumsum([int(r.shape[0]) for r in runs])])
-    if any(_is_tensor(r) for r in runs):
-        planes = torch.zeros((int(offs[-1]), Mp), dtype=torch.float32, device=dev)
-        for y, o in zip(runs, offs):
-            planes[o:o + y.shape[0], :M] = (y.detach() if _is_tensor(y) else torch.as_tensor(y)).to(dev, torch.float32)
-        if not bool(torch.isfinite(planes).all()):
-            raise ValueError('%s: series hold non-finite values' % who)
-        return planes
-    staged = np.zeros((int(offs[-1]), Mp), np.float32)
-    for y, o in zip(runs, offs):
-        staged[o:o + y.shape[0], :M] = y
-    return torch.as_tensor(staged).to(dev)
-
-
 def _event_patterns(planes, idx, M):
     """One float32 pattern per trial, ``[S, M]``: the mean of the trial's rows of the staged planes
     (chebgcn_gather_windows_indexed with one channel and ``fold`` = the rows of a trial; ``events.host_windows`` restates it)."""
@@ -888,15 +841,8 @@ def _from_events(runs, label_runs, target_name, block_dura, groups, folds, withi
     of ``_events_plan`` (``folds`` as there, or a function of the number of runs); the caller's ``check(stand_in, labels, folds,
     groups, classes)`` on a stand-in of the patterns' shape, which do not exist yet; staging and the patterns' gather.  Returns
     ``(the checked arguments with the patterns, the device, whether every run came as a tensor)``."""
-    single = isinstance(runs, np.ndarray) or _is_tensor(runs)
-    if single and runs.ndim != 2:
-        raise ValueError('%s: a run must be [T, M], got shape %r' % (who, tuple(runs.shape)))
-    runs = [runs] if single else [r if _is_tensor(r) else np.asarray(r) for r in runs]
-    if not runs or any(r.ndim != 2 for r in runs):
-        raise ValueError('%s: runs must be a non-empty list of [T, M] arrays' % who)
-    M = int(runs[0].shape[1])
-    if M < 1 or any(int(r.shape[1]) != M for r in runs):
-        raise ValueError('%s: runs differ in the number of vertices (or have none)' % who)
+    malformed = 'runs must be a non-empty list of [T, M] arrays'
+    runs, single, M, as_tensor = _runs.as_runs(runs, who, none=malformed, shape=malformed)
     if any(k in kw for k in refused[0]):
         raise ValueError(refused[1] % who)
     match_kw = {k: kw.pop(k) for k in _MATCH_KW if k in kw}
@@ -909,17 +855,16 @@ def _from_events(runs, label_runs, target_name, block_dura, groups, folds, withi
                                                 folds(len(runs)) if callable(folds) else folds, within, match_kw, who)
     device = kw.pop('device', None)
     a = check(np.zeros((idx.shape[0], M), np.float32), labels, tf, tg, classes)
-    runs = [r if _is_tensor(r) else _host_array(r, who) for r in runs]        # non-finite values: before the device is touched
+    dev, planes = _runs.stage(runs, M, device, who)             # non-finite values: before the device is touched
     import torch
-    dev = _device(device, next((r for r in runs if _is_tensor(r) and r.is_cuda), None))
     with torch.cuda.device(dev):
-        X = _event_patterns(_stage(runs, M, dev, who), torch.as_tensor(idx).to(dev), M)
-    return a._replace(X=X, tensor=True), dev, all(_is_tensor(r) for r in runs)
+        X = _event_patterns(planes, torch.as_tensor(idx).to(dev), M)
+    return a._replace(X=X, tensor=True), dev, as_tensor
 
 
 def searchlight_events(runs, label_runs, target_name, block_dura, neighbourhoods, groups=None, folds=None, within=True, **kw):
     """``searchlight`` on the trials of an event design: ``runs`` (one ``[T, M]`` array or a list; NumPy or torch) are staged
-    as ``[Ttot, plane_stride(M)]`` planes as ``first_level`` stages them, ``match_events(label_runs, target_name, block_dura)``
+    as ``[Ttot, plane_stride(M)]`` planes (``runs.stage``, as for ``first_level``), ``match_events(label_runs, target_name, block_dura)``
     cuts the trials (its keywords ``start_trial``, ``hrf_delay``, ``flag_event``, ``rest`` pass through; ``TRstep`` does not:
     the pattern of a trial is the float32 mean of its ``block_dura <= 16`` rows, formed on the device by
     ``ops.gather_windows_indexed(..., C=1, fold=block_dura)`` -- ``events.host_windows(run, index, fold=block_dura)`` restates
@@ -959,7 +904,7 @@ class RDMResult(collections.namedtuple('RDMResult', 'rdm shrinkage classes pairs
     def square(self, g=0):
         """The RDMs of group ``g`` as symmetric matrices with a zero diagonal: [U, C, C]."""
         C, r = len(self.classes), self.rdm[g]
-        if _is_tensor(r):
+        if is_tensor(r):
             import torch
             out = torch.zeros((r.shape[1], C, C), dtype=r.dtype, device=r.device)
             a, b = (torch.as_tensor(self.pairs[:, i]).to(r.device) for i in (0, 1))
@@ -1032,7 +977,7 @@ def crossnobis_host(samples, labels, neighbourhoods, partitions, groups=None, cl
     import scipy.linalg
     who = 'crossnobis_host'
     a = _check_rdm(samples, labels, neighbourhoods, partitions, groups, classes, shrinkage, batch_centres, who, limits=False)
-    X = _host_array(a.X, who).astype(np.float64)
+    X = host_array(a.X, who).astype(np.float64)
     C, U, G = len(a.classes), a.U, len(a.keys)
     pairs = _pairs(C)
     rdm = np.zeros((G, len(pairs), U))
@@ -1098,11 +1043,11 @@ def compare_rdms(rdm, models, method='pearson'):
     who = 'compare_rdms'
     if method not in ('pearson', 'cosine'):
         raise ValueError("%s: method must be 'pearson' or 'cosine', got %r" % (who, method))
-    tensor = _is_tensor(rdm)
+    tensor = is_tensor(rdm)
     x = rdm if tensor else np.asarray(rdm, np.float64)
     if x.ndim != 3 or x.shape[1] < 1:
         raise ValueError('%s: rdm must be [G, npairs, U], got shape %r' % (who, tuple(x.shape)))
-    mod = np.asarray(models.detach().cpu().numpy() if _is_tensor(models) else models, np.float64)
+    mod = np.asarray(models.detach().cpu().numpy() if is_tensor(models) else models, np.float64)
     if mod.ndim != 2 or mod.shape[0] < 1 or mod.shape[1] != x.shape[1] or not np.isfinite(mod).all():
         raise ValueError('%s: models must be finite [Q >= 1, npairs = %d], got shape %r' % (who, x.shape[1], mod.shape))
     if tensor:
@@ -1211,8 +1156,8 @@ def crossnobis(samples, labels, neighbourhoods, partitions, groups=None, classes
     who = 'crossnobis'
     a = _check_rdm(samples, labels, neighbourhoods, partitions, groups, classes, shrinkage, batch_centres, who)
     if not a.tensor:
-        a = a._replace(X=_host_array(a.X, who))                 # non-finite values: before the device is touched
-    return _crossnobis(a, _device(device, a.X if a.tensor else None), batch_centres, a.tensor, who)
+        a = a._replace(X=host_array(a.X, who))                  # non-finite values: before the device is touched
+    return _crossnobis(a, _runs.cuda_device(device, a.X), batch_centres, a.tensor, who)
 
 
 def crossnobis_events(runs, label_runs, target_name, block_dura, neighbourhoods, groups=None, **kw):

@@ -29,6 +29,7 @@ import torch
 
 from . import ops
 from .decode import check_run, check_table, run_list, window_starts    # (the validation shared with decode_series)  # noqa: F401
+from .runs import AUG_KEY, AUG_MUL1, AUG_MUL2, AUG_WINDOW, aug_draw     # (the generator ``stats`` draws with as well)  # noqa: F401
 
 
 def _is_int(v):
@@ -105,29 +106,9 @@ def jitter_rows(rows, lo, hi, jitter, rng):
     return np.clip(rows + d, lo, hi)
 
 
-# ---- the augmentation generator (include/chebgcn.h), restated in NumPy: uint32 values carried in uint64 and masked ----------------
-AUG_MUL1, AUG_MUL2, AUG_KEY, AUG_WINDOW, AUG_SHIFT_DRAW = 0x7FEB352D, 0x846CA68B, 0x9E3779B9, 0x85EBCA6B, 0xFFFFFFFF
+# ---- what the augmentation draws from ``runs.aug_draw``, the generator of include/chebgcn.h restated in NumPy ----------------------
+AUG_SHIFT_DRAW = 0xFFFFFFFF
 AUG_COPIES_MAX = 64
-_U32 = np.uint64(0xFFFFFFFF)
-
-
-def _aug_fin(x):
-    x = x ^ (x >> np.uint64(16))
-    x = (x * np.uint64(AUG_MUL1)) & _U32
-    x = x ^ (x >> np.uint64(15))
-    x = (x * np.uint64(AUG_MUL2)) & _U32
-    return x ^ (x >> np.uint64(16))
-
-
-def aug_draw(seed, refill, i, d):
-    """``chebgcn_aug_draw``: 32 uniform bits (in a uint64 array) for augmented windows ``i`` and draw indices ``d`` (arrays that
-    broadcast), a stateless function of ``(seed, refill, i, d)``."""
-    i = np.asarray(i, np.uint64) & _U32
-    d = np.asarray(d, np.uint64) & _U32
-    a = _aug_fin((_aug_fin(np.uint64(int(seed) & 0xFFFFFFFF)) + np.uint64(int(refill) & 0xFFFFFFFF)) & _U32)
-    k0 = _aug_fin((a + i) & _U32)
-    k1 = _aug_fin(((a ^ np.uint64(AUG_KEY)) + ((i * np.uint64(AUG_WINDOW)) & _U32)) & _U32)
-    return _aug_fin(_aug_fin((k0 + d) & _U32) ^ k1)
 
 
 def drop_vertices(seed, refill, i, D, M):

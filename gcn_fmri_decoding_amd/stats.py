@@ -33,6 +33,8 @@ import numpy as np
 import scipy.sparse as sp
 from scipy.sparse import csgraph
 
+from .runs import aug_draw, cuda_device, is_tensor
+
 CHUNK_BYTES = 256 << 20         # the t maps and the labelling state of one batch of permutations on the device, at most
 ARM = 0                         # chebgcn_cluster_enhance's arm: 0 automatic; 2 forces the streamed arm (measurements, tests)
 HOST_CHUNK = 1 << 22            # (permutation, vertex) pairs of one slice of the host restatement
@@ -43,9 +45,6 @@ PBMAX = 65535                   # permutations of one launch
 STATS = ('max', 'extent', 'tfce')
 _MODE = {'max': 0, 'extent': 1, 'tfce': 2}
 
-_MUL1, _MUL2, _KEY, _WINDOW = 0x7FEB352D, 0x846CA68B, 0x9E3779B9, 0x85EBCA6B      # chebgcn_aug_draw (include/chebgcn.h)
-_U32 = np.uint64(0xFFFFFFFF)
-
 MapTestResult = collections.namedtuple('MapTestResult', 't stat p null labels step n_perm exact seed')
 MapTestResult.__doc__ = """What ``map_test`` returns.  ``t`` float32 [C, M] the observed t map (of the negated maps for
 ``tail=-1``); ``stat`` float64 [C, M] the observed statistic; ``p`` float64 [C, M] family-wise corrected p-values (>= 1 / n_perm);
@@ -53,28 +52,6 @@ MapTestResult.__doc__ = """What ``map_test`` returns.  ``t`` float32 [C, M] the 
 below the threshold), else None; ``step`` the TFCE step per class (float64 [C], None for the other statistics); ``n_perm`` the
 permutations actually run; ``exact`` whether they enumerate all sign vectors; ``seed``.  For ``[S, M]`` input the class axis is
 dropped (``step`` a float)."""
-
-
-def _is_tensor(a):
-    return type(a).__module__.split('.')[0] == 'torch'
-
-
-def _fin(x):
-    x = x ^ (x >> np.uint64(16))
-    x = (x * np.uint64(_MUL1)) & _U32
-    x = x ^ (x >> np.uint64(15))
-    x = (x * np.uint64(_MUL2)) & _U32
-    return x ^ (x >> np.uint64(16))
-
-
-def _draw(seed, i, d):
-    """``chebgcn_aug_draw(seed, refill=0, i, d)`` (``series.aug_draw`` is the same function)."""
-    i = np.asarray(i, np.uint64) & _U32
-    d = np.asarray(d, np.uint64) & _U32
-    a = _fin(_fin(np.uint64(int(seed) & 0xFFFFFFFF)))
-    k0 = _fin((a + i) & _U32)
-    k1 = _fin(((a ^ np.uint64(_KEY)) + ((i * np.uint64(_WINDOW)) & _U32)) & _U32)
-    return _fin(_fin((k0 + d) & _U32) ^ k1)
 
 
 def sign_flips(S, n_perm, seed):
@@ -88,7 +65,8 @@ def sign_flips(S, n_perm, seed):
     if S < 62 and (1 << S) <= n_perm:
         neg = (np.arange(1 << S, dtype=np.int64)[:, None] >> np.arange(S, dtype=np.int64)[None, :]) & 1
         return (1 - 2 * neg).astype(np.int8), True
-    neg = (_draw(seed, np.arange(n_perm, dtype=np.uint64)[:, None], np.arange(S, dtype=np.uint64)[None, :]) >> np.uint64(31)).astype(np.int64)
+    neg = aug_draw(seed, 0, np.arange(n_perm, dtype=np.uint64)[:, None], np.arange(S, dtype=np.uint64)[None, :]) >> np.uint64(31)
+    neg = neg.astype(np.int64)
     neg[0] = 0
     return (1 - 2 * neg).astype(np.int8), False
 
@@ -123,7 +101,7 @@ _Plan = collections.namedtuple('_Plan', 'x single S C M ptr idx stat tail n_perm
 
 def _plan(maps, A, stat, n_perm, tail, threshold, step, E, H, seed):
     """Everything checked before any work (and before the device is touched); x: float32 host array [C, S, M], tail applied."""
-    if _is_tensor(maps):
+    if is_tensor(maps):
         if str(maps.dtype) != 'torch.float32':
             raise ValueError('map_test: maps must be float32, not %s' % maps.dtype)
         x = maps.detach().cpu().numpy()
@@ -318,13 +296,6 @@ def map_test_host(maps, A, stat='tfce', n_perm=5000, tail=0, threshold=None, ste
 
 # ---- the device ---------------------------------------------------------------------------------------------------------------------
 
-def _device_of(maps, device):
-    import torch
-    if device is None:
-        return maps.device if (_is_tensor(maps) and maps.is_cuda) else torch.device('cuda', torch.cuda.current_device())
-    return torch.device(device)
-
-
 def _run_device(pl, dev, P, exact, t_of):
     """The permutation loop on the device: per class the observed map, the TFCE step it sets, then the null in batches of
     permutations whose t maps and labelling state fit CHUNK_BYTES, the height tables grown when a batch needs more.
@@ -414,7 +385,7 @@ def map_test(maps, A, stat='tfce', n_perm=5000, tail=0, threshold=None, step=Non
     pl = _plan(maps, A, stat, n_perm, tail, threshold, step, E, H, seed)
     import torch
     from . import ops
-    dev = _device_of(maps, device)
+    dev = cuda_device(device, maps)
     exact = pl.S < 62 and (1 << pl.S) <= pl.n_perm
     P = (1 << pl.S) if exact else pl.n_perm
     bits = None
@@ -446,16 +417,6 @@ enumerates the permutations of a design, it draws ``n_perm`` of them (the identi
 _Design = collections.namedtuple('_Design', 'r dof Uf u unorm2 X Qz rows')
 
 
-def _draw_refill(seed, refill, i, d):
-    """``chebgcn_aug_draw(seed, refill, i, d)`` (``series.aug_draw``); ``_draw`` is its ``refill = 0``."""
-    i = np.asarray(i, np.uint64) & _U32
-    d = np.asarray(d, np.uint64) & _U32
-    a = _fin((_fin(np.uint64(int(seed) & 0xFFFFFFFF)) + np.uint64(int(refill) & 0xFFFFFFFF)) & _U32)
-    k0 = _fin((a + i) & _U32)
-    k1 = _fin(((a ^ np.uint64(_KEY)) + ((i * np.uint64(_WINDOW)) & _U32)) & _U32)
-    return _fin(_fin((k0 + d) & _U32) ^ k1)
-
-
 def _blocks(blocks, S):
     """The members of every block, ascending (one block of everybody for None)."""
     if blocks is None:
@@ -483,13 +444,13 @@ def permutations(S, n_perm, seed, blocks=None, flips=False):
     for m in _blocks(blocks, S):
         a = np.tile(m, (P, 1))
         for i in range(m.size - 1, 0, -1):
-            k = ((_draw_refill(seed, 0, p, np.uint64(m[i])) * np.uint64(i + 1)) >> np.uint64(32)).astype(np.int64)
+            k = ((aug_draw(seed, 0, p, np.uint64(m[i])) * np.uint64(i + 1)) >> np.uint64(32)).astype(np.int64)
             ai = a[:, i].copy()
             a[:, i] = a[ar, k]
             a[ar, k] = ai
         rows[:, m] = a
     if flips:
-        neg = _draw_refill(seed, 1, p[:, None], np.arange(S, dtype=np.uint64)[None, :]) >> np.uint64(31)
+        neg = aug_draw(seed, 1, p[:, None], np.arange(S, dtype=np.uint64)[None, :]) >> np.uint64(31)
         rows |= (neg << np.uint64(31)).astype(np.uint32)
     rows[0] = np.arange(S, dtype=np.uint32)
     return rows
@@ -639,7 +600,7 @@ def design_test(maps, A, design, contrast, stat='tfce', n_perm=5000, tail=0, blo
     ds = _design(design, contrast, blocks, flips, pl.S, pl.n_perm, pl.seed)
     import torch
     from . import ops
-    dev = _device_of(maps, device)
+    dev = cuda_device(device, maps)
     shared = []
 
     def t_of(c):

@@ -20,6 +20,7 @@ covariance ill-conditioned (there: effect 4.2e-13, t 3.9e-13, variance 9.4e-14);
 import numpy as np
 
 from gcn_fmri_decoding_amd import glm
+from gcn_fmri_decoding_amd.runs import host_array
 
 EPS32 = 2.0 ** -23
 MEASURED = 9.1e-12          # the sums statement against the host restatement, largest over the device cases (see above)
@@ -143,7 +144,7 @@ def sums_statement(runs, designs, contrasts=None, groups=None, rho=None):
     pl = glm._plan(runs, designs, contrasts, groups, 'sums_statement', limits=False)
     eff, var, bs, rhos, raws = [], [], [], [], []
     for y, tb in zip(pl.runs, pl.tables):
-        y = glm._host_array(y, 'sums_statement').astype(np.float64)
+        y = host_array(y, 'sums_statement').astype(np.float64)
         Q, k, T = tb.Q, tb.rank, tb.T
         Qs = np.zeros_like(Q)
         Qs[1:] += Q[:-1]

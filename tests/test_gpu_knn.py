@@ -415,6 +415,20 @@ def test_connectivity_graph_of_at_most_eight_time_points_runs_the_direct_arm():
     assert (idx != np.arange(M)[:, None]).all()
 
 
+def test_connectivity_graph_arrays_tensors_and_mixed_agree_to_the_bit():
+    """Runs of 2, 3 and 9 rows at M = 33 (one vertex beyond a plane stride of 32), staged from arrays, from device tensors and
+    from both."""
+    M, k = 33, 4
+    rs = np.random.RandomState(37)
+    runs = [rs.randn(T, M).astype(np.float32) for T in (2, 3, 9)]
+    on_device = [torch.as_tensor(r).to(DEV) for r in runs]
+    d, idx = graph.connectivity_graph(runs, k=k, device=DEV)
+    assert d.shape == (M, k) and np.isfinite(d).all() and (idx != np.arange(M)[:, None]).all()
+    for given in (on_device, [runs[0], on_device[1], runs[2]]):
+        d2, idx2 = graph.connectivity_graph(given, k=k, device=DEV)
+        assert np.array_equal(d2, d) and np.array_equal(idx2, idx)
+
+
 def test_series_normalise_refuses_mismatched_arguments():
     M = 70
     p = torch.zeros((10, ops.plane_stride(M)), device=DEV)

@@ -20,6 +20,7 @@ import scipy.sparse as sp
 
 from conftest import record_measured
 from gcn_fmri_decoding_amd import _lib, events, graph, searchlight as sl
+from gcn_fmri_decoding_amd.runs import stage
 
 pytestmark = pytest.mark.gpu
 
@@ -280,7 +281,7 @@ def test_searchlight_events_end_to_end(geo):
     want = np.concatenate([events.host_windows(runs[r], i, fold=dura)[:, :, 0] for r, i in zip(ev.kept, ev.index)])
     idx, lab, tg, tf, classes = sl._events_plan([T] * 4, labels, ['a', 'b'], dura, subjects, None, True, {})
     dev = torch.device('cuda')
-    planes = sl._stage(runs, M, dev, 't')
+    planes = stage(runs, M, dev, 't')[1]
     assert planes.shape == (4 * T, _lib.plane_stride(M)) and not planes[:, M:].any()
     planes[:, M:] = float('nan')                                # the pad of the staged planes never reaches a pattern
     got = sl._event_patterns(planes, torch.as_tensor(idx).to(dev), M)
