@@ -397,7 +397,9 @@ perm_data_kernel(const float* __restrict__ x, const int32_t* __restrict__ perm,
     if (threadIdx.x < 64) {
         const int i = i0 + threadIdx.x;
         const int node = i < M ? (perm ? perm[i] : i) : N;
-        nodes[threadIdx.x] = node < N ? node : N;
+        // outside [0, N) -- a fake vertex of the coarsening or a negative entry --: none.  Nothing read from memory is an
+        // address unchecked
+        nodes[threadIdx.x] = (unsigned)node < (unsigned)N ? node : N;
     }
     __syncthreads();
     // four gathers in flight per thread (one load, one LDS store per iteration compiles to a full wait per element,

@@ -362,7 +362,10 @@ int chebgcn_fused_layer_bwd_x(const chebgcn_graph* g, const float* dout, const u
  * fp32 cast and batch gather of fit() (models_gcn.py:138-146):
  *   out[s][f][i] = perm[i] < N ? x[sample[s]][perm[i]][f] : 0,   i < M
  * x: [S_total][N][F] row layout (device); perm: int32 [M] (device); sample: int32 [S]
- * (device) or NULL for the identity; out: [S][F][Mp(M)].
+ * (device) or NULL for the identity; out: [S][F][Mp(M)], zero in the pad [M, Mp).
+ * perm[i] outside [0, N) gives 0: the coarsening's fake vertices (perm[i] >= N) and negative entries alike; no entry of
+ * perm becomes an address unchecked.  sample[s] must lie in [0, S_total): that stays the caller's duty (the entry is not
+ * given S_total).  perm NULL: the identity, which needs M == N.
  * to_plane / from_plane convert between the reference's [B][M][F] and plane layout. */
 int chebgcn_perm_data(const float* x, const int32_t* perm, const int32_t* sample, float* out,
                       int S, int N, int M, int F, chebgcn_stream stream);

@@ -1,5 +1,5 @@
 """Guarded device regions and poison fills for tests that call a C entry point of libchebgcn.so directly (plain helpers, no
-fixtures; tests/test_gpu_analysis_buffers.py and its host companion use them).
+fixtures; tests/test_gpu_analysis_buffers.py, tests/test_gpu_staging_kernels.py and their host companions use them).
 
 ``Guarded`` generalises the float-only ``Guarded`` classes of test_gpu_head_kernels.py, test_gpu_fused_layer_arms.py and
 test_gpu_attribution_kernels.py (which stay as they are): a region of ANY dtype and byte size inside one larger allocation,
