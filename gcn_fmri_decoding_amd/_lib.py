@@ -20,6 +20,7 @@ FILTER_JMAX, FILTER_KMAX = 8, 256
 CLUSTER_MAX, CLUSTER_EXTENT, CLUSTER_TFCE = 0, 1, 2
 CLUSTER_AUTO, CLUSTER_ONCHIP, CLUSTER_STREAMED = 0, 1, 2
 CLUSTER_EHEIGHTS, CLUSTER_ELOOP = 1, 2
+CONNECTOME_KINDS = ('covariance', 'correlation', 'precision', 'partial correlation')      # CHEBGCN_CONNECTOME_* in this order
 
 
 class ChebgcnError(RuntimeError):
@@ -184,6 +185,11 @@ SIGNATURES = {
     'chebgcn_searchlight_svm_query': (_i, [_i]),
     'chebgcn_searchlight_svm': (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _i, _p, _i, _i, _p, _p, _i, _p, _i, _i, _i, C.c_double, _i, C.c_double, _i,
                                      _p, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    'chebgcn_connectome_query': (_i, [_i]),
+    'chebgcn_connectome_workspace': (C.c_size_t, [_i, _i]),
+    'chebgcn_connectome_cov': (_i, [_p, _i64, _p, _i, _i, _p, C.c_size_t, _p]),
+    'chebgcn_connectome_finish': (_i, [_p, C.c_size_t, _p, _i64, _i, _i, _i, C.c_double, _p, _p, _p, _p]),
+    'chebgcn_connectome_mean': (_i, [_p, _p, _i, _i, _p, _p]),
 }
 
 _lib = None

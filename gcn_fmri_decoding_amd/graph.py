@@ -9,6 +9,8 @@ here and absent on purpose: ``plot_spectrum`` and the dense NumPy recurrence ``c
 
 The one stage that does run on the device is the neighbour search: ``knn_device`` and ``connectivity_graph`` (chebgcn_knn)
 return the same ``[N, k]`` tables as ``distance_sklearn_metrics`` without the N x N matrix; ``adjacency`` (N k work) stays here.
+``connectivity_graph(kind='partial correlation')`` takes its mean matrix from ``connectome`` (chebgcn_connectome_*) and its
+neighbours from ``knn_from_similarity``.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -92,7 +94,28 @@ def knn_device(z, k=4, metric='euclidean', device=None):
         return d.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
 
 
-def connectivity_graph(series, k=8, device=None, return_sigma=False):
+def knn_from_similarity(matrix, k):
+    """The k most similar other vertices of every vertex from an explicit ``[N, N]`` similarity matrix: ``(values [N, k] in the
+    matrix's dtype, descending, idx int64 [N, k])``.  The rules of ``knn_device``: vertex i itself is excluded by index, whatever
+    the diagonal holds, and equal values order by lower index.  On the host (N k work on a matrix of atlas size, like
+    ``adjacency``); ``1 - values`` are distances for ``adjacency``."""
+    matrix = np.asarray(matrix)
+    if matrix.ndim != 2 or matrix.shape[0] != matrix.shape[1]:
+        raise ValueError('knn_from_similarity: matrix must be [N, N], got shape %r' % (matrix.shape,))
+    N = matrix.shape[0]
+    if int(k) != k or k < 1:
+        raise ValueError('knn_from_similarity: k = %r neighbours' % (k,))
+    if k >= N:
+        raise ValueError('knn_from_similarity: k = %d neighbours need more than %d vertices' % (k, N))
+    if not np.isfinite(matrix).all():
+        raise ValueError('knn_from_similarity: matrix holds non-finite values')
+    key = -matrix.astype(np.float64)
+    key[np.diag_indices(N)] = np.inf                             # self: last, whatever the diagonal holds
+    idx = np.argsort(key, axis=1, kind='stable')[:, :int(k)].astype(np.int64)
+    return np.take_along_axis(matrix, idx, axis=1), idx
+
+
+def connectivity_graph(series, k=8, device=None, return_sigma=False, kind='correlation', shrinkage='auto'):
     """Neighbours by functional connectivity, from the scans themselves: ``series`` is one ``[T, M]`` run or a list of runs
     (any lengths >= 2, same M; NumPy arrays, or torch tensors such as ``Parcellation.reduce`` returns, which are staged on the
     device without a host round trip and give the same result as their ``.cpu().numpy()``).
@@ -101,8 +124,21 @@ def connectivity_graph(series, k=8, device=None, return_sigma=False):
     is the mean over runs of the per-run Pearson correlation matrices r (never formed; a vertex constant in a run has
     correlation 0 with everything in that run).  Returns (d, idx) with ``d = 1 - r`` float32 [M, k] ascending and idx int64,
     as ``knn_device``; with ``return_sigma`` also the mean of the whole matrix r (diagonal included), the reference's kernel
-    width for its RSFC graph (model.py:126).  Tangent-space and partial correlation are out of scope."""
+    width for its RSFC graph (model.py:126).
+
+    ``kind='partial correlation'`` takes the neighbours from the mean over runs of the per-run partial correlation matrices of
+    the ``shrinkage``-shrunk covariance ('auto': Ledoit-Wolf) instead, the reference's structural-covariance graph
+    (model.py:93-106): ``connectome.connectome`` forms the matrices on the device (at most 512 regions; runs without a Cholesky
+    factor are left out of the mean), ``knn_from_similarity`` picks the neighbours of the mean matrix on the host.  ``d = 1 -
+    mean`` and the optional third value, the mean of the whole mean matrix, are as above.  The reference's ``tanh`` and
+    ``exp(. / sigma)`` steps are the caller's.  ``shrinkage`` has no meaning for the default kind.  Tangent-space connectivity is
+    out of scope."""
     who = 'connectivity_graph'
+    if kind not in ('correlation', 'partial correlation'):
+        raise ValueError("%s: kind must be 'correlation' or 'partial correlation', got %r (tangent-space connectivity is out "
+                         'of scope)' % (who, kind))
+    if kind == 'partial correlation':
+        return _partial_graph(series, k, device, return_sigma, shrinkage)
     if (isinstance(series, np.ndarray) or _runs.is_tensor(series)) and series.ndim != 2:
         series = list(series)                                   # (a stack [R, T, M] is taken as R runs)
     runs, _, M, _ = _runs.as_runs(series, who, min_rows=2, min_cols=0, width='runs differ in the number of vertices',
@@ -118,6 +154,24 @@ def connectivity_graph(series, k=8, device=None, return_sigma=False):
         if return_sigma:
             col = zn[:, :M].sum(dim=1, dtype=torch.float64)       # sum_ij r_ij = sum_t (sum_m zn[t][m])^2
             out += (float((col * col).sum().item()) / (M * M),)
+    return out
+
+
+def _partial_graph(series, k, device, return_sigma, shrinkage):
+    """``connectivity_graph(kind='partial correlation')``."""
+    from . import connectome as _connectome
+    who = 'connectivity_graph'
+    _connectome._check('partial correlation', shrinkage, who)
+    if (isinstance(series, np.ndarray) or _runs.is_tensor(series)) and series.ndim != 2:
+        series = list(series)
+    runs, _, M, _ = _runs.as_runs(series, who, min_rows=2, min_cols=0, width='runs differ in the number of vertices',
+                                  rows='a run needs at least two time points')
+    _knn_check(M, k)
+    mean = _connectome.connectome(runs, 'partial correlation', shrinkage, device=device).mean.cpu().numpy()
+    sim, idx = knn_from_similarity(mean, int(k))
+    out = (np.float32(1) - sim, idx)
+    if return_sigma:
+        out += (float(mean.astype(np.float64).sum()) / (M * M),)
     return out
 
 

@@ -1196,6 +1196,66 @@ def _cap():
     return capture_tag if (capture_tag is not None and torch.cuda.is_current_stream_capturing()) else None
 
 
+def connectome_geometry():
+    """The constants of the connectome kernels (chebgcn_connectome_query), so that callers and tests follow their edges:
+    ``max_regions``, ``max_runs`` of one call, ``tile`` the side of a covariance / gram tile, ``rows`` of a tile's operands in LDS
+    at once, ``panel`` the columns of a Cholesky panel, ``stage`` the finished columns staged at once, ``threads`` of a finish
+    workgroup, ``classes`` the row classes of beta_."""
+    q = _lib.lib().chebgcn_connectome_query
+    return {'max_regions': q(0), 'max_runs': q(1), 'tile': q(2), 'rows': q(3), 'panel': q(4), 'stage': q(5), 'threads': q(6),
+            'classes': q(7)}
+
+
+def connectome_cov(planes, run_offsets, R):
+    """Means, beta_ and the biased covariance of every staged run (chebgcn_connectome_cov): ``planes`` float32 [Ttot, Rp],
+    ``run_offsets`` int64 [S + 1] on the device -> the float64 workspace ``connectome_finish`` consumes (the next call on the
+    stream reuses it).  The arithmetic and the order of every sum: include/chebgcn.h."""
+    _require_cuda(planes, run_offsets)
+    Ttot, Rp, S = _staged_runs(planes, run_offsets, R, 'connectome_cov')
+    lib = _lib.lib()
+    nbytes = int(lib.chebgcn_connectome_workspace(S, int(R)))
+    ws = _workspace(max(nbytes, 16) + 16, planes.device, 'connectome')
+    ws = ws[(-ws.data_ptr()) % 16:]
+    _lib.check(_launch('connectome_cov', 4.0 * Ttot * Rp * 3 + 8.0 * S * Rp * Rp, 1.0 * Ttot * R * (R + 1),
+                       lambda: lib.chebgcn_connectome_cov(_p(planes), Ttot, _p(run_offsets), S, int(R), _p(ws), nbytes, _stream())),
+               'connectome_cov')
+    return ws
+
+
+def connectome_finish(ws, run_offsets, Ttot, R, kind, shrinkage, matrices, shrinkage_out, degenerate):
+    """Shrinkage and the matrices of one kind (chebgcn_connectome_finish) from what ``connectome_cov`` left in ``ws``, which it
+    overwrites: ``kind`` an index into ``_lib.CONNECTOME_KINDS``, ``shrinkage`` in [0, 1] or negative for Ledoit-Wolf.  Fills
+    ``matrices`` float32 [S, R, R], ``shrinkage_out`` float64 [S] and ``degenerate`` int32 [S], all on the device."""
+    _require_cuda(ws, run_offsets, matrices, shrinkage_out, degenerate)
+    S = int(run_offsets.numel()) - 1
+    _dense(run_offsets, torch.int64, (S + 1,), 'connectome_finish: run_offsets')
+    _dense(matrices, torch.float32, (S, R, R), 'connectome_finish: matrices')
+    _dense(shrinkage_out, torch.float64, (S,), 'connectome_finish: shrinkage_out')
+    _dense(degenerate, torch.int32, (S,), 'connectome_finish: degenerate')
+    lib = _lib.lib()
+    nbytes = int(lib.chebgcn_connectome_workspace(S, int(R)))
+    inverse = int(kind) >= 2
+    _lib.check(_launch('connectome_finish', 8.0 * S * R * R * (6 if inverse else 3), (2.0 if inverse else 0.0) * S * R * R * R,
+                       lambda: lib.chebgcn_connectome_finish(_p(ws), min(nbytes, ws.numel()), _p(run_offsets), int(Ttot), S, int(R), int(kind),
+                                                             float(shrinkage), _p(matrices), _p(shrinkage_out), _p(degenerate),
+                                                             _stream())), 'connectome_finish')
+
+
+def connectome_mean(matrices, degenerate):
+    """The mean over the runs that are not flagged (chebgcn_connectome_mean): ``matrices`` float32 [S, R, R], ``degenerate`` int32
+    [S] -> float32 [R, R]; a float64 sum in ascending run order, rounded once; zeros where every run is flagged."""
+    _require_cuda(matrices, degenerate)
+    if matrices.dim() != 3 or matrices.shape[1] != matrices.shape[2]:
+        raise _lib.ChebgcnError('connectome_mean: matrices must be float32 [S, R, R]')
+    S, R = int(matrices.shape[0]), int(matrices.shape[1])
+    _dense(matrices, torch.float32, (S, R, R), 'connectome_mean: matrices')
+    _dense(degenerate, torch.int32, (S,), 'connectome_mean: degenerate')
+    mean = torch.empty((R, R), dtype=torch.float32, device=matrices.device)
+    _lib.check(_launch('connectome_mean', 4.0 * (S + 1) * R * R, 1.0 * S * R * R, lambda: _lib.lib().chebgcn_connectome_mean(
+        _p(matrices), _p(degenerate), S, R, _p(mean), _stream())), 'connectome_mean')
+    return mean
+
+
 def _workspace(nbytes, device, tag=''):
     """Scratch of a library call, kept per device, stream and use: launches on one stream are ordered, so the buffer of the
     previous call of the same kind is free by the time the next one runs."""

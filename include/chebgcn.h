@@ -1291,6 +1291,66 @@ int chebgcn_searchlight_svm(const float* Xt, int S, int M, const int32_t* rowptr
  * Returns the identity where no ordered kernel serves the graph (nothing to gain).  Deterministic. */
 int chebgcn_bank_order(int M, const int32_t* rowptr, const int32_t* colidx, int sweeps, int32_t* perm_out, int64_t* stats);
 
+/* ---- functional connectivity matrices per run: shrunk covariance, correlation, precision, partial correlation (connectome) ------
+ * series: [Ttot][Rp] float32 planes, Rp = chebgcn_plane_stride(R), run s = rows [run_offsets[s], run_offsets[s + 1]) (each offset
+ * clamped into [0, Ttot], a descending pair an empty run), R regions.  The pad columns [R, Rp) may hold anything, NaN included:
+ * what they hold never reaches a result.  workspace: chebgcn_connectome_workspace(S, R) bytes, 16-byte aligned: per run the
+ * float64 matrix [Rp][Rp] and four vectors of Rp; connectome_cov fills it, connectome_finish consumes (and overwrites) it.
+ * Everything is float64 until the one rounding to float32; no float atomics; every sum below has ONE order, a function of the
+ * run's own T and of R alone, so a run's results are the same bits alone or among others, in any batch, in any call.
+ * connectome_cov, per run, T its rows, x_ti the float32 sample of region i:
+ *     mean_i = (sum_t (double)x_ti) / T                  one chain acc = acc + x over ascending t
+ *     d_ti = (double)x_ti - mean_i
+ *     q_t = sum_i d_ti^2                                 lane l: the chain fma(d, d, q) over i = l, l + 64, ...; then the 64 lanes by
+ *                                                        the butterfly q = q + q(lane ^ s), s = 1, 2, .., 32
+ *     beta_ = sum_t q_t^2                                class w = (t - t0) mod chebgcn_connectome_query(7): the chain fma(q, q, b)
+ *                                                        over its rows ascending; then the classes added in ascending w
+ *     C_ij = (sum_t d_ti d_tj) / T                       ONE chain fma(d_ti, d_tj, acc) from 0 over ascending t: a run is never
+ *                                                        cut along time; C_ij and C_ji are the same bits
+ *   chebgcn_last_dispatch(): connectome_centre_kernel + connectome_rowsq_kernel + connectome_cov_kernel.
+ * connectome_finish, per run (kind: CHEBGCN_CONNECTOME_*; shrinkage: a number in [0, 1], or negative for Ledoit-Wolf):
+ *     delta_ = sum_ij C_ij^2                             thread u of chebgcn_connectome_query(6): the chain fma(c, c, acc) over the
+ *                                                        entries e = i R + j = u, u + 512, ...; then the tree red[u] += red[u + h],
+ *                                                        h = 256, 128, .., 1.  tr = sum_i C_ii by the same tree
+ *     mu = tr / R;  beta = (beta_ / T - delta_) / (R T);  delta = ((delta_ - (2 mu) tr) + (R mu) mu) / R, every operation
+ *     rounded on its own (no fused multiply-add: for one region the terms then cancel to exactly 0)
+ *     s = max(min(beta, delta), 0) / delta, and 0 where delta is not > 0  (never a negative zero)
+ *     Sigma_ij = fma(1 - s, C_ij, i == j ? s mu : 0)
+ *     covariance: Sigma.   correlation: Sigma_ij / sqrt(Sigma_ii Sigma_jj), 0 where that product is not > 0; the diagonal 1.
+ *     precision P = Sigma^-1 by Cholesky without pivoting, Sigma = L L^T:
+ *         L_ij = (Sigma_ij - sum_{p < j} L_ip L_jp) (1 / L_jj), the chain fma(-L_ip, L_jp, acc) over ascending p, L_jj = sqrt(pivot);
+ *         M = L^-1:  M_ic = (delta_ic - sum_{c <= p < i} L_ip M_pc) (1 / L_ii), the chain fma(-L_ip, M_pc, acc) over ascending p;
+ *         P_ij = sum_{p >= max(i, j)} M_pi M_pj, the chain fma(M_pi, M_pj, acc) over ascending p, formed for i >= j and mirrored.
+ *       A pivot that is not > 4 R 2^-53 Sigma_jj (the round-off of its own chain), or not finite, makes the run DEGENERATE: its
+ *       flag is 1 and its matrix the identity (precision and partial correlation alike); no NaN for finite input.
+ *     partial correlation: -P_ij / sqrt(P_ii P_jj), the diagonal 1.
+ *   matrices: float32 [S][R][R], each value rounded ONCE, each matrix symmetric bit for bit.  shrinkage_out float64 [S],
+ *   degenerate int32 [S] (always 0 for covariance and correlation).
+ *   chebgcn_last_dispatch(): connectome_finish_kernel<plain> (covariance, correlation), or connectome_finish_kernel<inverse> +
+ *   connectome_invert_kernel + connectome_gram_kernel.
+ * connectome_mean: mean[i][j] = (float)((sum over the runs s with degenerate[s] == 0, ascending s, of (double)matrices[s][i][j]) /
+ *   their number), zeros where there is none.  float32 [R][R].  chebgcn_last_dispatch(): connectome_mean_kernel.
+ * connectome_query: 0 the largest R, 1 runs of one call, 2 side of a covariance / gram tile, 3 rows of a tile's operands in LDS at
+ *   once, 4 columns of a Cholesky panel, 5 finished columns staged in LDS at once, 6 threads of a finish workgroup, 7 row classes
+ *   of beta_; -1 otherwise.
+ * connectome_workspace: bytes for S runs of R regions (0: arguments out of range).
+ * Limits: R <= 512, S <= 65535 per call (connectome_mean: S <= 2^24), Ttot * Rp <= 2^39: CHEBGCN_EUNSUPPORTED beyond, before any
+ * launch, as every CHEBGCN_EINVAL (NULL, counts <= 0, an unknown kind, a shrinkage above 1 or NaN, a workspace too small, series
+ * and workspace not aligned to 16 bytes, the other pointers to their element).  The calls neither synchronise nor allocate. */
+enum {
+    CHEBGCN_CONNECTOME_COVARIANCE = 0,
+    CHEBGCN_CONNECTOME_CORRELATION = 1,
+    CHEBGCN_CONNECTOME_PRECISION = 2,
+    CHEBGCN_CONNECTOME_PARTIAL = 3
+};
+int chebgcn_connectome_query(int what);
+size_t chebgcn_connectome_workspace(int S, int R);
+int chebgcn_connectome_cov(const float* series, int64_t Ttot, const int64_t* run_offsets, int S, int R, double* workspace,
+                           size_t workspace_bytes, chebgcn_stream stream);
+int chebgcn_connectome_finish(double* workspace, size_t workspace_bytes, const int64_t* run_offsets, int64_t Ttot, int S, int R, int kind,
+                              double shrinkage, float* matrices, double* shrinkage_out, int32_t* degenerate, chebgcn_stream stream);
+int chebgcn_connectome_mean(const float* matrices, const int32_t* degenerate, int S, int R, float* mean, chebgcn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
