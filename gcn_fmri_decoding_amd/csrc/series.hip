@@ -14,14 +14,19 @@
 //            plane read once per group of 8 channels however much the windows overlap.  Sums run in float64 on the deviations
 //            d = series[u][m] - series[0][m] (a vertex that is constant over time has d = 0 and variance exactly 0; no
 //            cancellation against a large mean), in ascending u inside a chunk of rows, chunks added in index order: no float
-//            atomics, the result does not depend on the order of rows[] and is bit-identical from run to run.
+//            atomics, the result does not depend on the order of rows[] and is bit-identical from run to run.  Every sum is
+//            carried as an unevaluated pair (hi, lo) of doubles (dd_add below): the variance is the small difference of
+//            sum d^2 / S and (sum d / S)^2, and one rounding of either at ITS magnitude is an error of 2^-53 d^2 in the
+//            variance -- more than the variance itself where the windows lie closer to each other than to series[0] (few
+//            windows, folded windows, one window: variance 0).  The pairs keep the order of the sums and lose nothing to it.
 #include "gather_piece.h"
 
 namespace chebgcn {
 
 constexpr int WS_T = 256;               // threads of the statistics kernels
-constexpr int WS_CG = 8;                // channels a statistics workgroup accumulates (registers: 2 * 2 * WS_CG doubles)
-constexpr int WS_ROWS = 512;            // series rows of one chunk (a chunk's partials are 2 * C * Mp doubles)
+constexpr int WS_CG = 8;                // channels a statistics workgroup accumulates (registers: 2 * 2 * 2 * WS_CG doubles)
+constexpr int WS_ROWS = 512;            // series rows of one chunk (a chunk's partials are WS_PART * C * Mp doubles)
+constexpr int WS_PART = 4;              // slabs of a chunk's partials: the heads of sum n d and sum n d^2, then their tails
 
 // ---- what the gathers do to a piece (16 bytes of a window): float32 adds and divisions of one rounding each, then the epilogue
 // (finish_piece, gather_piece.h) ---
@@ -30,6 +35,33 @@ __device__ __forceinline__ float4 add4(float4 a, float4 b) {
 }
 __device__ __forceinline__ float4 div4(float4 a, float d) {
     return make_float4(__fdiv_rn(a.x, d), __fdiv_rn(a.y, d), __fdiv_rn(a.z, d), __fdiv_rn(a.w, d));
+}
+
+// ---- the statistics' sums: (h, l) += (th, tl), the heads by Knuth's branch-free TwoSum (its rounding error is exact), the error
+// and the tails into l.  Explicitly rounded operations: nothing here may be re-associated or contracted.
+__device__ __forceinline__ void dd_add(double& h, double& l, double th, double tl) {
+    const double s = __dadd_rn(h, th);
+    const double b = __dsub_rn(s, h);
+    const double e = __dadd_rn(__dsub_rn(h, __dsub_rn(s, b)), __dsub_rn(th, b));
+    h = s;
+    l = __dadd_rn(l, __dadd_rn(e, tl));
+}
+// (h, l) with the same value and |l| at most half a unit in the last place of h
+__device__ __forceinline__ void dd_norm(double& h, double& l) {
+    const double s = __dadd_rn(h, l);
+    const double b = __dsub_rn(s, h);
+    l = __dadd_rn(__dsub_rn(h, __dsub_rn(s, b)), __dsub_rn(l, b));
+    h = s;
+}
+// a * b as a pair: the rounded product and its exact error
+__device__ __forceinline__ void dd_mul(double a, double b, double& h, double& l) {
+    h = __dmul_rn(a, b);
+    l = fma(a, b, -h);
+}
+// (h, l) / n as a pair, n an integer held exactly
+__device__ __forceinline__ void dd_div(double h, double l, double n, double& qh, double& ql) {
+    qh = __ddiv_rn(h, n);
+    ql = __ddiv_rn(__dadd_rn(fma(-qh, n, h), l), n);
 }
 
 // block (piece of the window's C * Mp/4 float4s, window b)
@@ -261,7 +293,7 @@ gather_windows_indexed_kernel(IndexedArgs A, int fold, const long long* __restri
 // the gather forms in float32, so the kernel forms them the same way, window by window.  block (tile of 2 * WS_T vertices x
 // channel c, chunk g of `chunk` windows): part[g][k][c][m] as window_stats_partial_kernel writes it, windows in ascending
 // order; window_stats_finish_kernel adds the chunks in index order.
-constexpr int WSI_CHUNKS = 32;          // chunks at most (a chunk's partials are 2 * C * Mp doubles)
+constexpr int WSI_CHUNKS = 32;          // chunks at most (a chunk's partials are WS_PART * C * Mp doubles)
 constexpr int WSI_MIN = 16;             // windows of a chunk at least
 
 template <int FOLD>                     // 0: any fold
@@ -276,7 +308,7 @@ window_stats_indexed_partial_kernel(const float* __restrict__ series, long long 
     const long long w0 = (long long)g * chunk, w1 = min(w0 + chunk, S);
     const float2 base = *reinterpret_cast<const float2*>(series + m);
     const double k0 = (double)base.x, k1 = (double)base.y;
-    double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0};
+    double s1[2] = {0.0, 0.0}, s2[2] = {0.0, 0.0}, c1[2] = {0.0, 0.0}, c2[2] = {0.0, 0.0};
     for (long long wb = w0; wb < w1; wb += 4) {
         float2 x[4];
 #pragma unroll
@@ -303,17 +335,22 @@ window_stats_indexed_partial_kernel(const float* __restrict__ series, long long 
         for (int i = 0; i < 4; ++i) {
             if (wb + i < w1) {
                 const double d0 = (double)x[i].x - k0, d1 = (double)x[i].y - k1;
-                s1[0] += d0;
-                s1[1] += d1;
-                s2[0] = fma(d0, d0, s2[0]);
-                s2[1] = fma(d1, d1, s2[1]);
+                double q0, r0, q1, r1;
+                dd_mul(d0, d0, q0, r0);
+                dd_mul(d1, d1, q1, r1);
+                dd_add(s1[0], c1[0], d0, 0.0);
+                dd_add(s1[1], c1[1], d1, 0.0);
+                dd_add(s2[0], c2[0], q0, r0);
+                dd_add(s2[1], c2[1], q1, r1);
             }
         }
     }
     const size_t slab = (size_t)C * Mp, o = (size_t)c * Mp + m;
-    double* p = part + (size_t)g * 2 * slab;
+    double* p = part + (size_t)g * WS_PART * slab;
     *reinterpret_cast<double2*>(p + o) = make_double2(s1[0], s1[1]);
     *reinterpret_cast<double2*>(p + slab + o) = make_double2(s2[0], s2[1]);
+    *reinterpret_cast<double2*>(p + 2 * slab + o) = make_double2(c1[0], c1[1]);
+    *reinterpret_cast<double2*>(p + 3 * slab + o) = make_double2(c2[0], c2[1]);
 }
 
 static inline long long wsi_chunk(int64_t S) {
@@ -332,7 +369,7 @@ window_count_kernel(const long long* __restrict__ rows, long long S, long long l
 }
 
 // block (tile of 2 * WS_T vertices x group of WS_CG channels, chunk g of WS_ROWS rows): part[g][k][c][m], k = 0 the sum of
-// n d, k = 1 the sum of n d^2 over the chunk's rows in ascending order
+// n d, k = 1 the sum of n d^2 over the chunk's rows in ascending order (their heads; k = 2, 3: their tails)
 __global__ void __launch_bounds__(WS_T)
 window_stats_partial_kernel(const float* __restrict__ series, long long Ttot, const int* __restrict__ cnt, int C, int Mp,
                             int ncg, double* __restrict__ part) {
@@ -343,9 +380,9 @@ window_stats_partial_kernel(const float* __restrict__ series, long long Ttot, co
     if (m >= Mp) return;
     const float2 base = *reinterpret_cast<const float2*>(series + m);
     const double k0 = (double)base.x, k1 = (double)base.y;
-    double s1[WS_CG][2], s2[WS_CG][2];
+    double s1[WS_CG][2], s2[WS_CG][2], c1[WS_CG][2], c2[WS_CG][2];
 #pragma unroll
-    for (int j = 0; j < WS_CG; ++j) s1[j][0] = s1[j][1] = s2[j][0] = s2[j][1] = 0.0;
+    for (int j = 0; j < WS_CG; ++j) s1[j][0] = s1[j][1] = s2[j][0] = s2[j][1] = c1[j][0] = c1[j][1] = c2[j][0] = c2[j][1] = 0.0;
     const int nc = min(WS_CG, C - c0);
     for (long long u = u0; u < u1; u += 4) {
         float2 x[4];
@@ -361,17 +398,24 @@ window_stats_partial_kernel(const float* __restrict__ series, long long Ttot, co
         for (int i = 0; i < 4; ++i) {
             if (u + i < u1) {
                 const double d0 = (double)x[i].x - k0, d1 = (double)x[i].y - k1;
-                const double q0 = d0 * d0, q1 = d1 * d1;
+                double q0, r0, q1, r1;                                  // d^2 = q + r exactly
+                dd_mul(d0, d0, q0, r0);
+                dd_mul(d1, d1, q1, r1);
 #pragma unroll
                 for (int j = 0; j < WS_CG; ++j) {
                     if (j < nc) {
                         const int w = n[i - j + WS_CG - 1];
                         if (w != 0) {
                             const double wd = (double)w;
-                            s1[j][0] = fma(wd, d0, s1[j][0]);
-                            s1[j][1] = fma(wd, d1, s1[j][1]);
-                            s2[j][0] = fma(wd, q0, s2[j][0]);
-                            s2[j][1] = fma(wd, q1, s2[j][1]);
+                            double ph, pl;
+                            dd_mul(wd, d0, ph, pl);
+                            dd_add(s1[j][0], c1[j][0], ph, pl);
+                            dd_mul(wd, d1, ph, pl);
+                            dd_add(s1[j][1], c1[j][1], ph, pl);
+                            dd_mul(wd, q0, ph, pl);
+                            dd_add(s2[j][0], c2[j][0], ph, fma(wd, r0, pl));
+                            dd_mul(wd, q1, ph, pl);
+                            dd_add(s2[j][1], c2[j][1], ph, fma(wd, r1, pl));
                         }
                     }
                 }
@@ -379,13 +423,15 @@ window_stats_partial_kernel(const float* __restrict__ series, long long Ttot, co
         }
     }
     const size_t slab = (size_t)C * Mp;
-    double* p = part + (size_t)g * 2 * slab;
+    double* p = part + (size_t)g * WS_PART * slab;
 #pragma unroll
     for (int j = 0; j < WS_CG; ++j) {
         if (j < nc) {
             const size_t o = (size_t)(c0 + j) * Mp + m;
             *reinterpret_cast<double2*>(p + o) = make_double2(s1[j][0], s1[j][1]);
             *reinterpret_cast<double2*>(p + slab + o) = make_double2(s2[j][0], s2[j][1]);
+            *reinterpret_cast<double2*>(p + 2 * slab + o) = make_double2(c1[j][0], c1[j][1]);
+            *reinterpret_cast<double2*>(p + 3 * slab + o) = make_double2(c2[j][0], c2[j][1]);
         }
     }
 }
@@ -402,15 +448,27 @@ window_stats_finish_kernel(const float* __restrict__ series, const double* __res
     double mu = 0.0, va = 0.0;
     float sc = 0.f, sh = 0.f;
     if (m < M) {
-        double a = 0.0, q = 0.0;
+        double ah = 0.0, al = 0.0, qh = 0.0, ql = 0.0;
         for (int g = 0; g < G; ++g) {
-            a += part[(size_t)g * 2 * slab + e];
-            q += part[(size_t)g * 2 * slab + slab + e];
+            const double* p = part + (size_t)g * WS_PART * slab + e;
+            dd_add(ah, al, p[0], p[2 * slab]);
+            dd_add(qh, ql, p[slab], p[3 * slab]);
         }
-        const double n = (double)S, da = a / n;
-        mu = (double)series[m] + da;
-        va = q / n - da * da;
+        // mean deviation da = a / S and mean square q / S as pairs, da^2 as a pair; the variance is their difference, head
+        // from head (exact where they nearly cancel) and tail from tail
+        const double n = (double)S;
+        dd_norm(ah, al);
+        dd_norm(qh, ql);
+        double dh, dl, mh, ml, wh, wl;
+        dd_div(ah, al, n, dh, dl);
+        dd_div(qh, ql, n, mh, ml);
+        dd_mul(dh, dh, wh, wl);
+        wl = fma(2.0 * dh, dl, wl);
+        va = __dadd_rn(__dsub_rn(mh, wh), __dsub_rn(ml, wl));
         if (!(va > 0.0)) va = 0.0;
+        double base = (double)series[m], me = 0.0;
+        dd_add(base, me, dh, dl);       // series[0][m] + da, rounded once
+        mu = __dadd_rn(base, me);
         if (va == 0.0) {                // sklearn's _handle_zeros_in_scale: a constant entry is shifted, not scaled
             sc = 1.f;
             sh = (float)(-mu);
@@ -474,7 +532,7 @@ extern "C" int chebgcn_gather_windows_mix(const float* series, int64_t Ttot, con
 
 extern "C" size_t chebgcn_window_stats_workspace(int64_t Ttot, int M, int C) {
     if (Ttot <= 0 || M <= 0 || C <= 0 || Ttot > 0x7fffffffLL) return 0;
-    return ws_count_bytes(Ttot, C) + (size_t)ws_chunks(Ttot) * 2 * C * plane_stride(M) * sizeof(double);
+    return ws_count_bytes(Ttot, C) + (size_t)ws_chunks(Ttot) * WS_PART * C * plane_stride(M) * sizeof(double);
 }
 
 extern "C" int chebgcn_window_stats(const float* series, int64_t Ttot, const int64_t* rows, int64_t S, double* mean, double* var,
@@ -534,7 +592,7 @@ extern "C" int chebgcn_gather_windows_indexed(const float* series, int64_t Ttot,
 
 extern "C" size_t chebgcn_window_stats_indexed_workspace(int64_t S, int M, int C) {
     if (S <= 0 || M <= 0 || C <= 0 || S > 0x7fffffffLL) return 0;
-    return (size_t)wsi_chunks(S) * 2 * C * plane_stride(M) * sizeof(double);
+    return (size_t)wsi_chunks(S) * WS_PART * C * plane_stride(M) * sizeof(double);
 }
 
 extern "C" int chebgcn_window_stats_indexed(const float* series, int64_t Ttot, const int64_t* idx, int64_t S, int Cin, int fold,

@@ -634,9 +634,10 @@ int chebgcn_gradcam_map(const float* A, const float* G, const float* alpha, cons
  *   windows rows[0 .. S), float64 [C][Mp] (either may be NULL), and the float32 tables scale = 1/std, shift = -mean/std
  *   ([C][Mp]; where the variance is 0: scale 1, shift -mean; the pad of all four is 0).  One pass over the series whatever the
  *   overlap (a per-row count of the windows that start there, then  sum_u n[u - c] f(series[u][m])).  Float64 sums of the
- *   deviations from series[0][m] in ascending row order inside chunks of 512 rows, chunks added in index order: no float
- *   atomics, bit-identical from run to run and under any permutation of rows.  workspace: device scratch of at least
- *   chebgcn_window_stats_workspace() bytes, 16-byte aligned.  chebgcn_last_dispatch(): window_count_kernel +
+ *   deviations from series[0][m] in ascending row order inside chunks of 512 rows, chunks added in index order, every sum
+ *   carried as a pair of doubles (head + tail: no rounding of a sum or of a square reaches the variance, which is 0 for one
+ *   window): no float atomics, bit-identical from run to run and under any permutation of rows.  workspace: device scratch of
+ *   at least chebgcn_window_stats_workspace() bytes, 16-byte aligned.  chebgcn_last_dispatch(): window_count_kernel +
  *   window_stats_partial_kernel + window_stats_finish_kernel.
  *
  * Windows that are LISTS of rows (events.match_events: a trial padded by repeating its last volume, a chunk that straddles a rest
@@ -656,8 +657,9 @@ int chebgcn_gradcam_map(const float* A, const float* G, const float* alpha, cons
  *   (fold * n + 1) windows per output window.  chebgcn_last_dispatch(): gather_windows_indexed_kernel<plain | tables>.
  * window_stats_indexed: what window_stats computes, over piece(s), s < S -- the folded values as the gather forms them in
  *   float32, before the tables and without sources (what the reference's scaler sees, utils.py:573).  Float64 sums of the
- *   deviations from series[0][m]; one workgroup sums a chunk of windows in ascending order (chunks of max(16, ceil(S / 32))
- *   windows), chunks are added in index order: no float atomics, bit-identical from run to run.  workspace: at least
+ *   deviations from series[0][m], as pairs of doubles like window_stats'; one workgroup sums a chunk of windows in ascending
+ *   order (chunks of max(16, ceil(S / 32)) windows), chunks are added in index order: no float atomics, bit-identical from run
+ *   to run.  workspace: at least
  *   chebgcn_window_stats_indexed_workspace() bytes, 16-byte aligned.  chebgcn_last_dispatch():
  *   window_stats_indexed_partial_kernel + window_stats_finish_kernel. */
 int chebgcn_gather_windows(const float* series, int64_t Ttot, const int64_t* rows, const int32_t* sample, const float* scale,

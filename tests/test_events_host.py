@@ -246,10 +246,10 @@ def test_indexed_entry_points_abi():
     for n in ('chebgcn_gather_windows_indexed', 'chebgcn_window_stats_indexed', 'chebgcn_window_stats_indexed_workspace'):
         assert n in names and n in _lib.SIGNATURES
     lib = _lib.lib()
-    # the workspace: 2 * C * Mp doubles per chunk of max(16, ceil(S / 32)) windows
-    assert lib.chebgcn_window_stats_indexed_workspace(10, 360, 15) == 1 * 2 * 15 * 384 * 8
-    assert lib.chebgcn_window_stats_indexed_workspace(17, 33, 1) == 2 * 2 * 1 * 64 * 8
-    assert lib.chebgcn_window_stats_indexed_workspace(3888, 360, 15) == 32 * 2 * 15 * 384 * 8
+    # the workspace: 4 * C * Mp doubles (every sum a pair) per chunk of max(16, ceil(S / 32)) windows
+    assert lib.chebgcn_window_stats_indexed_workspace(10, 360, 15) == 1 * 4 * 15 * 384 * 8
+    assert lib.chebgcn_window_stats_indexed_workspace(17, 33, 1) == 2 * 4 * 1 * 64 * 8
+    assert lib.chebgcn_window_stats_indexed_workspace(3888, 360, 15) == 32 * 4 * 15 * 384 * 8
     for bad in ((0, 360, 15), (10, 0, 15), (10, 360, 0), (2 ** 31, 360, 15)):
         assert lib.chebgcn_window_stats_indexed_workspace(*bad) == 0
     buf = (ctypes.c_float * 4096)()

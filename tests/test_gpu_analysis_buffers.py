@@ -24,8 +24,6 @@ chebgcn_window_stats_workspace query 16 bytes short ("guard changed", window_sta
 ("base not kept", the LDA and SVM cases; "runs A/B differ", the naive-Bayes case).
 """
 import ctypes
-import os
-import re
 import types
 
 import numpy as np
@@ -36,20 +34,13 @@ from gcn_fmri_decoding_amd import _lib, series
 from gcn_fmri_decoding_amd._lib import plane_stride
 
 import guarded_buffers as gb
+from window_kernel_cases import source_constant, stats_bound as _stats_bound        # (shared with tests/test_gpu_window_kernels.py)
 
 pytestmark = pytest.mark.gpu
 
 BASE = 7                                # what an added-into count holds before the call
 WRITTEN, UNTOUCHED, ZERO, SCRATCH = 1, 0, 2, 3
 NAN = np.float32(np.nan)
-
-
-def source_constant(file, name):
-    """``constexpr int NAME = value;`` of a source under csrc/ (entries without a geometry query)."""
-    text = open(os.path.join(ROOT, 'gcn_fmri_decoding_amd', 'csrc', file)).read()
-    m = re.search(r'constexpr\s+int\s+%s\s*=\s*(\d+)\s*;' % re.escape(name), text)
-    assert m, '%s: no constexpr int %s' % (file, name)
-    return int(m.group(1))
 
 
 class Out:
@@ -282,17 +273,6 @@ for _t in (False, True):
 _gather_case('gather_windows-two_blocks', 'chebgcn_gather_windows', 360, 11, 2, 20, False)
 
 
-def _stats_bound(x):
-    """The bounds of test_window_stats_against_float64_and_sklearn (tests/test_gpu_fit_series.py), for windows x [S, C, M]
-    float64: two orderings of a float64 sum of S terms differ by at most S 2^-52 sum|x|."""
-    u = 2.0 ** -52
-    sum_abs, sum_sq = np.abs(x).sum(axis=0), (x * x).sum(axis=0)
-    ref_mean, ref_m2 = x.mean(axis=0), (x * x).mean(axis=0)
-    b_mean = u * sum_abs
-    b_var = u * sum_sq + 2 * np.abs(ref_mean) * b_mean + 4 * (u / 2) * (ref_m2 + ref_mean ** 2)
-    return ref_mean, x.var(axis=0), b_mean, b_var
-
-
 def _stats_compare(id, M):
     def compare(got, ref):
         mean, var = got['mean'][:, :M], got['var'][:, :M]
@@ -363,7 +343,7 @@ def _stats_indexed_case(fold):
         nws = int(lib().chebgcn_window_stats_indexed_workspace(S, M, C))
         chunk = max(16, -(-S // 32))                                                        # "chunks of max(16, ceil(S / 32)) windows"
         chunks = -(-S // chunk)
-        formula = chunks * 2 * C * Mp * 8                                                   # a partial per chunk: 2 [C][Mp] doubles
+        formula = chunks * 4 * C * Mp * 8                                                   # a partial per chunk: 4 [C][Mp] doubles
 
         def call(L, d, o, w, stream):
             ok(L.chebgcn_window_stats_indexed(P(d['planes']), Ttot, P(d['idx']), S, C * fold, fold, P(o['mean']), P(o['var']),

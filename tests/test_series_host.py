@@ -127,9 +127,9 @@ def test_series_entry_points_abi():
         assert n in names and n in _lib.SIGNATURES
     lib = _lib.lib()
     # workspace arithmetic: the count table (Ttot + C - 1 + 8 + 4 ints, rounded to 16 bytes) + ceil(Ttot / 512) chunks of
-    # 2 * C * Mp float64 partials
-    assert lib.chebgcn_window_stats_workspace(1000, 360, 15) == ((1000 + 14 + 12) * 4 + 15) // 16 * 16 + 2 * 2 * 15 * 384 * 8
-    assert lib.chebgcn_window_stats_workspace(512, 33, 1) == (512 + 12) * 4 + 1 * 2 * 1 * 64 * 8
+    # 4 * C * Mp float64 partials (every sum a pair of doubles)
+    assert lib.chebgcn_window_stats_workspace(1000, 360, 15) == ((1000 + 14 + 12) * 4 + 15) // 16 * 16 + 2 * 4 * 15 * 384 * 8
+    assert lib.chebgcn_window_stats_workspace(512, 33, 1) == (512 + 12) * 4 + 1 * 4 * 1 * 64 * 8
     for bad in ((0, 360, 15), (1000, 0, 15), (1000, 360, 0), (1 << 31, 360, 15)):
         assert lib.chebgcn_window_stats_workspace(*bad) == 0
     buf = (ctypes.c_float * 4096)()
