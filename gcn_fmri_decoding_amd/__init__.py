@@ -18,7 +18,7 @@ from .glm import TrialDesign, TrialResult, single_trial, single_trial_host, tria
 from .searchlight import SearchlightResult, SolverInfo, lda_shrinkage_host, searchlight_events, searchlight_host  # noqa: F401
 from .searchlight import RDMResult, compare_rdms, crossnobis, crossnobis_events, crossnobis_host  # noqa: F401
 # (the call itself is connectome.connectome: the package attribute stays the module)
-from .connectome import Connectome, connectome_host  # noqa: F401
+from .connectome import Connectome, connectome_host, Tangent, tangent, tangent_host  # noqa: F401
 
 __all__ = ['graph', 'coarsening', 'parcellation', 'Parcellation', 'filters', 'GraphFilter', 'splits', 'stats', 'map_test',
            'map_test_host', 'sign_flips', 'MapTestResult', 'design_test', 'design_test_host', 'permutations', 'perm_t_host',
@@ -26,7 +26,7 @@ __all__ = ['graph', 'coarsening', 'parcellation', 'Parcellation', 'filters', 'Gr
            'first_level', 'first_level_host', 'TrialDesign', 'TrialResult', 'trial_design', 'single_trial', 'single_trial_host',
            'searchlight', 'SearchlightResult', 'SolverInfo', 'searchlight_events', 'searchlight_host',
            'lda_shrinkage_host', 'RDMResult', 'compare_rdms', 'crossnobis', 'crossnobis_events', 'crossnobis_host', 'connectome', 'Connectome',
-           'connectome_host', 'models_gcn', 'ops']
+           'connectome_host', 'Tangent', 'tangent', 'tangent_host', 'models_gcn', 'ops']
 
 
 def __getattr__(name):

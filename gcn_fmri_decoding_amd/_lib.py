@@ -21,6 +21,7 @@ CLUSTER_MAX, CLUSTER_EXTENT, CLUSTER_TFCE = 0, 1, 2
 CLUSTER_AUTO, CLUSTER_ONCHIP, CLUSTER_STREAMED = 0, 1, 2
 CLUSTER_EHEIGHTS, CLUSTER_ELOOP = 1, 2
 CONNECTOME_KINDS = ('covariance', 'correlation', 'precision', 'partial correlation')      # CHEBGCN_CONNECTOME_* in this order
+SYM_FUNCTIONS = ('log', 'exp', 'sqrt', 'rsqrt')                                             # CHEBGCN_SYM_* in this order
 
 
 class ChebgcnError(RuntimeError):
@@ -190,6 +191,13 @@ SIGNATURES = {
     'chebgcn_connectome_cov': (_i, [_p, _i64, _p, _i, _i, _p, C.c_size_t, _p]),
     'chebgcn_connectome_finish': (_i, [_p, C.c_size_t, _p, _i64, _i, _i, _i, C.c_double, _p, _p, _p, _p]),
     'chebgcn_connectome_mean': (_i, [_p, _p, _i, _i, _p, _p]),
+    'chebgcn_connectome_sigma': (_i, [_p, C.c_size_t, _p, _i64, _i, _i, C.c_double, _p, _p, _p]),
+    'chebgcn_tangent_query': (_i, [_i]),
+    'chebgcn_tangent_workspace': (C.c_size_t, [_i, _i]),
+    'chebgcn_sym_eigh': (_i, [_p, _i, _i, _p, _p, _p, _p, _p, C.c_size_t, _p]),
+    'chebgcn_sym_function': (_i, [_p, _p, _i, _i, _i, C.c_double, _p, _i, _p, _p, _p]),
+    'chebgcn_sym_congruence': (_i, [_p, _p, _i, _i, _p, _p, _p]),
+    'chebgcn_sym_mean': (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -5,8 +5,11 @@ include/chebgcn.h).  The reference builds two of its three brain gr
 ``graph.connectivity_graph(kind='partial correlation')`` sits on top of this module.
 
 ``connectome`` runs the kernels; ``connectome_host`` is the NumPy yardstick, which deliberately uses none of their algebra
-(the centred product by ``@``, the inverse by ``numpy.linalg.inv``).  ``kind='tangent'`` is out of scope: it needs symmetric
-eigendecompositions of every matrix in every iteration of a geometric mean.
+(the centred product by ``@``, the inverse by ``numpy.linalg.inv``).
+
+``tangent`` is nilearn's ``ConnectivityMeasure(kind='tangent')``: the geometric mean G of the runs' shrunk covariances and the
+tangent matrices ``log(G^-1/2 Sigma_s G^-1/2)``, on a batched Jacobi eigensolver (chebgcn_sym_*); ``tangent_host``
+is its yardstick on ``numpy.linalg.eigh``; ``eigh`` is the solver alone.
 
 Host-only at import: NumPy and the constants of ``_lib`` (which loads the library only when asked); torch is imported by the
 functions that need it.
@@ -35,7 +38,7 @@ Connectome.__doc__ = """What ``connectome`` / ``connectome_host`` return.
 def _check(kind, shrinkage, who):
     """``kind`` and ``shrinkage`` checked -> (the index of the kind, the shrinkage as the C entry takes it: negative for 'auto')."""
     if kind not in KINDS:
-        raise ValueError('%s: unknown kind %r (one of %s; tangent-space connectivity is out of scope)' % (
+        raise ValueError('%s: unknown kind %r (one of %s; tangent-space connectivity is connectome.tangent)' % (
             who, kind, ', '.join(repr(k) for k in KINDS)))
     if isinstance(shrinkage, str):
         if shrinkage != 'auto':
@@ -182,3 +185,279 @@ def connectome(runs, kind='correlation', shrinkage='auto', device=None, batch_ru
             ops.connectome_finish(ws, o, int(rows.shape[0]), R, ikind, s, matrices[r0:r1], shrunk[r0:r1], flags[r0:r1])
         mean = ops.connectome_mean(matrices, flags)
         return Connectome(matrices, mean, shrunk.cpu().numpy(), flags.cpu().numpy() != 0, kind)
+
+
+# ---- tangent space ----------------------------------------------------------------------------------------------------------------
+
+Tangent = collections.namedtuple('Tangent', 'matrices mean whitening reference shrinkage degenerate iterations norms steps '
+                                            'converged sweeps eig_converged')
+Tangent.__doc__ = """What ``tangent`` / ``tangent_host`` return.
+
+``matrices``      float32 [S, R, R]: ``log(W Sigma_s W)`` per run, symmetric bit for bit; zeros for a degenerate run (a device
+                  tensor from ``tangent``, NumPy from ``tangent_host``, as ``mean`` and ``whitening``)
+``mean``          float32 [R, R]: the geometric mean G of the usable runs' shrunk covariances (nilearn's ``mean_``)
+``whitening``     float32 [R, R]: ``W = G^-1/2``
+``reference``     float64 [R, R] NumPy: G before its rounding; ``tangent(other_runs, reference=...)`` maps onto it
+``shrinkage``     float64 [S] NumPy
+``degenerate``    bool [S] NumPy: runs whose Sigma has an eigenvalue that is not above ``4 R 2^-53`` of its largest (or not finite)
+``iterations``    iterations of the geometric mean that ran (0 with ``reference=`` or without a usable run)
+``norms``         float64 NumPy: ``||mean_s log B_s||_F / R^2`` of every iteration
+``steps``         float64 NumPy: the step every iteration moved G with
+``converged``     whether the last norm fell below ``tol`` (True with ``reference=``; False without a usable run)
+``sweeps``        the most sweeps any eigendecomposition took (0 on the host)
+``eig_converged`` whether every eigendecomposition ended before the cap of sweeps (True on the host)"""
+
+
+def degenerate_floor(R):
+    """A run is degenerate when the smallest eigenvalue of its Sigma is not above ``degenerate_floor(R)`` times the largest."""
+    return 4.0 * R * 2.0 ** -53
+
+
+def _check_tangent(shrinkage, max_iter, tol, batch_runs, who):
+    _, s = _check('covariance', shrinkage, who)
+    if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+        raise ValueError('%s: max_iter must be an int >= 1, got %r' % (who, max_iter))
+    if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (numbers.Real, np.floating, np.integer)) or not (
+            0.0 <= float(tol) < np.inf):
+        raise ValueError('%s: tol must be a finite number >= 0, got %r' % (who, tol))
+    if batch_runs is not None and (isinstance(batch_runs, (bool, np.bool_)) or not isinstance(batch_runs, (int, np.integer))
+                                   or batch_runs < 1):
+        raise ValueError('%s: batch_runs must be an int >= 1, got %r' % (who, batch_runs))
+    return s, int(max_iter), float(tol)
+
+
+def _check_reference(reference, R, who):
+    """``reference=`` as a float64 [R, R] array: symmetric, finite and positive definite, or ``ValueError``."""
+    if reference is None:
+        return None
+    G = reference.detach().cpu().numpy() if _runs.is_tensor(reference) else np.asarray(reference)
+    if G.dtype.kind not in 'fiu' or G.shape != (R, R):
+        raise ValueError('%s: reference must be a real [%d, %d] matrix, got %s %r' % (who, R, R, G.dtype, G.shape))
+    G = np.ascontiguousarray(G, np.float64)
+    if not np.isfinite(G).all() or not np.array_equal(G, G.T):
+        raise ValueError('%s: reference must be finite and symmetric' % who)
+    try:
+        np.linalg.cholesky(G)
+    except np.linalg.LinAlgError:
+        raise ValueError('%s: reference is not positive definite' % who) from None
+    return G
+
+
+def _sym_fun_host(A, f):
+    """``V f(Lambda) V^T`` by ``numpy.linalg.eigh`` and ``@``, symmetrised."""
+    w, V = np.linalg.eigh(A)
+    out = (V * f(w)) @ V.T
+    return (out + out.T) / 2
+
+
+def _congruence_host(W, A):
+    out = W @ A @ W
+    return (out + out.T) / 2
+
+
+def geometric_mean_host(sigmas, max_iter=30, tol=1e-7):
+    """The geometric mean of SPD matrices by nilearn's rule (``_geometric_mean``), restated ->
+    ``(G, iterations, norms / R^2, steps, converged)``."""
+    R = sigmas[0].shape[0]
+    G = np.zeros((R, R))
+    for sig in sigmas:                                          # (ascending, as the device sums)
+        G = G + sig
+    G = G / len(sigmas)
+    step, norm_old = 1.0, np.inf
+    norms, steps, converged = [], [], False
+    for _ in range(max_iter):
+        W = _sym_fun_host(G, lambda w: 1.0 / np.sqrt(w))
+        H = _sym_fun_host(G, np.sqrt)
+        M = np.zeros((R, R))
+        for sig in sigmas:
+            M = M + _sym_fun_host(_congruence_host(W, sig), np.log)
+        M = M / len(sigmas)
+        norm = float(np.sqrt((M * M).sum()))
+        norms.append(norm / R ** 2)
+        steps.append(step)
+        G = _congruence_host(H, _sym_fun_host(M, lambda w: np.exp(step * w)))
+        if norm < norm_old:
+            norm_old = norm
+        elif norm > norm_old:
+            step = step / 2.0
+            norm = norm_old
+        if norm / R ** 2 < tol:
+            converged = True
+            break
+    return G, len(norms), np.array(norms), np.array(steps), converged
+
+
+def tangent_host(runs, shrinkage='auto', max_iter=30, tol=1e-7, reference=None):
+    """``tangent`` on the host in NumPy float64 with ``numpy.linalg.eigh`` and ``@``: the same definitions, none of the device's
+    algebra.  Returns a ``Tangent`` of NumPy arrays."""
+    who = 'tangent_host'
+    s, max_iter, tol = _check_tangent(shrinkage, max_iter, tol, None, who)
+    runs, R = _as_runs(runs, who, None)
+    G = _check_reference(reference, R, who)
+    host = [_runs.host_array(r, who, any_dtype=True) for r in runs]
+    out = [host_run(x, 'covariance', s) for x in host]
+    sigmas = [m for m, _, _ in out]
+    degenerate = np.zeros(len(runs), bool)
+    for r, sig in enumerate(sigmas):
+        ev = np.linalg.eigvalsh(sig) if np.isfinite(sig).all() else np.array([np.nan])
+        degenerate[r] = not (np.isfinite(ev).all() and ev.min() > degenerate_floor(R) * ev.max())
+    usable = [sig for sig, d in zip(sigmas, degenerate) if not d]
+    iterations, norms, steps, converged = 0, np.zeros(0), np.zeros(0), G is not None
+    if G is None:
+        if usable:
+            G, iterations, norms, steps, converged = geometric_mean_host(usable, max_iter, tol)
+        else:
+            G = np.eye(R)
+    W = _sym_fun_host(G, lambda w: 1.0 / np.sqrt(w))
+    matrices = np.zeros((len(runs), R, R), np.float32)
+    for r, sig in enumerate(sigmas):
+        if not degenerate[r]:
+            matrices[r] = _sym_fun_host(_congruence_host(W, sig), np.log).astype(np.float32)
+    return Tangent(matrices, G.astype(np.float32), W.astype(np.float32), G, np.array([v for _, v, _ in out], np.float64), degenerate,
+                   iterations, norms, steps, converged, 0, True)
+
+
+def eigh(matrices, device=None):
+    """Eigendecompositions of symmetric float64 matrices ``[S, R, R]`` (NumPy or a tensor; R <= 512) on the device, by the block
+    Jacobi method of chebgcn_sym_eigh -> ``(w [S, R] ascending, V [S, R, R] with the eigenvectors in its columns, sweeps int32
+    [S] NumPy)``, ``w`` and ``V`` device tensors.  The matrices must be symmetric bit for bit and finite (``ValueError``); a matrix
+    still rotating after the cap of sweeps raises ``ChebgcnError``."""
+    who = 'eigh'
+    tensor = _runs.is_tensor(matrices)
+    m = matrices if tensor else np.asarray(matrices)
+    if m.ndim != 3 or m.shape[1] != m.shape[2] or m.shape[0] < 1 or m.shape[1] < 1 or str(m.dtype).split('.')[-1] != 'float64':
+        raise ValueError('%s: matrices must be float64 [S, R, R], got %s %r' % (who, m.dtype, tuple(m.shape)))
+    limit = int(_lib.lib().chebgcn_tangent_query(0))
+    if m.shape[1] > limit:
+        raise ValueError('%s: %d rows; at most %d are served' % (who, m.shape[1], limit))
+    if not tensor and not (np.isfinite(m).all() and np.array_equal(m, m.transpose(0, 2, 1))):
+        raise ValueError('%s: matrices must be finite and symmetric' % who)
+    import torch
+    from . import ops
+    dev = _runs.cuda_device(device, m if tensor else None)
+    m = (m.detach() if tensor else torch.as_tensor(np.ascontiguousarray(m))).to(dev).contiguous()
+    with torch.cuda.device(dev):
+        if tensor and not bool((torch.isfinite(m) & (m == m.transpose(1, 2))).all()):
+            raise ValueError('%s: matrices must be finite and symmetric' % who)
+        S, R = int(m.shape[0]), int(m.shape[1])
+        step = int(_lib.lib().chebgcn_tangent_query(1))
+        w = torch.empty((S, R), dtype=torch.float64, device=dev)
+        V = torch.empty((S, R, R), dtype=torch.float64, device=dev)
+        sweeps = np.zeros(S, np.int32)
+        for s0 in range(0, S, step):
+            ws, Vt, sw, ok = ops.sym_eigh(m[s0:s0 + step])
+            if not bool(ok.all()):
+                raise _lib.ChebgcnError('%s: a matrix is still rotating after %d sweeps' % (who, int(sw.max())))
+            ws, order = torch.sort(ws, dim=1)
+            w[s0:s0 + step] = ws
+            V[s0:s0 + step] = torch.gather(Vt, 1, order[:, :, None].expand(-1, -1, R)).transpose(1, 2)
+            sweeps[s0:s0 + step] = sw.cpu().numpy()
+        return w, V, sweeps
+
+
+def tangent(runs, shrinkage='auto', max_iter=30, tol=1e-7, reference=None, device=None, batch_runs=None):
+    """Tangent-space connectivity on the device: nilearn's ``ConnectivityMeasure(kind='tangent')``.
+
+    ``runs``       as ``connectome`` takes them (R <= 512)
+    ``shrinkage``  'auto' (Ledoit-Wolf) or a number in [0, 1]
+    ``max_iter``   iterations of the geometric mean at most (an int >= 1)
+    ``tol``        the mean stops when ``||mean_s log B_s||_F / R^2 < tol`` (a finite number >= 0; 0 runs every iteration)
+    ``reference``  a fitted mean G (``Tangent.reference``): no iteration, the runs are mapped onto it (nilearn's ``transform``)
+    ``batch_runs`` runs per pass of the solver (default: what fits a quarter of the free device memory); the float64 Sigma of
+                   ALL runs stays resident, ``8 S R^2`` bytes
+
+    Per run ``Sigma_s`` is the shrunk covariance of ``connectome`` kept in float64.  G starts at the arithmetic mean and moves by
+    nilearn's rule: ``W = G^-1/2``, ``M = mean_s log(W Sigma_s W)``, ``G <- G^1/2 exp(step M) G^1/2``, the step halved when the norm
+    of M grows.  The outputs are ``W`` of the last G and ``log(W Sigma_s W)``.  A run whose Sigma is singular to round-off
+    (constant in time; no shrinkage with T <= R) is DEGENERATE: flagged, its matrix zeros, left out of every mean; with no usable
+    run ``mean`` and ``whitening`` are the identity.  Nothing raises and no NaN comes out of finite input.
+
+    Everything is float64 up to the one rounding of each output; every sum has one order (include/chebgcn.h), the means run over
+    the runs in ascending order.  So results are bit-identical under any ``batch_runs``, from call to call and between NumPy and
+    tensor input; with ``reference=`` also for a run alone or among others, in any run order; without it a permuted run order
+    gives the permuted result to rounding only.  Bad arguments and non-finite host arrays raise ``ValueError`` before the device
+    is touched.  Returns a ``Tangent``."""
+    who = 'tangent'
+    s, max_iter, tol = _check_tangent(shrinkage, max_iter, tol, batch_runs, who)
+    limit = int(_lib.lib().chebgcn_connectome_query(0))
+    runs, R = _as_runs(runs, who, limit)
+    Gref = _check_reference(reference, R, who)
+    dev, planes = _runs.stage(runs, R, device, who, any_dtype=True)
+    import torch
+    from . import ops
+    S = len(runs)
+    offs = _runs.offsets(runs)
+    lib = _lib.lib()
+    with torch.cuda.device(dev):
+        run_bytes = int(lib.chebgcn_connectome_workspace(1, R)) + 6 * 8 * R * R
+        batch = _runs.batch_size(batch_runs, S, min(int(lib.chebgcn_connectome_query(1)), int(lib.chebgcn_tangent_query(1))),
+                                 run_bytes, dev)
+        sigma = torch.empty((S, R, R), dtype=torch.float64, device=dev)
+        shrunk = torch.empty((S,), dtype=torch.float64, device=dev)
+        flags = torch.empty((S,), dtype=torch.int32, device=dev)
+        spans, counts, oks = [], [], []
+
+        def solve(m):
+            w, Vt, sw, ok = ops.sym_eigh(m)
+            counts.append(sw.max())
+            oks.append(ok.min())
+            return w, Vt
+
+        floor = degenerate_floor(R)
+        for r0, r1, rows, o in _runs.batches(planes, offs, batch):
+            spans.append((r0, r1))
+            ws = ops.connectome_cov(rows, o, R)
+            ops.connectome_sigma(ws, o, int(rows.shape[0]), R, s, sigma[r0:r1], shrunk[r0:r1])
+            w, _ = solve(sigma[r0:r1])
+            good = torch.isfinite(w).all(dim=1) & (w.min(dim=1).values > floor * w.max(dim=1).values)
+            flags[r0:r1] = (~good).to(torch.int32)
+        degenerate = flags.cpu().numpy() != 0
+        usable = int((~degenerate).sum())
+        eye = torch.eye(R, dtype=torch.float64, device=dev)
+        acc = torch.empty((R, R), dtype=torch.float64, device=dev)
+
+        def mean_of_batches(make):
+            """mean and norm of ``make(r0, r1)`` over the usable runs, the chain running through the batches in order."""
+            for b, (r0, r1) in enumerate(spans):
+                out = ops.sym_mean(make(r0, r1), flags[r0:r1], acc, first=b == 0, n_total=usable if b == len(spans) - 1 else 0)
+            return out
+
+        def logs(W, r0, r1, float32=False, out=None):
+            w, Vt = solve(ops.sym_congruence(W, sigma[r0:r1]))
+            return ops.sym_function(w, Vt, 'log', flags=flags[r0:r1].clone(), float32=float32, out=out)[0]
+
+        def powers(G, *funcs):
+            w, Vt = solve(G[None])
+            return [ops.sym_function(w, Vt, func)[0][0] for func in funcs]
+
+        norms, steps, converged = [], [], Gref is not None
+        if Gref is not None:
+            G = torch.as_tensor(Gref).to(dev)
+        elif usable == 0:
+            G = eye
+        else:
+            G = mean_of_batches(lambda r0, r1: sigma[r0:r1])[0]
+            step, norm_old = 1.0, np.inf
+            for _ in range(max_iter):
+                W, H = powers(G, 'rsqrt', 'sqrt')
+                M, norm = mean_of_batches(lambda r0, r1: logs(W, r0, r1))
+                norm = float(norm.cpu()[0])                     # the one readback of an iteration: the rule below runs on the host
+                norms.append(norm / R ** 2)
+                steps.append(step)
+                w, Vt = solve(M[None])
+                G = ops.sym_congruence(H, ops.sym_function(w, Vt, 'exp', a=step)[0])[0]
+                if norm < norm_old:
+                    norm_old = norm
+                elif norm > norm_old:
+                    step = step / 2.0
+                    norm = norm_old
+                if norm / R ** 2 < tol:
+                    converged = True
+                    break
+        W = eye if Gref is None and usable == 0 else powers(G, 'rsqrt')[0]
+        matrices = torch.empty((S, R, R), dtype=torch.float32, device=dev)
+        for r0, r1 in spans:
+            logs(W, r0, r1, float32=True, out=matrices[r0:r1])
+        return Tangent(matrices, G.to(torch.float32), W.to(torch.float32), G.cpu().numpy(), shrunk.cpu().numpy(), degenerate,
+                       len(norms), np.array(norms, np.float64), np.array(steps, np.float64), converged,
+                       int(torch.stack(counts).max()), bool(torch.stack(oks).min() != 0))

@@ -262,23 +262,16 @@ __device__ __forceinline__ double cn_delta(double delta_, double mu, double tr, 
 // 292 bytes of scratch a lane, measured), and the entry of a column that is not a constant then comes out of the registers
 typedef double cn_acc __attribute__((ext_vector_type(CN_NB)));
 
-// workgroup = run
-template <bool INV>
-__global__ void __launch_bounds__(CN_FT)
-connectome_finish_kernel(CnFinish p) {
-    __shared__ double red[CN_FT];
-    __shared__ double Ls[CN_PB][CN_NB];
-    __shared__ double Ld[CN_NB][CN_NB];         // Ld[j][c] = L[k0 + c][k0 + j]: the diagonal block, a column of L per row
-    __shared__ double dv[CN_NB];
-    __shared__ int bad;
-    const int r = blockIdx.x, tid = threadIdx.x;
+// The shrinkage of run r and Sigma = (1 - s) C + s mu I in place of C, for the finish and the sigma kernel alike (one body: the
+// float64 Sigma of chebgcn_connectome_sigma rounds to the bits of the covariance kind).  Every thread of a CN_FT workgroup calls
+// it (it holds barriers) and gets the shrinkage; thread 0 stores it
+__device__ __forceinline__ double cn_shrink(const CnFinish& p, int r, const CnRun& run, double* red) {
+    const int tid = threadIdx.x;
     const int R = p.R, Rp = p.Rp;
-    const CnRun run = cn_run(p.ws, r, Rp);
     double* A = run.A;
     long long t0, t1;
     glm_run(p.offs, r, p.Ttot, t0, t1);
     const double T = (double)(t1 - t0), Rd = (double)R;
-    if (tid == 0) bad = 0;
 
     // delta_ = sum_ij C_ij^2 and the trace
     double part = 0.0;
@@ -310,6 +303,39 @@ connectome_finish_kernel(CnFinish p) {
         run.scal[1] = s;
     }
     __syncthreads();
+    return s;
+}
+
+// workgroup = run: Sigma in float64, dense [R][R] (chebgcn_connectome_sigma; p.out is not used)
+__global__ void __launch_bounds__(CN_FT)
+connectome_sigma_kernel(CnFinish p, double* __restrict__ sigma) {
+    __shared__ double red[CN_FT];
+    const int r = blockIdx.x, R = p.R;
+    const CnRun run = cn_run(p.ws, r, p.Rp);
+    cn_shrink(p, r, run, red);
+    double* out = sigma + (size_t)r * R * R;
+    for (int e = threadIdx.x; e < R * R; e += CN_FT) {
+        const int i = e / R, j = e - i * R;
+        out[e] = run.A[(size_t)i * p.Rp + j];
+    }
+}
+
+// workgroup = run
+template <bool INV>
+__global__ void __launch_bounds__(CN_FT)
+connectome_finish_kernel(CnFinish p) {
+    __shared__ double red[CN_FT];
+    __shared__ double Ls[CN_PB][CN_NB];
+    __shared__ double Ld[CN_NB][CN_NB];         // Ld[j][c] = L[k0 + c][k0 + j]: the diagonal block, a column of L per row
+    __shared__ double dv[CN_NB];
+    __shared__ int bad;
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int R = p.R, Rp = p.Rp;
+    const CnRun run = cn_run(p.ws, r, Rp);
+    double* A = run.A;
+    const double Rd = (double)R;
+    if (tid == 0) bad = 0;
+    cn_shrink(p, r, run, red);
 
     if constexpr (!INV) {
         float* out = p.out + (size_t)r * R * R;
@@ -612,6 +638,26 @@ extern "C" int chebgcn_connectome_finish(double* workspace, size_t workspace_byt
         hipLaunchKernelGGL(connectome_gram_kernel, dim3((unsigned)cn_tiles(R), (unsigned)S), dim3(CN_CT), 0, stream, workspace, R, Rp, kind,
                            matrices);
     }
+    CG_HIP(hipGetLastError());
+    return CHEBGCN_OK;
+}
+
+extern "C" int chebgcn_connectome_sigma(double* workspace, size_t workspace_bytes, const int64_t* run_offsets, int64_t Ttot, int S, int R,
+                                        double shrinkage, double* sigma, double* shrinkage_out, chebgcn_stream stream_) {
+    CG_REQUIRE(workspace && run_offsets && sigma && shrinkage_out, "connectome_sigma: NULL argument");
+    CG_REQUIRE(Ttot >= 1 && cn_shape_ok(S, R), "connectome_sigma: bad shape (Ttot = %lld, S = %d, R = %d)", (long long)Ttot, S, R);
+    CG_REQUIRE(shrinkage < 0.0 || shrinkage <= 1.0, "connectome_sigma: a shrinkage of %g is neither negative (Ledoit-Wolf) nor in [0, 1]",
+               shrinkage);
+    if (!cn_served(S, R))
+        return fail(CHEBGCN_EUNSUPPORTED, "connectome_sigma: S = %d, R = %d; served: S <= %d, R <= %d", S, R, CN_SMAX, CN_RMAX);
+    CG_REQUIRE(workspace_bytes >= chebgcn_connectome_workspace(S, R), "connectome_sigma: workspace of %zu bytes, %zu needed",
+               workspace_bytes, chebgcn_connectome_workspace(S, R));
+    CG_REQUIRE(((uintptr_t)workspace & 15) == 0 && (((uintptr_t)run_offsets | (uintptr_t)shrinkage_out | (uintptr_t)sigma) & 7) == 0,
+               "connectome_sigma: unaligned argument");
+    CnFinish p{workspace, (const long long*)run_offsets, (long long)Ttot, R, plane_stride(R), CHEBGCN_CONNECTOME_COVARIANCE,
+               shrinkage < 0.0 ? -1.0 : shrinkage, nullptr, shrinkage_out, nullptr};
+    note_dispatch("connectome_sigma_kernel");
+    hipLaunchKernelGGL(connectome_sigma_kernel, dim3((unsigned)S), dim3(CN_FT), 0, (hipStream_t)stream_, p, sigma);
     CG_HIP(hipGetLastError());
     return CHEBGCN_OK;
 }

@@ -131,12 +131,12 @@ def connectivity_graph(series, k=8, device=None, return_sigma=False, kind='corre
     (model.py:93-106): ``connectome.connectome`` forms the matrices on the device (at most 512 regions; runs without a Cholesky
     factor are left out of the mean), ``knn_from_similarity`` picks the neighbours of the mean matrix on the host.  ``d = 1 -
     mean`` and the optional third value, the mean of the whole mean matrix, are as above.  The reference's ``tanh`` and
-    ``exp(. / sigma)`` steps are the caller's.  ``shrinkage`` has no meaning for the default kind.  Tangent-space connectivity is
-    out of scope."""
+    ``exp(. / sigma)`` steps are the caller's.  ``shrinkage`` has no meaning for the default kind.  The tangent-space graph of the
+    reference's ``RSFC`` setting is built from ``connectome.tangent(...).mean`` (INTEGRATION has the recipe)."""
     who = 'connectivity_graph'
     if kind not in ('correlation', 'partial correlation'):
-        raise ValueError("%s: kind must be 'correlation' or 'partial correlation', got %r (tangent-space connectivity is out "
-                         'of scope)' % (who, kind))
+        raise ValueError("%s: kind must be 'correlation' or 'partial correlation', got %r (the tangent-space graph is built "
+                         'from connectome.tangent)' % (who, kind))
     if kind == 'partial correlation':
         return _partial_graph(series, k, device, return_sigma, shrinkage)
     if (isinstance(series, np.ndarray) or _runs.is_tensor(series)) and series.ndim != 2:

@@ -1256,6 +1256,114 @@ def connectome_mean(matrices, degenerate):
     return mean
 
 
+def tangent_geometry():
+    """The constants of the tangent kernels (chebgcn_tangent_query): ``max_regions``, ``max_matrices`` of one call, ``block`` the
+    columns of a Jacobi block, ``threads`` of a step workgroup (a thread's second row starts there), ``sweeps`` the cap,
+    ``tile`` the side of a product tile, ``rows`` of a tile's operands in LDS at once, ``inner`` the sweeps inside a block pair."""
+    q = _lib.lib().chebgcn_tangent_query
+    return {'max_regions': q(0), 'max_matrices': q(1), 'block': q(2), 'threads': q(3), 'sweeps': q(4), 'tile': q(5), 'rows': q(6),
+            'inner': q(7)}
+
+
+def _sym_stack(m, what, S=None, R=None):
+    if m.dim() != 3 or m.shape[1] != m.shape[2]:
+        raise _lib.ChebgcnError('%s must be float64 [S, R, R]' % what)
+    S, R = int(m.shape[0]) if S is None else S, int(m.shape[1]) if R is None else R
+    _dense(m, torch.float64, (S, R, R), what)
+    return S, R
+
+
+def connectome_sigma(ws, run_offsets, Ttot, R, shrinkage, sigma, shrinkage_out):
+    """The shrunk covariance of every run in float64 (chebgcn_connectome_sigma) from what ``connectome_cov`` left in ``ws``, which
+    it overwrites: fills ``sigma`` float64 [S, R, R] and ``shrinkage_out`` float64 [S]."""
+    _require_cuda(ws, run_offsets, sigma, shrinkage_out)
+    S = int(run_offsets.numel()) - 1
+    _dense(run_offsets, torch.int64, (S + 1,), 'connectome_sigma: run_offsets')
+    _dense(sigma, torch.float64, (S, R, R), 'connectome_sigma: sigma')
+    _dense(shrinkage_out, torch.float64, (S,), 'connectome_sigma: shrinkage_out')
+    lib = _lib.lib()
+    nbytes = int(lib.chebgcn_connectome_workspace(S, int(R)))
+    _lib.check(_launch('connectome_sigma', 8.0 * S * R * R * 4, 0.0, lambda: lib.chebgcn_connectome_sigma(
+        _p(ws), min(nbytes, ws.numel()), _p(run_offsets), int(Ttot), S, int(R), float(shrinkage), _p(sigma), _p(shrinkage_out),
+        _stream())), 'connectome_sigma')
+
+
+def sym_eigh(matrices):
+    """Eigendecompositions of symmetric matrices (chebgcn_sym_eigh): ``matrices`` float64 [S, R, R] on the device ->
+    ``(w [S, R] in no particular order, Vt [S, R, R] with row p the eigenvector of w[p], sweeps int32 [S], converged int32
+    [S])``.  The call reads one int32 back per sweep.  The method and the order of every sum: include/chebgcn.h."""
+    _require_cuda(matrices)
+    S, R = _sym_stack(matrices, 'sym_eigh: matrices')
+    lib = _lib.lib()
+    nbytes = int(lib.chebgcn_tangent_workspace(S, R))
+    ws = _workspace(max(nbytes, 8) + 8, matrices.device, 'tangent_eigh')
+    ws = ws[(-ws.data_ptr()) % 8:]
+    w = torch.empty((S, R), dtype=torch.float64, device=matrices.device)
+    Vt = torch.empty((S, R, R), dtype=torch.float64, device=matrices.device)
+    sweeps = torch.empty((S,), dtype=torch.int32, device=matrices.device)
+    converged = torch.empty((S,), dtype=torch.int32, device=matrices.device)
+    _lib.check(_launch('sym_eigh', 8.0 * S * R * R * 4, 0.0, lambda: lib.chebgcn_sym_eigh(
+        _p(matrices), S, R, _p(w), _p(Vt), _p(sweeps), _p(converged), _p(ws), nbytes, _stream())), 'sym_eigh')
+    return w, Vt, sweeps, converged
+
+
+def sym_function(w, Vt, func, a=1.0, flags=None, float32=False, out=None):
+    """``V diag(f(a w)) V^T`` per matrix (chebgcn_sym_function) from what ``sym_eigh`` returned; ``func`` one of
+    ``_lib.SYM_FUNCTIONS``.  ``flags`` int32 [S] (default: fresh zeros) is set where a matrix has an eigenvalue the function cannot
+    take; flagged matrices come out as zeros.  -> ``(out float64 or float32 [S, R, R], flags)``."""
+    _require_cuda(w, Vt, flags, out)
+    S, R = _sym_stack(Vt, 'sym_function: Vt')
+    _dense(w, torch.float64, (S, R), 'sym_function: w')
+    if func not in _lib.SYM_FUNCTIONS:
+        raise _lib.ChebgcnError('sym_function: func must be one of %r, got %r' % (_lib.SYM_FUNCTIONS, func))
+    if flags is None:
+        flags = torch.zeros((S,), dtype=torch.int32, device=Vt.device)
+    _dense(flags, torch.int32, (S,), 'sym_function: flags')
+    dtype = torch.float32 if float32 else torch.float64
+    if out is None:
+        out = torch.empty((S, R, R), dtype=dtype, device=Vt.device)
+    _dense(out, dtype, (S, R, R), 'sym_function: out')
+    fvals = _workspace(8 * S * R + 8, Vt.device, 'tangent_fvals')
+    fvals = fvals[(-fvals.data_ptr()) % 8:]
+    _lib.check(_launch('sym_function', 8.0 * S * R * R * 2, 1.0 * S * R * R * (R + 1), lambda: _lib.lib().chebgcn_sym_function(
+        _p(w), _p(Vt), S, R, _lib.SYM_FUNCTIONS.index(func), float(a), _p(out), int(bool(float32)), _p(flags), _p(fvals), _stream())),
+        'sym_function')
+    return out, flags
+
+
+def sym_congruence(W, matrices, out=None):
+    """``W A_s W`` for one symmetric ``W`` float64 [R, R] and symmetric ``matrices`` float64 [S, R, R] (chebgcn_sym_congruence) ->
+    float64 [S, R, R], each symmetric bit for bit."""
+    _require_cuda(W, matrices, out)
+    S, R = _sym_stack(matrices, 'sym_congruence: matrices')
+    _dense(W, torch.float64, (R, R), 'sym_congruence: W')
+    if out is None:
+        out = torch.empty_like(matrices)
+    _dense(out, torch.float64, (S, R, R), 'sym_congruence: out')
+    scratch = _workspace(8 * S * R * R + 8, matrices.device, 'tangent_congruence')
+    scratch = scratch[(-scratch.data_ptr()) % 8:]
+    _lib.check(_launch('sym_congruence', 8.0 * S * R * R * 4, 3.0 * S * R * R * R, lambda: _lib.lib().chebgcn_sym_congruence(
+        _p(W), _p(matrices), S, R, _p(out), _p(scratch), _stream())), 'sym_congruence')
+    return out
+
+
+def sym_mean(matrices, flags, acc, first=True, n_total=0):
+    """The running sum of the unflagged matrices in ascending order (chebgcn_sym_mean): ``acc`` float64 [R, R] is started
+    (``first``) or continued; with ``n_total`` > 0 the call ends the mean -> ``(mean float64 [R, R], norm float64 [1])``, its
+    Frobenius norm; else ``None``."""
+    _require_cuda(matrices, flags, acc)
+    S, R = _sym_stack(matrices, 'sym_mean: matrices')
+    _dense(flags, torch.int32, (S,), 'sym_mean: flags')
+    _dense(acc, torch.float64, (R, R), 'sym_mean: acc')
+    mean = norm = None
+    if n_total > 0:
+        mean = torch.empty((R, R), dtype=torch.float64, device=matrices.device)
+        norm = torch.empty((1,), dtype=torch.float64, device=matrices.device)
+    _lib.check(_launch('sym_mean', 8.0 * (S + 2) * R * R, 1.0 * S * R * R, lambda: _lib.lib().chebgcn_sym_mean(
+        _p(matrices), _p(flags), S, R, int(bool(first)), int(n_total), _p(acc), _p(mean), _p(norm), _stream())), 'sym_mean')
+    return (mean, norm) if n_total > 0 else None
+
+
 def _workspace(nbytes, device, tag=''):
     """Scratch of a library call, kept per device, stream and use: launches on one stream are ordered, so the buffer of the
     previous call of the same kind is free by the time the next one runs."""

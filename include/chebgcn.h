@@ -1353,6 +1353,68 @@ int chebgcn_connectome_finish(double* workspace, size_t workspace_bytes, const i
                               double shrinkage, float* matrices, double* shrinkage_out, int32_t* degenerate, chebgcn_stream stream);
 int chebgcn_connectome_mean(const float* matrices, const int32_t* degenerate, int S, int R, float* mean, chebgcn_stream stream);
 
+/* ---- tangent-space connectivity: a batched symmetric eigensolver and the products around it (connectome.tangent) ----------------
+ * All matrices are float64 [S][R][R], dense (row stride R), 8-byte aligned; flags and counters int32.  No float atomics; every sum
+ * below has ONE order, a function of R alone, so a matrix's results are the same bits alone or among others, in any call.
+ * connectome_sigma: Sigma of connectome_finish (the same body: delta_, mu, the shrinkage, Sigma_ij = fma(1 - s, C_ij, ...)) from the
+ *   workspace connectome_cov left (overwritten), kept in float64: sigma [S][R][R], shrinkage_out [S].  (float)sigma is the
+ *   covariance kind of connectome_finish bit for bit.  chebgcn_last_dispatch(): connectome_sigma_kernel.
+ * sym_eigh: A_s = V_s diag(w_s) V_s^T for symmetric A_s (the lower and the upper triangle are both read; they must agree).
+ *   w [S][R] in NO particular order, Vt [S][R][R] with ROW p the eigenvector of w[p] (V transposed), sweeps [S], converged [S].
+ *   A block Jacobi method on X = A V and V (X <- A, V <- I), columns in blocks of chebgcn_tangent_query(2) = 8, the block pairs of
+ *   a sweep in round-robin order (player nb - 1 or the bye of an odd count stays, the others turn), one launch per step, a
+ *   workgroup per (pair, matrix); a matrix of one block works on that block alone.  Per pair, with x_i, v_i its 16 columns:
+ *       T_ij = ((sum_r v_ir x_jr) + (sum_r v_jr x_ir)) / 2     each sum ONE chain fma(v, x, acc) over ascending rows r; T_ij and T_ji
+ *                                                               come from the same two chains: T = sym(V^T A V) on the pair
+ *       a two-sided Jacobi on T accumulating Q, pairs (p, q) in the round-robin order of 16 players, up to query(7) sweeps:
+ *       zeta = (T_qq - T_pp) / (2 T_pq), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) (sign(0) = 1), c = 1 / sqrt(1 + t^2), s = c t;
+ *       a pair is left alone when |T_pq| <= max(R 2^-53 sqrt(|T_pp T_qq|), R 2^-53 max_ij |A_ij|), or is not finite
+ *       X_blk <- X_blk Q, V_blk <- V_blk Q                     each entry ONE chain over the pair's columns in ascending order
+ *   T is formed from V^T X and not from X^T X: the Gram matrix X^T X = V^T A^2 V cannot tell the eigenvalues lambda and -lambda
+ *   apart (A = [[0, 1], [1, 0]] has orthogonal columns and no rotation ever starts), and the mean of tangent vectors is indefinite.
+ *   A sweep in which no workgroup rotated ends the matrix (rotations are counted with integer atomics); finished matrices skip
+ *   later steps; after query(4) = 40 sweeps a matrix still rotating is reported with converged = 0.  sweeps counts the last,
+ *   idle sweep too.  w_p = sum_r v_pr x_pr, the Rayleigh quotient, signed, one chain over ascending r.
+ *   The call reads ONE int32 back per sweep (the number of matrices still open) and synchronises the stream for it: the only
+ *   entry of this family that does.  workspace: chebgcn_tangent_workspace(S, R) bytes, 8-byte aligned.
+ *   chebgcn_last_dispatch(): tangent_eigh_init_kernel + tangent_eigh_step_kernel + tangent_eigh_sweep_kernel +
+ *   tangent_eigh_values_kernel.
+ * sym_function: out_s = V_s diag(f(a w_s)) V_s^T, f one of CHEBGCN_SYM_*: out_ij = sum_p (f_p Vt_pi) Vt_pj, ONE chain fma over
+ *   ascending p, formed for i >= j and mirrored.  out is float64, or float32 rounded once (out_float32 = 1).  A value a w_p that is
+ *   not finite, that log, sqrt or 1/sqrt cannot take (not > 0), or whose exp overflows sets flags[s] = 1; a matrix whose flag is
+ *   set (by this call or before it) comes out as zeros.  flags are never cleared here.  fvals: scratch of S R doubles.
+ *   chebgcn_last_dispatch(): tangent_fvals_kernel + tangent_product_kernel<lower>.
+ * sym_congruence: out_s = W A_s W for ONE symmetric W [R][R] and symmetric A_s: scratch_s = A_s W (scratch_ij = sum_p A_pi W_pj),
+ *   then out_ij = sum_p W_pi scratch_pj for i >= j, mirrored; each ONE chain fma over ascending p.  scratch: S R R doubles.
+ *   chebgcn_last_dispatch(): tangent_product_kernel<full> + tangent_product_kernel<lower>.
+ * sym_mean: acc_ij = (first ? 0 : acc_ij) + sum over the s with flags[s] == 0, ascending, of matrices[s][i][j], the chain
+ *   acc = acc + m: runs may come in any number of calls.  With n_total > 0 the call also writes mean = acc / n_total and
+ *   norm[0] = sqrt(sum_ij mean_ij^2): thread u of 512 the chain fma(m, m, acc) over e = i R + j = u, u + 512, ..., then the tree
+ *   red[u] += red[u + h], h = 256, 128, .., 1.  chebgcn_last_dispatch(): tangent_mean_kernel (+ tangent_norm_kernel).
+ * tangent_query: 0 the largest R, 1 matrices of one call, 2 columns of a Jacobi block, 3 threads of a step workgroup (a thread's
+ *   second row), 4 the cap of sweeps, 5 side of a product tile, 6 rows of a tile's operands in LDS at once, 7 sweeps of the
+ *   Jacobi inside a pair; -1 otherwise.  tangent_workspace: bytes of sym_eigh's workspace (0: arguments out of range).
+ * Limits: R <= 512, S <= 65535 per call (sym_mean: S <= 2^24): CHEBGCN_EUNSUPPORTED beyond, before any launch, as every
+ * CHEBGCN_EINVAL (NULL, counts <= 0, an unknown function, a = NaN or inf, a workspace too small, a pointer not aligned to its
+ * element, scratch or Vt aliasing an operand).  Except for sym_eigh's readback the calls neither synchronise nor allocate. */
+enum {
+    CHEBGCN_SYM_LOG = 0,
+    CHEBGCN_SYM_EXP = 1,
+    CHEBGCN_SYM_SQRT = 2,
+    CHEBGCN_SYM_RSQRT = 3
+};
+int chebgcn_connectome_sigma(double* workspace, size_t workspace_bytes, const int64_t* run_offsets, int64_t Ttot, int S, int R,
+                             double shrinkage, double* sigma, double* shrinkage_out, chebgcn_stream stream);
+int chebgcn_tangent_query(int what);
+size_t chebgcn_tangent_workspace(int S, int R);
+int chebgcn_sym_eigh(const double* A, int S, int R, double* w, double* Vt, int32_t* sweeps, int32_t* converged, void* workspace,
+                     size_t workspace_bytes, chebgcn_stream stream);
+int chebgcn_sym_function(const double* w, const double* Vt, int S, int R, int func, double a, void* out, int out_float32, int32_t* flags,
+                         double* fvals, chebgcn_stream stream);
+int chebgcn_sym_congruence(const double* W, const double* A, int S, int R, double* out, double* scratch, chebgcn_stream stream);
+int chebgcn_sym_mean(const double* matrices, const int32_t* flags, int S, int R, int first, int n_total, double* acc, double* mean,
+                     double* norm, chebgcn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
