@@ -6,7 +6,7 @@ and ``lib_new.coarsening`` (pooling index maps), on PyTorch-ROCm tensors, with t
 arithmetic in hand-written gfx950 kernels behind the C ABI of ``include/chebgcn.h``.
 """
 from . import _lib  # noqa: F401
-from . import graph, coarsening, parcellation, filters, splits, stats, glm, searchlight, connectome  # noqa: F401
+from . import graph, coarsening, parcellation, filters, splits, stats, glm, searchlight, connectome, encoding  # noqa: F401
 from .parcellation import Parcellation  # noqa: F401
 from .filters import GraphFilter  # noqa: F401
 from .stats import MapTestResult, map_test, map_test_host, sign_flips  # noqa: F401
@@ -19,6 +19,7 @@ from .searchlight import SearchlightResult, SolverInfo, lda_shrinkage_host, sear
 from .searchlight import RDMResult, compare_rdms, crossnobis, crossnobis_events, crossnobis_host  # noqa: F401
 # (the call itself is connectome.connectome: the package attribute stays the module)
 from .connectome import Connectome, connectome_host, Tangent, tangent, tangent_host  # noqa: F401
+from .encoding import EncodingResult, delay_features, ridge_cv, ridge_cv_host  # noqa: F401
 
 __all__ = ['graph', 'coarsening', 'parcellation', 'Parcellation', 'filters', 'GraphFilter', 'splits', 'stats', 'map_test',
            'map_test_host', 'sign_flips', 'MapTestResult', 'design_test', 'design_test_host', 'permutations', 'perm_t_host',
@@ -26,7 +27,8 @@ __all__ = ['graph', 'coarsening', 'parcellation', 'Parcellation', 'filters', 'Gr
            'first_level', 'first_level_host', 'TrialDesign', 'TrialResult', 'trial_design', 'single_trial', 'single_trial_host',
            'searchlight', 'SearchlightResult', 'SolverInfo', 'searchlight_events', 'searchlight_host',
            'lda_shrinkage_host', 'RDMResult', 'compare_rdms', 'crossnobis', 'crossnobis_events', 'crossnobis_host', 'connectome', 'Connectome',
-           'connectome_host', 'Tangent', 'tangent', 'tangent_host', 'models_gcn', 'ops']
+           'connectome_host', 'Tangent', 'tangent', 'tangent_host', 'encoding', 'EncodingResult', 'delay_features', 'ridge_cv', 'ridge_cv_host',
+           'models_gcn', 'ops']
 
 
 def __getattr__(name):

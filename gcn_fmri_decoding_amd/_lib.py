@@ -22,6 +22,7 @@ CLUSTER_AUTO, CLUSTER_ONCHIP, CLUSTER_STREAMED = 0, 1, 2
 CLUSTER_EHEIGHTS, CLUSTER_ELOOP = 1, 2
 CONNECTOME_KINDS = ('covariance', 'correlation', 'precision', 'partial correlation')      # CHEBGCN_CONNECTOME_* in this order
 SYM_FUNCTIONS = ('log', 'exp', 'sqrt', 'rsqrt')                                             # CHEBGCN_SYM_* in this order
+RIDGE_SCORES = ('r2', 'r')                                                                  # CHEBGCN_RIDGE_* in this order
 
 
 class ChebgcnError(RuntimeError):
@@ -198,6 +199,11 @@ SIGNATURES = {
     'chebgcn_sym_function': (_i, [_p, _p, _i, _i, _i, C.c_double, _p, _i, _p, _p, _p]),
     'chebgcn_sym_congruence': (_i, [_p, _p, _i, _i, _p, _p, _p]),
     'chebgcn_sym_mean': (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    'chebgcn_ridge_query': (_i, [_i]),
+    'chebgcn_ridge_workspace': (C.c_size_t, [_i, _i, _i]),
+    'chebgcn_ridge_rotate': (_i, [_p, _i, _p, _p, _i, _p, _i, _i, _i, _p, C.c_size_t, _p]),
+    'chebgcn_ridge_score': (_i, [_p, C.c_size_t, _p, _i, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    'chebgcn_ridge_weights': (_i, [_p, C.c_size_t, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
 }
 
 _lib = None

@@ -1364,6 +1364,111 @@ def sym_mean(matrices, flags, acc, first=True, n_total=0):
     return (mean, norm) if n_total > 0 else None
 
 
+def ridge_geometry():
+    """The constants of the ridge kernels (chebgcn_ridge_query): ``tile`` the vertices of a workgroup, ``block`` the outputs of a
+    register block, ``max_F`` / ``max_A`` served, ``max_runs`` of one list, ``max_models`` of one call, ``threads`` of a
+    workgroup, ``buckets`` the buckets of F the score kernel is built for."""
+    q = _lib.lib().chebgcn_ridge_query
+    return {'tile': q(0), 'block': q(1), 'max_F': q(2), 'max_A': q(3), 'max_runs': q(4), 'max_models': q(5), 'threads': q(6),
+            'buckets': sorted({q(100 + F) for F in range(1, q(2) + 1)})}
+
+
+def _ridge_tables(what, c, list_ptr, list_runs, E, F):
+    """``c`` float64 [R, F, Mp] and the run lists of E models checked -> ``(R, Mp, nlist)``."""
+    if c.dim() != 3:
+        raise _lib.ChebgcnError('%s: c must be float64 [R, F, Mp]' % what)
+    R, Mp = int(c.shape[0]), int(c.shape[2])
+    _dense(c, torch.float64, (R, F, Mp), what + ': c')
+    _dense(list_ptr, torch.int32, (2 * E + 1,), what + ': list_ptr')
+    nlist = int(list_runs.numel())
+    _dense(list_runs, torch.int32, (nlist,), what + ': list_runs')
+    return R, Mp, nlist
+
+
+def ridge_workspace(E, F, M, device):
+    """The float64 workspace [E, 2, F, Mp] of the ridge kernels as ``(tensor, bytes)`` (chebgcn_ridge_workspace), kept per device
+    and stream like every scratch."""
+    nbytes = int(_lib.lib().chebgcn_ridge_workspace(int(E), int(F), int(M)))
+    ws = _workspace(max(nbytes, 8) + 8, device, 'ridge')
+    return ws[(-ws.data_ptr()) % 8:], nbytes
+
+
+def ridge_rotate(c, list_ptr, list_runs, V, M, ws=None):
+    """The run sums of every model's two lists, rotated into its eigenbasis (chebgcn_ridge_rotate): ``c`` float64 [R, F, Mp],
+    ``list_ptr`` int32 [2 E + 1] / ``list_runs`` int32 [nlist] (list 2 e the training runs of model e, 2 e + 1 its held-out
+    runs), ``V`` float64 [E, F, F] on the device -> the workspace ``(ws, bytes)`` that ``ridge_score`` and ``ridge_weights``
+    read (``ws``: one given by the caller, at least that large).  The chains: include/chebgcn.h."""
+    _require_cuda(c, list_ptr, list_runs, V, ws)
+    if V.dim() != 3:
+        raise _lib.ChebgcnError('ridge_rotate: V must be float64 [E, F, F]')
+    E, F = int(V.shape[0]), int(V.shape[1])
+    _dense(V, torch.float64, (E, F, F), 'ridge_rotate: V')
+    R, Mp, nlist = _ridge_tables('ridge_rotate', c, list_ptr, list_runs, E, F)
+    if Mp != plane_stride(M):
+        raise _lib.ChebgcnError('ridge_rotate: c must be [R, F, plane_stride(M)]')
+    lib = _lib.lib()
+    if ws is None:
+        ws, nbytes = ridge_workspace(E, F, M, c.device)
+    else:
+        nbytes = min(int(lib.chebgcn_ridge_workspace(E, F, int(M))), ws.numel() * ws.element_size())
+    _lib.check(_launch('ridge_rotate', 8.0 * E * F * Mp * 3, 4.0 * E * F * F * Mp, lambda: lib.chebgcn_ridge_rotate(
+        _p(c), R, _p(list_ptr), _p(list_runs), nlist, _p(V), E, F, int(M), _p(ws), nbytes, _stream())), 'ridge_rotate')
+    return ws, nbytes
+
+
+def ridge_score(ws, nbytes, tss, list_ptr, list_runs, H, d, fold_ptr, M, Ef, kind='r2', scores=False):
+    """Every fold model scored at every penalty and the folds of every subject averaged (chebgcn_ridge_score): ``ws`` from
+    ``ridge_rotate`` over E >= ``Ef`` models, ``tss`` float64 [R, Mp], ``H`` float64 [E, F, F] (symmetric bit for bit), ``d``
+    float64 [E, A, F], ``fold_ptr`` int32 [S + 1] (the folds of subject s are the models fold_ptr[s] .. fold_ptr[s + 1] - 1) ->
+    ``(score float32 [S, M], alpha_index int32 [S, M], scores float32 [S, A, M] or None, fold_scores float64 [Ef, A, Mp])``."""
+    _require_cuda(ws, tss, list_ptr, list_runs, H, d, fold_ptr)
+    if H.dim() != 3 or d.dim() != 3:
+        raise _lib.ChebgcnError('ridge_score: H must be float64 [E, F, F] and d float64 [E, A, F]')
+    E, F, A = int(H.shape[0]), int(H.shape[1]), int(d.shape[1])
+    _dense(H, torch.float64, (E, F, F), 'ridge_score: H')
+    _dense(d, torch.float64, (E, A, F), 'ridge_score: d')
+    if kind not in _lib.RIDGE_SCORES:
+        raise _lib.ChebgcnError('ridge_score: kind must be one of %r, got %r' % (_lib.RIDGE_SCORES, kind))
+    Mp = plane_stride(M)
+    R = int(tss.shape[0]) if tss.dim() == 2 else 0
+    _dense(tss, torch.float64, (R, Mp), 'ridge_score: tss')
+    _dense(list_ptr, torch.int32, (2 * E + 1,), 'ridge_score: list_ptr')
+    nlist = int(list_runs.numel())
+    _dense(list_runs, torch.int32, (nlist,), 'ridge_score: list_runs')
+    S = int(fold_ptr.numel()) - 1
+    _dense(fold_ptr, torch.int32, (S + 1,), 'ridge_score: fold_ptr')
+    dev = tss.device
+    Ef = int(Ef)
+    fold = torch.empty((max(Ef, 1), A, Mp), dtype=torch.float64, device=dev)
+    score = torch.empty((S, int(M)), dtype=torch.float32, device=dev)
+    index = torch.empty((S, int(M)), dtype=torch.int32, device=dev)
+    table = torch.empty((S, A, int(M)), dtype=torch.float32, device=dev) if scores else None
+    _lib.check(_launch('ridge_score', 8.0 * Ef * Mp * (2 * F + A), 2.0 * Ef * A * F * (F + 2) * Mp, lambda: _lib.lib().chebgcn_ridge_score(
+        _p(ws), nbytes, _p(tss), R, _p(list_ptr), _p(list_runs), nlist, _p(H), _p(d), _p(fold_ptr), E, Ef, S, F, A, int(M),
+        _lib.RIDGE_SCORES.index(kind), _p(fold), _p(score), _p(index), _p(table), _stream())), 'ridge_score')
+    return score, index, table, fold
+
+
+def ridge_weights(ws, nbytes, Vt, d, all_model, alpha_index, M):
+    """The refit of every subject at its selected penalties (chebgcn_ridge_weights): ``ws`` from ``ridge_rotate``, ``Vt`` float64
+    [E, F, F] (V transposed), ``d`` float64 [E, A, F], ``all_model`` int32 [S] the model trained on all the subject's runs,
+    ``alpha_index`` int32 [S, M] -> float32 [S, F, M]."""
+    _require_cuda(ws, Vt, d, all_model, alpha_index)
+    if Vt.dim() != 3 or d.dim() != 3:
+        raise _lib.ChebgcnError('ridge_weights: Vt must be float64 [E, F, F] and d float64 [E, A, F]')
+    E, F, A = int(Vt.shape[0]), int(Vt.shape[1]), int(d.shape[1])
+    _dense(Vt, torch.float64, (E, F, F), 'ridge_weights: Vt')
+    _dense(d, torch.float64, (E, A, F), 'ridge_weights: d')
+    S = int(all_model.numel())
+    _dense(all_model, torch.int32, (S,), 'ridge_weights: all_model')
+    _dense(alpha_index, torch.int32, (S, int(M)), 'ridge_weights: alpha_index')
+    weights = torch.empty((S, F, int(M)), dtype=torch.float32, device=Vt.device)
+    _lib.check(_launch('ridge_weights', 8.0 * S * F * plane_stride(M) + 4.0 * S * F * M, 2.0 * S * F * (F + 1) * M,
+                       lambda: _lib.lib().chebgcn_ridge_weights(_p(ws), nbytes, _p(Vt), _p(d), _p(all_model), _p(alpha_index), E, S, F,
+                                                                A, int(M), _p(weights), _stream())), 'ridge_weights')
+    return weights
+
+
 def _workspace(nbytes, device, tag=''):
     """Scratch of a library call, kept per device, stream and use: launches on one stream are ordered, so the buffer of the
     previous call of the same kind is free by the time the next one runs."""

@@ -1415,6 +1415,67 @@ int chebgcn_sym_congruence(const double* W, const double* A, int S, int R, doubl
 int chebgcn_sym_mean(const double* matrices, const int32_t* flags, int S, int R, int first, int n_total, double* acc, double* mean,
                      double* norm, chebgcn_stream stream);
 
+/* ---- cross-validated ridge encoding models: every fold and penalty scored from per-run statistics (encoding.ridge_cv) ------------
+ * The caller centres every run's features on the host, Xc_r float64 [T_r][F], and forms the per-run statistics with
+ * chebgcn_glm_project over the table [Xc_r | 1] (as many calls of at most 64 columns as F + 1 needs):
+ *   c      float64 [R][F][Mp]   c[r][j][m] = sum_t Xc_r[t][j] y_r[t][m], Mp = chebgcn_plane_stride(M)
+ *   tss    float64 [R][Mp]      tss_r = yy_r - s_r s_r / T_r (s_r the ones column), 0 where below 4 (T_r + 1) 2^-53 yy_r
+ * A MODEL e is a training list and a held-out list of runs: list_ptr int32 [2 E + 1], list 2 e = the training runs of model e,
+ * list 2 e + 1 its held-out runs, list l = list_runs[list_ptr[l] .. list_ptr[l + 1]) (int32 [nlist], run numbers of c and tss, the
+ * caller lists them ascending).  Per model the caller hands, from G_tr = sum Xc_r^T Xc_r = V diag(lambda) V^T and G_te likewise,
+ *   V      float64 [E][F][F]    V[j][i] = component j of eigenvector i
+ *   H      float64 [E][F][F]    (V^T G_te V + its transpose) / 2: symmetric BIT FOR BIT; the kernel reads H[j][i] where the chain
+ *                               below says H[i][j] (row j is contiguous in i), which is the same number only then
+ *   d      float64 [E][A][F]    d[a][j] = 1 / (max(lambda_j, 0) + alpha_a), or 0: the kernels never divide by a penalty
+ *   Vt     float64 [E][F][F]    Vt[j][i] = V[i][j] (ridge_weights)
+ * Every entry of list_ptr is clamped into [0, nlist], a descending pair is an empty list, a list is cut after
+ * chebgcn_ridge_query(4) = 64 entries, a run number outside [0, R) is skipped; fold_ptr is clamped into [0, Ef]; a model number of
+ * all_model outside [0, E) gives weights of zero; alpha_index is clamped into [0, A): nothing read from memory is an address or a
+ * trip count unchecked.  Float64 throughout; EVERY multiply, add, divide and square root is rounded on its own (no fused
+ * multiply-add), every chain starts from 0 and runs over ascending index; no float atomics.  A (model, vertex) result is the same
+ * bits whatever M, E and the other models are, from call to call.  What the pad columns [M, Mp) of c, tss and the workspace hold
+ * (NaN included) is never read; the pad of the workspace and of fold_scores is written as zero.
+ *
+ * ridge_rotate, per (model e, vertex m):  ct_j = sum_{r in train(e), list order} c[r][j][m],  cs_j likewise over test(e),
+ *     z_i = sum_j V[j][i] ct_j,   g_i = sum_j V[j][i] cs_j     (acc = acc + V[j][i] * ct_j over ascending j)
+ *   workspace: float64 [E][2][F][Mp], z then g of every model, chebgcn_ridge_workspace(E, F, M) bytes, 8-byte aligned.  The
+ *   statistics are read once per (model, list).  chebgcn_last_dispatch(): ridge_rotate_kernel.
+ * ridge_score, per (fold model e < Ef, vertex m), from the workspace ridge_rotate left for E >= Ef models:
+ *     tss = sum_{r in test(e), list order} tss[r][m]
+ *     per penalty a:  w_i = d[a][i] * z_i;   p = sum_i w_i * g_i;   h_i = sum_j H[i][j] * w_j;   q = sum_i w_i * h_i
+ *     kind CHEBGCN_RIDGE_R2:  rss = (tss - 2 p) + q;  value = tss > 0 ? 1 - rss / tss : 0
+ *     kind CHEBGCN_RIDGE_R:   value = (tss > 0 && q > 0) ? p / sqrt(tss * q) : 0          (never NaN for finite input)
+ *   fold_scores float64 [Ef][A][Mp] (scratch of the call, 8-byte aligned).  Then per (subject s, vertex m), the folds of subject s
+ *   being the models fold_ptr[s] .. fold_ptr[s + 1] - 1 (int32 [S + 1]), n of them:
+ *     mean_a = (sum over the folds in ascending order of value) / n  (0 where n = 0);   a* = the first a that attains the maximum
+ *     (scanned upwards with a strict >);   score[s][m] = (float)mean_a*, alpha_index[s][m] = a*, scores[s][a][m] = (float)mean_a.
+ *   score float32 [S][M], alpha_index int32 [S][M], scores float32 [S][A][M] or NULL: dense, no pad.
+ *   chebgcn_last_dispatch(): ridge_score_kernel<FB> + ridge_select_kernel, FB = chebgcn_ridge_query(100 + F) the bucket of F (64,
+ *   128 or 256).
+ * ridge_weights, per (subject s, vertex m), e = all_model[s] (int32 [S]: the model whose training list is all the subject's runs),
+ *   a = alpha_index[s][m]:   t_j = d[a][j] * z_j;   w_i = sum_j Vt[j][i] * t_j;   weights[s][i][m] = (float)w_i, float32 [S][F][M]
+ *   dense.  chebgcn_last_dispatch(): ridge_weights_kernel.
+ * ridge_query: 0 vertices of a workgroup, 1 outputs of a register block, 2 the largest F, 3 the largest A, 4 runs of a list at most,
+ *   5 models / subjects of one call, 6 threads of a workgroup, 100 + F the score kernel's bucket of F; -1 otherwise.
+ * ridge_workspace: bytes for E models (0: arguments out of range).
+ * Limits: F <= 256, A <= 32, E <= 65535, S <= 65535: CHEBGCN_EUNSUPPORTED beyond, before any launch, as every CHEBGCN_EINVAL (NULL,
+ * counts <= 0, Ef > E, an unknown kind, a workspace too small, a pointer not aligned to its element).  The calls neither
+ * synchronise nor allocate. */
+enum {
+    CHEBGCN_RIDGE_R2 = 0,
+    CHEBGCN_RIDGE_R = 1
+};
+int chebgcn_ridge_query(int what);
+size_t chebgcn_ridge_workspace(int E, int F, int M);
+int chebgcn_ridge_rotate(const double* c, int R, const int32_t* list_ptr, const int32_t* list_runs, int nlist, const double* V, int E,
+                         int F, int M, double* workspace, size_t workspace_bytes, chebgcn_stream stream);
+int chebgcn_ridge_score(const double* workspace, size_t workspace_bytes, const double* tss, int R, const int32_t* list_ptr,
+                        const int32_t* list_runs, int nlist, const double* H, const double* d, const int32_t* fold_ptr, int E, int Ef,
+                        int S, int F, int A, int M, int kind, double* fold_scores, float* score, int32_t* alpha_index, float* scores,
+                        chebgcn_stream stream);
+int chebgcn_ridge_weights(const double* workspace, size_t workspace_bytes, const double* Vt, const double* d, const int32_t* all_model,
+                          const int32_t* alpha_index, int E, int S, int F, int A, int M, float* weights, chebgcn_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
